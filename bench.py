@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the fused MI355X NavGym step (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: set-up, GPU spin-up, W warm-up steps, the K timed steps, the line.  `--full` adds
+everything else the bench measures (timed repeats, the passes with scan noise off and without spin-up, the CPU baseline, the
+N = 1 extras, with N > 1 the weak curve and the obs-gather pass).  `--dump-outputs DIR` writes what the last timed step
+returned (observation rows, reward, done, ...) as DIR/<name>.npy, for comparing two builds output for output.
 
 N = 1: BASELINE.json configs[1] -- 4096 arenas, 1081-beam lidar, 500x500 static occupancy map,
 diff-drive (KetiRobot kinematics), no pedestrians, auto-respawn of finished arenas in place.
@@ -10,16 +15,16 @@ as `python bench.py --gpus N`, this script spawns the N ranks itself before touc
 `--scaling strong`: the workload's TOTAL (c2: 4096) is split over the ranks by sharding.shard_range (ragged totals
 allowed).  `--scaling weak`: every rank owns the workload's per-GPU arena count (c2: 4096 per GPU; c4 / c5: 1/8 of their
 8-GPU totals, so `--workload c4 --gpus 8` is the configured 16384 and `--workload c5 --gpus 8` the configured 4096).
-Default (`--scaling auto`): with N > 1 ONE invocation measures both -- `value` is the STRONG number (BASELINE.json's metric
-reads "4096 envs ..., 1/2/4/8 MI355X": a fixed total), `value_weak` the weak one, each with its own `envs_total`; with
-N = 1 the two coincide.  Arenas are keyed by their global index either way.  The step has no exchange, so `value` involves
-no data-path collective; with N > 1 the line also carries `value_with_obs_gather`: the same K steps with the optional RCCL
-all-gather of the observation rows after every step (`--gather none` skips that pass).
-With N = 1 the default run appends short windows of the other BASELINE workloads (`other_workloads`: c3, c4, c5) and the
+Default (`--scaling auto`): with N > 1 `value` is the STRONG number (BASELINE.json's metric reads "4096 envs ..., 1/2/4/8
+MI355X": a fixed total); with `--full` the same invocation also measures the weak one, `value_weak`, each with its own
+`envs_total`; with N = 1 the two coincide.  Arenas are keyed by their global index either way.  The step has no exchange, so
+`value` involves no data-path collective; with N > 1 a `--full` line also carries `value_with_obs_gather`: the same K steps
+with the optional RCCL all-gather of the observation rows after every step (`--gather none` skips that pass).
+With N = 1 a `--full` run appends short windows of the other BASELINE workloads (`other_workloads`: c3, c4, c5) and the
 same steps through the gym API (`value_gym_api`: NavGymEnv.step with torch actions); `--no-extras` skips them.
 
 One "step" = one launch of navsim_step over all local arenas, inputs resident in HBM.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 with `roofline` (and, with `--full`, `cpu_baseline`).
 """
 import argparse
 import json
@@ -114,6 +119,31 @@ def build_sim(wl, base, E, seed=1234, device="cuda:0"):
     if wl.get("regen") and wl.get("pregen", False):
         s.enable_pregen(pipeline=int(wl.get("pipeline", 0)), install=bool(wl.get("pipeline", 0)) and wl.get("install", True))    # next worlds staged ahead of time on a side stream (navsim_regen_swap)
     return cfg, s, arrays, occ
+
+
+DUMP_BYTES = 64 << 20           # --dump-outputs: at most this much over all ranks
+
+
+def dump_outputs(path, sim, rank=0, world_size=1):
+    """--dump-outputs: what the latest step returned to its caller (NavSim.obs and NavSim.out: observation rows, reward, done,
+    is_success, is_crash, distance, goals) as DIR/<name>.npy in float32 / float64 (done: 0 / 1 as float32), and the global
+    index of every row as arena_index.npy.  Above DUMP_BYTES a fixed seeded sample of the arenas (the same rows of every
+    array).  With N > 1 every rank writes its own arenas as rank<r>_<name>.npy."""
+    import numpy as np
+    host = {}
+    for name, v in [("obs", sim.obs)] + sorted(sim.out.items()):
+        a = v.detach().cpu().numpy()
+        host[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    E = sim.cfg.n_envs
+    row_bytes = sum(a.nbytes // E for a in host.values()) + 8
+    keep = min(E, DUMP_BYTES // world_size // row_bytes)
+    rows = np.arange(E) if keep == E else np.sort(np.random.default_rng(0).choice(E, keep, replace=False))
+    host = {name: a[rows] for name, a in host.items()}
+    host["arena_index"] = (rows + int(sim.cfg.env_index_base)).astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    prefix = "rank%d_" % rank if world_size > 1 else ""
+    for name, a in host.items():
+        np.save(os.path.join(path, prefix + name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(wl, seconds=15.0):
@@ -388,7 +418,8 @@ def main():
     ap.add_argument("--field", default="u16t", choices=["u16t", "f32"], help="distance-field storage")
     ap.add_argument("--noise-std", type=float, default=0.02,
                     help="scan_noise_std of every arena in the timed steps (SURVEY.md 8d: 0.02 for throughput runs)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed repeats of K steps (the first one is `value`)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed repeats of K steps (the first one is `value`); default 5 with --full, else 1")
     ap.add_argument("--no-noise-off-pass", action="store_true",
                     help="skip the extra K steps timed with scan noise off (profiling runs: one kind of launch only)")
     ap.add_argument("--step-block", type=int, default=0, help="threads per arena (0 = library default)")
@@ -432,6 +463,11 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / reduction control flow only, no GPU work (tests/test_host_logic.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: timed repeats, the noise-off and no-spin-up passes, the CPU "
+                         "baseline, the N = 1 extras (other workloads, gym API), with N > 1 the weak curve and the obs-gather pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (obs, reward, done, ...) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus is None:                   # `torchrun --nproc-per-node N bench.py`: the launcher's world is the answer
@@ -449,6 +485,12 @@ def main():
     backend = os.environ.get("NAVSIM_BENCH_BACKEND", "nccl")
     if args.dry_run:
         return dry_run(args, rank, world_size, backend)
+    if not args.full:           # a plain run: spin-up, warm-up, the K timed steps and the line, nothing beside the headline
+        args.no_noise_off_pass = args.no_cold_pass = args.no_cpu_baseline = args.no_extras = True
+        if args.gather == "auto":                    # the obs-gather pass; --gather all is part of the headline's steps
+            args.gather = "none"
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     import torch
     dist = None
@@ -494,9 +536,9 @@ def main():
     coll_dev = device if backend == "nccl" else "cpu"
 
     ctx = dict(rank=rank, world_size=world_size, dist=dist, backend=backend, device=device, coll_dev=coll_dev)
-    if args.scaling == "auto" and world_size > 1:
+    if args.scaling == "auto" and world_size > 1 and args.full:
         # BOTH curves from one invocation: `value` is the strong number (the metric's fixed total), value_weak the weak one
-        out = measure(args, "strong", ctx)
+        out = measure(args, "strong", ctx, dump=args.dump_outputs)
         weak = measure(args, "weak", ctx, light=True)
         if rank == 0:
             out["value_weak"] = weak["value"]
@@ -505,7 +547,8 @@ def main():
                                kernel_ms=weak["roofline"]["kernel_ms"], value_with_obs_gather=weak.get("value_with_obs_gather"))
             out["value_strong"] = out["value"]
     else:
-        out = measure(args, "weak" if args.scaling == "auto" else args.scaling, ctx)
+        scaling = args.scaling if args.scaling != "auto" else ("strong" if world_size > 1 else "weak")
+        out = measure(args, scaling, ctx, dump=args.dump_outputs)
         if rank == 0:
             out["value_weak" if out["scaling"] == "weak" else "value_strong"] = out["value"]
     if rank == 0 and world_size == 1 and not args.no_extras and args.workload == "c2" and not args.envs:
@@ -788,9 +831,10 @@ def extras(args, device):
     return res
 
 
-def measure(args, scaling, ctx, light=False):
+def measure(args, scaling, ctx, light=False, dump=None):
     """One measurement of args.workload under `scaling`: W warm-up steps, EXACTLY K timed steps between barrier +
-    synchronize, max over ranks -> the line (rank 0) / None.  light: the timed steps only (no repeats, no extra passes)."""
+    synchronize, max over ranks -> the line (rank 0) / None.  light: the timed steps only (no repeats, no extra passes).
+    dump: directory for what the last timed step returned (dump_outputs), written before any further pass."""
     import torch
     rank, world_size, dist, backend, device, coll_dev = (ctx[k] for k in ("rank", "world_size", "dist", "backend", "device", "coll_dev"))
     wl = dict(WORKLOADS[args.workload])
@@ -943,6 +987,8 @@ def measure(args, scaling, ctx, light=False):
                 print("bench: hipGraph capture failed (%s); timing plain launches" % type(exc).__name__, file=sys.stderr)
 
     elapsed, kernel_ms = timed()                     # THE measurement (`value`)
+    if dump:
+        dump_outputs(dump, sim, rank, world_size)
     more = [timed() for _ in range(max(args.repeats - 1, 0))] if not light else []
     with_gather, gather_error = None, None
     if gatherer is not None and not gather_on[0]:    # the same K steps, every step followed by the obs all-gather
@@ -1142,8 +1188,8 @@ def dry_run(args, rank, world_size, backend):
         wl["envs"] = args.envs
     if args.total_envs:
         wl["total"] = args.total_envs
-    both = args.scaling == "auto" and world_size > 1            # value = strong, value_weak = weak, one invocation
-    scaling = "strong" if both else ("weak" if args.scaling == "auto" else args.scaling)
+    both = args.scaling == "auto" and world_size > 1 and args.full      # value = strong, value_weak = weak, one invocation
+    scaling = args.scaling if args.scaling != "auto" else ("strong" if world_size > 1 else "weak")
     base, count = shard_of(wl, scaling, rank, world_size)
     E_total = wl["total"] if scaling == "strong" else world_size * wl["envs"]
     gathered_ok = None

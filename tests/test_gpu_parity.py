@@ -2502,7 +2502,7 @@ def test_bench_collectives_through_rccl_on_one_gpu(gpu):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "NAVSIM_BENCH_BACKEND", "NAVSIM_BENCH_ONE_GPU", "MASTER_PORT"):
         env.pop(k, None)                                   # (MASTER_PORT: bench.py takes a free one)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--envs", "512", "--steps", "6", "--warmup", "2", "--repeats", "1",
-                        "--no-cpu-baseline", "--no-extras"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                        "--no-cpu-baseline", "--no-extras", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=900)
     ready = "navsim-bench: process group ready" in r.stderr
     if r.returncode != 0 and not ready and any(k in r.stderr for k in ("ncclSystemError", "ncclUnhandledCudaError", "ncclInternalError",
@@ -2532,7 +2532,7 @@ def test_bench_two_ranks_on_one_gpu(gpu):
     env = dict(os.environ, NAVSIM_BENCH_ONE_GPU="1", NAVSIM_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--envs", "256", "--steps", "6", "--scaling", "weak",
-                        "--warmup", "2", "--repeats", "1", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE,
+                        "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--full"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -2549,10 +2549,10 @@ def test_bench_two_ranks_on_one_gpu(gpu):
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["scaling"] == "strong" and out["config"]["envs_total"] == 301 and out["config"]["envs_per_gpu"] == 151
     assert abs(out["value"] - 301 * 6 / (out["ms_per_step"] * 6e-3)) < 1e-6 * out["value"]
-    # the default with N > 1: BOTH curves from one invocation -- value (= value_strong) on the fixed total, value_weak on
+    # the default scaling with N > 1 and --full: BOTH curves from one invocation -- value (= value_strong) on the fixed total, value_weak on
     # the per-GPU count, each with its own envs_total (round-3 verdict)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--total-envs", "600", "--envs", "256",
-                        "--steps", "6", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline"], env=env,
+                        "--steps", "6", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--full"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -2563,7 +2563,7 @@ def test_bench_two_ranks_on_one_gpu(gpu):
     # key the N > 1 line is read by, with the defaults the driver uses (no --envs / --total-envs: c2's 4096 strong, 4096 per
     # GPU weak); sizes kept small through --steps only.
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "1",
-                        "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
+                        "--no-cpu-baseline", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -2589,7 +2589,7 @@ def test_bench_line_contract(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ); env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--envs", "1024", "--cpu-seconds", "1"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        "--envs", "1024", "--cpu-seconds", "1", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -2633,9 +2633,9 @@ def test_kernel_arguments_read_in_place(gpu):
 
 
 def test_bench_c1_window(gpu):
-    """BASELINE.json configs[0] (1 arena, 64 beams, 100 x 100, no pedestrians) in the bench's default line: `other_workloads.c1`
+    """BASELINE.json configs[0] (1 arena, 64 beams, 100 x 100, no pedestrians) in the bench's --full line: `other_workloads.c1`
     with the GPU's microseconds per step (wall clock, device, kernel alone) and the oracle's on one CPU thread (round-5 review,
-    item 5).  The default line's extras run at the configured size only; `--only-windows c1` prints that one window."""
+    item 5).  The --full line's extras run at the configured size only; `--only-windows c1` prints that one window."""
     import json
     import subprocess
     import sys

@@ -415,11 +415,11 @@ def test_bench_strong_scaling_splits_the_configured_totals():
 
 
 def test_bench_default_with_several_gpus_reports_both_curves():
-    """Round-3 verdict: BASELINE.json's metric reads "4096 envs ..., 1/2/4/8 MI355X" -- a FIXED total.  With N > 1 the default
+    """Round-3 verdict: BASELINE.json's metric reads "4096 envs ..., 1/2/4/8 MI355X" -- a FIXED total.  With N > 1 a --full
     invocation therefore measures both curves: `value` (and value_strong) on the strong split of the 4096 arenas, value_weak
     on 4096 arenas PER GPU, each with its own envs_total.  (Dry run: the keys and the shards; values are null.)"""
     import json
-    r = _bench(["--gpus", "2", "--dry-run"], NAVSIM_BENCH_BACKEND="gloo")
+    r = _bench(["--gpus", "2", "--dry-run", "--full"], NAVSIM_BENCH_BACKEND="gloo")
     assert r.returncode == 0, r.stderr
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["scaling"] == "strong" and out["envs_total"] == 4096 and out["shards"] == [[0, 2048], [2048, 2048]]
