@@ -89,7 +89,7 @@ __device__ __forceinline__ void ped_scan_core(const navsim_config& c, const navs
         lanemask_t active = mask_of(true), hit = 0;
         while (active != 0)
             probe_round<Field, RULE, RECT>(field, rects, tpr, x0, y0, dx, dy, (unsigned)W, (unsigned)H, max_range, t, active, hit);
-        rng[k] = ray_result<RULE>(hit, x0, y0, dx, dy, t, max_range) * res;
+        rng[k] = ray_result<RULE>(hit, int_range_ok(H, W), i0_s, j0_s, x0, y0, dx, dy, t, max_range) * res;
     }
     __syncthreads();
     merge_prims_culled_core<BLOCK>(PB, lx_s, ly_s, (float)step, nseg_s, 0, pr, dir, rng);
@@ -298,6 +298,25 @@ __global__ void math_kernel(int fn, const double* x, const double* x2, double* o
             const bool fast = beam_dir_fast(lin, lth, ct, st, cT, sT, heading, dx, dy);
             nv::beam_dir(heading, rx, ry);
             out[i] = !fast ? 1.0 : ((__float_as_uint(dx) == __float_as_uint(rx) && __float_as_uint(dy) == __float_as_uint(ry)) ? 0.0 : 2.0);
+            break;
+        }
+        case 15: {
+            // the scan's integer hit range (kernels_step.hpp ray_result) against the float32 sqrtf form it replaced, for the
+            // offset (ix, iy) = (i % 2895 - 1447, i / 2895 - 1447) of a hit cell from the origin: every offset a map of at most
+            // kIntRangeMaxSide cells a side can produce.  out = 0 when bit-identical, else 1
+            const int ix = i % 2895 - 1447, iy = i / 2895 - 1447;
+            const float xd = (float)ix, yd = (float)iy;
+            out[i] = (__float_as_uint(hit_range_int(ix, iy)) == __float_as_uint(sqrtf(xd * xd + yd * yd))) ? 0.0 : 1.0;
+            break;
+        }
+        case 16: {
+            // gauss_noise's two float32 pieces against the forms they replaced (navsim_device.hpp), for m = i in [0, 2^24):
+            // logf of u1 = (m + 1) 2^-24 by nv::log_normal against the compiler's __logf, and the angle m * (6.28318530718f * 2^-24)
+            // against 6.28318530718f * (m * 2^-24).  out = 0 when both are bit-identical, else 1
+            const float u1 = ((float)(unsigned)i + 1.0f) * (1.0f / 16777216.0f), u2 = (float)(unsigned)i * (1.0f / 16777216.0f);
+            const bool log_eq = __float_as_uint(nv::log_normal(u1)) == __float_as_uint(__logf(u1));
+            const bool ang_eq = __float_as_uint((float)(unsigned)i * (6.28318530718f / 16777216.0f)) == __float_as_uint(6.28318530718f * u2);
+            out[i] = (log_eq && ang_eq) ? 0.0 : 1.0;
             break;
         }
         case 14: {

@@ -409,12 +409,30 @@ __device__ __forceinline__ void probe_round(const Field& field, const char* __re
     active = go & mask_flt(tn, max_range);
 }
 
-// raw range (cells) of a finished ray: the hit cell recomputed from the t of the hit probe
+// raw range (cells) of a finished ray: the hit cell recomputed from the t of the hit probe, its distance from the integer
+// origin (i0, j0) = (x0, y0).  A hit cell lies in the map, so on maps of at most kIntRangeMaxSide cells a side its offset
+// (ix, iy) from the origin has ix^2 + iy^2 <= 2 * 1447^2 < 2^22: the float32 sum of squares sqrtf was given is that exact
+// integer, and nv::sqrt_small_int is IEEE sqrtf on every integer below 2^22 (tests/test_gpu_parity.py, exhaustively).  Two
+// 24-bit integer multiplies and one conversion form it, and the square root is 5 instructions plus the zero select where
+// the compiler's sqrtf took 16 (denormal rescaling, two fma corrections): the same value in 12 vector instructions instead
+// of 23 per finished group of rays.  Larger maps (int_range false, a wave-uniform branch) keep the float32 form and sqrtf.
+constexpr int kIntRangeMaxSide = 1448;
+__host__ __device__ __forceinline__ bool int_range_ok(int H, int W) { return H <= kIntRangeMaxSide && W <= kIntRangeMaxSide; }
+__device__ __forceinline__ float hit_range_int(int ix, int iy) {
+    return nv::sqrt_small_int((float)(__mul24(ix, ix) + __mul24(iy, iy)));
+}
 template <int RULE>
-__device__ __forceinline__ float ray_result(lanemask_t hit, float x0, float y0, float dx, float dy, float t, float miss) {
-    const float xd = (float)(int)march_pos<RULE>(x0, dx, t) - x0;
-    const float yd = (float)(int)march_pos<RULE>(y0, dy, t) - y0;
-    return mask_sel(hit, sqrtf(xd * xd + yd * yd), miss);
+__device__ __forceinline__ float ray_result(lanemask_t hit, bool int_range, int i0, int j0, float x0, float y0, float dx, float dy,
+                                            float t, float miss) {
+    const int px = (int)march_pos<RULE>(x0, dx, t), py = (int)march_pos<RULE>(y0, dy, t);
+    float r;
+    if (int_range) {
+        r = hit_range_int(px - i0, py - j0);
+    } else {
+        const float xd = (float)px - x0, yd = (float)py - y0;
+        r = sqrtf(xd * xd + yd * yd);
+    }
+    return mask_sel(hit, r, miss);
 }
 
 // Parking.  A wavefront's 64 adjacent beams need 7.9 probes on average and 13.5 for the slowest (c2): the last
@@ -476,7 +494,9 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
     const float res = (float)c.resolution;
     const float rmax = (float)c.range_max;
     const double step = nv::linspace_step(c);
-    const float x0 = (float)sh.i0, y0 = (float)sh.j0;
+    const int i0 = sh.i0, j0 = sh.j0;
+    const float x0 = (float)i0, y0 = (float)j0;
+    const bool int_range = int_range_ok(H, W);
     const float lx = sh.lx, ly = sh.ly;
     const int nseg = sh.nseg, ndisc = sh.ndisc;
     const unsigned uW = (unsigned)W, uH = (unsigned)H;
@@ -531,7 +551,7 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
         if constexpr (!kPark) {
             while (active != 0)
                 probe_round<Field, RULE, RECT>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
-            if (valid) finish(k, dx, dy, ray_result<RULE>(hit, x0, y0, dx, dy, t, miss));
+            if (valid) finish(k, dx, dy, ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, miss));
         } else {
             while ((int)__builtin_popcountll(active) > park_lanes)
                 probe_round<Field, RULE, RECT>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
@@ -550,7 +570,7 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
                     }
                 }
             }
-            if (valid & !marching) finish(k, dx, dy, ray_result<RULE>(hit, x0, y0, dx, dy, t, miss));
+            if (valid & !marching) finish(k, dx, dy, ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, miss));
         }
     }
     // the parked rays, 64 at a time
@@ -579,7 +599,7 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
         lanemask_t hit = 0;
         while (active != 0)
             probe_round<Field, RULE, RECT>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
-        if (valid) finish(k, dx, dy, ray_result<RULE>(hit, x0, y0, dx, dy, t, miss));
+        if (valid) finish(k, dx, dy, ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, miss));
     }
     if (TO_LDS) {
         __syncthreads();

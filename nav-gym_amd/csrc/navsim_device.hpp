@@ -227,6 +227,19 @@ __device__ __forceinline__ double discomfort_ratio(double s, float thr, float dt
     return (s - (double)thr) / (double)den;
 }
 
+// logf(x) for a NORMAL float32 x > 0, bit for bit what the compiler emits for __logf / logf on gfx950: v_log_f32 (log2),
+// then the product with ln 2 carried in two pieces (ln2_hi * y rounded, its rounding error by an fma, ln2_lo * y by a
+// second fma).  The compiler's expansion adds a rescaling of denormal inputs (compare, select, v_ldexp, and the matching
+// subtraction of 32 ln 2) and a select that passes +-inf through: neither can change a normal input's result, and they
+// were seven of the noise's vector instructions.  tests/test_step_exactness.py compares both on every u1 of gauss_noise.
+__device__ __forceinline__ float log_normal(float x) {
+    const float ln2_hi = __uint_as_float(0x3F317217u), ln2_lo = __uint_as_float(0x3377D1CFu);
+    const float y = __builtin_amdgcn_logf(x);
+    const float r = y * ln2_hi;
+    const float e = __builtin_fmaf(y, ln2_lo, __builtin_fmaf(y, ln2_hi, -r));
+    return r + e;
+}
+
 // Gaussian scan noise (env.py:437-440).  Counter-based -- keyed by (seed, global arena, episode / step / scan, beam)
 // -- so results do not depend on the launch geometry; not bit-comparable with numpy's global Mersenne stream
 // (tested statistically).  noise_stream() is the per-scan part of the key, evaluated once per thread.
@@ -240,9 +253,11 @@ __device__ __forceinline__ float gauss_noise(uint64_t stream, uint32_t beam) {
     a ^= a >> 16; a *= 0x7FEB352Du; a ^= a >> 15; a *= 0x846CA68Bu; a ^= a >> 16;
     uint32_t b = (uint32_t)(stream >> 32) ^ a;
     b ^= b >> 16; b *= 0x7FEB352Du; b ^= b >> 15;
-    float u1 = ((float)(a >> 8) + 1.0f) * (1.0f / 16777216.0f);              // (0, 1]
-    float u2 = (float)(b >> 8) * (1.0f / 16777216.0f);
-    return __builtin_amdgcn_sqrtf(-2.0f * __logf(u1)) * __cosf(6.28318530718f * u2);   // noise: 1-ulp sqrt is plenty
+    float u1 = ((float)(a >> 8) + 1.0f) * (1.0f / 16777216.0f);              // [2^-24, 1]: always a normal number
+    // 6.28318530718f * u2 with u2 = (b >> 8) * 2^-24: scaling by a power of two is exact here (no underflow), so the two
+    // products are ONE product with the constant 6.28318530718f * 2^-24 -- the same float32 value, one multiply fewer
+    float a2 = (float)(b >> 8) * (6.28318530718f / 16777216.0f);
+    return __builtin_amdgcn_sqrtf(-2.0f * log_normal(u1)) * __cosf(a2);   // noise: 1-ulp sqrt is plenty
 }
 
 }  // namespace nv
