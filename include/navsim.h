@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NAVSIM_ABI_VERSION 6
+#define NAVSIM_ABI_VERSION 7
 
 /* error codes */
 #define NAVSIM_OK            0
@@ -226,6 +226,18 @@ typedef struct navsim_config {
                                          with a pipeline) and still be installed deterministically -- a world staged when an
                                          arena restarts is guaranteed complete regen_min_steps steps later.  0 (default): every
                                          finished arena is eligible.  Needs st->done_steps. */
+    /* ---- ABI 7 ---- */
+    int32_t max_episode_steps;        /* T > 0: time limit (old gym's TimeLimit, per arena).  An arena whose step count after
+                                         this step's increment (navsim_state.steps) reaches T and which neither succeeded nor
+                                         crashed in this step is TRUNCATED: io->done = 1, io->truncated = 1; reward, is_success
+                                         (0), is_crash (0) and distance are the step's own.  Success or crash at step T wins
+                                         (done 1, truncated 0).  A truncated arena is then every other finished arena: cfg.auto_reset
+                                         restarts it (SAME_STEP: io->final_obs, done_steps = T; NEXT_STEP: the next call's
+                                         io->reset_mask), navsim_regen / the staged worlds key on its done flag.  Under
+                                         NAVSIM_AUTORESET_NONE an arena stepped past T stays truncated.  Reset-only launches and
+                                         the resets of io->reset_mask are not steps.  0 (default): no limit, the outputs of ABI 6
+                                         bit for bit.  (Sits in the structure's tail padding: sizeof(navsim_config) is unchanged.)
+                                         The CPU oracle (oracle/) ignores the field. */
 } navsim_config;
 
 /* navsim_config.auto_reset.  The reference's step() returns the LAST observation of an episode together with done = True
@@ -416,6 +428,11 @@ typedef struct navsim_step_io {
     /* [E] uint8 or NULL: arenas to RESET instead of stepping (NAVSIM_AUTORESET_NEXT_STEP: the done flags of the previous
      * call; their state was restarted when they finished).  Must not alias io->done. */
     const uint8_t* reset_mask;
+    /* ---- ABI 7 ---- */
+    /* [E] uint8 or NULL: 1 = the arena's episode was cut by cfg.max_episode_steps in this call (done is 1 as well), 0 for every
+     * other arena the call steps; NEXT_STEP resets (io->reset_mask) write 0 beside their zeroed done.  Written only when
+     * cfg.max_episode_steps > 0; untouched otherwise.  The CPU oracle (oracle/) never writes it. */
+    uint8_t* truncated;
 } navsim_step_io;
 
 /* ---- library ---------------------------------------------------------------------------- */

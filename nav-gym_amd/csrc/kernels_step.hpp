@@ -1158,6 +1158,7 @@ __device__ __forceinline__ void install_arena(const navsim_config& c, const navs
 // register allocation in the probe loop the few extra live values of these paths disturb: measured on c2, same box, the one
 // kernel with everything in it 42.3 M env-steps/s against 43.0 M, and 41.1-41.5 M for two semantically equal formulations of the
 // new paths (profiles/r06_abi6/: the probe loop has the same 60 instructions in all of them and other registers).
+// The time limit (cfg.max_episode_steps, ABI 7) is compiled into the FEAT form only, for the same reason.
 template <int BLOCK, bool PEDS, typename Field, int RULE, int RECT, bool PINL, bool INSTALL = false, bool FEAT = true>
 __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_state& st, const navsim_step_io& io, const int e,
                                            int reset_only, const int peds_done, const uint8_t* __restrict__ reset_mask,
@@ -1219,6 +1220,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
         reset_only = 1;
         if (tid == 0) {
             io.reward[e] = 0.0; io.done[e] = 0; io.is_success[e] = 0.0f; io.is_crash[e] = 0.0f; io.distance[e] = 0.0;
+            if (c.max_episode_steps > 0 && io.truncated) io.truncated[e] = 0;
             if (st.ped_due) st.ped_due[e] = 0ull;
         }
         // cfg.defer_reset_scan: the navsim_regen that follows (io->done = the same mask) writes the row
@@ -1495,6 +1497,15 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
             double vel[2] = {pa_g[0], pa_g[1]};                 // env.py:453: the PREVIOUS action
             double goal[2] = {goal_g[0], goal_g[1]};
             nv::RewardOut o = nv::reward_scalar(c, prev_xy, pose, vel, goal, crash != 0, discomfort != 0, rmin);
+            if constexpr (kFeat) {
+                // cfg.max_episode_steps (ABI 7): an episode that reaches T steps without success or crash is truncated -- its
+                // done flag is set like any other, so every restart / new-world path below and behind the step takes it
+                if (c.max_episode_steps > 0) {
+                    const bool trunc = !o.done && sh.steps_now >= c.max_episode_steps;
+                    if (io.truncated) io.truncated[e] = (uint8_t)trunc;
+                    if (trunc) o.done = 1;
+                }
+            }
             io.reward[e] = o.reward;
             io.done[e] = (uint8_t)o.done;
             if constexpr (INSTALL) { if (in->late) in->late[e] = 0; if (in->late_next) in->late_next[e] = 0; }

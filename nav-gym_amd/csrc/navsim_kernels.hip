@@ -439,7 +439,7 @@ static int check_step_args(const navsim_config* c, const navsim_state* st, const
         if (io->reset_mask == io->done) return NAVSIM_E_ARG;                       // the launch reads one and writes the other
         if (c->ped_model != NAVSIM_PED_NONE && ped_split_on(c)) return NAVSIM_E_UNSUPPORTED;   // ped_update_kernel advances every arena
     }
-    if (c->regen_min_steps < 0) return NAVSIM_E_ARG;
+    if (c->regen_min_steps < 0 || c->max_episode_steps < 0) return NAVSIM_E_ARG;
     if (st->map_slot && c->shared_field) return NAVSIM_E_ARG;              // one map for all arenas has no slots to choose from
     if (c->ped_model != NAVSIM_PED_NONE && (c->max_waypoints < 1 || c->max_waypoints > NAVSIM_MAX_WAYPOINTS)) return NAVSIM_E_ARG;
     if (st->rect_table && (c->field_format != NAVSIM_FIELD_U16T || c->map_h > 1024 || c->map_w > 1024)) return NAVSIM_E_UNSUPPORTED;
@@ -776,7 +776,7 @@ int navsim_regen(const navsim_config* c, const navsim_state* st, const navsim_st
     navsim_step_io io2 = *io;
     io2.obs_prev = io->obs;
     io2.reset_mask = nullptr;                                // (a reset-only launch: its mask is the kernel's own argument)
-    io2.final_obs = nullptr; io2.final_goals = nullptr;
+    io2.final_obs = nullptr; io2.final_goals = nullptr; io2.truncated = nullptr;
     navsim_state st2 = *st;
     st2.arena_cost = nullptr;
     if (c->defer_reset_scan) {

@@ -68,8 +68,10 @@ int launch_step_pinl(const navsim_config* c, const navsim_state* st, const navsi
     if (reset_only & 16) return NAVSIM_E_UNSUPPORTED;
     if constexpr (!PEDS) {
         // the plain form (kernels_step.hpp step_arena FEAT = false: no terminal observation, no next-step reset compiled in) for
-        // the calls that use neither -- round 5's code, and what the c2 / c4 bench lines run
-        const bool feat = io->final_obs || io->reset_mask || c->auto_reset == NAVSIM_AUTORESET_NEXT_STEP;
+        // the calls that use neither -- round 5's code, and what the c2 / c4 bench lines run.  A step under a time limit
+        // (cfg.max_episode_steps) takes the featured form too; reset-only launches count no steps and need none of it.
+        const bool feat = io->final_obs || io->reset_mask || c->auto_reset == NAVSIM_AUTORESET_NEXT_STEP ||
+                          (c->max_episode_steps > 0 && !(reset_only & 1));
         if (!feat) {
             if (allow_lds((const void*)navsim_step_kernel<BLOCK, PEDS, Field, RULE, RECT, PINL, false>, p.lds) != NAVSIM_OK) return NAVSIM_E_UNSUPPORTED;
             if (g_prepare_only) return NAVSIM_OK;

@@ -6,7 +6,7 @@ Field order and types must match include/navsim.h exactly; tests/test_abi.py com
 """
 import ctypes as C
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 OK = 0
 E_ARG = -1
@@ -134,6 +134,7 @@ class NavsimConfig(C.Structure):
         ("closed_maps", C.c_int32),
         ("defer_reset_scan", C.c_int32),
         ("regen_min_steps", C.c_int32),
+        ("max_episode_steps", C.c_int32),      # ABI 7 (in the tail padding: the size stays 624 bytes)
     ]
 
     def copy(self):
@@ -200,6 +201,7 @@ class NavsimStepIO(C.Structure):
         "action", "obs_prev", "obs", "achieved_goal", "desired_goal",
         "reward", "done", "is_success", "is_crash", "distance",
         "final_obs", "final_goals", "reset_mask",          # ABI 6
+        "truncated",                                       # ABI 7
     )]
 
 
@@ -263,6 +265,13 @@ IO_LAYOUT = {
 FINAL_LAYOUT = {
     "final_obs": ("float32", ("E", "D")),
     "final_goals": ("float32", ("E", 4)),           # achieved_goal (2), desired_goal (2) of that observation
+}
+
+
+# ABI 7: the arenas whose episode cfg.max_episode_steps cut in the step.  Allocated (and wired into io.truncated) only for a
+# state made with a limit, so that what a step returns without one keeps its ABI-6 keys; the oracle has no limit and no such array
+LIMIT_LAYOUT = {
+    "truncated": ("uint8", ("E",)),
 }
 
 

@@ -53,6 +53,13 @@ and default to the reference's behaviour for num_envs == 1:
                     reference, and the arena is reset by the NEXT step() -- its action is ignored, reward 0, done False, the
                     observation is the new episode's first one, info['reset_mask'] marks it.  final_observation=False drops
                     the terminal rows of 'same_step' (and their second scan after a crash).
+    max_episode_steps  time limit T (old gym's TimeLimit, per arena, decided inside the fused step): an episode that reaches
+                    T steps without success or crash ends with done = True and info['TimeLimit.truncated'] = True (reward
+                    and the other info keys are the step's own; success or crash at step T wins, truncated False).  It then
+                    restarts like any finished arena under auto_reset -- same_step: info['final_observation'] holds its
+                    terminal row; next_step: the next step() resets it (info['reset_mask']).  Without auto_reset an arena
+                    stepped past T stays truncated until reset().  info['TimeLimit.truncated'] is a bool (num_envs == 1)
+                    or a torch.bool [num_envs] view; None (default): no limit, the reference's behaviour and no such key.
     reset(mask)     reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
                     [num_envs]; the others keep their state and their rows.  Not with the pipelined reset path.
 
@@ -71,6 +78,7 @@ Pickling (env.py:30, 56-78: the reference is an EzPickle): `pickle.dumps(env)` s
 arguments; the copy is a fresh environment that has not been reset().  `state_dict()` / `load_state_dict()` move the
 simulation state itself.  When `gym` is importable the class is a gym.Env (`unwrapped`, `spec`, `reward_range`).
 """
+import numbers
 import warnings
 
 import numpy as np
@@ -187,7 +195,7 @@ class NavGymEnv(_EnvBase):
                  field_format=abi.FIELD_U16T, n_spawn=None, randomize_maps=False, plan_paths=True,
                  action_kind="twist", clip_actions=False, max_waypoints=64, march_rule=None, use_graphs=None,
                  regen_min_steps=0, pregen_pipeline=None, pregen_stage_cap=None, autoreset_mode="same_step",
-                 final_observation=True, pregen_fallback_poll=None):
+                 final_observation=True, pregen_fallback_poll=None, max_episode_steps=None):
         from . import lib
         if robot_type not in robots.ROBOTS:
             raise NotImplementedError(robot_type)            # env.py:772-773
@@ -206,7 +214,8 @@ class NavGymEnv(_EnvBase):
             randomize_maps=randomize_maps, plan_paths=plan_paths, action_kind=action_kind, clip_actions=clip_actions,
             max_waypoints=max_waypoints, march_rule=march_rule, use_graphs=use_graphs,
             regen_min_steps=regen_min_steps, pregen_pipeline=pregen_pipeline, pregen_stage_cap=pregen_stage_cap,
-            autoreset_mode=autoreset_mode, final_observation=final_observation, pregen_fallback_poll=pregen_fallback_poll)
+            autoreset_mode=autoreset_mode, final_observation=final_observation, pregen_fallback_poll=pregen_fallback_poll,
+            max_episode_steps=max_episode_steps)
         self.robot_type = robot_type
         self.time_step = time_step
         self.min_turning_radius = min_turning_radius
@@ -235,6 +244,10 @@ class NavGymEnv(_EnvBase):
         if autoreset_mode not in ("same_step", "next_step"):
             raise ValueError("autoreset_mode must be 'same_step' or 'next_step'")
         self.autoreset_mode = autoreset_mode
+        if max_episode_steps is not None and not (isinstance(max_episode_steps, numbers.Integral) and
+                                                  not isinstance(max_episode_steps, bool) and max_episode_steps > 0):
+            raise ValueError("max_episode_steps must be None or a positive int, not %r" % (max_episode_steps,))
+        self.max_episode_steps = None if max_episode_steps is None else int(max_episode_steps)
         self.final_observation = bool(final_observation) and self.auto_reset and autoreset_mode == "same_step"
         self._num_humans_fixed = num_humans
         self._episode_batch = 0
@@ -330,6 +343,7 @@ class NavGymEnv(_EnvBase):
         # launch is one generation of workgroups -- a few arenas per CU
         cfg.defer_reset_scan = int(self.randomize_maps and self.auto_reset and self.num_envs <= 1024)
         cfg.regen_min_steps = self.regen_min_steps if (self.randomize_maps and self.auto_reset) else 0
+        cfg.max_episode_steps = self.max_episode_steps or 0     # (0: no limit -- the step's plain form where it has one)
         if self.pregen_pipeline:
             cfg.defer_reset_scan = 0              # a staged world brings its first observation; restarts in place scan in the step
             cfg.regen_cap = self.num_envs         # every finished arena decides alone inside the step (navsim_step_install)
@@ -595,6 +609,8 @@ class NavGymEnv(_EnvBase):
                                              "achieved_goal": g[:2], "desired_goal": g[2:]}
             if self.auto_reset and self.autoreset_mode == "next_step":
                 info["reset_mask"] = bool(self.sim.reset_flags[0].item())
+            if self.max_episode_steps is not None:
+                info["TimeLimit.truncated"] = bool(out["truncated"][0].item())
             return obs, float(out["reward"][0].item()), done, info
         # (views of the buffers the kernel wrote, made ONCE per buffer parity: a step of 4096 arenas is 95 us on the device, and
         #  every tensor slice or .view() costs the host 3-5 us -- round 6 measured 42 -> 36 M env-steps/s through this method
@@ -607,6 +623,8 @@ class NavGymEnv(_EnvBase):
                               "desired_goal": fin["final_goals"][:, 2:]}
             if self.auto_reset and self.autoreset_mode == "next_step":
                 v["reset"] = self.sim.reset_flags.view(self._bool)
+            if self.max_episode_steps is not None:
+                v["truncated"] = out["truncated"].view(self._bool)
             self._views[self.sim.cur] = v
         info = {"is_success": out["is_success"], "is_crash": out["is_crash"], "distance": out["distance"]}
         done = v["done"]
@@ -615,6 +633,8 @@ class NavGymEnv(_EnvBase):
             info["final_mask"] = done
         if "reset" in v:
             info["reset_mask"] = v["reset"]
+        if "truncated" in v:
+            info["TimeLimit.truncated"] = v["truncated"]
         return obs, out["reward"], done, info
 
     def counters(self, reset=True):
@@ -648,12 +668,15 @@ class NavGymEnv(_EnvBase):
         return self._rd(obs)["reward"].cpu().numpy()
 
     def compute_terminals(self, obs):
+        """Success or crash of each observation (env.py:491-512).  Terminal only: the time limit (max_episode_steps) is not a
+        function of the observation and is not part of it -- step() reports it as info['TimeLimit.truncated']."""
         return self._rd(obs)["done"].cpu().numpy().astype(bool)
 
     def compute_reward(self, action, obs, make_render_reward_txt=False):
         return self.compute_rewards(np.asarray(action)[None], {k: np.asarray(v)[None] for k, v in obs.items()})[0]
 
     def compute_done(self, obs):
+        """compute_terminals of one observation: success or crash, never the time limit."""
         return self.compute_terminals({k: np.asarray(v)[None] for k, v in obs.items()})[0]
 
     def compute_info(self, obs):

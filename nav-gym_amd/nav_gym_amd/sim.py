@@ -482,6 +482,12 @@ class NavSim(object):
         # env handed out views of single buffers that the next step overwrote -- `obs = next_obs`, `dones.append(done)`)
         self.out_buf = [{k: torch.zeros(abi.resolve_shape(s, self.cfg), dtype=_dtype(d), device=self.device)
                          for k, (d, s) in abi.IO_LAYOUT.items() if k not in ("obs", "obs_prev", "action")} for _ in range(2)]
+        # ABI 7: with a time limit (cfg.max_episode_steps > 0 when the simulator is made) the step also returns `truncated`,
+        # flipped with the other outputs; without one io.truncated stays NULL and the outputs keep their ABI-6 keys
+        if self.cfg.max_episode_steps > 0:
+            for b in self.out_buf:
+                b.update({k: torch.zeros(abi.resolve_shape(s, self.cfg), dtype=_dtype(d), device=self.device)
+                          for k, (d, s) in abi.LIMIT_LAYOUT.items()})
         self.action = torch.zeros((E, 2), dtype=torch.float64, device=self.device)
         self.io = abi.NavsimStepIO()
         self.io.action = self.action.data_ptr()
@@ -500,7 +506,8 @@ class NavSim(object):
 
     @property
     def out(self):
-        """reward / done / is_success / is_crash / distance / achieved_goal / desired_goal of the latest step."""
+        """reward / done / is_success / is_crash / distance / achieved_goal / desired_goal of the latest step; with a time limit
+        (cfg.max_episode_steps > 0 when the simulator was made) also truncated: the arenas whose episode the limit cut."""
         return self.out_buf[self.cur]
 
     @property
@@ -543,11 +550,13 @@ class NavSim(object):
         if mask is not None:
             import torch
             m = torch.as_tensor(mask).to(device=self.device, dtype=torch.uint8).contiguous()
-        # an arena that is reset is not finished: its done flag (NEXT_STEP: the next launch's reset mask) is cleared
-        if m is None:
-            self.out_buf[1 - self.cur]["done"].zero_()
-        else:
-            self.out_buf[1 - self.cur]["done"].mul_(m == 0)
+        # an arena that is reset is not finished: its done flag (NEXT_STEP: the next launch's reset mask) is cleared, and with
+        # it the time limit's truncated flag
+        for k in [k for k in ("done", "truncated") if k in self.out_buf[0]]:
+            if m is None:
+                self.out_buf[1 - self.cur][k].zero_()
+            else:
+                self.out_buf[1 - self.cur][k].mul_(m == 0)
         self._flip()
         check(self.lib.navsim_reset_obs(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), _ptr(m), _stream()),
               "navsim_reset_obs")
@@ -1094,6 +1103,8 @@ class NavSim(object):
                   "navsim_regen (reset of all arenas)")
         for b in self.out_buf:                             # nobody is finished after a reset (NEXT_STEP: the next launch's reset mask)
             b["done"].zero_()
+            if "truncated" in b:
+                b["truncated"].zero_()
         torch.cuda.current_stream().synchronize()          # `ws` and `done` are released on return
         return self.obs
 
