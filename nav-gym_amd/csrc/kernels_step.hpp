@@ -1724,8 +1724,13 @@ struct StepInstallKernargs { navsim_config c; navsim_state st; navsim_step_io io
 #else
 #define NAVSIM_KERNARGS(View, ...) const View ka = {__VA_ARGS__}
 #endif
-// The fused step.  One workgroup = one arena (template arguments: step_arena).  reset_only: bit 0 = a reset-only launch, bit 1 =
-// ped_update_kernel has advanced the pedestrians, bits 2-3 = the NAVSIM_STEP_* part of navsim_step_part.
+// The `int reset_only` of navsim_step_kernel and navsim_step_install_kernel, built from a StepLaunch in ONE place (step_plan.hpp
+// step_kernel_word): bit 0 = a reset-only launch, bit 1 = ped_update_kernel has advanced the pedestrians, bits 2-3 = the part --
+// NAVSIM_STEP_ALL / NOT_DUE / DUE of navsim_step_part, or kStepPartReplan for navsim_step_replan (the host picks that form's and
+// NAVSIM_STEP_DUE's own kernels below; this one only acts on NAVSIM_STEP_NOT_DUE).
+constexpr int kStepWordResetOnly = 1, kStepWordPedsDoneBit = 1, kStepWordPartShift = 2, kStepWordPartMask = 3;
+constexpr int kStepPartReplan = 3;
+// The fused step.  One workgroup = one arena (template arguments: step_arena).
 template <int BLOCK, bool PEDS, typename Field, int RULE, int RECT, bool PINL, bool FEAT = true>
 // Wavefronts per SIMD the kernel is compiled for = its register budget.  The 256-thread pedestrian variants with the index
 // rows in LDS are resident at FIVE workgroups per CU (plan_step: 30 KB of LDS each) -- five wavefronts per SIMD, 96 registers
@@ -1744,9 +1749,9 @@ void navsim_step_kernel(navsim_config c_, navsim_state st_,
                                                             unsigned dyn_lds_bytes, int park_lanes, unsigned rect_lds_offset) {
     NAVSIM_KERNARGS(StepKernargs, c_, st_, io_);
     const navsim_config& c = ka.c; const navsim_state& st = ka.st; const navsim_step_io& io = ka.io;
-    const int peds_done = (reset_only >> 1) & 1;
-    const int part = (reset_only >> 2) & 3;
-    reset_only &= 1;
+    const int peds_done = (reset_only >> kStepWordPedsDoneBit) & 1;
+    const int part = (reset_only >> kStepWordPartShift) & kStepWordPartMask;
+    reset_only &= kStepWordResetOnly;
     // longest-first launch order (a scheduling hint: which arena a workgroup takes never changes a result)
     const int e = st.launch_order ? st.launch_order[blockIdx.x] : (int)blockIdx.x;
     if (e < 0) return;              // navsim_regen's first-observation launch: one workgroup per list slot, -1 = empty slot
@@ -1768,7 +1773,7 @@ void navsim_step_install_kernel(navsim_config c_, navsim_state st_, navsim_step_
     const navsim_config& c = ka.c; const navsim_state& st = ka.st; const navsim_step_io& io = ka.io; const StepInstall& in = ka.in;
     const int e = st.launch_order ? st.launch_order[blockIdx.x] : (int)blockIdx.x;
     if (e < 0) return;
-    step_arena<BLOCK, PEDS, Field, RULE, RECT, PEDS, true>(c, st, io, e, reset_only & 1, 0, reset_mask, dyn_lds_bytes, park_lanes, rect_lds_offset, &in);
+    step_arena<BLOCK, PEDS, Field, RULE, RECT, PEDS, true>(c, st, io, e, reset_only & kStepWordResetOnly, 0, reset_mask, dyn_lds_bytes, park_lanes, rect_lds_offset, &in);
 }
 
 // navsim_step_part, NAVSIM_STEP_DUE: the few arenas that waited for navsim_replan, as a COMPACT launch -- workgroup b steps the

@@ -19,7 +19,8 @@
 //   kernels_policy.hpp   pedestrian control block with the HumanPolicy actor
 //   kernels_pedscan.hpp  pedestrian scans, CrowdSim collision block, beam table, test hooks
 //   kernels_crowd_maps.hpp  CrowdSim local maps;  kernels_crowd_orca.hpp  CrowdSim pedestrians (ORCA, Agent.step)
-//   step_plan.hpp        launch geometry of the fused step (shared by this file and navsim_step_inst.hip)
+//   step_plan.hpp        launch geometry of the fused step and the descriptors of a launch (shared by this file and
+//                        navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off per unit (nav-gym_amd/csrc/Makefile, driven by build.sh).
 #include "preamble.hpp"
@@ -36,15 +37,15 @@ namespace {
 #include "kernels_pedscan.hpp"
 #include "kernels_crowd_maps.hpp"
 #include "kernels_crowd_orca.hpp"
-#include "step_plan.hpp"
 
 }  // namespace
+#include "step_plan.hpp"
 
 // the step kernel's instantiations live in eight units of their own (navsim_step_inst.hip): one launcher per
 // (threads per arena, pedestrians or not)
 #define NAVSIM_STEP_FAMILY(B, P) \
-    extern "C" int navsim_step_launch_##B##_##P(const navsim_config*, const navsim_state*, const navsim_step_io*, int, \
-                                                const uint8_t*, void*, int, int, int, const void*); \
+    extern "C" int navsim_step_launch_##B##_##P(const navsim_config*, const navsim_state*, const navsim_step_io*, \
+                                                const StepLaunch*, const StepPlan*); \
     extern "C" int navsim_step_set_stamps_##B##_##P(unsigned long long*);
 NAVSIM_STEP_FAMILY(64, 0) NAVSIM_STEP_FAMILY(64, 1) NAVSIM_STEP_FAMILY(256, 0) NAVSIM_STEP_FAMILY(256, 1)
 NAVSIM_STEP_FAMILY(512, 0) NAVSIM_STEP_FAMILY(512, 1) NAVSIM_STEP_FAMILY(1024, 0) NAVSIM_STEP_FAMILY(1024, 1)
@@ -71,44 +72,198 @@ __global__ void kernarg_layout_probe_kernel(navsim_config c_, navsim_state st_, 
             same(&in_, &ka.in, sizeof(in_)) && tail_view == tail && tail == 0x1234567) ? 1 : 0;
 }
 
-// navsim_prepare: walk the dispatch chain of a launch down to its kernel, set what has to be set once per kernel
-// (hipFuncSetAttribute for dynamic LDS above 64 KB) and launch nothing -- so that nothing of the kind happens inside a
-// hipGraph capture (round-3 advisor: navsim_regen's lone first-observation launch instantiates its own variant)
-thread_local bool g_prepare_only = false;
-
-// grid > 0: that many workgroups instead of one per arena; st->launch_order then names each workgroup's arena, -1 = none
-// (navsim_regen's first observations: one workgroup per regenerated arena)
-int dispatch_step(const navsim_config* c, const navsim_state* st, const navsim_step_io* io,
-                  int reset_only, const uint8_t* mask, hipStream_t s, int grid = 0, int aux = 0, const StepInstall* install = nullptr) {
-    int rc;
-    const StepPlan p = plan_step(c, st, ((reset_only >> 2) & 3) >= NAVSIM_STEP_DUE ? 0 : grid);
+// One launch of the fused step: plans it and hands it to the family's launcher (navsim_step_inst.hip).
+int dispatch_step(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, StepLaunch l) {
+    // (a NAVSIM_STEP_DUE launch and the front of the re-plan are the ordinary step on other workgroups: their grid does not change the plan)
+    const StepPlan p = plan_step(c, st, l.part == NAVSIM_STEP_DUE || l.part == kStepPartReplan ? 0 : l.grid);
     const bool peds = c->ped_model != NAVSIM_PED_NONE;
+    const bool split = peds && !l.reset_only && ped_split_on(c);               // pedestrians ahead of the step (ped_split_on)
     // a state with slot tables (navsim_state.map_slot): only the INSTALL instantiations look a map up through the table -- every
     // launch goes to them, with nothing to install unless navsim_step_install says so
     const StepInstall no_install = {};
-    if (st->map_slot && !install) {
-        if (((reset_only >> 2) & 3) != 0 || c->field_format != NAVSIM_FIELD_U16T || (peds && ped_split_on(c) && !(reset_only & 1)))
+    if (st->map_slot && !l.install) {
+        if (l.part != NAVSIM_STEP_ALL || c->field_format != NAVSIM_FIELD_U16T || split)
             return NAVSIM_E_UNSUPPORTED;                                    // navsim_step_part / navsim_step_replan, float32 fields
-        install = &no_install;
-        reset_only |= 16;
+        l.install = &no_install;
     }
-    if (peds && !(reset_only & 1) && ped_split_on(c) && !g_prepare_only) {            // pedestrians ahead of the step (ped_split_on)
+    if (split && !l.prepare_only) {
         const size_t pl = ped_update_lds_bytes(c);
         const int G = ped_pack(c->max_peds), pgrid = (c->n_envs + G - 1) / G;
-        if (c->field_format == NAVSIM_FIELD_U16T) ped_update_kernel<FieldU16T><<<pgrid, kPedUpdateBlock, pl, s>>>(*c, *st);
-        else                                      ped_update_kernel<FieldF32><<<pgrid, kPedUpdateBlock, pl, s>>>(*c, *st);
-        reset_only |= 2;
+        if (c->field_format == NAVSIM_FIELD_U16T) ped_update_kernel<FieldU16T><<<pgrid, kPedUpdateBlock, pl, l.stream>>>(*c, *st);
+        else                                      ped_update_kernel<FieldF32><<<pgrid, kPedUpdateBlock, pl, l.stream>>>(*c, *st);
+        l.peds_done = true;
     }
-    const int po = g_prepare_only ? 1 : 0;
+    int rc;
 #define NAVSIM_STEP_CASE(B) \
-    case B: rc = peds ? navsim_step_launch_##B##_1(c, st, io, reset_only, mask, (void*)s, grid, po, aux, install) \
-                      : navsim_step_launch_##B##_0(c, st, io, reset_only, mask, (void*)s, grid, po, aux, install); break;
+    case B: rc = peds ? navsim_step_launch_##B##_1(c, st, io, &l, &p) : navsim_step_launch_##B##_0(c, st, io, &l, &p); break;
     switch (p.block) {
         NAVSIM_STEP_CASE(64) NAVSIM_STEP_CASE(256) NAVSIM_STEP_CASE(512) NAVSIM_STEP_CASE(1024)
         default:   return NAVSIM_E_UNSUPPORTED;
     }
 #undef NAVSIM_STEP_CASE
     return rc != NAVSIM_OK ? rc : launch_status();
+}
+
+// workgroups of navsim_step_part's compact launch and of navsim_step_replan's front: the arenas with a waiting pedestrian are
+// few (~2 % per step on the c3 world) -- E / 16, as many as wait in an ordinary step several times over
+int compact_grid(const navsim_config* c) {
+    const int g = c->n_envs / 16 < 32 ? 32 : (c->n_envs / 16 > 1024 ? 1024 : c->n_envs / 16);
+    return g > c->n_envs ? c->n_envs : g;
+}
+
+// May navsim_replan of the previous step's flags run inside this step's launch (navsim_step_replan, navsim_step_install_replan)?
+// NAVSIM_OK, or the code the entry points refuse the call with.  navsim_prepare asks about the configuration alone
+// (strict = false: no pair of flag buffers, any costmap plan_fits accepts) and skips the form where the answer is no.
+int replan_in_step(const navsim_config* c, const navsim_state* st, bool strict) {
+    if (c->ped_model == NAVSIM_PED_NONE || !st->costmap) return NAVSIM_E_ARG;
+    if (strict && (!st->ped_due_prev || !st->ped_due || st->ped_due == st->ped_due_prev)) return NAVSIM_E_ARG;
+    if (ped_split_on(c)) return NAVSIM_E_UNSUPPORTED;                  // ped_update_kernel advances the pedestrians ahead of the launch
+    const int Hc = c->map_h / 5, Wc = c->map_w / 5;
+    if (!plan_fits(Hc, Wc) || (strict && (Hc < 1 || Wc < 1 || plan_lds(Hc, Wc) > 64 * 1024))) return NAVSIM_E_UNSUPPORTED;
+    // the search inside the step's launch owns one costmap word per thread (its registers are the step kernel's): costmaps of
+    // more words than the arena's workgroup has threads go through navsim_replan + navsim_step_part
+    return (int)plan_words(Hc, Wc) > plan_step(c, st).block ? NAVSIM_E_UNSUPPORTED : NAVSIM_OK;
+}
+
+int check_step_args(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, int reset_only) {
+    if (!c || !st || !io) return NAVSIM_E_ARG;
+    if (c->n_envs < 0 || c->n_beams < 1 || c->n_scan_stack < 1 || c->map_h < 1 || c->map_w < 1) return NAVSIM_E_ARG;
+    if (c->max_peds > NAVSIM_MAX_PEDS) return NAVSIM_E_UNSUPPORTED;
+    if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
+    if (c->march_rule < NAVSIM_MARCH_F64 || c->march_rule > NAVSIM_MARCH_F32_FMA) return NAVSIM_E_ARG;
+    if (c->action_kind != NAVSIM_ACTION_TWIST && c->action_kind != NAVSIM_ACTION_WHEELS) return NAVSIM_E_ARG;
+    if (c->action_kind == NAVSIM_ACTION_WHEELS && !(c->wheel_track > 0.0)) return NAVSIM_E_ARG;
+    if (c->defer_reset_scan != 0 && c->defer_reset_scan != 1) return NAVSIM_E_ARG;
+    if (c->auto_reset < NAVSIM_AUTORESET_NONE || c->auto_reset > NAVSIM_AUTORESET_NEXT_STEP) return NAVSIM_E_ARG;
+    if (io->final_goals && !io->final_obs) return NAVSIM_E_ARG;
+    if (io->reset_mask && !reset_only) {
+        if (io->reset_mask == io->done) return NAVSIM_E_ARG;                       // the launch reads one and writes the other
+        if (c->ped_model != NAVSIM_PED_NONE && ped_split_on(c)) return NAVSIM_E_UNSUPPORTED;   // ped_update_kernel advances every arena
+    }
+    if (c->regen_min_steps < 0 || c->max_episode_steps < 0) return NAVSIM_E_ARG;
+    if (st->map_slot && c->shared_field) return NAVSIM_E_ARG;              // one map for all arenas has no slots to choose from
+    if (c->ped_model != NAVSIM_PED_NONE && (c->max_waypoints < 1 || c->max_waypoints > NAVSIM_MAX_WAYPOINTS)) return NAVSIM_E_ARG;
+    if (st->rect_table && (c->field_format != NAVSIM_FIELD_U16T || c->map_h > 1024 || c->map_w > 1024)) return NAVSIM_E_UNSUPPORTED;
+    if (st->rect_index && !st->rect_table) return NAVSIM_E_ARG;
+    if (c->step_block != 0 && c->step_block != 64 && c->step_block != 256 && c->step_block != 512 &&
+        c->step_block != 1024) return NAVSIM_E_ARG;
+    if (c->ped_split < 0 || c->ped_split > 2 || c->rect_lds < 0 || c->rect_lds > 2) return NAVSIM_E_ARG;
+    if (c->ped_model != NAVSIM_PED_NONE && c->max_peds < 1) return NAVSIM_E_ARG;
+    if (plan_step(c, st).lds > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;   // beams x pedestrians beyond one CU's LDS
+    // navsim_regen's first observations are a launch of their own geometry (plan_step's `lone` rule): validate it here too
+    if (c->regen_cap > 0 && plan_step(c, st, c->regen_cap).lds > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;
+    if (!st->field || !st->scan_threshold || !st->scan_discomfort || !st->robot_pose || !st->robot_goal ||
+        !st->prev_action || !st->prev_pose || !st->n_hist || !st->episode || !st->steps || !io->obs)
+        return NAVSIM_E_ARG;
+    if (!reset_only && (!io->action || !io->reward || !io->done || !io->is_success || !io->is_crash ||
+                        !io->distance))
+        return NAVSIM_E_ARG;
+    if (!reset_only && c->n_scan_stack > 1 && !io->obs_prev) return NAVSIM_E_ARG;
+    if (c->ped_model != NAVSIM_PED_NONE) {
+        if (!st->n_peds || !st->ped_pose || !st->ped_vel || !st->ped_prev_yaw || !st->ped_dist ||
+            !st->ped_has_legs || !st->ped_waypoints || !st->ped_n_waypoints || !st->ped_wp_head)
+            return NAVSIM_E_ARG;
+        if (c->ped_model == NAVSIM_PED_EXTERNAL && !st->ped_cmd && !reset_only) return NAVSIM_E_ARG;
+        if (c->ped_model == NAVSIM_PED_SFM && !st->ped_v_pref) return NAVSIM_E_ARG;
+    }
+    if (c->auto_reset && c->n_spawn > 0 && (!st->spawn_pose || !st->spawn_goal)) return NAVSIM_E_ARG;
+    return NAVSIM_OK;
+}
+
+// navsim_regen_swap / navsim_step_install: the live and the staged state as a pair
+int check_stage_pair(const navsim_config* c, const navsim_state* live, const navsim_state* stage) {
+    if (c->regen_cap < 1 || c->n_spawn < 1 || !c->auto_reset) return NAVSIM_E_ARG;
+    if (c->defer_reset_scan) return NAVSIM_E_UNSUPPORTED;     // a staged world brings its own first observation; arenas beyond the cap would get none
+    if (!live->field || !stage->field || !live->episode || !stage->episode || !live->spawn_pose || !stage->spawn_pose ||
+        !live->spawn_goal || !stage->spawn_goal || !stage->robot_pose || !stage->robot_goal)
+        return NAVSIM_E_ARG;
+    // the two states must hold the same optional buffers
+    if ((live->field_overflow != nullptr) != (stage->field_overflow != nullptr) ||
+        (live->rect_table != nullptr) != (stage->rect_table != nullptr) || (live->rect_index != nullptr) != (stage->rect_index != nullptr) ||
+        (live->costmap != nullptr) != (stage->costmap != nullptr) || (live->ped_goal != nullptr) != (stage->ped_goal != nullptr))
+        return NAVSIM_E_ARG;
+    return NAVSIM_OK;
+}
+// navsim_state.map_slot: both states or neither, and then over the SAME five arrays
+int check_map_slots(const navsim_state* live, const navsim_state* stage) {
+    if ((live->map_slot != nullptr) != (stage->map_slot != nullptr)) return NAVSIM_E_ARG;
+    if (live->map_slot && (live->map_slot == stage->map_slot || live->field != stage->field || live->field_overflow != stage->field_overflow ||
+                           live->rect_table != stage->rect_table || live->rect_index != stage->rect_index || live->costmap != stage->costmap))
+        return NAVSIM_E_ARG;
+    return NAVSIM_OK;
+}
+template <typename Big>
+void stage_big_buffers(const navsim_config* c, const navsim_state* live, const navsim_state* stage, Big big[5]) {
+    const int H = c->map_h, W = c->map_w;
+    big[0] = {(char*)live->field, (const char*)stage->field, navsim_field_bytes(1, H, W, c->field_format)};
+    if (live->field_overflow) big[1] = {(char*)live->field_overflow, (const char*)stage->field_overflow, (size_t)H * W * sizeof(float)};
+    if (live->rect_table) big[2] = {(char*)live->rect_table, (const char*)stage->rect_table, navsim_rect_table_bytes(1, H, W)};
+    if (live->costmap) big[3] = {(char*)live->costmap, (const char*)stage->costmap, (size_t)(H / 5) * (W / 5)};
+    if (live->rect_index) big[4] = {(char*)live->rect_index, (const char*)stage->rect_index, rect_index_row_bytes(H, W)};
+}
+
+int step_install_impl(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, const navsim_state* stage,
+                      const float* stage_obs, uint8_t* mark, const long long* ready, uint8_t* late, uint8_t* late_next,
+                      const uint8_t* late_prev, int32_t max_queries, void* stream) {
+    (void)hipGetLastError();
+    int rc = check_step_args(c, st, io, 0);
+    if (rc != NAVSIM_OK) return rc;
+    if (!stage || !stage_obs || !mark || !ready || ((uintptr_t)mark & 3) != 0 || !st->done_steps) return NAVSIM_E_ARG;
+    // what makes the outcome independent of the staging passes' timing: the rule (cfg.regen_min_steps, with the caller's order of
+    // passes and waits) or the fallback (late: arenas whose world was not ready are generated by the caller's navsim_regen)
+    // NEXT_STEP, neither: an arena that finds nothing staged regenerates its own world inside the launch (regen_lone) -- worlds of
+    // outdoor maps without planning / costmap, at least 256 threads per arena
+    const bool lone = c->auto_reset == NAVSIM_AUTORESET_NEXT_STEP && !late && !late_next && c->regen_min_steps < 1;
+    if (lone && (c->regen_indoor_ratio > 0.0 || c->regen_plan || st->costmap || plan_step(c, st).block < 256 || c->map_h != c->map_w ||
+                 march_rule_variant(c) != NAVSIM_MARCH_F32 ||
+                 c->obstacle_number > 64 || c->obstacle_number_hi > 64))
+        return NAVSIM_E_UNSUPPORTED;
+    if (c->regen_min_steps < 1 && !late && !late_next && !lone) return NAVSIM_E_ARG;
+    rc = check_stage_pair(c, st, stage);
+    if (rc != NAVSIM_OK) return rc;
+    // every finished arena decides for itself: there is no cap to apply in index order (navsim_regen_swap has one)
+    if (c->regen_cap < c->n_envs) return NAVSIM_E_UNSUPPORTED;
+    if (c->field_format != NAVSIM_FIELD_U16T || (c->ped_model != NAVSIM_PED_NONE && ped_split_on(c))) return NAVSIM_E_UNSUPPORTED;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    rc = check_map_slots(st, stage);
+    if (rc != NAVSIM_OK) return rc;
+    StepInstall in = {};
+    in.stage = *stage; in.stage_obs = stage_obs; in.mark = mark; in.ready = ready; in.late = late;
+    in.late_next = late_next; in.late_prev = late_prev; in.lone = lone ? 1 : 0;
+    if (!st->map_slot) stage_big_buffers(c, st, stage, in.big);             // (with slot tables the maps stay where they are)
+    StepLaunch l;
+    l.install = &in;
+    l.stream = (hipStream_t)stream;
+    if (max_queries >= 0) {     // ... with navsim_replan of the previous step's flags inside the launch (navsim_step_replan's conditions)
+        rc = replan_in_step(c, st, true);
+        if (rc != NAVSIM_OK) return rc;
+        l.part = kStepPartReplan;
+        l.grid = compact_grid(c);
+        l.max_queries = max_queries;
+    }
+    return dispatch_step(c, st, io, l);
+}
+
+// navsim_regen's fork: the distance transform of the new corridor maps beside the planner's first stage (which needs the
+// occupancy grid and the costmap only).  One helper stream and two events per host thread and device, created on first use;
+// inside a hipGraph capture the helper joins the capture through the first wait and leaves it through the second.
+struct RegenFork { int device = -1; hipStream_t side = nullptr; hipEvent_t forked = nullptr, joined = nullptr; };
+thread_local hipStream_t g_regen_helper = nullptr;          // navsim_regen_helper: the caller's choice of helper stream
+RegenFork* regen_fork() {
+    thread_local RegenFork f;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    if (f.device == dev && g_regen_helper && f.side != g_regen_helper) f.side = g_regen_helper;     // (the events stay)
+    if (f.device != dev) {
+        RegenFork n;
+        if (g_regen_helper) n.side = g_regen_helper;
+        else if (hipStreamCreateWithFlags(&n.side, hipStreamNonBlocking) != hipSuccess) return nullptr;
+        if (hipEventCreateWithFlags(&n.forked, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&n.joined, hipEventDisableTiming) != hipSuccess) return nullptr;
+        n.device = dev;
+        f = n;                                               // (what an earlier device of this thread held stays allocated)
+    }
+    return &f;
 }
 
 }  // namespace
@@ -423,52 +578,6 @@ int navsim_beam_table(const navsim_config* c, double* table, void* stream) {
     return launch_status();
 }
 
-static int check_step_args(const navsim_config* c, const navsim_state* st, const navsim_step_io* io,
-                           int reset_only) {
-    if (!c || !st || !io) return NAVSIM_E_ARG;
-    if (c->n_envs < 0 || c->n_beams < 1 || c->n_scan_stack < 1 || c->map_h < 1 || c->map_w < 1) return NAVSIM_E_ARG;
-    if (c->max_peds > NAVSIM_MAX_PEDS) return NAVSIM_E_UNSUPPORTED;
-    if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
-    if (c->march_rule < NAVSIM_MARCH_F64 || c->march_rule > NAVSIM_MARCH_F32_FMA) return NAVSIM_E_ARG;
-    if (c->action_kind != NAVSIM_ACTION_TWIST && c->action_kind != NAVSIM_ACTION_WHEELS) return NAVSIM_E_ARG;
-    if (c->action_kind == NAVSIM_ACTION_WHEELS && !(c->wheel_track > 0.0)) return NAVSIM_E_ARG;
-    if (c->defer_reset_scan != 0 && c->defer_reset_scan != 1) return NAVSIM_E_ARG;
-    if (c->auto_reset < NAVSIM_AUTORESET_NONE || c->auto_reset > NAVSIM_AUTORESET_NEXT_STEP) return NAVSIM_E_ARG;
-    if (io->final_goals && !io->final_obs) return NAVSIM_E_ARG;
-    if (io->reset_mask && !reset_only) {
-        if (io->reset_mask == io->done) return NAVSIM_E_ARG;                       // the launch reads one and writes the other
-        if (c->ped_model != NAVSIM_PED_NONE && ped_split_on(c)) return NAVSIM_E_UNSUPPORTED;   // ped_update_kernel advances every arena
-    }
-    if (c->regen_min_steps < 0 || c->max_episode_steps < 0) return NAVSIM_E_ARG;
-    if (st->map_slot && c->shared_field) return NAVSIM_E_ARG;              // one map for all arenas has no slots to choose from
-    if (c->ped_model != NAVSIM_PED_NONE && (c->max_waypoints < 1 || c->max_waypoints > NAVSIM_MAX_WAYPOINTS)) return NAVSIM_E_ARG;
-    if (st->rect_table && (c->field_format != NAVSIM_FIELD_U16T || c->map_h > 1024 || c->map_w > 1024)) return NAVSIM_E_UNSUPPORTED;
-    if (st->rect_index && !st->rect_table) return NAVSIM_E_ARG;
-    if (c->step_block != 0 && c->step_block != 64 && c->step_block != 256 && c->step_block != 512 &&
-        c->step_block != 1024) return NAVSIM_E_ARG;
-    if (c->ped_split < 0 || c->ped_split > 2 || c->rect_lds < 0 || c->rect_lds > 2) return NAVSIM_E_ARG;
-    if (c->ped_model != NAVSIM_PED_NONE && c->max_peds < 1) return NAVSIM_E_ARG;
-    if (plan_step(c, st).lds > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;   // beams x pedestrians beyond one CU's LDS
-    // navsim_regen's first observations are a launch of their own geometry (plan_step's `lone` rule): validate it here too
-    if (c->regen_cap > 0 && plan_step(c, st, c->regen_cap).lds > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;
-    if (!st->field || !st->scan_threshold || !st->scan_discomfort || !st->robot_pose || !st->robot_goal ||
-        !st->prev_action || !st->prev_pose || !st->n_hist || !st->episode || !st->steps || !io->obs)
-        return NAVSIM_E_ARG;
-    if (!reset_only && (!io->action || !io->reward || !io->done || !io->is_success || !io->is_crash ||
-                        !io->distance))
-        return NAVSIM_E_ARG;
-    if (!reset_only && c->n_scan_stack > 1 && !io->obs_prev) return NAVSIM_E_ARG;
-    if (c->ped_model != NAVSIM_PED_NONE) {
-        if (!st->n_peds || !st->ped_pose || !st->ped_vel || !st->ped_prev_yaw || !st->ped_dist ||
-            !st->ped_has_legs || !st->ped_waypoints || !st->ped_n_waypoints || !st->ped_wp_head)
-            return NAVSIM_E_ARG;
-        if (c->ped_model == NAVSIM_PED_EXTERNAL && !st->ped_cmd && !reset_only) return NAVSIM_E_ARG;
-        if (c->ped_model == NAVSIM_PED_SFM && !st->ped_v_pref) return NAVSIM_E_ARG;
-    }
-    if (c->auto_reset && c->n_spawn > 0 && (!st->spawn_pose || !st->spawn_goal)) return NAVSIM_E_ARG;
-    return NAVSIM_OK;
-}
-
 int navsim_ped_scans(const navsim_config* c, const navsim_state* st, float* out, void* stream) {
     if (!c) return NAVSIM_E_ARG;
     return navsim_ped_scans_part(c, st, out, 0, c->n_envs, stream);
@@ -557,32 +666,6 @@ size_t navsim_regen_workspace_bytes(const navsim_config* c) {
     }
     return b + 1024;
 }
-
-extern "C++" {
-namespace {
-// navsim_regen's fork: the distance transform of the new corridor maps beside the planner's first stage (which needs the
-// occupancy grid and the costmap only).  One helper stream and two events per host thread and device, created on first use;
-// inside a hipGraph capture the helper joins the capture through the first wait and leaves it through the second.
-struct RegenFork { int device = -1; hipStream_t side = nullptr; hipEvent_t forked = nullptr, joined = nullptr; };
-thread_local hipStream_t g_regen_helper = nullptr;          // navsim_regen_helper: the caller's choice of helper stream
-RegenFork* regen_fork() {
-    thread_local RegenFork f;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    if (f.device == dev && g_regen_helper && f.side != g_regen_helper) f.side = g_regen_helper;     // (the events stay)
-    if (f.device != dev) {
-        RegenFork n;
-        if (g_regen_helper) n.side = g_regen_helper;
-        else if (hipStreamCreateWithFlags(&n.side, hipStreamNonBlocking) != hipSuccess) return nullptr;
-        if (hipEventCreateWithFlags(&n.forked, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&n.joined, hipEventDisableTiming) != hipSuccess) return nullptr;
-        n.device = dev;
-        f = n;                                               // (what an earlier device of this thread held stays allocated)
-    }
-    return &f;
-}
-}  // namespace
-}  // extern "C++"
 
 int navsim_regen_helper(void* stream) {
     g_regen_helper = (hipStream_t)stream;
@@ -779,64 +862,25 @@ int navsim_regen(const navsim_config* c, const navsim_state* st, const navsim_st
     io2.final_obs = nullptr; io2.final_goals = nullptr; io2.truncated = nullptr;
     navsim_state st2 = *st;
     st2.arena_cost = nullptr;
+    StepLaunch l;
+    l.reset_only = true;
+    l.stream = s;
     if (c->defer_reset_scan) {
         // the step left every restart's first observation to this call: one launch over all arenas, masked by the done
         // flags -- the regenerated arenas and those beyond the cap that restarted in place (a workgroup whose flag is
         // clear returns at once)
         st2.launch_order = nullptr;
-        return dispatch_step(c, &st2, &io2, 1, io->done, s);
+        l.mask = io->done;
+    } else {
+        st2.launch_order = list;
+        l.grid = M;
     }
-    st2.launch_order = list;
-    return dispatch_step(c, &st2, &io2, 1, nullptr, s, M);
+    return dispatch_step(c, &st2, &io2, l);
 }
-
-extern "C++" {
-namespace {
-// navsim_regen_swap / navsim_step_install: the live and the staged state as a pair
-int check_stage_pair(const navsim_config* c, const navsim_state* live, const navsim_state* stage) {
-    if (c->regen_cap < 1 || c->n_spawn < 1 || !c->auto_reset) return NAVSIM_E_ARG;
-    if (c->defer_reset_scan) return NAVSIM_E_UNSUPPORTED;     // a staged world brings its own first observation; arenas beyond the cap would get none
-    if (!live->field || !stage->field || !live->episode || !stage->episode || !live->spawn_pose || !stage->spawn_pose ||
-        !live->spawn_goal || !stage->spawn_goal || !stage->robot_pose || !stage->robot_goal)
-        return NAVSIM_E_ARG;
-    // the two states must hold the same optional buffers
-    if ((live->field_overflow != nullptr) != (stage->field_overflow != nullptr) ||
-        (live->rect_table != nullptr) != (stage->rect_table != nullptr) || (live->rect_index != nullptr) != (stage->rect_index != nullptr) ||
-        (live->costmap != nullptr) != (stage->costmap != nullptr) || (live->ped_goal != nullptr) != (stage->ped_goal != nullptr))
-        return NAVSIM_E_ARG;
-    return NAVSIM_OK;
-}
-// navsim_state.map_slot: both states or neither, and then over the SAME five arrays
-int check_map_slots(const navsim_state* live, const navsim_state* stage) {
-    if ((live->map_slot != nullptr) != (stage->map_slot != nullptr)) return NAVSIM_E_ARG;
-    if (live->map_slot && (live->map_slot == stage->map_slot || live->field != stage->field || live->field_overflow != stage->field_overflow ||
-                           live->rect_table != stage->rect_table || live->rect_index != stage->rect_index || live->costmap != stage->costmap))
-        return NAVSIM_E_ARG;
-    return NAVSIM_OK;
-}
-template <typename Big>
-void stage_big_buffers(const navsim_config* c, const navsim_state* live, const navsim_state* stage, Big big[5]) {
-    const int H = c->map_h, W = c->map_w;
-    big[0] = {(char*)live->field, (const char*)stage->field, navsim_field_bytes(1, H, W, c->field_format)};
-    if (live->field_overflow) big[1] = {(char*)live->field_overflow, (const char*)stage->field_overflow, (size_t)H * W * sizeof(float)};
-    if (live->rect_table) big[2] = {(char*)live->rect_table, (const char*)stage->rect_table, navsim_rect_table_bytes(1, H, W)};
-    if (live->costmap) big[3] = {(char*)live->costmap, (const char*)stage->costmap, (size_t)(H / 5) * (W / 5)};
-    if (live->rect_index) big[4] = {(char*)live->rect_index, (const char*)stage->rect_index, rect_index_row_bytes(H, W)};
-}
-}  // namespace
-}  // extern "C++"
 
 int navsim_step_install(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, const navsim_state* stage,
                         const float* stage_obs, uint8_t* mark, const long long* ready, uint8_t* late, void* stream) {
     return navsim_step_install_replan(c, st, io, stage, stage_obs, mark, ready, late, -1, stream);
-}
-
-extern "C++" {
-namespace {
-int step_install_impl(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, const navsim_state* stage,
-                      const float* stage_obs, uint8_t* mark, const long long* ready, uint8_t* late, uint8_t* late_next,
-                      const uint8_t* late_prev, int32_t max_queries, void* stream);
-}
 }
 
 int navsim_step_install_replan(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, const navsim_state* stage,
@@ -852,52 +896,6 @@ int navsim_step_install_next(const navsim_config* c, const navsim_state* st, con
         return NAVSIM_E_ARG;
     return step_install_impl(c, st, io, stage, stage_obs, mark, ready, nullptr, late_next, late_prev, max_queries, stream);
 }
-
-extern "C++" {
-namespace {
-int step_install_impl(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, const navsim_state* stage,
-                      const float* stage_obs, uint8_t* mark, const long long* ready, uint8_t* late, uint8_t* late_next,
-                      const uint8_t* late_prev, int32_t max_queries, void* stream) {
-    (void)hipGetLastError();
-    int rc = check_step_args(c, st, io, 0);
-    if (rc != NAVSIM_OK) return rc;
-    if (!stage || !stage_obs || !mark || !ready || ((uintptr_t)mark & 3) != 0 || !st->done_steps) return NAVSIM_E_ARG;
-    // what makes the outcome independent of the staging passes' timing: the rule (cfg.regen_min_steps, with the caller's order of
-    // passes and waits) or the fallback (late: arenas whose world was not ready are generated by the caller's navsim_regen)
-    // NEXT_STEP, neither: an arena that finds nothing staged regenerates its own world inside the launch (regen_lone) -- worlds of
-    // outdoor maps without planning / costmap, at least 256 threads per arena
-    const bool lone = c->auto_reset == NAVSIM_AUTORESET_NEXT_STEP && !late && !late_next && c->regen_min_steps < 1;
-    if (lone && (c->regen_indoor_ratio > 0.0 || c->regen_plan || st->costmap || plan_step(c, st).block < 256 || c->map_h != c->map_w ||
-                 march_rule_variant(c) != NAVSIM_MARCH_F32 ||
-                 c->obstacle_number > 64 || c->obstacle_number_hi > 64))
-        return NAVSIM_E_UNSUPPORTED;
-    if (c->regen_min_steps < 1 && !late && !late_next && !lone) return NAVSIM_E_ARG;
-    rc = check_stage_pair(c, st, stage);
-    if (rc != NAVSIM_OK) return rc;
-    // every finished arena decides for itself: there is no cap to apply in index order (navsim_regen_swap has one)
-    if (c->regen_cap < c->n_envs) return NAVSIM_E_UNSUPPORTED;
-    if (c->field_format != NAVSIM_FIELD_U16T || (c->ped_model != NAVSIM_PED_NONE && ped_split_on(c))) return NAVSIM_E_UNSUPPORTED;
-    if (c->n_envs == 0) return NAVSIM_OK;
-    rc = check_map_slots(st, stage);
-    if (rc != NAVSIM_OK) return rc;
-    StepInstall in = {};
-    in.stage = *stage; in.stage_obs = stage_obs; in.mark = mark; in.ready = ready; in.late = late;
-    in.late_next = late_next; in.late_prev = late_prev; in.lone = lone ? 1 : 0;
-    if (!st->map_slot) stage_big_buffers(c, st, stage, in.big);             // (with slot tables the maps stay where they are)
-    if (max_queries < 0) return dispatch_step(c, st, io, 16, nullptr, (hipStream_t)stream, 0, 0, &in);
-    // ... with navsim_replan of the previous step's flags inside the launch (navsim_step_replan's conditions)
-    if (c->ped_model == NAVSIM_PED_NONE || !st->costmap || !st->ped_due_prev || !st->ped_due || st->ped_due == st->ped_due_prev)
-        return NAVSIM_E_ARG;
-    const int Hc = c->map_h / 5, Wc = c->map_w / 5;
-    if (Hc < 1 || Wc < 1 || !plan_fits(Hc, Wc) || plan_lds(Hc, Wc) > 64 * 1024) return NAVSIM_E_UNSUPPORTED;
-    if ((int)plan_words(Hc, Wc) > plan_step(c, st).block) return NAVSIM_E_UNSUPPORTED;
-    int front = c->n_envs / 16;
-    front = front < 32 ? 32 : (front > 1024 ? 1024 : front);
-    front = front > c->n_envs ? c->n_envs : front;
-    return dispatch_step(c, st, io, (3 << 2) | 16, nullptr, (hipStream_t)stream, front, max_queries, &in);
-}
-}  // namespace
-}  // extern "C++"
 
 int navsim_regen_swap(const navsim_config* c, const navsim_state* live, const navsim_state* stage, const navsim_step_io* io,
                       const float* stage_obs, const uint8_t* want, uint8_t* mark, const long long* ready, void* stream) {
@@ -1146,7 +1144,9 @@ int navsim_step(const navsim_config* c, const navsim_state* st, const navsim_ste
     int rc = check_step_args(c, st, io, 0);
     if (rc != NAVSIM_OK) return rc;
     if (c->n_envs == 0) return NAVSIM_OK;
-    return dispatch_step(c, st, io, 0, nullptr, (hipStream_t)stream);
+    StepLaunch l;
+    l.stream = (hipStream_t)stream;
+    return dispatch_step(c, st, io, l);
 }
 
 int navsim_step_part(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, int32_t part, void* stream) {
@@ -1159,42 +1159,36 @@ int navsim_step_part(const navsim_config* c, const navsim_state* st, const navsi
     if (c->ped_model == NAVSIM_PED_NONE) return NAVSIM_E_ARG;                               // nobody ever waits: there are no parts
     if (ped_split_on(c)) return NAVSIM_E_UNSUPPORTED;                                       // ped_update_kernel advances every arena
     if (c->n_envs == 0) return NAVSIM_OK;
-    // the arenas with a waiting pedestrian are few (~2 % per step on the c3 world): a compact launch of E / 16 workgroups,
-    // each of which takes the b-th, (b + grid)-th, ... such arena (kernels_step.hpp due_arena_pick)
-    int grid = 0;
+    StepLaunch l;
+    l.part = part;
+    l.stream = (hipStream_t)stream;
     navsim_config c2 = *c;
     if (part == NAVSIM_STEP_DUE) {
-        grid = c->n_envs / 16;
-        grid = grid < 32 ? 32 : (grid > 1024 ? 1024 : grid);
-        grid = grid > c->n_envs ? c->n_envs : grid;
+        // a compact launch, each workgroup of which takes the b-th, (b + grid)-th, ... arena with a waiting pedestrian
+        // (kernels_step.hpp due_arena_pick)
+        l.grid = compact_grid(c);
         // twice the other part's threads per arena: the compact launch ends the step, and its arenas share their SIMDs with the
         // other part's wavefronts (c3 world through the gym API, 256 / 512 / 1024 threads: 19.3 / 19.8 / 18.8 M env-steps/s --
         // a 1024-thread workgroup has to wait for 16 free wave slots on one CU; profiles/r05_replan/README.md)
         if (!c->step_block) { const int b = pick_step_block(c); c2.step_block = b >= 512 ? 1024 : (b >= 256 ? 512 : b); }
     }
-    return dispatch_step(&c2, st, io, part << 2, nullptr, (hipStream_t)stream, grid);
+    return dispatch_step(&c2, st, io, l);
 }
 
 int navsim_step_replan(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, int32_t max_queries, void* stream) {
     (void)hipGetLastError();
     int rc = check_step_args(c, st, io, 0);
     if (rc != NAVSIM_OK) return rc;
-    if (max_queries < 0 || c->ped_model == NAVSIM_PED_NONE || !st->costmap || !st->ped_due_prev || !st->ped_due ||
-        st->ped_due == st->ped_due_prev)
-        return NAVSIM_E_ARG;
-    if (ped_split_on(c)) return NAVSIM_E_UNSUPPORTED;                  // ped_update_kernel advances the pedestrians ahead of the launch
-    const int Hc = c->map_h / 5, Wc = c->map_w / 5;
-    if (Hc < 1 || Wc < 1 || !plan_fits(Hc, Wc) || plan_lds(Hc, Wc) > 64 * 1024) return NAVSIM_E_UNSUPPORTED;
-    // the search inside the step's launch owns one costmap word per thread (its registers are the step kernel's): costmaps of
-    // more words than the arena's workgroup has threads go through navsim_replan + navsim_step_part
-    if ((int)plan_words(Hc, Wc) > plan_step(c, st).block) return NAVSIM_E_UNSUPPORTED;
+    if (max_queries < 0) return NAVSIM_E_ARG;
+    rc = replan_in_step(c, st, true);
+    if (rc != NAVSIM_OK) return rc;
     if (c->n_envs == 0) return NAVSIM_OK;
-    // front workgroups: one per arena with a waiting pedestrian, as many as wait in an ordinary step several times over
-    // (~2 % of the arenas on the c3 world); more than that and the arena's own workgroup plans (kernels_step.hpp)
-    int front = c->n_envs / 16;
-    front = front < 32 ? 32 : (front > 1024 ? 1024 : front);
-    front = front > c->n_envs ? c->n_envs : front;
-    return dispatch_step(c, st, io, 3 << 2, nullptr, (hipStream_t)stream, front, max_queries);
+    StepLaunch l;
+    l.part = kStepPartReplan;
+    l.grid = compact_grid(c);      // front workgroups, one per arena with a waiting pedestrian; more than that and the arena's own
+    l.max_queries = max_queries;   // workgroup plans (kernels_step.hpp)
+    l.stream = (hipStream_t)stream;
+    return dispatch_step(c, st, io, l);
 }
 
 int navsim_prepare(const navsim_config* c, const navsim_state* st, const navsim_step_io* io) {
@@ -1202,20 +1196,23 @@ int navsim_prepare(const navsim_config* c, const navsim_state* st, const navsim_
     int rc = check_step_args(c, st, io, 1);
     if (rc != NAVSIM_OK) return rc;
     if (c->n_envs == 0) return NAVSIM_OK;
-    g_prepare_only = true;
-    rc = dispatch_step(c, st, io, 0, nullptr, nullptr);                       // the step
-    if (rc == NAVSIM_OK) rc = dispatch_step(c, st, io, 1, nullptr, nullptr);  // first observations of a reset
-    if (rc == NAVSIM_OK && c->regen_cap > 0) rc = dispatch_step(c, st, io, 1, nullptr, nullptr, c->regen_cap);   // navsim_regen's lone launch
-    if (rc == NAVSIM_OK && c->ped_model != NAVSIM_PED_NONE && !ped_split_on(c))                                  // navsim_step_part's pair
-        rc = dispatch_step(c, st, io, NAVSIM_STEP_DUE << 2, nullptr, nullptr, 32);
-    if (rc == NAVSIM_OK && c->ped_model != NAVSIM_PED_NONE && !ped_split_on(c) && st->costmap &&                 // navsim_step_replan
-        plan_fits(c->map_h / 5, c->map_w / 5) && (int)plan_words(c->map_h / 5, c->map_w / 5) <= plan_step(c, st).block)
-        rc = dispatch_step(c, st, io, 3 << 2, nullptr, nullptr, 32, 0);
-    if (rc == NAVSIM_OK && c->field_format == NAVSIM_FIELD_U16T && !(c->ped_model != NAVSIM_PED_NONE && ped_split_on(c))) {
-        const StepInstall none = {};                                                                             // navsim_step_install
-        rc = dispatch_step(c, st, io, 16, nullptr, nullptr, 0, 0, &none);
-    }
-    g_prepare_only = false;
+    // every form of the launch this configuration can ask for, walked down to its kernel
+    const bool fused_peds = c->ped_model != NAVSIM_PED_NONE && !ped_split_on(c);
+    const StepInstall none = {};
+    StepLaunch l;
+    l.prepare_only = true;
+    rc = dispatch_step(c, st, io, l);                                                                // the step
+    l.reset_only = true;
+    if (rc == NAVSIM_OK) rc = dispatch_step(c, st, io, l);                                           // first observations of a reset
+    l.grid = c->regen_cap;
+    if (rc == NAVSIM_OK && c->regen_cap > 0) rc = dispatch_step(c, st, io, l);                       // navsim_regen's lone launch
+    l.reset_only = false; l.grid = 32; l.part = NAVSIM_STEP_DUE;
+    if (rc == NAVSIM_OK && fused_peds) rc = dispatch_step(c, st, io, l);                             // navsim_step_part's pair
+    l.part = kStepPartReplan;
+    if (rc == NAVSIM_OK && replan_in_step(c, st, false) == NAVSIM_OK) rc = dispatch_step(c, st, io, l);   // navsim_step_replan
+    l.grid = 0; l.part = NAVSIM_STEP_ALL; l.install = &none;
+    if (rc == NAVSIM_OK && c->field_format == NAVSIM_FIELD_U16T && (c->ped_model == NAVSIM_PED_NONE || fused_peds))
+        rc = dispatch_step(c, st, io, l);                                                            // navsim_step_install
     if (rc != NAVSIM_OK) return rc;
     if (c->regen_plan && c->regen_indoor_ratio > 0.0) (void)regen_fork();     // navsim_regen's helper stream: not created inside a capture
     const int Hc = c->map_h / 5, Wc = c->map_w / 5;
@@ -1231,7 +1228,11 @@ int navsim_reset_obs(const navsim_config* c, const navsim_state* st, const navsi
     int rc = check_step_args(c, st, io, 1);
     if (rc != NAVSIM_OK) return rc;
     if (c->n_envs == 0) return NAVSIM_OK;
-    return dispatch_step(c, st, io, 1, mask, (hipStream_t)stream);
+    StepLaunch l;
+    l.reset_only = true;
+    l.mask = mask;
+    l.stream = (hipStream_t)stream;
+    return dispatch_step(c, st, io, l);
 }
 
 int navsim_restart(const navsim_config* c, const navsim_state* st, const uint8_t* mask, void* stream) {

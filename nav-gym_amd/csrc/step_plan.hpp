@@ -1,6 +1,33 @@
 // step_plan.hpp -- launch geometry of the fused step (threads per arena, where the probes find the rect records, dynamic
-// LDS), shared by the C ABI (navsim_kernels.hip) and the units that instantiate the step kernel (navsim_step_inst.hip).
-// Included inside the anonymous namespace, behind kernels_step.hpp.
+// LDS) and the two descriptors a launch is made of, shared by the C ABI (navsim_kernels.hip) and the units that instantiate
+// the step kernel (navsim_step_inst.hip).  Included BEHIND the unit's anonymous namespace with the kernels_*.hpp sections:
+// StepPlan and StepLaunch cross from one unit to the others (navsim_step_launch_<BLOCK>_<PEDS>) and are ordinary global
+// types, everything else stays internal to the unit.
+
+// How a step is launched: threads per arena, where the probes find the rect records, the dynamic LDS.
+struct StepPlan {
+    int block;              // threads per arena
+    int rect;               // 0 no rect records, 1 records read from global memory, 2 the arena's table staged in LDS
+    int park;               // rays a wavefront parks per chunk
+    size_t lds;             // dynamic LDS per workgroup
+    unsigned rect_off;      // byte offset of the staged table inside it
+};
+// What is launched: the C ABI's entry points fill one by field name, dispatch_step (navsim_kernels.hip) plans it and hands both
+// to the launcher of the (threads per arena, pedestrians or not) family, which picks the kernel.
+struct StepLaunch {
+    bool reset_only = false;                // first observations only (navsim_reset_obs, navsim_regen): nothing is integrated
+    bool peds_done = false;                 // ped_update_kernel has advanced the pedestrians ahead of this launch (dispatch_step)
+    int part = NAVSIM_STEP_ALL;             // NAVSIM_STEP_* of navsim_step_part, or kStepPartReplan (navsim_step_replan)
+    const uint8_t* mask = nullptr;          // reset-only: the arenas to reset, NULL = all
+    int grid = 0;                           // > 0: that many workgroups instead of one per arena, st->launch_order names their arenas, -1 =
+                                            // none (navsim_regen's first observations); the compact launch's; the re-plan's FRONT workgroups
+    int max_queries = 0;                    // kStepPartReplan: navsim_replan's cap
+    const StepInstall* install = nullptr;   // navsim_step_install: the staged worlds (the install kernels)
+    bool prepare_only = false;              // navsim_prepare: walk down to the kernel, set what is set once per kernel (allow_lds), launch nothing
+    hipStream_t stream = nullptr;
+};
+
+namespace {
 // kernels that want more than 64 KB of dynamic LDS must say so once per (device, kernel); more than the CU has is refused.
 // What has been granted is remembered (round-4 advisor: every call above 64 KB used to repeat hipFuncSetAttribute, also
 // inside a hipGraph capture): after navsim_prepare no later launch of the same configuration touches an attribute.
@@ -99,14 +126,10 @@ int march_rule_variant(const navsim_config* c) {
     return (c->field_format == NAVSIM_FIELD_U16T && side <= 1448) ? kMarchF64Exact32 : NAVSIM_MARCH_F64;
 }
 
-// How a step is launched: threads per arena, where the probes find the rect records, the dynamic LDS.
-struct StepPlan {
-    int block;              // threads per arena
-    int rect;               // 0 no rect records, 1 records read from global memory, 2 the arena's table staged in LDS
-    int park;               // rays a wavefront parks per chunk
-    size_t lds;             // dynamic LDS per workgroup
-    unsigned rect_off;      // byte offset of the staged table inside it
-};
+// the `int reset_only` of navsim_step_kernel / navsim_step_install_kernel (layout: kernels_step.hpp kStepWord*)
+int step_kernel_word(const StepLaunch& l) {
+    return (l.reset_only ? kStepWordResetOnly : 0) | ((l.peds_done ? 1 : 0) << kStepWordPedsDoneBit) | (l.part << kStepWordPartShift);
+}
 // The record table in LDS ("map tiles staged through LDS").  Round 3 staged the 16-byte records themselves: 63.5 KB per
 // 500 x 500 arena, two 1024-thread workgroups per CU, +10-13 % for launches of up to 4 arenas per CU and a loss beyond
 // (profiles/r03_rect_lds/).  Round 4 stages the INDEX form (kernels_rect.hpp: 10 KB) at the residency the block size implies
@@ -139,3 +162,4 @@ StepPlan plan_step(const navsim_config* c, const navsim_state* st, int grid = 0)
     }
     return p;
 }
+}  // namespace
