@@ -826,6 +826,35 @@ int navsim_crowd_orca(const navsim_orca_params* p, int32_t n_queries, int32_t ma
                       const int32_t* n_agents, const double* pref_vel, int32_t max_obst, int32_t n_vert,
                       const double* verts, const int32_t* n_obst, const int32_t* obst_set, const double* theta,
                       double* out_vel, double* out_action, void* stream);
+/* ---- NavGym-v0 pedestrians driven by ORCA (a build-defined model; UNPINNED: rvo2 absent) ----------
+ * navsim_ped_orca follows navsim_ped_policy's protocol: called in front of a navsim_step with NAVSIM_PED_EXTERNAL, it fills
+ * ped_cmd from the simulator's own state.  For every live pedestrian i < n_peds[e] of every arena e, in float64 unless
+ * stated otherwise and with nothing contracted into FMA:
+ *  1. waypoint pop as the policy head and the step do it (sqrt(dx*dx+dy*dy) < 1.0 while head + 1 < n_waypoints); the new
+ *     head is written to st->ped_wp_head.
+ *  2. preferred velocity (orca.py:116-120): g = wp[head] - pos, s = sqrt(gx*gx + gy*gy), pref = s > 1 ? g / s : g.
+ *  3. agent list: the pedestrian itself, the other live pedestrians of the arena in ascending index, then the robot if
+ *     robot_visible.  Entries are (px, py, vx, vy, radius, max_speed): pedestrian velocities from ped_vel, pedestrian
+ *     radius (ped_radius + 0.01) + safety_space, robot radius (robot_radius + 0.01) + safety_space, max_speed =
+ *     ped_v_pref[e,i] for every entry; the robot's velocity is the one the social force sees,
+ *     prev_action[e,0] * (cos, sin)(robot_pose[e,2]).  No obstacle polygons: static obstacles are NOT ORCA obstacles in
+ *     this model -- pedestrians follow routes planned on the 1 m-inflated costmap (NAVSIM_PED_SFM is the model with a
+ *     wall force).
+ *  4. navsim_crowd_orca's algorithm on that query with theta = ped_pose[e,i,2]: inputs rounded to float32 where that
+ *     function rounds them; neighbour selection, half-planes and linear programs in float32; ActionRot
+ *     v = sqrt(vx*vx + vy*vy), r = atan2(vy, vx) - theta (orca.py:128-130).
+ *  5. ped_cmd[e,i] = (v, r / cfg->time_step): Human.set_vel's theta + omega dt turns the pedestrian into its ORCA velocity
+ *     and it moves by v dt along it.
+ * Rows of slots >= n_peds[e] are left untouched.  Bit-identical to that composition of the oracle's functions.
+ * NAVSIM_E_ARG (before any device call): NULL p or ped_cmd, cfg->ped_model != NAVSIM_PED_EXTERNAL,
+ * max_peds + robot_visible > NAVSIM_ORCA_MAX_AGENTS, a non-positive radius / time_step / time_horizon, max_neighbors < 0. */
+typedef struct navsim_ped_orca_params {
+    navsim_orca_params orca;    /* time_step, neighbor_dist, time_horizon, time_horizon_obst (unused: no obstacles), max_neighbors */
+    double ped_radius, robot_radius, safety_space;
+    int32_t robot_visible;      /* 1: the robot is the last agent of every pedestrian's list */
+} navsim_ped_orca_params;
+int navsim_ped_orca(const navsim_config* cfg, const navsim_state* st, const navsim_ped_orca_params* p,
+                    double* ped_cmd /* [E,N,2] out */, void* stream);
 /* Agent.step with an ActionRot (agent.py:108-141): theta' = theta + r; p += (cos, sin)(theta') * v * dt;
  * vel = v * (cos, sin)(theta'); theta = theta' mod 2 pi.  pose [n,3] in/out, action [n,2], vel [n,2] or NULL. */
 int navsim_crowd_agent_step(double* pose, const double* action, double* vel, int32_t n, double time_step, void* stream);

@@ -25,16 +25,33 @@ __device__ __forceinline__ float length(V2 a) { return sqrtf(dot(a, a)); }
 __device__ __forceinline__ V2 normalize(V2 a) { return a / length(a); }
 __device__ __forceinline__ float sqr(float a) { return a * a; }
 
-__device__ bool lp1(const Line* lines, int line_no, float radius, V2 opt, bool direction_opt, V2& result) {
-    const Line& L = lines[line_no];
+// How a list of half-planes is addressed: lp1 / lp2 / lp3 and the neighbour insertion below are written once over
+// get / set, for the thread-private arrays of crowd_orca_kernel (PrivLines, PrivNeighbors) and for the lane-interleaved
+// LDS lists of ped_orca_kernel (kernels_ped_orca.hpp).  Same operations in the same order either way.
+struct PrivLines {
+    Line* a;
+    __device__ __forceinline__ Line get(int i) const { return a[i]; }
+    __device__ __forceinline__ void set(int i, const Line& l) const { a[i] = l; }
+};
+struct PrivNeighbors {
+    int* id; float* d;
+    __device__ __forceinline__ float dist(int i) const { return d[i]; }
+    __device__ __forceinline__ int index(int i) const { return id[i]; }
+    __device__ __forceinline__ void set(int i, int k, float v) const { id[i] = k; d[i] = v; }
+};
+
+template <class LS>
+__device__ bool lp1(const LS& lines, int line_no, float radius, V2 opt, bool direction_opt, V2& result) {
+    const Line L = lines.get(line_no);
     const float dp = dot(L.point, L.direction);
     const float disc = sqr(dp) + sqr(radius) - abs_sq(L.point);
     if (disc < 0.0f) return false;
     const float sd = sqrtf(disc);
     float t_left = -dp - sd, t_right = -dp + sd;
     for (int i = 0; i < line_no; ++i) {
-        const float den = det(L.direction, lines[i].direction);
-        const float num = det(lines[i].direction, L.point - lines[i].point);
+        const Line Li = lines.get(i);
+        const float den = det(L.direction, Li.direction);
+        const float num = det(Li.direction, L.point - Li.point);
         if (fabsf(den) <= kEps) {
             if (num < 0.0f) return false;
             continue;
@@ -55,12 +72,14 @@ __device__ bool lp1(const Line* lines, int line_no, float radius, V2 opt, bool d
     return true;
 }
 
-__device__ int lp2(const Line* lines, int n, float radius, V2 opt, bool direction_opt, V2& result) {
+template <class LS>
+__device__ int lp2(const LS& lines, int n, float radius, V2 opt, bool direction_opt, V2& result) {
     if (direction_opt) result = radius * opt;
     else if (abs_sq(opt) > sqr(radius)) result = radius * normalize(opt);
     else result = opt;
     for (int i = 0; i < n; ++i) {
-        if (det(lines[i].direction, lines[i].point - result) > 0.0f) {
+        const Line Li = lines.get(i);
+        if (det(Li.direction, Li.point - result) > 0.0f) {
             const V2 keep = result;
             if (!lp1(lines, i, radius, opt, direction_opt, result)) { result = keep; return i; }
         }
@@ -68,29 +87,83 @@ __device__ int lp2(const Line* lines, int n, float radius, V2 opt, bool directio
     return n;
 }
 
-__device__ void lp3(const Line* lines, int n, int n_obst_lines, int begin, float radius, V2& result, Line* proj) {
+template <class LS>
+__device__ void lp3(const LS& lines, int n, int n_obst_lines, int begin, float radius, V2& result, const LS& proj) {
     float distance = 0.0f;
     for (int i = begin; i < n; ++i) {
-        if (det(lines[i].direction, lines[i].point - result) > distance) {
+        const Line Li = lines.get(i);
+        if (det(Li.direction, Li.point - result) > distance) {
             int np = 0;
-            for (int j = 0; j < n_obst_lines; ++j) proj[np++] = lines[j];
+            for (int j = 0; j < n_obst_lines; ++j) proj.set(np++, lines.get(j));
             for (int j = n_obst_lines; j < i; ++j) {
+                const Line Lj = lines.get(j);
                 Line l;
-                const float d = det(lines[i].direction, lines[j].direction);
+                const float d = det(Li.direction, Lj.direction);
                 if (fabsf(d) <= kEps) {
-                    if (dot(lines[i].direction, lines[j].direction) > 0.0f) continue;
-                    l.point = 0.5f * (lines[i].point + lines[j].point);
+                    if (dot(Li.direction, Lj.direction) > 0.0f) continue;
+                    l.point = 0.5f * (Li.point + Lj.point);
                 } else {
-                    l.point = lines[i].point + (det(lines[j].direction, lines[i].point - lines[j].point) / d) * lines[i].direction;
+                    l.point = Li.point + (det(Lj.direction, Li.point - Lj.point) / d) * Li.direction;
                 }
-                l.direction = normalize(lines[j].direction - lines[i].direction);
-                proj[np++] = l;
+                l.direction = normalize(Lj.direction - Li.direction);
+                proj.set(np++, l);
             }
             const V2 keep = result;
-            if (lp2(proj, np, radius, v2(-lines[i].direction.y, lines[i].direction.x), true, result) < np) result = keep;
-            distance = det(lines[i].direction, lines[i].point - result);
+            if (lp2(proj, np, radius, v2(-Li.direction.y, Li.direction.x), true, result) < np) result = keep;
+            distance = det(Li.direction, Li.point - result);
         }
     }
+}
+
+// Agent::insertAgentNeighbor: agent k at squared distance d joins the (at most max_n) nearest, kept in ascending order
+template <class NB>
+__device__ __forceinline__ void insert_neighbor(const NB& nb, int& n_agn, int max_n, int k, float d, float& range_sq) {
+    if (d < range_sq) {
+        if (n_agn < max_n) ++n_agn;
+        int i = n_agn - 1;
+        while (i != 0 && d < nb.dist(i - 1)) { nb.set(i, nb.index(i - 1), nb.dist(i - 1)); --i; }
+        nb.set(i, k, d);
+        if (n_agn == max_n) range_sq = nb.dist(n_agn - 1);
+    }
+}
+
+// Agent::computeNewVelocity, the half-plane of one other agent (o_*: its position, velocity, radius)
+__device__ __forceinline__ Line agent_line(V2 position, V2 velocity, float radius, V2 o_position, V2 o_velocity, float o_radius,
+                                           float inv_th, float time_step) {
+    const V2 rel_p = o_position - position;
+    const V2 rel_v = velocity - o_velocity;
+    const float dist_sq = abs_sq(rel_p);
+    const float comb = radius + o_radius, comb_sq = sqr(comb);
+    Line line;
+    V2 u;
+    if (dist_sq > comb_sq) {
+        const V2 w = rel_v - inv_th * rel_p;
+        const float w_sq = abs_sq(w);
+        const float dp1 = dot(w, rel_p);
+        if (dp1 < 0.0f && sqr(dp1) > comb_sq * w_sq) {
+            const float wl = sqrtf(w_sq);
+            const V2 uw = w / wl;
+            line.direction = v2(uw.y, -uw.x);
+            u = (comb * inv_th - wl) * uw;
+        } else {
+            const float leg = sqrtf(dist_sq - comb_sq);
+            if (det(rel_p, w) > 0.0f)
+                line.direction = v2(rel_p.x * leg - rel_p.y * comb, rel_p.x * comb + rel_p.y * leg) / dist_sq;
+            else
+                line.direction = -(v2(rel_p.x * leg + rel_p.y * comb, -rel_p.x * comb + rel_p.y * leg) / dist_sq);
+            const float dp2 = dot(rel_v, line.direction);
+            u = dp2 * line.direction - rel_v;
+        }
+    } else {
+        const float inv_dt = 1.0f / time_step;
+        const V2 w = rel_v - inv_dt * rel_p;
+        const float wl = length(w);
+        const V2 uw = w / wl;
+        line.direction = v2(uw.y, -uw.x);
+        u = (comb * inv_dt - wl) * uw;
+    }
+    line.point = velocity + 0.5f * u;
+    return line;
 }
 
 // the obstacle vertices of one polygon set, addressed by a flat edge index k = polygon * n_vert + vertex
@@ -155,16 +228,9 @@ __global__ __launch_bounds__(64) void crowd_orca_kernel(navsim_orca_params p, in
     if (p.max_neighbors > 0) {
         float range_sq = sqr(p.neighbor_dist);
         const int max_n = p.max_neighbors < NAVSIM_ORCA_MAX_AGENTS ? p.max_neighbors : NAVSIM_ORCA_MAX_AGENTS;
-        for (int k = 1; k < na; ++k) {
-            const float d = abs_sq(position - v2((float)ag[6 * k], (float)ag[6 * k + 1]));
-            if (d < range_sq) {
-                if (n_agn < max_n) ++n_agn;
-                int i = n_agn - 1;
-                while (i != 0 && d < agd[i - 1]) { agn[i] = agn[i - 1]; agd[i] = agd[i - 1]; --i; }
-                agn[i] = k; agd[i] = d;
-                if (n_agn == max_n) range_sq = agd[n_agn - 1];
-            }
-        }
+        const PrivNeighbors nb = {agn, agd};
+        for (int k = 1; k < na; ++k)
+            insert_neighbor(nb, n_agn, max_n, k, abs_sq(position - v2((float)ag[6 * k], (float)ag[6 * k + 1])), range_sq);
     }
     // ---- Agent::computeNewVelocity: obstacle half-planes
     Line lines[kMaxLines];
@@ -267,46 +333,16 @@ __global__ __launch_bounds__(64) void crowd_orca_kernel(navsim_orca_params p, in
     const float inv_th = 1.0f / p.time_horizon;
     for (int i = 0; i < n_agn; ++i) {
         const double* o = ag + 6 * agn[i];
-        const V2 rel_p = v2((float)o[0], (float)o[1]) - position;
-        const V2 rel_v = velocity - v2((float)o[2], (float)o[3]);
-        const float dist_sq = abs_sq(rel_p);
-        const float comb = radius + (float)o[4], comb_sq = sqr(comb);
-        Line line;
-        V2 u;
-        if (dist_sq > comb_sq) {
-            const V2 w = rel_v - inv_th * rel_p;
-            const float w_sq = abs_sq(w);
-            const float dp1 = dot(w, rel_p);
-            if (dp1 < 0.0f && sqr(dp1) > comb_sq * w_sq) {
-                const float wl = sqrtf(w_sq);
-                const V2 uw = w / wl;
-                line.direction = v2(uw.y, -uw.x);
-                u = (comb * inv_th - wl) * uw;
-            } else {
-                const float leg = sqrtf(dist_sq - comb_sq);
-                if (det(rel_p, w) > 0.0f)
-                    line.direction = v2(rel_p.x * leg - rel_p.y * comb, rel_p.x * comb + rel_p.y * leg) / dist_sq;
-                else
-                    line.direction = -(v2(rel_p.x * leg + rel_p.y * comb, -rel_p.x * comb + rel_p.y * leg) / dist_sq);
-                const float dp2 = dot(rel_v, line.direction);
-                u = dp2 * line.direction - rel_v;
-            }
-        } else {
-            const float inv_dt = 1.0f / p.time_step;
-            const V2 w = rel_v - inv_dt * rel_p;
-            const float wl = length(w);
-            const V2 uw = w / wl;
-            line.direction = v2(uw.y, -uw.x);
-            u = (comb * inv_dt - wl) * uw;
-        }
-        line.point = velocity + 0.5f * u;
-        lines[nl++] = line;
+        lines[nl++] = agent_line(position, velocity, radius, v2((float)o[0], (float)o[1]), v2((float)o[2], (float)o[3]), (float)o[4],
+                                 inv_th, p.time_step);
     }
     V2 nv;
-    const int fail = lp2(lines, nl, max_speed, pref, false, nv);
+    const PrivLines ls = {lines};
+    const int fail = lp2(ls, nl, max_speed, pref, false, nv);
     if (fail < nl) {
         Line proj[kMaxLines];
-        lp3(lines, nl, n_obst_lines, fail, max_speed, nv, proj);
+        const PrivLines pl = {proj};
+        lp3(ls, nl, n_obst_lines, fail, max_speed, nv, pl);
     }
     out_vel[2 * q] = (double)nv.x; out_vel[2 * q + 1] = (double)nv.y;
     if (out_action) {                                                       // orca.py:128-130

@@ -19,6 +19,7 @@
 //   kernels_policy.hpp   pedestrian control block with the HumanPolicy actor
 //   kernels_pedscan.hpp  pedestrian scans, CrowdSim collision block, beam table, test hooks
 //   kernels_crowd_maps.hpp  CrowdSim local maps;  kernels_crowd_orca.hpp  CrowdSim pedestrians (ORCA, Agent.step)
+//   kernels_ped_orca.hpp  NavGym pedestrians driven by ORCA from the simulator's state (navsim_ped_orca)
 //   step_plan.hpp        launch geometry of the fused step and the descriptors of a launch (shared by this file and
 //                        navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
 //
@@ -37,6 +38,7 @@ namespace {
 #include "kernels_pedscan.hpp"
 #include "kernels_crowd_maps.hpp"
 #include "kernels_crowd_orca.hpp"
+#include "kernels_ped_orca.hpp"
 
 }  // namespace
 #include "step_plan.hpp"
@@ -1120,6 +1122,28 @@ int navsim_crowd_orca(const navsim_orca_params* p, int32_t n_queries, int32_t ma
     crowd_orca_kernel<<<(n_queries + 63) / 64, 64, 0, (hipStream_t)stream>>>(*p, n_queries, max_agents, agents, n_agents,
                                                                           pref_vel, max_obst, n_vert, verts, n_obst,
                                                                           obst_set, theta, out_vel, out_action);
+    return launch_status();
+}
+
+int navsim_ped_orca(const navsim_config* c, const navsim_state* st, const navsim_ped_orca_params* p, double* ped_cmd, void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !p || !ped_cmd) return NAVSIM_E_ARG;
+    if (c->ped_model != NAVSIM_PED_EXTERNAL || c->n_envs < 0 || c->max_peds < 1) return NAVSIM_E_ARG;
+    if (p->robot_visible != 0 && p->robot_visible != 1) return NAVSIM_E_ARG;
+    if ((long)c->max_peds + p->robot_visible > NAVSIM_ORCA_MAX_AGENTS) return NAVSIM_E_ARG;
+    if (!(p->ped_radius > 0.0) || !(p->robot_radius > 0.0) || !(p->orca.time_step > 0.0f) || !(p->orca.time_horizon > 0.0f) ||
+        !(c->time_step > 0.0) || p->orca.max_neighbors < 0)
+        return NAVSIM_E_ARG;
+    if (c->max_waypoints < 1 || c->max_waypoints > NAVSIM_MAX_WAYPOINTS) return NAVSIM_E_ARG;
+    if (!st->n_peds || !st->ped_pose || !st->ped_vel || !st->ped_v_pref || !st->ped_waypoints || !st->ped_n_waypoints ||
+        !st->ped_wp_head || (p->robot_visible && (!st->robot_pose || !st->prev_action)))
+        return NAVSIM_E_ARG;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    const int N = c->max_peds, G = ped_orca_pack(N);
+    const size_t lds = ped_orca_lds_bytes(N, ped_orca_list_len(N, p->orca.max_neighbors, p->robot_visible));
+    const int rc = allow_lds((const void*)ped_orca_kernel, lds);
+    if (rc != NAVSIM_OK) return rc;
+    ped_orca_kernel<<<(c->n_envs + G - 1) / G, 64, lds, (hipStream_t)stream>>>(*c, *st, *p, ped_cmd);
     return launch_status();
 }
 

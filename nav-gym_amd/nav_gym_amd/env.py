@@ -17,8 +17,11 @@ and default to the reference's behaviour for num_envs == 1:
                     Maps above 1000 cells per side fall back to False (the search lives in LDS).
     pedestrian_model 'policy' (the reference's HumanPolicy actor on the device, env.py:617-662; needs
                     policy_weights = the state_dict of human_policy.pth, a path to it, or a dict of arrays),
-                    'sfm' (build-defined social force), 'external' (caller supplies (v, w) per
-                    pedestrian -- the slot the reference fills with HumanPolicy) or 'none'
+                    'sfm' (build-defined social force), 'orca' (build-defined: reciprocal velocity obstacles among the
+                    arena's pedestrians and the robot toward the current waypoint, NavSim.ped_orca in front of every step;
+                    orca_params = dict overriding sim.ped_orca_defaults, unknown keys raise ValueError; static obstacles
+                    are not ORCA obstacles; ordered like 'policy': no graphs, no pregen_pipeline), 'external' (caller
+                    supplies (v, w) per pedestrian -- the slot the reference fills with HumanPolicy) or 'none'
     action_kind     'twist' (default): action = (v, omega) like the reference (env.py:591); 'wheels': action = the
                     angular speeds (left, right) of a skid-steer base's wheel pairs in rad/s, converted on the device
                     with the robot's wheel radius / track (robots.py; Husky: husky.urdf.xacro:61-67)
@@ -195,7 +198,7 @@ class NavGymEnv(_EnvBase):
                  field_format=abi.FIELD_U16T, n_spawn=None, randomize_maps=False, plan_paths=True,
                  action_kind="twist", clip_actions=False, max_waypoints=64, march_rule=None, use_graphs=None,
                  regen_min_steps=0, pregen_pipeline=None, pregen_stage_cap=None, autoreset_mode="same_step",
-                 final_observation=True, pregen_fallback_poll=None, max_episode_steps=None):
+                 final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None):
         from . import lib
         if robot_type not in robots.ROBOTS:
             raise NotImplementedError(robot_type)            # env.py:772-773
@@ -215,7 +218,7 @@ class NavGymEnv(_EnvBase):
             max_waypoints=max_waypoints, march_rule=march_rule, use_graphs=use_graphs,
             regen_min_steps=regen_min_steps, pregen_pipeline=pregen_pipeline, pregen_stage_cap=pregen_stage_cap,
             autoreset_mode=autoreset_mode, final_observation=final_observation, pregen_fallback_poll=pregen_fallback_poll,
-            max_episode_steps=max_episode_steps)
+            max_episode_steps=max_episode_steps, orca_params=orca_params)
         self.robot_type = robot_type
         self.time_step = time_step
         self.min_turning_radius = min_turning_radius
@@ -240,6 +243,18 @@ class NavGymEnv(_EnvBase):
         self.device = device
         self.seed_value = int(seed)
         self.pedestrian_model = pedestrian_model
+        # 'policy' and 'orca' compute the pedestrians' commands in a launch of their own IN FRONT of the step (which then runs
+        # as PED_EXTERNAL): that launch reads the routes, so the re-plan stays behind the step, and neither graphs nor the
+        # pipelined reset path cover it
+        self._cmd_in_front = pedestrian_model in ("policy", "orca")
+        from . import sim as _simmod
+        if orca_params is not None and pedestrian_model != "orca":
+            raise ValueError("orca_params needs pedestrian_model='orca'")
+        for k in (orca_params or {}):
+            if k not in _simmod.PED_ORCA_KEYS:
+                raise ValueError("unknown key %r in orca_params (known: %s)" % (k, ", ".join(_simmod.PED_ORCA_KEYS)))
+        self.orca_params = None if orca_params is None else dict(orca_params)
+        self._orca_struct = None
         self.auto_reset = (self.num_envs > 1) if auto_reset is None else bool(auto_reset)
         if autoreset_mode not in ("same_step", "next_step"):
             raise ValueError("autoreset_mode must be 'same_step' or 'next_step'")
@@ -272,7 +287,7 @@ class NavGymEnv(_EnvBase):
         # pregen_pipeline=0, bit for bit.
         self._pregen_auto = pregen_pipeline is None
         if pregen_pipeline is None:
-            available = (pedestrian_model != "policy" and field_format == abi.FIELD_U16T and
+            available = (not self._cmd_in_front and field_format == abi.FIELD_U16T and
                          (map_size == "reference" or int(map_size) <= 1024))
             heavy = bool(plan_paths) and float(indoor_ratio) > 0.0 and (map_size == "reference" or int(map_size) <= 1000)
             # (worlds of corridor maps with planned starts: a pass every 4 steps too since round 6 -- their passes alternate between
@@ -288,8 +303,8 @@ class NavGymEnv(_EnvBase):
             # regen_min_steps >= 4 P: the rule (fastest; short episodes keep their map).  Below that -- 0 is the reference's own
             # "a new map at every reset()" -- an arena that finishes before its world is staged is generated on the spot by
             # navsim_regen (NavSim.enable_pregen fallback): same rollout as without the pipeline, bit for bit
-            if pedestrian_model == "policy":
-                raise ValueError("pregen_pipeline is not available with pedestrian_model='policy'")
+            if self._cmd_in_front:
+                raise ValueError("pregen_pipeline is not available with pedestrian_model=%r" % pedestrian_model)
             self.use_graphs = False
         self._graphed = False
         self._overlap_replan = False
@@ -309,7 +324,7 @@ class NavGymEnv(_EnvBase):
         spec = robots.ROBOTS[robot_type]
         nh_hi = int(env_param_range["num_humans"][0][1]) if num_humans is None else int(num_humans)
         ped = {"none": abi.PED_NONE, "external": abi.PED_EXTERNAL, "sfm": abi.PED_SFM,
-               "policy": abi.PED_EXTERNAL}[pedestrian_model]
+               "policy": abi.PED_EXTERNAL, "orca": abi.PED_EXTERNAL}[pedestrian_model]
         if pedestrian_model == "policy" and policy_weights is None:
             raise ValueError("pedestrian_model='policy' needs policy_weights (human_policy.pth is not shipped)")
         self._policy_weights = policy_weights
@@ -483,7 +498,7 @@ class NavGymEnv(_EnvBase):
         self.sim.regenerate_all(new_episode=not first)
         # pedestrians on planned routes: navsim_replan overlaps the step (not with 'policy', whose control block runs in
         # front of every step and reads the routes)
-        self._overlap_replan = ("costmap" in self.sim.t and self.sim.due is not None and self.pedestrian_model != "policy"
+        self._overlap_replan = ("costmap" in self.sim.t and self.sim.due is not None and not self._cmd_in_front
                                 and not self.pregen_pipeline)
         if self.pregen_pipeline and first and self._pregen_auto:
             # the pipeline keeps a second, staged copy of every array navsim_regen writes (the maps above all) and builds it
@@ -500,7 +515,7 @@ class NavGymEnv(_EnvBase):
                     c_.defer_reset_scan = int(self.num_envs <= 1024)
                 if self._use_graphs_arg is None:
                     self.use_graphs = not (self.plan_paths and float(self.indoor_ratio) > 0.0)
-                self._overlap_replan = ("costmap" in self.sim.t and self.sim.due is not None and self.pedestrian_model != "policy")
+                self._overlap_replan = ("costmap" in self.sim.t and self.sim.due is not None and not self._cmd_in_front)
         if self.pregen_pipeline:
             if cfg.field_format != abi.FIELD_U16T:
                 raise ValueError("pregen_pipeline needs the packed distance field (map_size <= 1024)")
@@ -509,7 +524,7 @@ class NavGymEnv(_EnvBase):
                                        fallback_poll=self.pregen_fallback_poll)
             else:
                 self.sim.restage_all()                    # the worlds behind the ones this reset() just drew
-        if first and self.use_graphs and self.pedestrian_model != "policy":
+        if first and self.use_graphs and not self._cmd_in_front:
             self.sim.enable_graphs(regen=self.randomize_maps and self.auto_reset,
                                    replan_cap=self.replan_cap if "costmap" in self.sim.t else 0)
             self._graphed = True
@@ -565,13 +580,18 @@ class NavGymEnv(_EnvBase):
             self.sim.set_ped_cmd(human_actions)
         elif self.pedestrian_model == "policy":
             self.sim.ped_policy()                           # scans -> HumanPolicy actor -> (v, omega)
+        elif self.pedestrian_model == "orca":
+            if self._orca_struct is None:
+                from . import sim as simmod
+                self._orca_struct = simmod.ped_orca_params(self.sim.cfg, self.orca_params, self.robot_type)
+            self.sim.ped_orca(self._orca_struct)            # the simulator's state -> ORCA -> (v, omega), one launch
         a = np.asarray(action, dtype=np.float64).reshape(self.num_envs, 2) if not hasattr(action, "is_cuda") else action
         if self._graphed:                                   # step + regen + replan: one graph launch (NavSim.enable_graphs)
             _, out = self.sim.step_graphed(a)
         elif self.pregen_pipeline:
             # navsim_step_install: finished arenas take their staged worlds; with planned routes the re-plan of the PREVIOUS
             # step's arrivals inside the same launch where the search fits the arena's workgroup (else behind the step)
-            in_step = "costmap" in self.sim.t and self.pedestrian_model != "policy"
+            in_step = "costmap" in self.sim.t and not self._cmd_in_front
             if in_step and self.sim.pg_replan_cap == 0:
                 self.sim.pg_replan_cap = self.replan_cap
             _, out = self.sim.step(a)
@@ -592,7 +612,7 @@ class NavGymEnv(_EnvBase):
             if self.randomize_maps and self.auto_reset:
                 self.sim.regen()
             if "costmap" in self.sim.t:
-                self.sim.replan(self.replan_cap)           # ('policy': the control block in front of the next step reads the routes)
+                self.sim.replan(self.replan_cap)           # ('policy', 'orca': the launch in front of the next step reads the routes)
         obs = self._obs_dict()
         # the LAST observation of an episode that ended in this step (env.py:700-728 returns it with done = True): under
         # same-step auto-reset the row above already is the next episode's first one and the terminal one rides in info;

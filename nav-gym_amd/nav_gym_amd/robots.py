@@ -63,5 +63,10 @@ def wheels_from_twist(v, omega, radius, track):
     return (v - 0.5 * track * omega) / radius, (v + 0.5 * track * omega) / radius
 
 
+def footprint_radius(footprint):
+    """Largest distance of a footprint's vertices from its origin: the disc ORCA takes the agent for."""
+    return float(max(np.hypot(x, y) for x, y in footprint))
+
+
 def footprint_array(robot, key):
     return np.asarray(ROBOTS[robot][key], dtype=np.float32)

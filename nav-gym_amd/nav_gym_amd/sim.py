@@ -261,6 +261,35 @@ def crowd_local_map(params, free_map, robot, rotate=True):
     return out
 
 
+ORCA_KEYS = ("time_step", "neighbor_dist", "time_horizon", "time_horizon_obst", "max_neighbors")
+PED_ORCA_KEYS = ORCA_KEYS + ("ped_radius", "robot_radius", "safety_space", "robot_visible")
+
+
+def ped_orca_defaults(cfg, robot_type="keti"):
+    """The parameters of navsim_ped_orca as a dict: orca.py:62-65's neighbourhood, the simulator's time step, discs around
+    the footprints of robots.py (the pedestrian's ~ 0.291 m), no safety space, the robot visible."""
+    from . import robots
+    return dict(time_step=cfg.time_step, neighbor_dist=10.0, time_horizon=5.0, time_horizon_obst=5.0, max_neighbors=10,
+                ped_radius=robots.footprint_radius(robots.HUMAN["footprint"]),
+                robot_radius=robots.footprint_radius(robots.ROBOTS[robot_type]["footprint"]),
+                safety_space=0.0, robot_visible=1)
+
+
+def ped_orca_params(cfg, params=None, robot_type="keti"):
+    """abi.NavsimPedOrcaParams of ped_orca_defaults(cfg) overridden by the dict `params`; an unknown key raises ValueError."""
+    d = ped_orca_defaults(cfg, robot_type)
+    for k, v in (params or {}).items():
+        if k not in d:
+            raise ValueError("unknown ORCA parameter %r (known: %s)" % (k, ", ".join(PED_ORCA_KEYS)))
+        d[k] = v
+    p = abi.NavsimPedOrcaParams()
+    for k in ORCA_KEYS:
+        setattr(p.orca, k, int(d[k]) if k == "max_neighbors" else float(d[k]))
+    p.ped_radius, p.robot_radius, p.safety_space = float(d["ped_radius"]), float(d["robot_radius"]), float(d["safety_space"])
+    p.robot_visible = int(bool(d["robot_visible"]))
+    return p
+
+
 def crowd_orca(params, agents, pref_vel, verts=None, n_agents=None, n_obst=None, obst_set=None, theta=None):
     """navsim_crowd_orca: ORCA.predict (orca.py:85-135) for Q pedestrians: agents [Q,A,6] (agent 0 = the pedestrian),
     pref_vel [Q,2], verts [S,O,V,2] CCW polygons -> (new velocity [Q,2], ActionRot (v, r) [Q,2]), float64 tensors."""
@@ -1312,6 +1341,23 @@ class NavSim(object):
                                          _ptr(self.t["policy_prev_actions"]), _ptr(self.t["ped_cmd"]), _ptr(ws),
                                          ws.numel(), _stream()), "navsim_ped_policy")
         return self.t["ped_cmd"], self.t["policy_prev_actions"]
+
+    def ped_orca(self, params=None):
+        """navsim_ped_orca: ORCA pedestrians from the simulator's own state -> ped_cmd for a NAVSIM_PED_EXTERNAL step, one
+        kernel on the simulator's stream (waypoint pop, preferred velocity, neighbours out of LDS, the linear programs).
+        params: None, a dict (ped_orca_params: unknown keys raise ValueError) or a ready abi.NavsimPedOrcaParams.
+        Returns ped_cmd [E,N,2] float64; rows of slots >= n_peds[e] are left as they were."""
+        if not isinstance(params, abi.NavsimPedOrcaParams):
+            if params is None and getattr(self, "_orca_default", None) is not None:
+                params = self._orca_default
+            else:
+                made = ped_orca_params(self.cfg, params)
+                if params is None:
+                    self._orca_default = made
+                params = made
+        check(self.lib.navsim_ped_orca(C.byref(self.cfg), C.byref(self.st), C.byref(params), _ptr(self.t["ped_cmd"]), _stream()),
+              "navsim_ped_orca")
+        return self.t["ped_cmd"]
 
     def ped_scans(self):
         """Scan of every pedestrian (env.py:685-693) from the current state -> float32 [E, N, 512]."""
