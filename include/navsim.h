@@ -817,16 +817,28 @@ typedef struct navsim_orca_params {
  * its goal) and the other agents it sees (preferred velocity 0), plus the static obstacle polygons; one doStep();
  * the new velocity of agent 0 and the ActionRot(v, r = atan2(vy, vx) - theta) made of it.  Only agent 0's
  * velocity is read back, so only it is computed.  rvo2's source is not in the reference tree: the RVO2 Library 2.0
- * algorithm is restated (oracle/navsim_ref.c says where it knowingly differs: no kd-trees) -- UNPINNED.
+ * algorithm is restated (oracle/navsim_ref.c says where it knowingly differs: no kd-trees); its half-plane conventions are
+ * UNPINNED, its solve, neighbour list and obstacle safety are checked independently (below).
  * agents [Q, A, 6] float64 = px, py, vx, vy, radius, max_speed (A <= NAVSIM_ORCA_MAX_AGENTS); n_agents [Q] or NULL;
  * pref_vel [Q,2]; verts [S, O, V, 2] counter-clockwise polygons (O * V <= NAVSIM_ORCA_MAX_EDGES), n_obst [S] or
  * NULL, obst_set [Q] polygon set of each query or NULL (= set 0); theta [Q] or NULL; out_vel [Q,2]; out_action
- * [Q,2] or NULL.  float32 arithmetic like the library's. */
+ * [Q,2] or NULL.  float32 arithmetic like the library's.
+ * What the answer is, apart from how RVO2 computes it: among the velocities within max_speed that satisfy the half-plane
+ * of each of the max_neighbors nearest agents strictly inside neighbor_dist (ties by list order), the one nearest to the
+ * preferred velocity; if there is none, a velocity within max_speed that minimises the largest penetration of an agent
+ * half-plane, obstacle half-planes kept.  Against a float64 evaluation of that statement (tests/orca_f64.py) the velocity
+ * holds to 2e-5 m/s, the largest penetration to 4e-5 and the speed to max_speed + 4e-3 when the program is infeasible and
+ * no two half-plane directions have |det| < 0.01, and the disc swept for time_horizon_obst enters no polygon by more than
+ * 3e-6 m.  NOT bounded: an infeasible program with nearly parallel half-planes.  float32 cancels in linearProgram1's
+ * discriminant there, as in the library: speeds up to 1.37 m/s ABOVE max_speed and velocities 1.5 m/s from the float64
+ * optimum were seen in crowds of 12-16 agents on 2-6 m.  Callers that need |v| <= max_speed clamp.
+ * Degenerate inputs: a half-plane with NaN components (coincident agents with equal velocities) compares false everywhere
+ * and is ignored. */
 int navsim_crowd_orca(const navsim_orca_params* p, int32_t n_queries, int32_t max_agents, const double* agents,
                       const int32_t* n_agents, const double* pref_vel, int32_t max_obst, int32_t n_vert,
                       const double* verts, const int32_t* n_obst, const int32_t* obst_set, const double* theta,
                       double* out_vel, double* out_action, void* stream);
-/* ---- NavGym-v0 pedestrians driven by ORCA (a build-defined model; UNPINNED: rvo2 absent) ----------
+/* ---- NavGym-v0 pedestrians driven by ORCA (a build-defined model; rvo2 absent) ---------------------
  * navsim_ped_orca follows navsim_ped_policy's protocol: called in front of a navsim_step with NAVSIM_PED_EXTERNAL, it fills
  * ped_cmd from the simulator's own state.  For every live pedestrian i < n_peds[e] of every arena e, in float64 unless
  * stated otherwise and with nothing contracted into FMA:
@@ -844,7 +856,8 @@ int navsim_crowd_orca(const navsim_orca_params* p, int32_t n_queries, int32_t ma
  *     function rounds them; neighbour selection, half-planes and linear programs in float32; ActionRot
  *     v = sqrt(vx*vx + vy*vy), r = atan2(vy, vx) - theta (orca.py:128-130).
  *  5. ped_cmd[e,i] = (v, r / cfg->time_step): Human.set_vel's theta + omega dt turns the pedestrian into its ORCA velocity
- *     and it moves by v dt along it.
+ *     and it moves by v dt along it.  Neither Human.set_vel nor the step clamps v: where navsim_crowd_orca exceeds
+ *     max_speed (see there: infeasible, ill-conditioned programs in packed crowds) the pedestrian exceeds ped_v_pref.
  * Rows of slots >= n_peds[e] are left untouched.  Bit-identical to that composition of the oracle's functions.
  * NAVSIM_E_ARG (before any device call): NULL p or ped_cmd, cfg->ped_model != NAVSIM_PED_EXTERNAL,
  * max_peds + robot_visible > NAVSIM_ORCA_MAX_AGENTS, a non-positive radius / time_step / time_horizon, max_neighbors < 0. */
