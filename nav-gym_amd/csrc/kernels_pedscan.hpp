@@ -8,11 +8,17 @@
 // march from the pedestrian's integer cell, bearing-culled polygon merge, clip to 6 m.
 // ============================================================================================
 // The scan of pedestrian i of arena e (n live pedestrians) by its BLOCK-thread workgroup, into rng[0 .. PB) of the
-// dynamic LDS region `dyn` (ped_scan_lds_bytes: float2 dir[PB], float rng[PB], then the rectangle sides of the other agents and
+// dynamic LDS region `dyn` (ped_scan_lds_bytes below: float2 dir[PB], float rng[PB], then the rectangle sides of the other agents and
 // their beam-index intervals (prim_in_range), sized by cfg.max_peds): merged, NOT yet clipped.  Ends with a barrier.
 // tab (optional): cos / sin of the robot-frame beam angles -- the beam direction by beam_dir_fast (one float64 angle
 // addition whose float32 rounding is proven per beam), else the full sincos; identical results.
 struct PedScanShared { double cT, sT; int nseg, i0, j0; float lx, ly, lth; };
+// Host side of that region, in the order of the four pointers ped_scan_core derives: dir (8 B per beam) and rng (4 B per
+// beam), rounded up to 16 B; seg, four sides x 16 B, and info_s, four intervals x 8 B, per other agent (the others + the robot).
+inline size_t ped_scan_lds_bytes(const navsim_config* c) {
+    const size_t beams = (size_t)c->ped_n_beams * (sizeof(float2) + sizeof(float));
+    return ((beams + 15) & ~(size_t)15) + (size_t)(c->max_peds + 1) * (4 * 16 + 4 * 8);
+}
 template <typename Field, int BLOCK, int RULE, bool RECT>
 __device__ __forceinline__ void ped_scan_core(const navsim_config& c, const navsim_state& st, int e, int i, int n,
                                                 const double* __restrict__ tab, char* dyn, PedScanShared& ss) {

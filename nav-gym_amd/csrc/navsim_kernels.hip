@@ -17,11 +17,14 @@
 //   kernels_plan.hpp     shortest paths on the costmap, waypoints, the re-plan of one pedestrian
 //   kernels_reset.hpp    navsim_regen, costmap, navsim_plan, navsim_replan
 //   kernels_policy.hpp   pedestrian control block with the HumanPolicy actor
-//   kernels_pedscan.hpp  pedestrian scans, CrowdSim collision block, beam table, test hooks
+//   kernels_pedscan.hpp  pedestrian scans (+ ped_scan_lds_bytes, host side), CrowdSim collision block, beam table, test hooks
 //   kernels_crowd_maps.hpp  CrowdSim local maps;  kernels_crowd_orca.hpp  CrowdSim pedestrians (ORCA, Agent.step)
 //   kernels_ped_orca.hpp  NavGym pedestrians driven by ORCA from the simulator's state (navsim_ped_orca)
-//   step_plan.hpp        launch geometry of the fused step and the descriptors of a launch (shared by this file and
-//                        navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
+//   step_plan.hpp        launch geometry of the fused step, the descriptors of a launch and the march-rule dispatch (shared by this
+//                        file and navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
+// Host code of this file, ahead of the C ABI: dispatch_step and the argument checks; the workspaces (Carver and one layout
+// function per workspace -- rect_ws, regen_ws, replan_ws, policy_ws -- which the size queries run without a base); the
+// shared launchers launch_dt, launch_build_rects, launch_ped_scan, launch_ped_scan_features.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off per unit (nav-gym_amd/csrc/Makefile, driven by build.sh).
 #include "preamble.hpp"
@@ -268,6 +271,173 @@ RegenFork* regen_fork() {
     return &f;
 }
 
+// ---- workspaces: each layout is written once; its size query is the same walk without a base ----
+// Carves a caller's buffer: every sub-buffer starts on a 256-byte boundary.  base may be null: the pointers are then
+// null and only the offset, the bytes needed so far, means anything.
+struct Carver {
+    char* base;
+    size_t off = 0;
+    template <typename T> T* take(size_t count) {
+        off = (off + 255) & ~(size_t)255;
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += count * sizeof(T);
+        return p;
+    }
+};
+template <typename T> T* at(T* p, size_t i) { return p ? p + i : nullptr; }       // an element of one take (null stays null)
+
+// the rect builder's scratch for m maps: transposed occupancy, then the four int16 run arrays hl, hr, vt, vb
+struct RectWs { uint8_t* occT; int16_t* run[4]; size_t bytes; };
+RectWs rect_ws(void* base, size_t m, size_t cells) {
+    Carver w{(char*)base};
+    RectWs r;
+    r.occT = w.take<uint8_t>(m * cells);
+    int16_t* runs = w.take<int16_t>(4 * m * cells);
+    for (int k = 0; k < 4; ++k) r.run[k] = at(runs, k * m * cells);
+    r.bytes = w.off;
+    return r;
+}
+
+// navsim_regen.  ovf: the exact float plane of large packed maps; rects: rect records to rebuild; plan: cfg.regen_plan
+struct RegenWs {
+    int *count, *list, *slots;      // the selection: count (4 words), the listed arenas, the map slots of the list (navsim_state.map_slot)
+    uint8_t *occ, *grids;           // occupancy scratch, corridor grids
+    uint16_t* cols;                 // column pass of the distance transform
+    char* field;                    // the new maps' fields, fbytes each
+    int* kind; float* ovf; RectWs rect;
+    RegenPlanWs plan;               // (its pointers; navsim_regen fills in the rest)
+    size_t fbytes, bytes;
+};
+RegenWs regen_ws(const navsim_config* c, void* base, bool ovf, bool rects, bool plan) {
+    const size_t M = (size_t)c->regen_cap, cells = (size_t)c->map_h * c->map_w;
+    Carver w{(char*)base};
+    RegenWs r = {};
+    r.count = w.take<int>(4 + 2 * M);
+    r.list = at(r.count, 4);
+    r.slots = at(r.list, M);
+    w.take<uint8_t>((size_t)c->n_envs);                     // (a mask per arena: no kernel uses it any more)
+    r.occ = w.take<uint8_t>(M * cells);
+    r.cols = w.take<uint16_t>(M * cells);
+    r.fbytes = navsim_field_bytes(1, c->map_h, c->map_w, c->field_format);
+    r.field = w.take<char>(M * r.fbytes);
+    r.grids = w.take<uint8_t>(M * 10000);
+    r.kind = w.take<int>(M);
+    if (ovf) r.ovf = w.take<float>(M * cells);
+    if (rects) r.rect = rect_ws(w.take<char>(rect_ws(nullptr, M, cells).bytes), M, cells);
+    if (plan) {
+        const size_t cc = (size_t)(c->map_h / 5) * (c->map_w / 5), P = (size_t)(c->max_waypoints > 0 ? c->max_waypoints : 1);
+        const size_t n = M * kRegenRounds * (size_t)(c->n_spawn > c->max_peds ? c->n_spawn : c->max_peds);     // [M, R, Q]
+        r.plan.cost = w.take<uint8_t>(M * cc);
+        r.plan.qstart = w.take<double>(n * 2);
+        r.plan.qgoal = w.take<double>(n * 2);
+        r.plan.qtheta = w.take<double>(n);
+        r.plan.qwp = w.take<double>(n * P * 2);
+        r.plan.qlen = w.take<double>(n);
+        r.plan.qcut = w.take<unsigned long long>(n);
+        r.plan.qnwp = w.take<int32_t>(n);
+        r.plan.active = w.take<uint8_t>(n);
+        r.plan.res_robot = w.take<uint8_t>(M * (size_t)c->n_spawn);
+    }
+    r.bytes = w.off;
+    return r;
+}
+// The layout of a call on `st`: the optional parts that state asks for.  Every sub-buffer sits at a sum of 256-rounded sizes
+// of the parts taken before it, so a call that leaves parts out puts nothing further back and never needs more than
+// navsim_regen_workspace_bytes, which takes every part that cfg alone cannot exclude.
+RegenWs regen_ws_of(const navsim_config* c, const navsim_state* st, void* base) {
+    return regen_ws(c, base, c->field_format == NAVSIM_FIELD_U16T && st->field_overflow,
+                    st->rect_table && c->regen_indoor_ratio > 0.0, c->regen_plan != 0);
+}
+
+// navsim_replan.  due: the flags of the pass over the state (a state without ped_due).  The 256 bytes and the max_queries
+// words ahead of them are not used: they held an earlier form's counter and query list, and keep the query what it was.
+struct ReplanWs { uint64_t* due; size_t bytes; };
+ReplanWs replan_ws(const navsim_config* c, int32_t max_queries, void* base, bool due) {
+    Carver w{(char*)base};
+    ReplanWs r = {};
+    w.take<char>(256);
+    w.take<int32_t>((size_t)max_queries);
+    if (due) r.due = w.take<uint64_t>((size_t)c->n_envs);
+    r.bytes = w.off;
+    return r;
+}
+
+// navsim_ped_policy / navsim_ped_scan_policy, `chunk` pedestrians per pass
+constexpr int kPolicyChunk = 32768;          // pedestrians per pass: bounds the feature scratch (512 MiB)
+size_t policy_chunk(const navsim_config* c) {
+    const size_t P = (size_t)c->n_envs * (size_t)c->max_peds;
+    return P < (size_t)kPolicyChunk ? P : (size_t)kPolicyChunk;
+}
+struct PolicyWs {
+    float *w2t, *cv2t;              // fc2 and conv2 weights, transposed (policy_transpose_kernel)
+    double* tab;                    // cos / sin of the 512 beam angles
+    float *feat, *h1;               // [chunk, kPolFeat], [chunk, kPolH1]
+    size_t bytes;
+};
+PolicyWs policy_ws(void* base, size_t chunk) {
+    Carver w{(char*)base};
+    PolicyWs r;
+    r.w2t = w.take<float>(kPolH2 * kPolIn2);
+    r.cv2t = w.take<float>(32 * 32 * 3);
+    r.tab = w.take<double>(2 * 512);
+    r.feat = w.take<float>(chunk * kPolFeat);
+    r.h1 = w.take<float>(chunk * kPolH1);
+    r.bytes = w.off;
+    return r;
+}
+
+// the two passes of the distance transform for `m` maps: columns into cols, rows into field (format; a packed field also
+// fills overflow / n_saturated where given); count + kind: navsim_regen's slot list and map kinds
+void launch_dt(const uint8_t* occ, int m, int H, int W, uint16_t* cols, int format, void* field, float* overflow,
+               int32_t* n_saturated, const int* count, const int* kind, hipStream_t s) {
+    dt_columns_kernel<<<dim3((W + 63) / 64, m), 64 * kColSeg, 0, s>>>(occ, cols, H, W, count, kind);
+    if (format == NAVSIM_FIELD_F32)
+        dt_rows_kernel<0><<<dim3(H, m), 256, (size_t)W * 4, s>>>(cols, field, nullptr, nullptr, H, W, count, kind);
+    else
+        dt_rows_kernel<1><<<dim3(H, m), 256, (size_t)W * 4, s>>>(cols, field, overflow, n_saturated, H, W, count, kind);
+}
+
+// the three builder passes for `m` maps whose occupancy / field start at occ / field (per-map strides cells /
+// field_stride), on the scratch r = rect_ws(m maps); n_live + list: navsim_regen's slot indirection (see rect_tiles_kernel)
+void launch_build_rects(const uint8_t* occ, int m, int H, int W, const void* field, size_t field_stride, int format,
+                        const float* overflow, uint4* table, const RectWs& r, const int* n_live, const int* list, hipStream_t s) {
+    int16_t *hl = r.run[0], *hr = r.run[1], *vt = r.run[2], *vb = r.run[3];
+    rect_transpose_kernel<<<dim3((W + 31) / 32, (H + 31) / 32, m), 256, 0, s>>>(occ, r.occT, H, W, n_live);
+    rect_runs_kernel<<<dim3(H > W ? H : W, m, 2), 256, (size_t)(H > W ? H : W) * 2 * sizeof(int16_t), s>>>(
+        occ, hl, hr, r.occT, vt, vb, H, W, n_live);
+    const int n_tiles = (int)rect_tiles_per_map(H, W);
+    rect_tiles_kernel<<<dim3((n_tiles + 3) / 4, m), 256, 0, s>>>(occ, hl, hr, vt, vb, H, W, field, overflow, format,
+                                                                field_stride, table, n_live, list);
+}
+
+// the pedestrian scans' kernels for one field type: the march rule becomes their template argument (with_march_rule)
+#ifndef NAVSIM_ONLY_RULE
+// (Never launched: a float32 field takes no kMarchF64Exact32.  The library has always carried the two; pruning is another change.)
+template __global__ void ped_scan_kernel<FieldF32, 128, kMarchF64Exact32, false>(navsim_config, navsim_state, float* __restrict__, int);
+template __global__ void ped_scan_features_kernel<FieldF32, kMarchF64Exact32, false>(
+    navsim_config, navsim_state, int, int, const double* __restrict__, float* __restrict__, const float* __restrict__,
+    const float* __restrict__, const float* __restrict__, const float* __restrict__, float* __restrict__);
+#endif
+template <typename F, bool RECT>
+int launch_ped_scan(const navsim_config* c, const navsim_state* st, float* out, int e0, int n_e, hipStream_t s) {
+    // 128 threads per pedestrian (measured 64 / 128 / 256 / 512: 1.11 / 0.78 / 0.93 / 1.50 ms on c3)
+    return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
+        ped_scan_kernel<F, 128, decltype(rule)::value, RECT><<<dim3(c->max_peds, n_e), 128, ped_scan_lds_bytes(c), s>>>(*c, *st, out, e0);
+        return NAVSIM_OK;
+    });
+}
+template <typename F, bool RECT>
+int launch_ped_scan_features(const navsim_config* c, const navsim_state* st, int p0, int n, const PolicyWs& ws, float* scans_out,
+                             const navsim_policy_weights* w, hipStream_t s) {
+    // dynamic LDS: the scan region (navsim_ped_scans) and conv1's output [kConvCh][258] share it
+    const size_t lds = ped_scan_lds_bytes(c) < kConvLdsBytes ? kConvLdsBytes : ped_scan_lds_bytes(c);
+    return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
+        ped_scan_features_kernel<F, decltype(rule)::value, RECT><<<n, 256, lds, s>>>(*c, *st, p0, n, ws.tab, scans_out, w->cv1_w, w->cv1_b,
+                                                                                  ws.cv2t, w->cv2_b, ws.feat);
+        return NAVSIM_OK;
+    });
+}
+
 }  // namespace
 
 
@@ -437,14 +607,8 @@ int navsim_build_field(const uint8_t* occ, int32_t n_maps, int32_t H, int32_t W,
         (void)hipMemsetAsync(field, 0xFF, field_per_map * (size_t)n_maps, s);
     for (int32_t m0 = 0; m0 < n_maps; m0 += (int32_t)chunk) {
         int32_t m = (n_maps - m0 < (int32_t)chunk) ? n_maps - m0 : (int32_t)chunk;
-        dt_columns_kernel<<<dim3((W + 63) / 64, m), 64 * kColSeg, 0, s>>>(occ + (size_t)m0 * H * W,
-                                                                   (uint16_t*)workspace, H, W, nullptr);
-        void* f = (char*)field + field_per_map * (size_t)m0;
-        float* o = overflow ? overflow + (size_t)m0 * H * W : nullptr;
-        if (format == NAVSIM_FIELD_F32)
-            dt_rows_kernel<0><<<dim3(H, m), 256, (size_t)W * 4, s>>>((const uint16_t*)workspace, f, nullptr, nullptr, H, W, nullptr);
-        else
-            dt_rows_kernel<1><<<dim3(H, m), 256, (size_t)W * 4, s>>>((const uint16_t*)workspace, f, o, n_saturated, H, W, nullptr);
+        launch_dt(occ + (size_t)m0 * H * W, m, H, W, (uint16_t*)workspace, format, (char*)field + field_per_map * (size_t)m0,
+                  overflow ? overflow + (size_t)m0 * H * W : nullptr, n_saturated, nullptr, nullptr, s);
     }
     return launch_status();
 }
@@ -454,30 +618,13 @@ size_t navsim_rect_table_bytes(int32_t n_maps, int32_t H, int32_t W) {
     return (size_t)n_maps * rect_tiles_per_map(H, W) * sizeof(uint4);
 }
 
-// scratch per map: transposed occupancy (1 byte per cell) + four int16 run arrays
+// Scratch per map: transposed occupancy (1 byte per cell) + four int16 run arrays, rounded up to 256 bytes.  A caller who
+// wants n_maps maps built in a single pass adds 256 bytes to the product (rect_ws rounds once per array, not per map);
+// with less, navsim_build_rects takes the maps in chunks.
 constexpr size_t kRectWsPerCell = 1 + 4 * sizeof(int16_t);
 size_t navsim_build_rects_workspace_bytes(int32_t n_maps, int32_t H, int32_t W) {
     if (n_maps <= 0 || H <= 0 || W <= 0) return 0;
     return (size_t)n_maps * (((size_t)H * W * kRectWsPerCell + 255) & ~(size_t)255);
-}
-
-// the three builder passes for `m` maps whose occupancy / field start at occ / field (per-map strides cells /
-// field_stride); n_live + list: navsim_regen's slot indirection (see rect_tiles_kernel)
-static void launch_build_rects(const uint8_t* occ, int m, int H, int W, const void* field, size_t field_stride,
-                               int format, const float* overflow, uint4* table, char* ws, const int* n_live,
-                               const int* list, hipStream_t s) {
-    const size_t cells = (size_t)H * W;
-    uint8_t* occT = (uint8_t*)ws;
-    int16_t* hl = (int16_t*)(ws + (((size_t)m * cells + 255) & ~(size_t)255));
-    int16_t* hr = hl + (size_t)m * cells;
-    int16_t* vt = hr + (size_t)m * cells;
-    int16_t* vb = vt + (size_t)m * cells;
-    rect_transpose_kernel<<<dim3((W + 31) / 32, (H + 31) / 32, m), 256, 0, s>>>(occ, occT, H, W, n_live);
-    rect_runs_kernel<<<dim3(H > W ? H : W, m, 2), 256, (size_t)(H > W ? H : W) * 2 * sizeof(int16_t), s>>>(
-        occ, hl, hr, occT, vt, vb, H, W, n_live);
-    const int n_tiles = (int)rect_tiles_per_map(H, W);
-    rect_tiles_kernel<<<dim3((n_tiles + 3) / 4, m), 256, 0, s>>>(occ, hl, hr, vt, vb, H, W, field, overflow, format,
-                                                                field_stride, table, n_live, list);
 }
 
 int navsim_build_rects(const uint8_t* occ, int32_t n_maps, int32_t H, int32_t W, const void* field, int32_t format,
@@ -487,10 +634,10 @@ int navsim_build_rects(const uint8_t* occ, int32_t n_maps, int32_t H, int32_t W,
     if (format != NAVSIM_FIELD_F32 && format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
     if (H > 1024 || W > 1024) return NAVSIM_E_UNSUPPORTED;                 // int16 runs, 4 cells per thread in the scans
     const size_t cells = (size_t)H * W;
-    const size_t per_map = navsim_build_rects_workspace_bytes(1, H, W) + 256;
-    size_t chunk = workspace_bytes / per_map;
-    if (chunk == 0) return NAVSIM_E_ARG;
+    size_t chunk = workspace_bytes / (cells * kRectWsPerCell);             // the largest chunk whose layout fits
     if (chunk > 32768) chunk = 32768;
+    while (chunk > 0 && rect_ws(nullptr, chunk, cells).bytes > workspace_bytes) --chunk;
+    if (chunk == 0) return NAVSIM_E_ARG;
     hipStream_t s = (hipStream_t)stream;
     const size_t fstride = navsim_field_bytes(1, H, W, format);
     const size_t n_tiles = rect_tiles_per_map(H, W);
@@ -498,7 +645,7 @@ int navsim_build_rects(const uint8_t* occ, int32_t n_maps, int32_t H, int32_t W,
         const int32_t m = (n_maps - m0 < (int32_t)chunk) ? n_maps - m0 : (int32_t)chunk;
         launch_build_rects(occ + (size_t)m0 * cells, m, H, W, (const char*)field + fstride * (size_t)m0, fstride, format,
                            overflow ? overflow + (size_t)m0 * cells : nullptr, (uint4*)table + (size_t)m0 * n_tiles,
-                           (char*)workspace, nullptr, nullptr, s);
+                           rect_ws(workspace, (size_t)m, cells), nullptr, nullptr, s);
     }
     return launch_status();
 }
@@ -592,31 +739,13 @@ int navsim_ped_scans_part(const navsim_config* c, const navsim_state* st, float*
     if (e0 < 0 || n_e < 0 || (long)e0 + n_e > c->n_envs) return NAVSIM_E_ARG;
     if (c->max_peds > NAVSIM_MAX_PEDS || c->ped_n_beams > 4096) return NAVSIM_E_UNSUPPORTED;
     if (n_e == 0) return NAVSIM_OK;
-    dim3 grid(c->max_peds, n_e);
-    // dir + rng per beam, then 4 sides x 16 B + 4 intervals x 8 B per other agent (kernels_pedscan.hpp)
-    size_t lds = (((size_t)c->ped_n_beams * (sizeof(float2) + sizeof(float)) + 15) & ~(size_t)15) + (size_t)(c->max_peds + 1) * (64 + 32);
     hipStream_t s = (hipStream_t)stream;
-    // 128 threads per pedestrian (measured 64 / 128 / 256 / 512: 1.11 / 0.78 / 0.93 / 1.50 ms on c3)
-    const int rule = march_rule_variant(c);
-#ifdef NAVSIM_ONLY_RULE
-    if (rule != NAVSIM_ONLY_RULE) return NAVSIM_E_UNSUPPORTED;
-#define NAVSIM_PSCAN(F, RECT) ped_scan_kernel<F, 128, NAVSIM_ONLY_RULE, RECT><<<grid, 128, lds, s>>>(*c, *st, out, e0)
-#else
-#define NAVSIM_PSCAN(F, RECT) \
-    do { if (rule == NAVSIM_MARCH_F32)      ped_scan_kernel<F, 128, NAVSIM_MARCH_F32, RECT><<<grid, 128, lds, s>>>(*c, *st, out, e0); \
-         else if (rule == NAVSIM_MARCH_F32_FMA) ped_scan_kernel<F, 128, NAVSIM_MARCH_F32_FMA, RECT><<<grid, 128, lds, s>>>(*c, *st, out, e0); \
-         else if (rule == kMarchF64Exact32 && !std::is_same<F, FieldF32>::value) \
-                                            ped_scan_kernel<F, 128, kMarchF64Exact32, RECT><<<grid, 128, lds, s>>>(*c, *st, out, e0); \
-         else                               ped_scan_kernel<F, 128, NAVSIM_MARCH_F64, RECT><<<grid, 128, lds, s>>>(*c, *st, out, e0); } while (0)
-#endif
-    if (c->field_format == NAVSIM_FIELD_U16T) {
-        if (st->rect_table) NAVSIM_PSCAN(FieldU16T, true); else NAVSIM_PSCAN(FieldU16T, false);
-    } else if (c->field_format == NAVSIM_FIELD_F32) {
-        NAVSIM_PSCAN(FieldF32, false);
-    } else {
-        return NAVSIM_E_UNSUPPORTED;
-    }
-#undef NAVSIM_PSCAN
+    int rc = NAVSIM_E_UNSUPPORTED;
+    if (c->field_format == NAVSIM_FIELD_U16T)
+        rc = st->rect_table ? launch_ped_scan<FieldU16T, true>(c, st, out, e0, n_e, s) : launch_ped_scan<FieldU16T, false>(c, st, out, e0, n_e, s);
+    else if (c->field_format == NAVSIM_FIELD_F32)
+        rc = launch_ped_scan<FieldF32, false>(c, st, out, e0, n_e, s);
+    if (rc != NAVSIM_OK) return rc;
     return launch_status();
 }
 
@@ -645,28 +774,9 @@ int navsim_plan(const uint8_t* cost, const int32_t* map_index, int32_t n, int32_
 
 size_t navsim_regen_workspace_bytes(const navsim_config* c) {
     if (!c || c->regen_cap < 1) return 0;
-    const size_t M = (size_t)c->regen_cap, cells = (size_t)c->map_h * c->map_w;
-    size_t b = 16 + M * 8;                                  // count, list, map slots of the list (navsim_state.map_slot)
-    b = (b + 255) & ~(size_t)255;
-    b += ((size_t)c->n_envs + 255) & ~(size_t)255;          // mask
-    b += M * cells;                                         // occupancy scratch
-    b += M * cells * sizeof(uint16_t);                      // column pass
-    b += M * navsim_field_bytes(1, c->map_h, c->map_w, c->field_format);
-    if (c->field_format == NAVSIM_FIELD_U16T) {             // rect records of the regenerated arenas; the exact
-        b += navsim_build_rects_workspace_bytes((int32_t)M, c->map_h, c->map_w) + 512;      // float plane of maps
-        if (c->map_h > kRegenMaxPackedSide) b += M * cells * sizeof(float) + 256;           // that can saturate
-    }
-    b += M * (10000 + sizeof(int)) + 512;                   // corridor grids, map kinds
-    if (c->regen_plan) {
-        const size_t cc = (size_t)(c->map_h / 5) * (c->map_w / 5), P = (size_t)(c->max_waypoints > 0 ? c->max_waypoints : 1);
-        const size_t Q = (size_t)(c->n_spawn > c->max_peds ? c->n_spawn : c->max_peds), R = kRegenRounds;
-        b += M * cc + 256;                                            // costmaps
-        b += M * R * Q * (2 + 2 + 1 + 2 * P + 1 + 1) * sizeof(double) + 256;   // start, goal, heading, waypoints, length, cut flag
-        b += M * R * Q * sizeof(int32_t) + 256;                       // waypoint counts
-        b += M * (R * Q + (size_t)c->n_spawn) + 256;                  // active, resolved flags
-        b += 12 * 256;                                                // alignment of the sub-buffers
-    }
-    return b + 1024;
+    // no state to ask: a packed field may keep rect records, and comes with the float plane above kRegenMaxPackedSide cells per side
+    const bool packed = c->field_format == NAVSIM_FIELD_U16T;
+    return regen_ws(c, nullptr, packed && c->map_h > kRegenMaxPackedSide, packed, c->regen_plan != 0).bytes;
 }
 
 int navsim_regen_helper(void* stream) {
@@ -694,7 +804,8 @@ int navsim_regen(const navsim_config* c, const navsim_state* st, const navsim_st
     if (c->field_format == NAVSIM_FIELD_U16T && (big != (st->field_overflow != nullptr))) return NAVSIM_E_UNSUPPORTED;
     if (c->field_format == NAVSIM_FIELD_F32 && st->field_overflow) return NAVSIM_E_UNSUPPORTED;
     if (st->rect_table && (c->field_format != NAVSIM_FIELD_U16T || c->map_h > 1024)) return NAVSIM_E_UNSUPPORTED;
-    if (workspace_bytes < navsim_regen_workspace_bytes(c) || !st->spawn_pose || !st->spawn_goal) return NAVSIM_E_ARG;
+    const RegenWs ws = regen_ws_of(c, st, workspace);
+    if (ws.bytes > workspace_bytes || !st->spawn_pose || !st->spawn_goal) return NAVSIM_E_ARG;
     if (c->regen_plan && (c->max_waypoints < 1 || c->max_waypoints > NAVSIM_MAX_WAYPOINTS)) return NAVSIM_E_ARG;
     if (c->regen_min_steps < 0 || (c->regen_min_steps > 0 && !st->done_steps)) return NAVSIM_E_ARG;
     if (c->regen_plan && (c->n_spawn > 256 || c->map_h < 5 || !plan_fits(c->map_h / 5, c->map_w / 5) ||
@@ -706,29 +817,12 @@ int navsim_regen(const navsim_config* c, const navsim_state* st, const navsim_st
     hipStream_t s = (hipStream_t)stream;
     const int M = c->regen_cap, H = c->map_h, W = c->map_w;
     const size_t cells = (size_t)H * W;
-    char* w = (char*)workspace;
-    int* count = (int*)w;
-    int* list = count + 4;
-    int* mlist = st->map_slot ? list + M : list;            // where the maps of the listed arenas live (regen_map_list_kernel)
-    size_t off = (16 + (size_t)M * 8 + 255) & ~(size_t)255;
-    uint8_t* mask = (uint8_t*)(w + off);
-    off += ((size_t)c->n_envs + 255) & ~(size_t)255;
-    uint8_t* occ = (uint8_t*)(w + off);
-    off += (size_t)M * cells;
-    off = (off + 255) & ~(size_t)255;
-    uint16_t* cols = (uint16_t*)(w + off);
-    off += (size_t)M * cells * sizeof(uint16_t);
-    off = (off + 255) & ~(size_t)255;
-    char* fscratch = w + off;
-    const size_t fbytes = navsim_field_bytes(1, H, W, c->field_format);
-    off += fbytes * (size_t)M;
-    off = (off + 255) & ~(size_t)255;
-    uint8_t* grids = (uint8_t*)(w + off);
-    off += (size_t)M * 10000;
-    off = (off + 255) & ~(size_t)255;
-    int* kind = (int*)(w + off);
-    off += (size_t)M * sizeof(int);
-    (void)mask;
+    int *count = ws.count, *list = ws.list, *kind = ws.kind;
+    int* mlist = st->map_slot ? ws.slots : list;            // where the maps of the listed arenas live (regen_map_list_kernel)
+    uint8_t *occ = ws.occ, *grids = ws.grids;
+    char* fscratch = ws.field;
+    const size_t fbytes = ws.fbytes;
+    float* ovf_scratch = ws.ovf;                            // exact float plane of the new maps (large packed maps), or null
     // opens the call: every workgroup selects its arena from the done flags (list[b], -1 = none; count), draws the
     // per-episode parameters and the map kind, grows the corridor tree of a corridor map
     // (worlds of outdoor maps only: regen_maps_kernel opens the call itself, one launch less)
@@ -738,12 +832,6 @@ int navsim_regen(const navsim_config* c, const navsim_state* st, const navsim_st
     uint4* direct_rects = (direct && st->rect_table) ? (uint4*)st->rect_table : nullptr;
     char* direct_index = (direct_rects && st->rect_index) ? (char*)st->rect_index : nullptr;
     if (!direct) regen_indoor_kernel<<<M, 256, 0, s>>>(*c, *st, io->done, M, count, list, grids, kind);
-    float* ovf_scratch = nullptr;                           // exact float plane of the new maps (large packed maps)
-    if (c->field_format == NAVSIM_FIELD_U16T && st->field_overflow) {
-        off = (off + 255) & ~(size_t)255;
-        ovf_scratch = (float*)(w + off);
-        off += (size_t)M * cells * sizeof(float);
-    }
     // Outdoor maps only and no rect records to rebuild: the field of a new map is written straight into the arena's
     // own buffers (no per-slot scratch, no copy kernel), and the occupancy scratch only if a costmap wants it.
     const bool need_occ = !direct || c->regen_plan || st->costmap;
@@ -769,18 +857,9 @@ int navsim_regen(const navsim_config* c, const navsim_state* st, const navsim_st
         if (hipEventRecord(fk->forked, s) != hipSuccess || hipStreamWaitEvent(fk->side, fk->forked, 0) != hipSuccess) fk = nullptr;
         else sf = fk->side;
     }
-    if (c->regen_indoor_ratio > 0.0) {
-        dt_columns_kernel<<<dim3((W + 63) / 64, M), 64 * kColSeg, 0, sf>>>(occ, cols, H, W, count, kind);
-        if (c->field_format == NAVSIM_FIELD_F32)
-            dt_rows_kernel<0><<<dim3(H, M), 256, (size_t)W * 4, sf>>>(cols, fscratch, nullptr, nullptr, H, W, count, kind);
-        else
-            dt_rows_kernel<1><<<dim3(H, M), 256, (size_t)W * 4, sf>>>(cols, fscratch, ovf_scratch, nullptr, H, W, count, kind);
-    }
+    if (!direct) launch_dt(occ, M, H, W, ws.cols, c->field_format, fscratch, ovf_scratch, nullptr, count, kind, sf);
     if (st->rect_table && !direct) {                        // keep the rect records of the regenerated arenas current
-        off = (off + 255) & ~(size_t)255;
-        char* rect_ws = w + off;
-        off += navsim_build_rects_workspace_bytes(M, H, W) + 256;
-        launch_build_rects(occ, M, H, W, fscratch, fbytes, c->field_format, ovf_scratch, (uint4*)st->rect_table, rect_ws,
+        launch_build_rects(occ, M, H, W, fscratch, fbytes, c->field_format, ovf_scratch, (uint4*)st->rect_table, ws.rect,
                            count, mlist, sf);
         if (st->rect_index)
             rect_index_kernel<<<M, 256, 0, sf>>>((const uint4*)st->rect_table, H, W, (char*)st->rect_index, nullptr, count, mlist);
@@ -797,27 +876,14 @@ int navsim_regen(const navsim_config* c, const navsim_state* st, const navsim_st
         if (join_pending) { (void)hipStreamWaitEvent(s, fk->joined, 0); join_pending = false; }
     };
     if (c->regen_plan) {
-        const int Hc = H / 5, Wc = W / 5, P = c->max_waypoints, R = kRegenRounds;
-        const size_t cc = (size_t)Hc * Wc;
-        const int Q = c->n_spawn > c->max_peds ? c->n_spawn : c->max_peds;
-        auto take = [&](size_t bytes) { off = (off + 255) & ~(size_t)255; char* p = w + off; off += bytes; return p; };
-        RegenPlanWs ws;
-        ws.Q = Q;
-        ws.kind = kind;
-        ws.cost = (uint8_t*)take((size_t)M * cc);
-        ws.cost_by_arena = st->costmap != nullptr;
-        if (st->costmap) ws.cost = st->costmap;
-        ws.qstart = (double*)take((size_t)M * R * Q * 2 * sizeof(double));
-        ws.qgoal = (double*)take((size_t)M * R * Q * 2 * sizeof(double));
-        ws.qtheta = (double*)take((size_t)M * R * Q * sizeof(double));
-        ws.qwp = (double*)take((size_t)M * R * Q * P * 2 * sizeof(double));
-        ws.qlen = (double*)take((size_t)M * R * Q * sizeof(double));
-        ws.qcut = (unsigned long long*)take((size_t)M * R * Q * sizeof(unsigned long long));
-        ws.qnwp = (int32_t*)take((size_t)M * R * Q * sizeof(int32_t));
-        ws.active = (uint8_t*)take((size_t)M * R * Q);
-        ws.res_robot = (uint8_t*)take((size_t)M * c->n_spawn);
+        const int Hc = H / 5, Wc = W / 5, R = kRegenRounds;
+        RegenPlanWs pw = ws.plan;                            // the scratch arrays; the costmap is the resident one where there is one
+        pw.Q = c->n_spawn > c->max_peds ? c->n_spawn : c->max_peds;
+        pw.kind = kind;
+        pw.cost_by_arena = st->costmap != nullptr;
+        if (st->costmap) pw.cost = st->costmap;
         const size_t lds = plan_lds(Hc, Wc);
-        costmap_kernel<<<dim3(((int)cc + 255) / 256, M), 256, 0, s>>>(occ, H, W, ws.cost, count,
+        costmap_kernel<<<dim3((Hc * Wc + 255) / 256, M), 256, 0, s>>>(occ, H, W, pw.cost, count,
                                                                       st->costmap ? mlist : nullptr);
         // the rounds of the reference's rejection loops (kernels_reset.hpp): all candidates drawn at once, round 0 planned, then
         // rounds 1-3 of the slots it left open in one launch, the first round that passes taken -- four launches per stage
@@ -829,21 +895,21 @@ int navsim_regen(const navsim_config* c, const navsim_state* st, const navsim_st
             // CU) waits for its longest search; a staging pass of dozens of arenas is thousands of searches -- generations of
             // workgroups -- and gets through them faster twice as many at a time (round 6).
             const bool many = (long long)grid > (long long)NAVSIM_PLAN_MANY_SEARCHES && plan_words(Hc, Wc) <= 2 * 512;
-            if (plan_block(Hc, Wc) == 1024 && many) regen_plan_kernel<512><<<grid, 512, lds, s>>>(*c, *st, count, list, ws, ped_stage, pass, Qs);
-            else if (plan_block(Hc, Wc) == 1024)    regen_plan_kernel<1024><<<grid, 1024, lds, s>>>(*c, *st, count, list, ws, ped_stage, pass, Qs);
-            else                                    regen_plan_kernel<256><<<grid, 256, lds, s>>>(*c, *st, count, list, ws, ped_stage, pass, Qs);
+            if (plan_block(Hc, Wc) == 1024 && many) regen_plan_kernel<512><<<grid, 512, lds, s>>>(*c, *st, count, list, pw, ped_stage, pass, Qs);
+            else if (plan_block(Hc, Wc) == 1024)    regen_plan_kernel<1024><<<grid, 1024, lds, s>>>(*c, *st, count, list, pw, ped_stage, pass, Qs);
+            else                                    regen_plan_kernel<256><<<grid, 256, lds, s>>>(*c, *st, count, list, pw, ped_stage, pass, Qs);
         };
-        regen_robot_sample_kernel<<<M, 256, 0, s>>>(*c, *st, count, list, ws);
+        regen_robot_sample_kernel<<<M, 256, 0, s>>>(*c, *st, count, list, pw);
         plan_pass(0, 0);
         plan_pass(0, 1);
         join();
-        if (c->field_format == NAVSIM_FIELD_F32) regen_robot_accept_kernel<FieldF32><<<M, 256, 0, s>>>(*c, *st, count, list, ws);
-        else                                     regen_robot_accept_kernel<FieldU16T><<<M, 256, 0, s>>>(*c, *st, count, list, ws);
+        if (c->field_format == NAVSIM_FIELD_F32) regen_robot_accept_kernel<FieldF32><<<M, 256, 0, s>>>(*c, *st, count, list, pw);
+        else                                     regen_robot_accept_kernel<FieldU16T><<<M, 256, 0, s>>>(*c, *st, count, list, pw);
         if (c->ped_model != NAVSIM_PED_NONE && c->max_peds > 0) {
-            regen_ped_sample_kernel<<<M, 256, 0, s>>>(*c, *st, count, list, ws);
+            regen_ped_sample_kernel<<<M, 256, 0, s>>>(*c, *st, count, list, pw);
             plan_pass(1, 0);
             plan_pass(1, 1);
-            regen_ped_accept_kernel<<<M, 256, 0, s>>>(*c, *st, count, list, ws);
+            regen_ped_accept_kernel<<<M, 256, 0, s>>>(*c, *st, count, list, pw);
         }
     } else if (st->costmap) {
         costmap_kernel<<<dim3(((H / 5) * (W / 5) + 255) / 256, M), 256, 0, s>>>(occ, H, W, st->costmap, count, mlist);
@@ -939,14 +1005,14 @@ int navsim_regen_stage_part(const navsim_config* c, const navsim_state* stage, c
     cs.regen_min_steps = 0;
     const int rc = navsim_regen(&cs, stage, io, workspace, workspace_bytes, stream);
     if (rc != NAVSIM_OK) return rc;
-    const int* count = (const int*)workspace;                // navsim_regen's selection: count, list
-    regen_clear_want_kernel<<<1, 256, 0, (hipStream_t)stream>>>(count, count + 4, want, ready, c->n_envs);
+    const RegenWs ws = regen_ws_of(&cs, stage, workspace);   // navsim_regen's selection: count, list
+    regen_clear_want_kernel<<<1, 256, 0, (hipStream_t)stream>>>(ws.count, ws.list, want, ready, c->n_envs);
     return launch_status();
 }
 
 size_t navsim_replan_workspace_bytes(const navsim_config* c, int32_t max_queries) {
     if (!c || max_queries < 0) return 0;
-    return 256 + (((size_t)max_queries * sizeof(int32_t) + 255) & ~(size_t)255) + (size_t)c->n_envs * sizeof(uint64_t);
+    return replan_ws(c, max_queries, nullptr, true).bytes;
 }
 
 int navsim_replan(const navsim_config* c, const navsim_state* st, int32_t max_queries, void* workspace,
@@ -955,16 +1021,17 @@ int navsim_replan(const navsim_config* c, const navsim_state* st, int32_t max_qu
     if (!c || !st || !workspace || max_queries < 0 || !st->costmap || !st->ped_pose || !st->ped_waypoints ||
         !st->ped_n_waypoints || !st->ped_wp_head || !st->n_peds || !st->steps || !st->episode)
         return NAVSIM_E_ARG;
-    if (workspace_bytes < navsim_replan_workspace_bytes(c, max_queries)) return NAVSIM_E_ARG;
+    // (without the flags' array the layout is only shorter: it comes last)
+    const ReplanWs ws = replan_ws(c, max_queries, workspace, st->ped_due == nullptr);
+    if (ws.bytes > workspace_bytes) return NAVSIM_E_ARG;
     if (c->ped_model == NAVSIM_PED_NONE || c->n_envs == 0) return NAVSIM_OK;
     if (c->max_waypoints < 1 || c->max_waypoints > NAVSIM_MAX_WAYPOINTS) return NAVSIM_E_ARG;
     const int Hc = c->map_h / 5, Wc = c->map_w / 5;
     if (Hc < 1 || Wc < 1 || !plan_fits(Hc, Wc) || plan_lds(Hc, Wc) > 64 * 1024) return NAVSIM_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    uint64_t* due = (uint64_t*)((char*)workspace + 256 + (((size_t)max_queries * sizeof(int32_t) + 255) & ~(size_t)255));
     // who is due: the flags the last step left in st->ped_due (ABI 5), else a pass over the state
     const uint64_t* flags = (const uint64_t*)st->ped_due;
-    if (!flags) { replan_flag_kernel<<<c->n_envs, 64, 0, s>>>(*c, *st, due); flags = due; }
+    if (!flags) { replan_flag_kernel<<<c->n_envs, 64, 0, s>>>(*c, *st, ws.due); flags = ws.due; }
     // one workgroup per query slot; each finds its own pedestrian in the flags (replan_pick), slot 0 counts.  At least one
     // workgroup even at max_queries = 0: the call still counts who waits.
     if (plan_block(Hc, Wc) == 1024) replan_kernel<1024><<<max_queries > 0 ? max_queries : 1, 1024, plan_lds(Hc, Wc), s>>>(*c, *st, flags, max_queries);
@@ -972,13 +1039,8 @@ int navsim_replan(const navsim_config* c, const navsim_state* st, int32_t max_qu
     return launch_status();
 }
 
-constexpr int kPolicyChunk = 32768;          // pedestrians per pass: bounds the feature scratch (512 MiB)
-
 size_t navsim_ped_policy_workspace_bytes(const navsim_config* c) {
-    if (!c) return 0;
-    size_t P = (size_t)c->n_envs * (size_t)c->max_peds;
-    size_t chunk = P < (size_t)kPolicyChunk ? P : (size_t)kPolicyChunk;
-    return 2048 + 8192 + (size_t)(kPolH2 * kPolIn2 + 32 * 32 * 3) * sizeof(float) + chunk * (size_t)(kPolFeat + kPolH1) * sizeof(float);
+    return c ? policy_ws(nullptr, policy_chunk(c)).bytes : 0;
 }
 
 // ped_scans != NULL: the network reads those scans (navsim_ped_policy); NULL: every chunk's scans are taken by the fused
@@ -995,7 +1057,9 @@ static int ped_policy_run(const navsim_config* c, const navsim_state* st, const 
         return NAVSIM_E_ARG;
     if (c->ped_n_beams != 512 || c->max_peds < 1) return NAVSIM_E_UNSUPPORTED;
     if (c->max_waypoints < 1 || c->max_waypoints > NAVSIM_MAX_WAYPOINTS) return NAVSIM_E_ARG;
-    if (workspace_bytes < navsim_ped_policy_workspace_bytes(c)) return NAVSIM_E_ARG;
+    const size_t chunk = policy_chunk(c);                             // (the workspace's capacity)
+    const PolicyWs ws = policy_ws(workspace, chunk);
+    if (ws.bytes > workspace_bytes) return NAVSIM_E_ARG;
     const bool fused = ped_scans == nullptr;
     if (fused) {                                  // what navsim_ped_scans checks
         if (c->ped_model == NAVSIM_PED_NONE || !st->robot_pose || !st->field) return NAVSIM_E_ARG;
@@ -1008,46 +1072,24 @@ static int ped_policy_run(const navsim_config* c, const navsim_state* st, const 
     const size_t P = (size_t)(p_begin + p_count);                     // the chunks below walk [p_begin, P)
     if (p_count == 0) return NAVSIM_OK;
     hipStream_t s = (hipStream_t)stream;
-    float* w2t = (float*)workspace;
-    float* cv2t = (float*)((char*)workspace + ((kPolH2 * kPolIn2 * sizeof(float) + 255) & ~(size_t)255));
-    double* tab = (double*)((char*)cv2t + ((32 * 32 * 3 * sizeof(float) + 1023) & ~(size_t)1023));
-    float* feat = (float*)((char*)tab + 8192);
-    const size_t chunk = P_all < (size_t)kPolicyChunk ? P_all : (size_t)kPolicyChunk;      // (the workspace's capacity)
-    float* h1 = feat + chunk * kPolFeat;
     constexpr size_t fc1_lds = (size_t)2 * (128 + 128) * 33 * sizeof(float);       // 67,584 B
     if (allow_lds((const void*)policy_fc1_kernel, fc1_lds) != NAVSIM_OK) return NAVSIM_E_UNSUPPORTED;
-    policy_transpose_kernel<<<(kPolH2 * kPolIn2 + 255) / 256, 256, 0, s>>>(w->fc2_w, w2t, w->cv2_w, cv2t, *c, fused ? tab : nullptr);
-    // fused kernel's dynamic LDS: the scan region (navsim_ped_scans) and conv1's output [kConvCh][258] share it
-    size_t lds = (((size_t)c->ped_n_beams * (sizeof(float2) + sizeof(float)) + 15) & ~(size_t)15) + (size_t)(c->max_peds + 1) * (64 + 32);
-    lds = lds < kConvLdsBytes ? kConvLdsBytes : lds;
-    const int rule = march_rule_variant(c);
-#ifdef NAVSIM_ONLY_RULE
-    if (fused && rule != NAVSIM_ONLY_RULE) return NAVSIM_E_UNSUPPORTED;
-#define NAVSIM_PSF(F, RECT) ped_scan_features_kernel<F, NAVSIM_ONLY_RULE, RECT><<<n, 256, lds, s>>>(*c, *st, (int)p0, n, tab, scans_out, w->cv1_w, w->cv1_b, cv2t, w->cv2_b, feat)
-#else
-#define NAVSIM_PSF_(F, R, RECT) ped_scan_features_kernel<F, R, RECT><<<n, 256, lds, s>>>(*c, *st, (int)p0, n, tab, scans_out, w->cv1_w, w->cv1_b, cv2t, w->cv2_b, feat)
-#define NAVSIM_PSF(F, RECT) \
-    do { if (rule == NAVSIM_MARCH_F32)          NAVSIM_PSF_(F, NAVSIM_MARCH_F32, RECT); \
-         else if (rule == NAVSIM_MARCH_F32_FMA) NAVSIM_PSF_(F, NAVSIM_MARCH_F32_FMA, RECT); \
-         else if (rule == kMarchF64Exact32 && !std::is_same<F, FieldF32>::value) NAVSIM_PSF_(F, kMarchF64Exact32, RECT); \
-         else                                   NAVSIM_PSF_(F, NAVSIM_MARCH_F64, RECT); } while (0)
-#endif
+    policy_transpose_kernel<<<(kPolH2 * kPolIn2 + 255) / 256, 256, 0, s>>>(w->fc2_w, ws.w2t, w->cv2_w, ws.cv2t, *c, fused ? ws.tab : nullptr);
     for (size_t p0 = (size_t)p_begin; p0 < P; p0 += chunk) {
         const int n = (int)(P - p0 < chunk ? P - p0 : chunk);
+        int rc = NAVSIM_OK;
         if (!fused) {
-            policy_features_kernel<<<n, 256, 0, s>>>(ped_scans, (int)p0, n, w->cv1_w, w->cv1_b, cv2t, w->cv2_b, feat);
+            policy_features_kernel<<<n, 256, 0, s>>>(ped_scans, (int)p0, n, w->cv1_w, w->cv1_b, ws.cv2t, w->cv2_b, ws.feat);
         } else if (c->field_format == NAVSIM_FIELD_U16T) {
-            if (st->rect_table) NAVSIM_PSF(FieldU16T, true); else NAVSIM_PSF(FieldU16T, false);
+            rc = st->rect_table ? launch_ped_scan_features<FieldU16T, true>(c, st, (int)p0, n, ws, scans_out, w, s)
+                                : launch_ped_scan_features<FieldU16T, false>(c, st, (int)p0, n, ws, scans_out, w, s);
         } else {
-            NAVSIM_PSF(FieldF32, false);
+            rc = launch_ped_scan_features<FieldF32, false>(c, st, (int)p0, n, ws, scans_out, w, s);
         }
-        policy_fc1_kernel<<<dim3((n + 127) / 128, 2), 256, fc1_lds, s>>>(feat, n, w->fc1_w, w->fc1_b, h1);
-        policy_head_kernel<<<(n + kHeadPeds - 1) / kHeadPeds, 128, 0, s>>>(*c, *st, (int)p0, n, h1, w2t, *w, prev_actions, ped_cmd);
+        if (rc != NAVSIM_OK) return rc;
+        policy_fc1_kernel<<<dim3((n + 127) / 128, 2), 256, fc1_lds, s>>>(ws.feat, n, w->fc1_w, w->fc1_b, ws.h1);
+        policy_head_kernel<<<(n + kHeadPeds - 1) / kHeadPeds, 128, 0, s>>>(*c, *st, (int)p0, n, ws.h1, ws.w2t, *w, prev_actions, ped_cmd);
     }
-#undef NAVSIM_PSF
-#ifndef NAVSIM_ONLY_RULE
-#undef NAVSIM_PSF_
-#endif
     return launch_status();
 }
 

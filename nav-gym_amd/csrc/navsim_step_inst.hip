@@ -85,20 +85,9 @@ int launch_step_kernel(const navsim_config* c, const navsim_state* st, const nav
 template <int BLOCK, bool PEDS, typename Field, int RECT>
 int launch_step_rule(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, const StepLaunch& l,
                      const StepPlan& p) {
-#ifdef NAVSIM_ONLY_RULE     // experiment builds (profiles/_diag/build_variant.sh): one march rule compiled, a quarter of the build time
-    if (march_rule_variant(c) != NAVSIM_ONLY_RULE) return NAVSIM_E_UNSUPPORTED;
-    return launch_step_kernel<BLOCK, PEDS, Field, RECT, NAVSIM_ONLY_RULE>(c, st, io, l, p);
-#else
-    switch (march_rule_variant(c)) {
-        case NAVSIM_MARCH_F32: return launch_step_kernel<BLOCK, PEDS, Field, RECT, NAVSIM_MARCH_F32>(c, st, io, l, p);
-        case NAVSIM_MARCH_F32_FMA: return launch_step_kernel<BLOCK, PEDS, Field, RECT, NAVSIM_MARCH_F32_FMA>(c, st, io, l, p);
-        case kMarchF64Exact32:
-            if constexpr (!std::is_same<Field, FieldF32>::value)
-                return launch_step_kernel<BLOCK, PEDS, Field, RECT, kMarchF64Exact32>(c, st, io, l, p);
-            [[fallthrough]];
-        default: return launch_step_kernel<BLOCK, PEDS, Field, RECT, NAVSIM_MARCH_F64>(c, st, io, l, p);
-    }
-#endif
+    return with_march_rule<Field>(march_rule_variant(c), [&](auto rule) {
+        return launch_step_kernel<BLOCK, PEDS, Field, RECT, decltype(rule)::value>(c, st, io, l, p);
+    });
 }
 
 template <int BLOCK, bool PEDS, typename Field>

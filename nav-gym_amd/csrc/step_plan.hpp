@@ -125,6 +125,24 @@ int march_rule_variant(const navsim_config* c) {
     const int side = c->map_h > c->map_w ? c->map_h : c->map_w;
     return (c->field_format == NAVSIM_FIELD_U16T && side <= 1448) ? kMarchF64Exact32 : NAVSIM_MARCH_F64;
 }
+// f(std::integral_constant<int, RULE>) for that form (`rule` = march_rule_variant): the one place a march rule becomes a
+// template argument, for the step and the pedestrian scans alike.  A float32 field never takes kMarchF64Exact32.
+template <typename Field, typename F>
+int with_march_rule(int rule, F&& f) {
+#ifdef NAVSIM_ONLY_RULE     // experiment builds (profiles/_diag/build_variant.sh): one march rule compiled, a quarter of the build time
+    if (rule != NAVSIM_ONLY_RULE) return NAVSIM_E_UNSUPPORTED;
+    return f(std::integral_constant<int, NAVSIM_ONLY_RULE>{});
+#else
+    switch (rule) {
+        case NAVSIM_MARCH_F32: return f(std::integral_constant<int, NAVSIM_MARCH_F32>{});
+        case NAVSIM_MARCH_F32_FMA: return f(std::integral_constant<int, NAVSIM_MARCH_F32_FMA>{});
+        case kMarchF64Exact32:
+            if constexpr (!std::is_same<Field, FieldF32>::value) return f(std::integral_constant<int, kMarchF64Exact32>{});
+            [[fallthrough]];
+        default: return f(std::integral_constant<int, NAVSIM_MARCH_F64>{});
+    }
+#endif
+}
 
 // the `int reset_only` of navsim_step_kernel / navsim_step_install_kernel (layout: kernels_step.hpp kStepWord*)
 int step_kernel_word(const StepLaunch& l) {

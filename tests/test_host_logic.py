@@ -121,6 +121,44 @@ def test_argument_validation_of_round2_entry_points():
     assert L.navsim_step(C.byref(c2), C.byref(st), C.byref(io), None) == abi.E_ARG              # one shared map has no slots
 
 
+def test_workspace_size_queries():
+    """The four workspace queries over a grid of configurations (they run without a device): every size is positive,
+    navsim_regen_workspace_bytes never shrinks with regen_cap or n_envs and grows from cap 1 to cap 2 (NavSim's staging
+    passes probe the per-arena cost by that difference), navsim_replan_workspace_bytes never shrinks with max_queries,
+    and null or invalid arguments give 0."""
+    from nav_gym_amd import lib
+    L = lib.load()
+    caps, envs = (1, 2, 3, 4, 5, 64), (1, 40, 4096)
+    for fmt in (abi.FIELD_F32, abi.FIELD_U16T):
+        for side in (100, 260, 520, 528, 1000):
+            for plan in (0, 1):
+                for peds in (0, 6, 64):
+                    cfg = lib.default_config(map_h=side, map_w=side, field_format=fmt, regen_plan=plan, max_peds=peds,
+                                             n_spawn=8, ped_model=abi.PED_SFM if peds else abi.PED_NONE)
+                    regen = {}
+                    for E in envs:
+                        for cap in caps:
+                            cfg.n_envs, cfg.regen_cap = E, cap
+                            regen[E, cap] = L.navsim_regen_workspace_bytes(C.byref(cfg))
+                            assert regen[E, cap] > 0, (fmt, side, plan, peds, E, cap)
+                        assert all(regen[E, a] <= regen[E, b] for a, b in zip(caps, caps[1:])), (fmt, side, plan, peds, E)
+                        assert regen[E, 2] - regen[E, 1] >= 1
+                        assert L.navsim_ped_policy_workspace_bytes(C.byref(cfg)) > 0
+                        replan = [L.navsim_replan_workspace_bytes(C.byref(cfg), q) for q in (0, 1, 5, 64, 4096)]
+                        assert replan[0] > 0 and all(a <= b for a, b in zip(replan, replan[1:])), (E, replan)
+                    for cap in caps:
+                        assert all(regen[a, cap] <= regen[b, cap] for a, b in zip(envs, envs[1:])), (fmt, side, plan, peds, cap)
+            for m in (1, 3, 64):
+                assert L.navsim_build_rects_workspace_bytes(m, side, side) > 0
+    cfg = lib.default_config()
+    assert L.navsim_regen_workspace_bytes(None) == 0 and L.navsim_ped_policy_workspace_bytes(None) == 0
+    assert L.navsim_replan_workspace_bytes(None, 4) == 0 and L.navsim_replan_workspace_bytes(C.byref(cfg), -1) == 0
+    cfg.regen_cap = 0
+    assert L.navsim_regen_workspace_bytes(C.byref(cfg)) == 0
+    for bad in ((0, 100, 100), (3, 0, 100), (3, 100, -1)):
+        assert L.navsim_build_rects_workspace_bytes(*bad) == 0
+
+
 def test_registry_and_env_surface(golden_dir):
     import nav_gym_env
     from nav_gym_amd import registry
