@@ -199,26 +199,11 @@ class NavGymEnv(_EnvBase):
                  action_kind="twist", clip_actions=False, max_waypoints=64, march_rule=None, use_graphs=None,
                  regen_min_steps=0, pregen_pipeline=None, pregen_stage_cap=None, autoreset_mode="same_step",
                  final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None):
+        # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
+        self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
         from . import lib
         if robot_type not in robots.ROBOTS:
             raise NotImplementedError(robot_type)            # env.py:772-773
-        # EzPickle (env.py:56-78): what the environment was made with is what a pickle of it carries
-        self._ctor_kwargs = dict(
-            robot_type=robot_type, time_step=time_step, min_turning_radius=min_turning_radius,
-            distance_threshold=distance_threshold, num_scan_stack=num_scan_stack, linvel_range=linvel_range,
-            rotvel_range=rotvel_range, human_v_pref_range=human_v_pref_range, human_has_legs_ratio=human_has_legs_ratio,
-            indoor_ratio=indoor_ratio, min_goal_dist=min_goal_dist, max_goal_dist=max_goal_dist, reward_scale=reward_scale,
-            reward_success_factor=reward_success_factor, reward_crash_factor=reward_crash_factor,
-            reward_progress_factor=reward_progress_factor, reward_forward_factor=reward_forward_factor,
-            reward_rotation_factor=reward_rotation_factor, reward_discomfort_factor=reward_discomfort_factor,
-            env_param_range=env_param_range, num_envs=num_envs, n_beams=n_beams, lidar=lidar, map_size=map_size,
-            pedestrian_model=pedestrian_model, policy_weights=policy_weights, num_humans=num_humans, device=device, seed=seed,
-            env_index_base=env_index_base, auto_reset=auto_reset, field_format=field_format, n_spawn=n_spawn,
-            randomize_maps=randomize_maps, plan_paths=plan_paths, action_kind=action_kind, clip_actions=clip_actions,
-            max_waypoints=max_waypoints, march_rule=march_rule, use_graphs=use_graphs,
-            regen_min_steps=regen_min_steps, pregen_pipeline=pregen_pipeline, pregen_stage_cap=pregen_stage_cap,
-            autoreset_mode=autoreset_mode, final_observation=final_observation, pregen_fallback_poll=pregen_fallback_poll,
-            max_episode_steps=max_episode_steps, orca_params=orca_params)
         self.robot_type = robot_type
         self.time_step = time_step
         self.min_turning_radius = min_turning_radius
@@ -274,7 +259,6 @@ class NavGymEnv(_EnvBase):
             n_spawn = 4 if self.randomize_maps else 16
         self.replan_cap = 1024                              # pedestrians re-planned per step, at most
         self._use_graphs_arg = use_graphs
-        self.use_graphs = bool(randomize_maps) if use_graphs is None else bool(use_graphs)
         # pregen_pipeline = P > 0 (with randomize_maps): the next world of every arena is generated ahead of time by staging
         # passes on a side stream, one every P steps, and a finished arena takes it inside the step's own launch
         # (navsim_step_install) -- navsim_regen leaves the step's critical path.  It rests on regen_min_steps >= 4 P: an
@@ -289,30 +273,21 @@ class NavGymEnv(_EnvBase):
         if pregen_pipeline is None:
             available = (not self._cmd_in_front and field_format == abi.FIELD_U16T and
                          (map_size == "reference" or int(map_size) <= 1024))
-            heavy = bool(plan_paths) and float(indoor_ratio) > 0.0 and (map_size == "reference" or int(map_size) <= 1000)
             # (worlds of corridor maps with planned starts: a pass every 4 steps too since round 6 -- their passes alternate between
             #  two side streams, NavSim.enable_pregen stage_lanes, i.e. each stream still starts one every 8 steps)
             pregen_pipeline = 4 if available else 0
             if use_graphs:                         # (asked for: the graph replay of step + navsim_regen is the other form)
                 pregen_pipeline = 0
-        self.pregen_pipeline = int(pregen_pipeline) if (self.randomize_maps and self.auto_reset) else 0
         self.regen_min_steps = int(regen_min_steps)
         self.pregen_stage_cap = pregen_stage_cap        # arenas one staging pass serves at most (None: NavSim.enable_pregen's default)
         self.pregen_fallback_poll = pregen_fallback_poll   # None: NavSim.enable_pregen's default (on for corridor maps / planned starts)
-        if self.pregen_pipeline:
-            # regen_min_steps >= 4 P: the rule (fastest; short episodes keep their map).  Below that -- 0 is the reference's own
-            # "a new map at every reset()" -- an arena that finishes before its world is staged is generated on the spot by
-            # navsim_regen (NavSim.enable_pregen fallback): same rollout as without the pipeline, bit for bit
-            if self._cmd_in_front:
-                raise ValueError("pregen_pipeline is not available with pedestrian_model=%r" % pedestrian_model)
-            self.use_graphs = False
+        if self.randomize_maps and self.auto_reset and self._cmd_in_front and int(pregen_pipeline):
+            raise ValueError("pregen_pipeline is not available with pedestrian_model=%r" % pedestrian_model)
         self._graphed = False
         self._overlap_replan = False
+        # which sequence step() runs and what it launches behind the step (_choose_step_path, at the first reset())
+        self._step_path, self._regen_behind, self._replan_behind = None, False, False
         self.plan_paths = bool(plan_paths) and int(map_size) <= 1000
-        if self._use_graphs_arg is None and self.plan_paths and float(indoor_ratio) > 0.0:
-            # corridor maps with planned starts: navsim_regen forks its distance transform beside the searches; as fork / join
-            # nodes of a hipGraph that gains nothing (reference defaults, 1024 arenas: 0.92 M graphed, 0.96 M plain launches)
-            self.use_graphs = False
         if plan_paths and not self.plan_paths:
             self._warn_once("plan_paths", "NavGymEnv: map_size %d > 1000: the planner's search lives in LDS (costmaps up to "
                             "200 x 200 cells), plan_paths falls back to False -- pedestrians head straight for their goals"
@@ -353,15 +328,8 @@ class NavGymEnv(_EnvBase):
         cfg.max_waypoints = int(max_waypoints)
         if march_rule is not None:                    # include/navsim.h NAVSIM_MARCH_*: the unpinned rounding of range_libc
             cfg.march_rule = int(march_rule)
-        # with randomize_maps every step() is navsim_step + navsim_regen: the restarted arenas' first observations come from
-        # regen's masked launch instead of a second scan inside the step (include/navsim.h defer_reset_scan), where a
-        # launch is one generation of workgroups -- a few arenas per CU
-        cfg.defer_reset_scan = int(self.randomize_maps and self.auto_reset and self.num_envs <= 1024)
         cfg.regen_min_steps = self.regen_min_steps if (self.randomize_maps and self.auto_reset) else 0
         cfg.max_episode_steps = self.max_episode_steps or 0     # (0: no limit -- the step's plain form where it has one)
-        if self.pregen_pipeline:
-            cfg.defer_reset_scan = 0              # a staged world brings its first observation; restarts in place scan in the step
-            cfg.regen_cap = self.num_envs         # every finished arena decides alone inside the step (navsim_step_install)
         cfg.regen_plan = int(self.plan_paths)
         cfg.regen_indoor_ratio = float(indoor_ratio)
         cfg.outdoor_map_size = int(self.outdoor_map_size)
@@ -393,10 +361,11 @@ class NavGymEnv(_EnvBase):
             cfg.angle_min = spec["angle_min"]
             cfg.angle_last = spec["angle_max"] - spec["angle_increment"]
         self.cfg = cfg
+        self.sim = None
+        self._choose_reset_path(pregen_pipeline, plain_cap=cfg.regen_cap)      # (without the pipeline: the library's default cap)
         self._override_reward_factor(reward_scale, reward_success_factor, reward_crash_factor,
                                      reward_progress_factor, reward_forward_factor, reward_rotation_factor,
                                      reward_discomfort_factor)
-        self.sim = None
         self.prev_obs = None
         self._bool = None
         self._views = {}                                    # per buffer parity: what step() hands out beside the observation
@@ -430,13 +399,56 @@ class NavGymEnv(_EnvBase):
         self.reward_forward_factor = reward_forward_factor
         self.reward_rotation_factor = reward_rotation_factor
         self.reward_discomfort_factor = reward_discomfort_factor
-        for k in ("scale", "success_factor", "crash_factor", "progress_factor", "forward_factor",
-                  "rotation_factor", "discomfort_factor"):
-            setattr(self.cfg, "reward_" + k, float(getattr(self, "reward_" + k)))
-        if getattr(self, "sim", None) is not None:
+        for c_ in (self.cfg,) if self.sim is None else (self.cfg, self.sim.cfg):      # (the simulator holds its own copy)
             for k in ("scale", "success_factor", "crash_factor", "progress_factor", "forward_factor",
                       "rotation_factor", "discomfort_factor"):
-                setattr(self.sim.cfg, "reward_" + k, float(getattr(self, "reward_" + k)))
+                setattr(c_, "reward_" + k, float(getattr(self, "reward_" + k)))
+
+    def _choose_reset_path(self, pipeline, plain_cap=None):
+        """How finished arenas get their next world, decided in this one place: pregen_pipeline, use_graphs, cfg.defer_reset_scan
+        and cfg.regen_cap (self.cfg and the simulator's own copy) from the constructor's facts.  pipeline = P > 0: staging passes
+        and navsim_step_install; 0: navsim_regen behind every step, as a hipGraph or as plain launches.
+        plain_cap: cfg.regen_cap without the pipeline -- the constructor passes the library's default (64), the memory fallback
+        of reset() passes nothing and gets min(num_envs, 64)."""
+        regen = self.randomize_maps and self.auto_reset
+        heavy = self.plan_paths and float(self.indoor_ratio) > 0.0
+        self.pregen_pipeline = int(pipeline) if regen else 0
+        if self.pregen_pipeline:
+            self.use_graphs = False
+        elif self._use_graphs_arg is not None:
+            self.use_graphs = bool(self._use_graphs_arg)
+        else:
+            # corridor maps with planned starts: navsim_regen forks its distance transform beside the searches; as fork / join
+            # nodes of a hipGraph that gains nothing (reference defaults, 1024 arenas: 0.92 M graphed, 0.96 M plain launches)
+            self.use_graphs = self.randomize_maps and not heavy
+        for c_ in (self.cfg,) if self.sim is None else (self.cfg, self.sim.cfg):
+            if self.pregen_pipeline:
+                c_.defer_reset_scan = 0           # a staged world brings its first observation; restarts in place scan in the step
+                c_.regen_cap = self.num_envs      # every finished arena decides alone inside the step (navsim_step_install)
+            else:
+                # every step() is navsim_step + navsim_regen: the restarted arenas' first observations come from regen's masked
+                # launch instead of a second scan inside the step (include/navsim.h defer_reset_scan), where a launch is one
+                # generation of workgroups -- a few arenas per CU
+                c_.defer_reset_scan = int(regen and self.num_envs <= 1024)
+                c_.regen_cap = min(self.num_envs, 64) if plain_cap is None else plain_cap
+
+    def _choose_step_path(self):
+        """Which of its four sequences step() runs, with the fixed facts they need (at the end of the first reset(): the world's
+        arrays and the reset path are known then)."""
+        routes = "costmap" in self.sim.t
+        self._regen_behind = self.randomize_maps and self.auto_reset      # navsim_regen behind the step
+        self._replan_behind = routes                                      # navsim_replan behind the step (or inside / beside it)
+        # pedestrians on planned routes: navsim_replan overlaps the step (not with 'policy' / 'orca', whose control block runs in
+        # front of every step and reads the routes)
+        self._overlap_replan = routes and self.sim.due is not None and not self._cmd_in_front and not self.pregen_pipeline
+        if self._graphed:
+            self._step_path = "graphed"
+        elif self.pregen_pipeline:
+            self._step_path = "pipelined"
+            if routes and self.sim.pg_replan_cap == 0:      # the re-plan of the previous step's arrivals inside the step's launch
+                self.sim.pg_replan_cap = self.replan_cap
+        else:
+            self._step_path = "overlapped" if self._overlap_replan else "plain"
 
     # ---- reset (env.py:730-831), all arenas ---------------------------------------------------------
     def reset(self, mask=None):
@@ -496,10 +508,6 @@ class NavGymEnv(_EnvBase):
             self.sim.t["policy_prev_actions"].zero_()           # env.py:739
         self._episode_batch += 1
         self.sim.regenerate_all(new_episode=not first)
-        # pedestrians on planned routes: navsim_replan overlaps the step (not with 'policy', whose control block runs in
-        # front of every step and reads the routes)
-        self._overlap_replan = ("costmap" in self.sim.t and self.sim.due is not None and not self._cmd_in_front
-                                and not self.pregen_pipeline)
         if self.pregen_pipeline and first and self._pregen_auto:
             # the pipeline keeps a second, staged copy of every array navsim_regen writes (the maps above all) and builds it
             # through a few GB of scratch: where that does not fit, the env's own choice falls back to navsim_regen after every step
@@ -509,13 +517,7 @@ class NavGymEnv(_EnvBase):
                 self._warn_once("pregen_memory", "NavGymEnv: %.0f GB free on the device, the pipelined reset path would need about "
                                 "%.0f GB more than the world itself: pregen_pipeline falls back to 0 (navsim_regen after every step)"
                                 % (free / 2 ** 30, need / 2 ** 30))
-                self.pregen_pipeline = 0
-                for c_ in (cfg, self.sim.cfg):             # (the simulator holds its own copy)
-                    c_.regen_cap = min(self.num_envs, 64)
-                    c_.defer_reset_scan = int(self.num_envs <= 1024)
-                if self._use_graphs_arg is None:
-                    self.use_graphs = not (self.plan_paths and float(self.indoor_ratio) > 0.0)
-                self._overlap_replan = ("costmap" in self.sim.t and self.sim.due is not None and not self._cmd_in_front)
+                self._choose_reset_path(0)
         if self.pregen_pipeline:
             if cfg.field_format != abi.FIELD_U16T:
                 raise ValueError("pregen_pipeline needs the packed distance field (map_size <= 1024)")
@@ -528,6 +530,8 @@ class NavGymEnv(_EnvBase):
             self.sim.enable_graphs(regen=self.randomize_maps and self.auto_reset,
                                    replan_cap=self.replan_cap if "costmap" in self.sim.t else 0)
             self._graphed = True
+        if first:
+            self._choose_step_path()
         self._map_info = None                             # read back from the device when somebody asks (map_info)
         self._humans_of_episode = None
         return self._obs_dict()
@@ -586,22 +590,21 @@ class NavGymEnv(_EnvBase):
                 self._orca_struct = simmod.ped_orca_params(self.sim.cfg, self.orca_params, self.robot_type)
             self.sim.ped_orca(self._orca_struct)            # the simulator's state -> ORCA -> (v, omega), one launch
         a = np.asarray(action, dtype=np.float64).reshape(self.num_envs, 2) if not hasattr(action, "is_cuda") else action
-        if self._graphed:                                   # step + regen + replan: one graph launch (NavSim.enable_graphs)
+        path = self._step_path
+        if path == "graphed":                               # step + regen + replan: one graph launch (NavSim.enable_graphs)
             _, out = self.sim.step_graphed(a)
-        elif self.pregen_pipeline:
+        elif path == "pipelined":
             # navsim_step_install: finished arenas take their staged worlds; with planned routes the re-plan of the PREVIOUS
-            # step's arrivals inside the same launch where the search fits the arena's workgroup (else behind the step)
-            in_step = "costmap" in self.sim.t and not self._cmd_in_front
-            if in_step and self.sim.pg_replan_cap == 0:
-                self.sim.pg_replan_cap = self.replan_cap
+            # step's arrivals inside the same launch where the search fits the arena's workgroup (else behind the step: the
+            # library may refuse the in-launch search at run time)
             _, out = self.sim.step(a)
             self.sim.regen()                               # ... and every P steps a staging pass goes to the side stream
-            if "costmap" in self.sim.t and not (in_step and self.sim.pg_replan_in_step):
+            if self._replan_behind and not self.sim.pg_replan_in_step:
                 self.sim.replan(self.replan_cap)
-        elif self._overlap_replan:
+        elif path == "overlapped":
             # planned routes: the re-plan of the previous step runs beside this step's launch (NavSim.launch_step_overlapped)
             _, out = self.sim.step_overlapped(a, self.replan_cap)
-            if self.randomize_maps and self.auto_reset:
+            if self._regen_behind:
                 self.sim.regen()
         else:
             _, out = self.sim.step(a)                      # (a float64 tensor on the device is read in place: no copy)
@@ -609,9 +612,9 @@ class NavGymEnv(_EnvBase):
                 # a new episode starts with prev_human_actions = 0 (env.py:739)
                 started = self.sim.reset_flags if self.autoreset_mode == "next_step" else out["done"]
                 self.sim.t["policy_prev_actions"].mul_((started == 0).to(self.sim.t["policy_prev_actions"].dtype)[:, None, None])
-            if self.randomize_maps and self.auto_reset:
+            if self._regen_behind:
                 self.sim.regen()
-            if "costmap" in self.sim.t:
+            if self._replan_behind:
                 self.sim.replan(self.replan_cap)           # ('policy', 'orca': the launch in front of the next step reads the routes)
         obs = self._obs_dict()
         # the LAST observation of an episode that ended in this step (env.py:700-728 returns it with done = True): under
@@ -831,7 +834,7 @@ class NavGymEnv(_EnvBase):
                     if "final.%d.%s" % (i, k) in sd:
                         v.copy_(sd["final.%d.%s" % (i, k)])
         self.sim.cur = int(sd["cur"])
-        if getattr(self.sim, "pregen", False):             # the staged worlds are not part of the snapshot: stage them again
+        if self.sim.pregen:                                # the staged worlds are not part of the snapshot: stage them again
             self.sim.restage_all(slots_from_live=True)
         self.sim._steps_launched = int(sd["steps_launched"])
         self._episode_batch = int(sd["episode_batch"])

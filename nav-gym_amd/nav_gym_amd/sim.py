@@ -429,6 +429,24 @@ class NavSim(object):
         self.lib = load()
         self.cfg = cfg.copy()
         self.device = torch.device(device)
+        # everything the enable_* calls and the lazily made streams set, at its "not enabled" value
+        # staging (enable_pregen): the staged state, what a pass serves, the lanes (lane 0 = want / stage_io / stage_ws / side)
+        self.pregen = self.pg_install = False
+        self.pg_period = self.pg_k = self.pg_passes = self.stage_cap = 0
+        self.pg_open, self.pg_swapped, self.pg_staged, self.stage_lane = [], [], [], []
+        self.stage_t, self.stage_st, self.stage_cfg, self.stage_obs, self.stage_io, self.stage_ws = {}, None, None, None, None, None
+        self.want = self.mark = self.ready = self.side = self.ev_swapped = self.ev_staged = None
+        # fallback: the arenas that finished before their world was staged (flags the step writes, navsim_regen for them)
+        self.late, self.late_cfg, self.late_ws, self.late_cap = None, None, None, 0
+        self.late_poll = self.lone = False
+        # next-step "beside" form: the fallback on a stream of its own beside the next step's launch
+        self.late2 = self.urgent = self.ev_stepped = self.ev_urgent = None
+        # overlap and graphs: the re-plan inside or beside the step, the captured steps
+        self.pg_replan_cap, self.pg_replan_in_step = 0, True
+        self._side = self._regen_helper = self._action_ref = None
+        self._graphs, self._graph_args, self._graph_cfg = {}, None, None
+        # policy and orca
+        self.policy_t, self.policy_w, self._scan_stream, self._orca_default = {}, None, None, None
         self.t = {}
         self.st = abi.NavsimState()
         for name, (dtype, shape) in abi.STATE_LAYOUT.items():
@@ -493,7 +511,7 @@ class NavSim(object):
         # only when a launch runs several generations of workgroups: with one generation everything starts
         # at once and the order is irrelevant (threads per arena as dispatch_step picks them)
         n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count or 256
-        block = self.cfg.step_block or (                    # navsim_kernels.hip pick_step_block
+        block = self.cfg.step_block or (                    # step_plan.hpp pick_step_block (the ABI has no query for it)
             64 if self.cfg.n_beams <= 64 else (256 if self.cfg.n_envs >= 12 * n_cu or self.cfg.n_beams <= 256 else
                                                (512 if self.cfg.n_envs > 2 * n_cu or self.cfg.n_beams <= 512 else 1024)))
         generations = self.cfg.n_envs * (block // 64) / float(32 * n_cu)
@@ -602,17 +620,22 @@ class NavSim(object):
             check(self.lib.navsim_launch_order(_ptr(self.t["arena_cost"]), _ptr(self.t["launch_order"]), self.cfg.n_envs,
                                                _stream()), "navsim_launch_order")
 
+    def _set_action(self, action):
+        """io.action -> the caller's tensor where it is resident in the step's own format (stream-ordered: no copy), else the
+        simulator's buffer with a copy of it."""
+        import torch
+        if (isinstance(action, torch.Tensor) and action.is_cuda and action.dtype == torch.float64 and action.is_contiguous()
+                and action.device == self.device and action.numel() == self.action.numel()):
+            self.io.action = action.data_ptr()
+            self._action_ref = action
+        else:
+            self.action.copy_(self._as(action, self.action))
+            self.io.action = self.action.data_ptr()
+
     def step(self, action=None):
         """One fused launch: NavGymEnv.step for all E arenas.  `action` [E,2] (v, omega)."""
         if action is not None:
-            import torch
-            if (isinstance(action, torch.Tensor) and action.is_cuda and action.dtype == torch.float64 and action.is_contiguous()
-                    and action.device == self.device and action.numel() == self.action.numel()):
-                self.io.action = action.data_ptr()         # resident actions are read where they are (stream-ordered: no copy)
-                self._action_ref = action
-            else:
-                self.action.copy_(self._as(action, self.action))
-                self.io.action = self.action.data_ptr()
+            self._set_action(action)
         self._reorder()
         self._flip()
         self._launch()
@@ -621,7 +644,7 @@ class NavSim(object):
 
     def _launch(self):
         """The step's launch on the current stream: navsim_step, or navsim_step_install behind the staging pass it may rest on."""
-        if not getattr(self, "pg_install", False):
+        if not self.pg_install:
             rc = self.lib.navsim_step(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), _stream())
             if rc:
                 check(rc, "navsim_step")
@@ -631,62 +654,45 @@ class NavSim(object):
         P, k = self.pg_period, self.pg_k
         if k % P == 0 and k >= 2 * P:
             main.wait_event(self.pg_staged[(k // P - 2) % 3])   # the pass queued two periods ago; the later two may still run
-        if getattr(self, "late2", None) is not None:
-            return self._launch_next_step(main)
+        # what every navsim_step_install* call starts with; behind it: the late flags, the re-plan cap, the stream
+        head = (C.byref(self.cfg), C.byref(self.st), C.byref(self.io), C.byref(self.stage_st), _ptr(self.stage_obs), _ptr(self.mark),
+                _ptr(self.ready))
+        stream = C.c_void_p(main.cuda_stream)
+        if self.late2 is not None:
+            return self._launch_next_step(main, head, stream)
         # pg_replan_cap > 0 (worlds with planned pedestrian routes): navsim_replan of the previous step's flags inside this launch
         # where the search fits the arena's workgroup (navsim_step_install_replan); else the caller re-plans behind the step
-        late = None if getattr(self, "lone", False) else self.late
-        if getattr(self, "pg_replan_cap", 0) > 0 and self.pg_replan_in_step:
-            rc = self.lib.navsim_step_install_replan(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), C.byref(self.stage_st),
-                                                     _ptr(self.stage_obs), _ptr(self.mark), _ptr(self.ready), _ptr(late),
-                                                     int(self.pg_replan_cap), C.c_void_p(main.cuda_stream))
+        late = None if self.lone else self.late
+        if self.pg_replan_cap > 0 and self.pg_replan_in_step:
+            rc = self.lib.navsim_step_install_replan(*head, _ptr(late), int(self.pg_replan_cap), stream)
             if rc == 0:
                 return
             if rc != abi.E_UNSUPPORTED:
                 check(rc, "navsim_step_install_replan")
             self.pg_replan_in_step = False
-        rc = self.lib.navsim_step_install(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), C.byref(self.stage_st),
-                                          _ptr(self.stage_obs), _ptr(self.mark), _ptr(self.ready), _ptr(late),
-                                          C.c_void_p(main.cuda_stream))
+        rc = self.lib.navsim_step_install(*head, _ptr(late), stream)
         if rc == abi.E_UNSUPPORTED and late is None and self.late is not None:
             self.lone = False                                   # (fewer than 256 threads per arena: flags + navsim_regen behind the step)
-            rc = self.lib.navsim_step_install(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), C.byref(self.stage_st),
-                                              _ptr(self.stage_obs), _ptr(self.mark), _ptr(self.ready), _ptr(self.late),
-                                              C.c_void_p(main.cuda_stream))
+            rc = self.lib.navsim_step_install(*head, _ptr(self.late), stream)
         check(rc, "navsim_step_install")
 
-    def _launch_next_step(self, main):
+    def _launch_next_step(self, main, head, stream):
         """NEXT_STEP with staged worlds: the step's launch (arenas that finished in the previous call install their staged worlds
         at its front) and, on the `urgent` stream at the same time, navsim_regen for the arenas that call flagged as late."""
-        import torch
         prev, nxt = self.late2[self.cur], self.late2[1 - self.cur]      # (self.cur: the buffers of the PREVIOUS call)
-        cap = int(getattr(self, "pg_replan_cap", 0)) if self.pg_replan_in_step else 0
-        rc = self.lib.navsim_step_install_next(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), C.byref(self.stage_st),
-                                               _ptr(self.stage_obs), _ptr(self.mark), _ptr(self.ready), _ptr(nxt), _ptr(prev),
-                                               cap if cap > 0 else -1, C.c_void_p(main.cuda_stream))
+        cap = int(self.pg_replan_cap) if self.pg_replan_in_step else 0
+        rc = self.lib.navsim_step_install_next(*head, _ptr(nxt), _ptr(prev), cap if cap > 0 else -1, stream)
         if rc == abi.E_UNSUPPORTED and cap > 0:                 # the search does not fit the arena's workgroup: re-plan behind the step
             self.pg_replan_in_step = False
-            rc = self.lib.navsim_step_install_next(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), C.byref(self.stage_st),
-                                                   _ptr(self.stage_obs), _ptr(self.mark), _ptr(self.ready), _ptr(nxt), _ptr(prev),
-                                                   -1, C.c_void_p(main.cuda_stream))
+            rc = self.lib.navsim_step_install_next(*head, _ptr(nxt), _ptr(prev), -1, stream)
         check(rc, "navsim_step_install_next")
         # beside it: the new worlds of the arenas the previous call found unstaged (mostly nobody: launches that find nothing to do)
         urgent = self.urgent
         urgent.wait_event(self.ev_stepped)                      # the previous call (its flags, its state) -- NOT this launch
-        C.memmove(C.byref(self.late_cfg), C.byref(self.cfg), C.sizeof(self.cfg))
-        self.late_cfg.regen_cap = self.late_cap
-        self.late_cfg.defer_reset_scan = 1
-        io = abi.NavsimStepIO()
-        C.memmove(C.byref(io), C.byref(self.io), C.sizeof(io))  # (self.io: this call's buffers -- _flip() ran)
-        io.done = prev.data_ptr()
-        io.reset_mask = None
-        helper = getattr(self, "_regen_helper", None)
-        if helper is not None:                                  # no fork: the helper stream belongs to the staging passes
-            self.lib.navsim_regen_helper(C.c_void_p(urgent.cuda_stream))
-        check(self.lib.navsim_regen(C.byref(self.late_cfg), C.byref(self.st), C.byref(io), _ptr(self.late_ws), self.late_ws.numel(),
-                                    C.c_void_p(urgent.cuda_stream)), "navsim_regen (arenas whose world was not staged, beside the step)")
-        if helper is not None:
-            self.lib.navsim_regen_helper(C.c_void_p(helper.cuda_stream))
+        self._late_cfg_now().defer_reset_scan = 1
+        # (self.io: this call's buffers -- _flip() ran: its obs stays; no fork: the helper stream belongs to the staging passes)
+        self._call_regen(self.late_cfg, self.late_ws, urgent, "navsim_regen (arenas whose world was not staged, beside the step)",
+                         current_obs=False, latest_flags=False, fork=False, done=prev, reset_mask=None)
         self.ev_urgent.record(urgent)
         main.wait_event(self.ev_urgent)                         # whatever follows this step on the caller's stream sees both
         self.ev_stepped.record(main)
@@ -821,7 +827,7 @@ class NavSim(object):
             raise ValueError("enable_pregen(stage_lanes=%r): 1, or 2 with install=True and pipeline > 0" % (stage_lanes,))
         # lane 0 = the objects above; lane 1: its own want[], io, workspace, stream and helper stream
         self.stage_lane = [dict(want=self.want, io=self.stage_io, ws=self.stage_ws, side=self.side,
-                                helper=getattr(self, "_regen_helper", None))]
+                                helper=self._regen_helper)]
         if lanes == 2:
             want2 = torch.zeros(E, dtype=torch.uint8, device=self.device)
             io2 = abi.NavsimStepIO()
@@ -829,7 +835,7 @@ class NavSim(object):
             io2.done = want2.data_ptr()
             side2 = concurrent_stream(self.device, beside=[torch.cuda.current_stream(self.device), self.side], priority=0)
             helper2 = None
-            if getattr(self, "_regen_helper", None) is not None:
+            if self._regen_helper is not None:
                 helper2 = concurrent_stream(self.device, beside=[torch.cuda.current_stream(self.device), self.side, side2])
             self.stage_lane.append(dict(want=want2, io=io2, ws=torch.zeros(nbytes, dtype=torch.uint8, device=self.device), side=side2,
                                         helper=helper2))
@@ -883,10 +889,10 @@ class NavSim(object):
         the second time, new episode numbers) -- stage the world behind each arena's current one again.
         slots_from_live: the live slot table was replaced (load_state_dict) -- the staged one is its complement."""
         import torch
-        for ln in getattr(self, "stage_lane", [dict(side=self.side)]):
+        for ln in self.stage_lane:
             ln["side"].synchronize()
         torch.cuda.current_stream().synchronize()
-        for ln in getattr(self, "stage_lane", [])[1:]:
+        for ln in self.stage_lane[1:]:
             ln["want"].zero_()
         if slots_from_live and "map_slot" in self.t:
             free = torch.ones(2 * self.cfg.n_envs, dtype=torch.bool, device=self.device)
@@ -895,7 +901,7 @@ class NavSim(object):
         self.stage_t["episode"].copy_(self.t["episode"] + 1)
         self.want.fill_(1)
         self.mark.zero_()
-        if getattr(self, "late2", None) is not None:
+        if self.late2 is not None:
             self.urgent.synchronize()
             for b in self.late2:
                 b.zero_()
@@ -909,12 +915,7 @@ class NavSim(object):
         import torch
         E = self.cfg.n_envs
         cfg = self.cfg.copy()
-        cfg.regen_cap = 1
-        per = self.lib.navsim_regen_workspace_bytes(C.byref(cfg))
-        cfg.regen_cap = 2
-        per = max(self.lib.navsim_regen_workspace_bytes(C.byref(cfg)) - per, 1)
-        cfg.regen_cap = int(max(1, min(E, scratch_bytes // per)))
-        ws = torch.empty(self.lib.navsim_regen_workspace_bytes(C.byref(cfg)), dtype=torch.uint8, device=self.device)
+        ws = self._regen_chunk(cfg, scratch_bytes)
         for _ in range((E + cfg.regen_cap - 1) // cfg.regen_cap):
             check(self.lib.navsim_regen_stage(C.byref(cfg), C.byref(self.stage_st), C.byref(self.stage_io), _ptr(self.want),
                                               _ptr(self.mark), _ptr(self.ready), _ptr(ws), ws.numel(), _stream()),
@@ -929,28 +930,16 @@ class NavSim(object):
         self.pg_k += 1
         j = k // P if P else 0
         if self.pg_install:                              # step() has installed; only the passes are left
-            need = self.late is not None and getattr(self, "late2", None) is None and not getattr(self, "lone", False)
-            if need and getattr(self, "late_poll", False) and not torch.cuda.is_current_stream_capturing():
+            need = self.late is not None and self.late2 is None and not self.lone
+            if need and self.late_poll and not torch.cuda.is_current_stream_capturing():
                 # (the host waits for the step's launch here; what it saves is the fallback's blind launches behind EVERY step)
                 need = bool(self.late.any().item())
             if need:   # ... and whoever finished before its world was staged (rare): now
-                C.memmove(C.byref(self.late_cfg), C.byref(self.cfg), C.sizeof(self.cfg))
-                self.late_cfg.regen_cap = self.late_cap
-                io = abi.NavsimStepIO()
-                C.memmove(C.byref(io), C.byref(self.io), C.sizeof(io))
-                io.obs = self.obs_buf[self.cur].data_ptr()
-                io.done = self.late.data_ptr()
-                self._latest_flags()
                 # this call does not fork: navsim_regen's helper stream belongs to the staging passes, whose distance transforms the
                 # fallback's (mostly empty) fork / join would queue behind -- the pass back on the step's critical path
                 # (round-5 advisor).  A helper equal to the call's own stream means "no fork" (include/navsim.h).
-                helper = getattr(self, "_regen_helper", None)
-                if helper is not None:
-                    self.lib.navsim_regen_helper(C.c_void_p(main.cuda_stream))
-                check(self.lib.navsim_regen(C.byref(self.late_cfg), C.byref(self.st), C.byref(io), _ptr(self.late_ws),
-                                            self.late_ws.numel(), C.c_void_p(main.cuda_stream)), "navsim_regen (arenas whose world was not staged)")
-                if helper is not None:
-                    self.lib.navsim_regen_helper(C.c_void_p(helper.cuda_stream))
+                self._call_regen(self._late_cfg_now(), self.late_ws, main, "navsim_regen (arenas whose world was not staged)",
+                                 fork=False, done=self.late)
             if k % P == 0:
                 self._latest_flags()
                 self._queue_pass(main, self.pg_swapped[j % 3], self.pg_staged[j % 3])
@@ -960,9 +949,7 @@ class NavSim(object):
         elif k % P == 0 and j >= 2:
             main.wait_event(self.pg_staged[(j - 2) % 3])    # the pass queued two periods ago; the later two may still run
         self._latest_flags()
-        io = abi.NavsimStepIO()
-        C.memmove(C.byref(io), C.byref(self.io), C.sizeof(io))
-        io.obs = self.obs_buf[self.cur].data_ptr()
+        io = self._io_copy(obs=self.obs)
         check(self.lib.navsim_regen_swap(C.byref(self.cfg), C.byref(self.st), C.byref(self.stage_st), C.byref(io),
                                          _ptr(self.stage_obs), _ptr(self.want), _ptr(self.mark), _ptr(self.ready),
                                          C.c_void_p(main.cuda_stream)),
@@ -978,7 +965,7 @@ class NavSim(object):
         next 2 P steps then rest on no earlier pass.  Call it before capturing steps into a hipGraph: a captured wait must
         not refer to an event recorded outside the capture."""
         import torch
-        for ln in getattr(self, "stage_lane", [dict(side=self.side)]):
+        for ln in self.stage_lane:
             ln["side"].synchronize()
         torch.cuda.current_stream().synchronize()
         self.pg_k = 0
@@ -997,12 +984,11 @@ class NavSim(object):
     def _queue_pass(self, main, swapped, staged):
         """A staging pass on the side stream, behind everything `main` holds now."""
         if self.pg_period:
-            self.pg_open = (getattr(self, "pg_open", []) + [staged])[-2:]
-        lanes = getattr(self, "stage_lane", None) or [dict(want=self.want, io=self.stage_io, ws=self.stage_ws, side=self.side, helper=None)]
-        n = len(lanes)
-        ln = lanes[self.pg_passes % n] if n > 1 else lanes[0]
+            self.pg_open = (self.pg_open + [staged])[-2:]
+        n = len(self.stage_lane)
         part = self.pg_passes % n
-        self.pg_passes = getattr(self, "pg_passes", 0) + 1
+        ln = self.stage_lane[part]
+        self.pg_passes += 1
         side = ln["side"]
         swapped.record(main)
         side.wait_event(swapped)
@@ -1015,15 +1001,15 @@ class NavSim(object):
                                                _ptr(self.mark), _ptr(self.ready), _ptr(ws), ws.numel(), part, n,
                                                C.c_void_p(side.cuda_stream)),
               "navsim_regen_stage_part")
-        if n > 1 and ln["helper"] is not None and getattr(self, "_regen_helper", None) is not None:
+        if n > 1 and ln["helper"] is not None and self._regen_helper is not None:
             self.lib.navsim_regen_helper(C.c_void_p(self._regen_helper.cuda_stream))
         staged.record(side)
 
     def close(self):
         """Waits for what this simulator has in flight on streams of its own (staging passes, the overlapped re-plan): their
         kernels write into arrays that are about to be released."""
-        extra = [ln[k] for ln in getattr(self, "stage_lane", [])[1:] for k in ("side", "helper")]
-        for st in [getattr(self, name, None) for name in ("side", "_side", "_scan_stream", "_regen_helper", "urgent")] + extra:
+        extra = [ln[k] for ln in self.stage_lane[1:] for k in ("side", "helper")]
+        for st in [self.side, self._side, self._scan_stream, self._regen_helper, self.urgent] + extra:
             if st is not None:
                 try:
                     st.synchronize()
@@ -1039,28 +1025,76 @@ class NavSim(object):
     def _choose_regen_helper(self):
         """navsim_regen's helper stream for worlds whose reset forks (include/navsim.h navsim_regen_helper): one that really runs
         beside the current stream, chosen once (before any hipGraph capture of the call)."""
-        if getattr(self, "_regen_helper", None) is None and self.cfg.regen_plan and self.cfg.regen_indoor_ratio > 0.0:
+        if self._regen_helper is None and self.cfg.regen_plan and self.cfg.regen_indoor_ratio > 0.0:
             self._regen_helper = concurrent_stream(self.device)
             check(self.lib.navsim_regen_helper(C.c_void_p(self._regen_helper.cuda_stream)), "navsim_regen_helper")
 
-    def regen(self):
-        """navsim_regen right after step(): finished arenas get a new map, tables, pedestrians, first obs."""
-        import torch
-        if getattr(self, "pregen", False):
-            return self._regen_pregen()
-        self._choose_regen_helper()
-        if "regen_ws" not in self.t:
-            nbytes = self.lib.navsim_regen_workspace_bytes(C.byref(self.cfg))
-            self.t["regen_ws"] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+    def _io_copy(self, **fields):
+        """self.io by value, with `fields` (name = tensor or None) on top."""
         io = abi.NavsimStepIO()
         C.memmove(C.byref(io), C.byref(self.io), C.sizeof(io))
-        io.obs = self.obs_buf[self.cur].data_ptr()
-        if self.next_step:                              # the arenas the latest step RESET: those that finished the step before
-            io.done = self.reset_flags.data_ptr()
-        self._latest_flags()
-        ws = self.t["regen_ws"]
-        check(self.lib.navsim_regen(C.byref(self.cfg), C.byref(self.st), C.byref(io), _ptr(ws), ws.numel(), _stream()),
-              "navsim_regen")
+        for k, v in fields.items():
+            setattr(io, k, None if v is None else v.data_ptr())
+        return io
+
+    def _regen_ws(self):
+        """navsim_regen's workspace for self.cfg, made on first use."""
+        if "regen_ws" not in self.t:
+            import torch
+            nbytes = self.lib.navsim_regen_workspace_bytes(C.byref(self.cfg))
+            self.t["regen_ws"] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        return self.t["regen_ws"]
+
+    def _replan_ws(self, cap):
+        """navsim_replan's workspace for `cap` queries, made on first use."""
+        key = "replan_ws_%d" % cap
+        if key not in self.t:
+            import torch
+            nbytes = self.lib.navsim_replan_workspace_bytes(C.byref(self.cfg), cap)
+            self.t[key] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        return self.t[key]
+
+    def _regen_chunk(self, cfg, scratch_bytes):
+        """cfg.regen_cap = as many arenas as `scratch_bytes` of navsim_regen workspace serve (what one more arena costs: the
+        difference of two size queries) -> that workspace."""
+        import torch
+        cfg.regen_cap = 1
+        per = self.lib.navsim_regen_workspace_bytes(C.byref(cfg))
+        cfg.regen_cap = 2
+        per = max(self.lib.navsim_regen_workspace_bytes(C.byref(cfg)) - per, 1)
+        cfg.regen_cap = int(max(1, min(self.cfg.n_envs, scratch_bytes // per)))
+        return torch.empty(self.lib.navsim_regen_workspace_bytes(C.byref(cfg)), dtype=torch.uint8, device=self.device)
+
+    def _late_cfg_now(self):
+        """late_cfg = the configuration as it stands NOW, with the fallback's own cap."""
+        C.memmove(C.byref(self.late_cfg), C.byref(self.cfg), C.sizeof(self.cfg))
+        self.late_cfg.regen_cap = self.late_cap
+        return self.late_cfg
+
+    def _call_regen(self, cfg, ws, stream, what, current_obs=True, latest_flags=True, fork=True, **fields):
+        """navsim_regen on `stream` (None: the current one) with a copy of self.io: obs -> the current buffer (current_obs) and
+        `fields` on top (done = the flags of the arenas to serve).  latest_flags: st.ped_due -> the flags of the latest step.
+        fork=False: the call's own stream is handed to the library as helper stream for its duration (include/navsim.h: no fork)."""
+        if current_obs:
+            fields["obs"] = self.obs
+        io = self._io_copy(**fields)
+        if latest_flags:
+            self._latest_flags()
+        stream = _stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        helper = None if fork else self._regen_helper
+        if helper is not None:
+            self.lib.navsim_regen_helper(stream)
+        check(self.lib.navsim_regen(C.byref(cfg), C.byref(self.st), C.byref(io), _ptr(ws), ws.numel(), stream), what)
+        if helper is not None:
+            self.lib.navsim_regen_helper(C.c_void_p(helper.cuda_stream))
+
+    def regen(self):
+        """navsim_regen right after step(): finished arenas get a new map, tables, pedestrians, first obs."""
+        if self.pregen:
+            return self._regen_pregen()
+        self._choose_regen_helper()
+        # NEXT_STEP: the arenas the latest step RESET, i.e. those that finished the step before
+        self._call_regen(self.cfg, self._regen_ws(), None, "navsim_regen", **({"done": self.reset_flags} if self.next_step else {}))
         return self.obs
 
     def reset_arenas(self, mask, new_world=False, scratch_bytes=1 << 30):
@@ -1069,7 +1103,7 @@ class NavSim(object):
         (navsim_reset_obs) on the same map, or with new_world=True a new world each (navsim_regen in chunks of cfg.regen_cap
         arenas; worlds that draw a map per episode).  The other arenas keep their state and their rows."""
         import torch
-        if getattr(self, "pregen", False):
+        if self.pregen:
             raise ValueError("reset_arenas is not available with enable_pregen (the staged worlds follow the episodes' own order)")
         m = torch.as_tensor(mask).to(device=self.device).ne(0).to(torch.uint8).contiguous()
         check(self.lib.navsim_restart(C.byref(self.cfg), C.byref(self.st), _ptr(m), _stream()), "navsim_restart")
@@ -1080,21 +1114,13 @@ class NavSim(object):
             self._choose_regen_helper()
             cfg = self.cfg.copy()
             cfg.regen_min_steps = 0
-            if "regen_ws" not in self.t:
-                self.t["regen_ws"] = torch.zeros(self.lib.navsim_regen_workspace_bytes(C.byref(self.cfg)), dtype=torch.uint8, device=self.device)
-            ws = self.t["regen_ws"]
-            io = abi.NavsimStepIO()
-            C.memmove(C.byref(io), C.byref(self.io), C.sizeof(io))
-            io.obs = self.obs_buf[self.cur].data_ptr()
-            self._latest_flags()
+            ws = self._regen_ws()
             idx = torch.nonzero(m).flatten()
             chunk = torch.zeros_like(m)
-            io.done = chunk.data_ptr()
             for a in range(0, int(idx.numel()), int(self.cfg.regen_cap)):
                 chunk.zero_()
                 chunk[idx[a:a + int(self.cfg.regen_cap)]] = 1
-                check(self.lib.navsim_regen(C.byref(cfg), C.byref(self.st), C.byref(io), _ptr(ws), ws.numel(), _stream()),
-                      "navsim_regen (reset of some arenas)")
+                self._call_regen(cfg, ws, None, "navsim_regen (reset of some arenas)", done=chunk)
             torch.cuda.current_stream().synchronize()  # `chunk` is released on return
         return self.obs
 
@@ -1107,29 +1133,17 @@ class NavSim(object):
         must not reproduce the maps of the first)."""
         import torch
         E = self.cfg.n_envs
-        self._latest_flags()
         self._choose_regen_helper()
         if new_episode:
             self.t["episode"] += 1
         cfg = self.cfg.copy()
         cfg.regen_min_steps = 0                 # a reset of everything: whatever the last episodes' lengths
-        cfg.regen_cap = 1
-        per = self.lib.navsim_regen_workspace_bytes(C.byref(cfg))
-        cfg.regen_cap = 2
-        per = max(self.lib.navsim_regen_workspace_bytes(C.byref(cfg)) - per, 1)
-        chunk = int(max(1, min(E, scratch_bytes // per)))
-        cfg.regen_cap = chunk
-        ws = torch.empty(self.lib.navsim_regen_workspace_bytes(C.byref(cfg)), dtype=torch.uint8, device=self.device)
+        ws = self._regen_chunk(cfg, scratch_bytes)
         done = torch.zeros(E, dtype=torch.uint8, device=self.device)
-        io = abi.NavsimStepIO()
-        C.memmove(C.byref(io), C.byref(self.io), C.sizeof(io))
-        io.obs = self.obs_buf[self.cur].data_ptr()
-        io.done = done.data_ptr()
-        for a in range(0, E, chunk):
+        for a in range(0, E, cfg.regen_cap):
             done.zero_()
-            done[a:a + chunk] = 1
-            check(self.lib.navsim_regen(C.byref(cfg), C.byref(self.st), C.byref(io), _ptr(ws), ws.numel(), _stream()),
-                  "navsim_regen (reset of all arenas)")
+            done[a:a + cfg.regen_cap] = 1
+            self._call_regen(cfg, ws, None, "navsim_regen (reset of all arenas)", done=done)
         for b in self.out_buf:                             # nobody is finished after a reset (NEXT_STEP: the next launch's reset mask)
             b["done"].zero_()
             if "truncated" in b:
@@ -1164,12 +1178,7 @@ class NavSim(object):
         the waypoints of a planned path.  Needs the resident costmap (world.make_world(plan_paths=True)).
         flags=True: the candidates are the pedestrians the last step flagged (navsim_state.ped_due); False: the call
         finds them by its own pass over the state (after the caller moved pedestrians by hand)."""
-        import torch
-        key = "replan_ws_%d" % max_queries
-        if key not in self.t:
-            nbytes = self.lib.navsim_replan_workspace_bytes(C.byref(self.cfg), max_queries)
-            self.t[key] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        ws = self.t[key]
+        ws = self._replan_ws(max_queries)
         self._latest_flags()
         st = self.st
         if not flags:
@@ -1188,21 +1197,11 @@ class NavSim(object):
     # result is what the serial sequence gives.
     replan_in_step = True             # planned routes: navsim_step_replan (one launch) instead of the two-stream overlap
 
-    def launch_step_replan(self, replan_cap=1024, reorder=True):
-        """navsim_step_replan: the re-plan of the PREVIOUS step's flags inside this step's launch (include/navsim.h)."""
-        if reorder:
-            self._reorder()
-        self._flip()
-        rc = self.lib.navsim_step_replan(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), int(replan_cap), _stream())
-        if rc:
-            check(rc, "navsim_step_replan")
-        self.cur = 1 - self.cur
-
     overlap_big_first = False         # which stream takes the big launch (launch_step_overlapped); A/B: profiles/r05_replan/
 
     def _overlap_streams(self):
         import torch
-        if not hasattr(self, "_side"):
+        if self._side is None:
             self._side = concurrent_stream(self.device, priority=-1 if self.overlap_big_first else 0)
         return torch.cuda.current_stream(self.device), self._side
 
@@ -1226,14 +1225,9 @@ class NavSim(object):
             self.replan_in_step = False             # a costmap of more words than the arena's workgroup has threads: two streams
             self._flip()                            # (idempotent: the same parity)
             reorder = False
-        import torch
         main, side = self._overlap_streams()
         big, chain = (main, side) if self.overlap_big_first else (side, main)
-        key = "replan_ws_%d" % replan_cap
-        if key not in self.t:
-            self.t[key] = torch.zeros(self.lib.navsim_replan_workspace_bytes(C.byref(self.cfg), replan_cap), dtype=torch.uint8,
-                                      device=self.device)
-        ws = self.t[key]
+        ws = self._replan_ws(replan_cap)
         if reorder:
             self._reorder()
         for s_ in {big, chain} - {main}:            # the previous step (both parts were joined on `main`), regen, the actions
@@ -1259,14 +1253,7 @@ class NavSim(object):
         (launch_step_overlapped).  The sequence of calls  step_overlapped, step_overlapped, ...  equals
         step, replan, step, replan, ...  shifted by one replan: finish a rollout with replan() to leave the same state."""
         if action is not None:
-            import torch
-            if (isinstance(action, torch.Tensor) and action.is_cuda and action.dtype == torch.float64 and action.is_contiguous()
-                    and action.device == self.device and action.numel() == self.action.numel()):
-                self.io.action = action.data_ptr()
-                self._action_ref = action
-            else:
-                self.action.copy_(self._as(action, self.action))
-                self.io.action = self.action.data_ptr()
+            self._set_action(action)
         self.launch_step_overlapped(replan_cap)
         return self.obs, self.out
 
@@ -1295,7 +1282,7 @@ class NavSim(object):
         smaller slices run the layer below its peak, and every slice costs two cross-stream waits."""
         import torch
         main = torch.cuda.current_stream(self.device)
-        if not hasattr(self, "_scan_stream"):
+        if self._scan_stream is None:
             self._scan_stream = torch.cuda.Stream(device=self.device)
             self.t["ped_scan_rows"] = torch.zeros((self.cfg.n_envs, self.cfg.max_peds, self.cfg.ped_n_beams), dtype=torch.float32,
                                                   device=self.device)
@@ -1348,7 +1335,7 @@ class NavSim(object):
         params: None, a dict (ped_orca_params: unknown keys raise ValueError) or a ready abi.NavsimPedOrcaParams.
         Returns ped_cmd [E,N,2] float64; rows of slots >= n_peds[e] are left as they were."""
         if not isinstance(params, abi.NavsimPedOrcaParams):
-            if params is None and getattr(self, "_orca_default", None) is not None:
+            if params is None and self._orca_default is not None:
                 params = self._orca_default
             else:
                 made = ped_orca_params(self.cfg, params)
@@ -1378,22 +1365,15 @@ class NavSim(object):
         generation, where it does not matter).  Same kernels, same arguments, same per-arena order: same results.
         The configuration is captured BY VALUE: step_graphed() re-captures when self.cfg has changed since."""
         import torch
-        if getattr(self, "pregen", False):
+        if self.pregen:
             raise ValueError("enable_graphs and enable_pregen are alternatives")
         if regen:
             self._choose_regen_helper()                   # (timed with host synchronisation: before the capture)
-        io = abi.NavsimStepIO()
-        C.memmove(C.byref(io), C.byref(self.io), C.sizeof(io))
-        io.obs = self.obs_buf[self.cur].data_ptr()
-        check(self.lib.navsim_prepare(C.byref(self.cfg), C.byref(self.st), C.byref(io)), "navsim_prepare")
-        if regen and "regen_ws" not in self.t:
-            nbytes = self.lib.navsim_regen_workspace_bytes(C.byref(self.cfg))
-            self.t["regen_ws"] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        check(self.lib.navsim_prepare(C.byref(self.cfg), C.byref(self.st), C.byref(self._io_copy(obs=self.obs))), "navsim_prepare")
+        if regen:                                         # (the workspaces: allocated before the capture)
+            self._regen_ws()
         if replan_cap:
-            key = "replan_ws_%d" % replan_cap
-            if key not in self.t:
-                self.t[key] = torch.zeros(self.lib.navsim_replan_workspace_bytes(C.byref(self.cfg), replan_cap), dtype=torch.uint8,
-                                          device=self.device)
+            self._replan_ws(replan_cap)
         self.io.action = self.action.data_ptr()
         self._graph_args = (bool(regen), int(replan_cap), bool(overlap))
         overlap = bool(overlap) and replan_cap > 0

@@ -261,6 +261,47 @@ def test_env_picks_the_pipelined_reset_path_where_it_pays():
     assert mk(num_envs=8, map_size=500, randomize_maps=True, indoor_ratio=0.0, pregen_pipeline=2).pregen_pipeline == 2
 
 
+def test_env_reset_path_chosen_after_the_fact_equals_the_explicit_one():
+    """NavGymEnv._choose_reset_path(0) -- what reset() calls when the staged copy of the world does not fit -- leaves the
+    environment as pregen_pipeline=0 makes it, except for cfg.regen_cap: the fallback takes min(num_envs, 64), the constructor
+    leaves the library's 64.  The expected tuples (pregen_pipeline, cfg.defer_reset_scan, cfg.regen_cap, use_graphs) of the
+    explicit form were recorded from the constructor before the choice had a method of its own."""
+    import nav_gym_env
+    grid = [(dict(num_envs=8, map_size="reference", randomize_maps=True), (0, 1, 64, False)),
+            (dict(num_envs=8, map_size="reference", randomize_maps=True, pregen_pipeline=0), (0, 1, 64, False)),
+            (dict(num_envs=8, map_size=500, randomize_maps=True, indoor_ratio=0.0, use_graphs=True), (0, 1, 64, True)),
+            (dict(num_envs=8, map_size="reference", randomize_maps=True, pregen_pipeline=2, regen_min_steps=8), (0, 1, 64, False)),
+            (dict(num_envs=8, map_size="reference"), (0, 0, 64, False)),
+            (dict(num_envs=1, map_size="reference", randomize_maps=True), (0, 0, 64, False)),
+            (dict(num_envs=8, map_size=500, randomize_maps=True, indoor_ratio=0.0), (0, 1, 64, True)),
+            (dict(num_envs=8, map_size=500, randomize_maps=True, plan_paths=False), (0, 1, 64, True)),
+            (dict(num_envs=8, map_size=1100, randomize_maps=True), (0, 1, 64, True)),
+            (dict(num_envs=8, map_size=500, randomize_maps=True, indoor_ratio=0.0, pregen_pipeline=2), (0, 1, 64, True))]
+    for kw, want in grid:
+        a = nav_gym_env.make("NavGym-v0", **kw)
+        a._choose_reset_path(0)
+        b = nav_gym_env.make("NavGym-v0", **dict(kw, pregen_pipeline=0))
+        assert (b.pregen_pipeline, b.cfg.defer_reset_scan, b.cfg.regen_cap, b.use_graphs) == want, kw
+        assert (a.pregen_pipeline, a.cfg.defer_reset_scan, a.use_graphs) == (want[0], want[1], want[3]), kw
+        assert a.cfg.regen_cap == min(kw["num_envs"], 64), kw          # THE difference between the two
+        a.cfg.regen_cap = b.cfg.regen_cap
+        assert bytes(a.cfg) == bytes(b.cfg), kw
+
+
+def test_host_classes_declare_their_state():
+    """NavSim and NavGymEnv assign their attributes in __init__: no method asks getattr(self, "name", ...) or
+    hasattr(self, "name") for one that may not exist yet (a computed name, getattr(self, "reward_" + k), is another thing)."""
+    import ast
+    import nav_gym_amd
+    for name in ("sim.py", "env.py"):
+        tree = ast.parse(open(os.path.join(os.path.dirname(nav_gym_amd.__file__), name)).read())
+        bad = [n.lineno for n in ast.walk(tree)
+               if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id in ("getattr", "hasattr")
+               and len(n.args) >= 2 and isinstance(n.args[0], ast.Name) and n.args[0].id == "self"
+               and isinstance(n.args[1], ast.Constant) and isinstance(n.args[1].value, str)]
+        assert not bad, "%s: getattr / hasattr of self with a literal name at lines %s" % (name, bad)
+
+
 def test_world_generation_is_shard_invariant():
     import torch
     from nav_gym_amd import lib, world
