@@ -26,6 +26,7 @@ import torch  # noqa: E402
 
 E = 4096
 benv = nav_gym_env.make("NavGym-v0", num_envs=E, n_beams=1081, map_size=500, pedestrian_model="sfm", num_humans=10)
+# (pedestrian_model="orca", orca_params=dict(max_obst_rects=8, time_horizon_obst=2.0): ORCA pedestrians that also avoid walls)
 obs = benv.reset()
 actions = torch.rand((E, 2), dtype=torch.float64, device="cuda:0")
 actions[:, 0] *= 0.5

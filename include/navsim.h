@@ -850,8 +850,8 @@ int navsim_crowd_orca(const navsim_orca_params* p, int32_t n_queries, int32_t ma
  *     radius (ped_radius + 0.01) + safety_space, robot radius (robot_radius + 0.01) + safety_space, max_speed =
  *     ped_v_pref[e,i] for every entry; the robot's velocity is the one the social force sees,
  *     prev_action[e,0] * (cos, sin)(robot_pose[e,2]).  No obstacle polygons: static obstacles are NOT ORCA obstacles in
- *     this model -- pedestrians follow routes planned on the 1 m-inflated costmap (NAVSIM_PED_SFM is the model with a
- *     wall force).
+ *     this entry -- pedestrians follow routes planned on the 1 m-inflated costmap (navsim_ped_orca_walls below adds the
+ *     arena's listed rectangles; NAVSIM_PED_SFM has a wall force).
  *  4. navsim_crowd_orca's algorithm on that query with theta = ped_pose[e,i,2]: inputs rounded to float32 where that
  *     function rounds them; neighbour selection, half-planes and linear programs in float32; ActionRot
  *     v = sqrt(vx*vx + vy*vy), r = atan2(vy, vx) - theta (orca.py:128-130).
@@ -862,12 +862,51 @@ int navsim_crowd_orca(const navsim_orca_params* p, int32_t n_queries, int32_t ma
  * NAVSIM_E_ARG (before any device call): NULL p or ped_cmd, cfg->ped_model != NAVSIM_PED_EXTERNAL,
  * max_peds + robot_visible > NAVSIM_ORCA_MAX_AGENTS, a non-positive radius / time_step / time_horizon, max_neighbors < 0. */
 typedef struct navsim_ped_orca_params {
-    navsim_orca_params orca;    /* time_step, neighbor_dist, time_horizon, time_horizon_obst (unused: no obstacles), max_neighbors */
+    navsim_orca_params orca;    /* time_step, neighbor_dist, time_horizon, time_horizon_obst (navsim_ped_orca_walls only), max_neighbors */
     double ped_radius, robot_radius, safety_space;
     int32_t robot_visible;      /* 1: the robot is the last agent of every pedestrian's list */
 } navsim_ped_orca_params;
 int navsim_ped_orca(const navsim_config* cfg, const navsim_state* st, const navsim_ped_orca_params* p,
                     double* ped_cmd /* [E,N,2] out */, void* stream);
+/* navsim_ped_orca with the arena's LISTED rectangles as ORCA obstacles.  Steps 1, 2, 3 and 5 are navsim_ped_orca's; step 4 is
+ * navsim_crowd_orca's algorithm on the same query WITH a polygon set, chosen per pedestrian:
+ *  - the rectangle list of arena e: entries k = 0 .. 254 of the arena's st->rect_index row (the first 256 x 8 bytes: int16
+ *    x0, y0, x1, y1, one distinct rectangle of occupied cells each), the row found through st->map_slot and
+ *    cfg->shared_field as the step finds it.  Entries that are all zero are skipped wherever they stand -- so the lone cell
+ *    (0,0) as a rectangle of its own is NOT an obstacle -- and so is an entry with x1 < x0 or y1 < y0 (no builder writes one).
+ *    x is the index xy_to_ij returns first.
+ *  - vertices in float64, rounded to float32 where navsim_crowd_orca rounds its verts: xa = origin_x + (double)x0 * resolution,
+ *    xb = origin_x + (double)(x1 + 1) * resolution, ya / yb likewise with origin_y; counter-clockwise (xa,ya), (xb,ya),
+ *    (xb,yb), (xa,yb).
+ *  - selection, float32 with nothing contracted: range_sq = sqr(time_horizon_obst * max_speed + radius) (navsim_crowd_orca's
+ *    obstacle range), dx = max(max(xa - px, px - xb), 0), dy likewise, d2 = dx*dx + dy*dy; in range when d2 < range_sq.  The
+ *    max_rects nearest in-range rectangles are kept by Agent::insertAgentNeighbor's rule over ascending k: strict <, ties to
+ *    the lower k, the range shrinks to the farthest kept rectangle once the list is full.
+ *  - dropped[e,i] (or NULL) = in-range rectangles - kept ones: the cap is observable, no call fails because of it.
+ *  - the polygon set of the query: the kept rectangles in ascending k, n_vert = 4; obstacle neighbour edges, the obstacle
+ *    half-planes, the agent half-planes behind them, linearProgram2, linearProgram3 with the obstacle half-planes kept are
+ *    navsim_crowd_orca's.  (A point outside an axis-aligned rectangle is strictly outside at most two of its edges: at most
+ *    2 max_rects obstacle edges and half-planes per pedestrian.)
+ * What is an obstacle: the LISTED rectangles and nothing else.  On worlds from navsim_regen with outdoor maps these are the
+ * border ring and every box; on other maps the rectangles of the valid tile records (navsim_build_rects) -- a subset of the
+ * occupied cells, never a free cell; occupied cells no record names are not seen.  With the default time_horizon_obst = 5
+ * the range is about 5 m, more rectangles are in range than kept and dropped is often non-zero: the NEAREST are kept.
+ * max_rects = 0: navsim_ped_orca bit for bit (no rectangle is read, rect_index may be NULL, dropped = 0 for live pedestrians).
+ * Bit-identical to that composition (tests/ped_orca_walls_spec.py).  Checked in float64 (tests/orca_f64.py): with
+ * time_horizon_obst 0.5 and 2 the disc swept for time_horizon_obst along the answer enters no kept rectangle by more than
+ * 3e-6 m where it starts clear by 1 mm and nothing was dropped (every max_rects).  NOT bounded: time_horizon_obst = 5 with
+ * ten rectangles of a 6 m map in range -- 2 of 90 queries of a 33-pedestrian arena were sent into a box (the centre's path
+ * 0.05 m from its corner within the horizon), and other scenes of the kind show the same: a box more than 1.2 m away gets no
+ * half-plane, as in navsim_crowd_orca on the same polygons.  Prefer time_horizon_obst <= 2.
+ * NAVSIM_E_ARG: navsim_ped_orca's refusals; max_rects < 0 or > NAVSIM_PED_ORCA_MAX_RECTS; max_rects > 0 with
+ * st->rect_index == NULL, time_horizon_obst <= 0, cfg->resolution <= 0, cfg->map_h or map_w < 1 (the row cannot be found or
+ * turned into metres), or st->map_slot together with cfg->shared_field (which navsim_step refuses too).  NAVSIM_E_UNSUPPORTED, before any launch: the lists of one wavefront --
+ * 4 (5 G (N + 1) + (10 L + 16 max_rects) G N) bytes, G = 64 / N arenas (1 above 32), L = min(max_neighbors, N - 1 +
+ * robot_visible) -- exceed a CU's 160 KB of LDS. */
+#define NAVSIM_PED_ORCA_MAX_RECTS 32   /* 4 x 32 = NAVSIM_ORCA_MAX_EDGES: navsim_crowd_orca can always express the query */
+int navsim_ped_orca_walls(const navsim_config* cfg, const navsim_state* st, const navsim_ped_orca_params* p,
+                          int32_t max_rects, double* ped_cmd /* [E,N,2] out */, int32_t* dropped /* [E,N] out or NULL */,
+                          void* stream);
 /* Agent.step with an ActionRot (agent.py:108-141): theta' = theta + r; p += (cos, sin)(theta') * v * dt;
  * vel = v * (cos, sin)(theta'); theta = theta' mod 2 pi.  pose [n,3] in/out, action [n,2], vel [n,2] or NULL. */
 int navsim_crowd_agent_step(double* pose, const double* action, double* vel, int32_t n, double time_step, void* stream);

@@ -180,70 +180,47 @@ struct Obstacles {
     }
 };
 
-}  // namespace orca
-
-__global__ __launch_bounds__(64) void crowd_orca_kernel(navsim_orca_params p, int n_queries, int max_agents,
-                                                        const double* __restrict__ agents, const int32_t* __restrict__ n_agents,
-                                                        const double* __restrict__ pref_vel, int max_obst, int n_vert,
-                                                        const double* __restrict__ verts, const int32_t* __restrict__ n_obst,
-                                                        const int32_t* __restrict__ obst_set, const double* __restrict__ theta,
-                                                        double* __restrict__ out_vel, double* __restrict__ out_action) {
-    using namespace orca;
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n_queries) return;
-    const double* ag = agents + (size_t)q * max_agents * 6;
-    int na = n_agents ? n_agents[q] : max_agents;
-    na = na > max_agents ? max_agents : na;
-    if (na < 1) { out_vel[2 * q] = 0.0; out_vel[2 * q + 1] = 0.0; return; }
-    const V2 position = v2((float)ag[0], (float)ag[1]), velocity = v2((float)ag[2], (float)ag[3]);
-    const float radius = (float)ag[4], max_speed = (float)ag[5];
-    const V2 pref = v2((float)pref_vel[2 * q], (float)pref_vel[2 * q + 1]);
-    const int set = obst_set ? obst_set[q] : 0;
-    int no = max_obst ? (n_obst ? n_obst[set] : max_obst) : 0;
-    no = no > max_obst ? max_obst : no;
-    const Obstacles ob = {verts + (size_t)set * max_obst * n_vert * 2, n_vert};
-    const int n_edges = no * n_vert;
-    // ---- Agent::computeNeighbors
-    int obn[NAVSIM_ORCA_MAX_EDGES]; float obd[NAVSIM_ORCA_MAX_EDGES]; int n_obn = 0;
-    {
-        const float range_sq = sqr(p.time_horizon_obst * max_speed + radius);
-        for (int k = 0; k < n_edges; ++k) {
-            const V2 a = ob.point(k), b = ob.point(ob.next(k));
-            const float left_of = det(a - position, b - a);
-            const float d_line = sqr(left_of) / abs_sq(b - a);
-            if (!(d_line < range_sq) || !(left_of < 0.0f)) continue;
-            const float r = dot(position - a, b - a) / abs_sq(b - a);
-            float d;
-            if (r < 0.0f) d = abs_sq(position - a);
-            else if (r > 1.0f) d = abs_sq(position - b);
-            else d = abs_sq(position - (a + r * (b - a)));
-            if (d < range_sq) {
-                int i = n_obn++;
-                while (i != 0 && d < obd[i - 1]) { obn[i] = obn[i - 1]; obd[i] = obd[i - 1]; --i; }
-                obn[i] = k; obd[i] = d;
-            }
+// Agent::computeNeighbors, the obstacle part: the edges k < n_edges of `ob` that have the agent strictly on their outer side
+// and lie nearer than the range, in ascending distance (ties: ascending k) -> how many.  OB: Obstacles or a source of the
+// same interface (kernels_ped_orca.hpp Rects); NB: PrivNeighbors or LdsNeighbors.
+template <class OB, class NB>
+__device__ int obstacle_neighbors(const OB& ob, int n_edges, V2 position, float range_sq, const NB& nb) {
+    int n_obn = 0;
+    for (int k = 0; k < n_edges; ++k) {
+        const V2 a = ob.point(k), b = ob.point(ob.next(k));
+        const float left_of = det(a - position, b - a);
+        const float d_line = sqr(left_of) / abs_sq(b - a);
+        if (!(d_line < range_sq) || !(left_of < 0.0f)) continue;
+        const float r = dot(position - a, b - a) / abs_sq(b - a);
+        float d;
+        if (r < 0.0f) d = abs_sq(position - a);
+        else if (r > 1.0f) d = abs_sq(position - b);
+        else d = abs_sq(position - (a + r * (b - a)));
+        if (d < range_sq) {
+            int i = n_obn++;
+            while (i != 0 && d < nb.dist(i - 1)) { nb.set(i, nb.index(i - 1), nb.dist(i - 1)); --i; }
+            nb.set(i, k, d);
         }
     }
-    int agn[NAVSIM_ORCA_MAX_AGENTS]; float agd[NAVSIM_ORCA_MAX_AGENTS]; int n_agn = 0;
-    if (p.max_neighbors > 0) {
-        float range_sq = sqr(p.neighbor_dist);
-        const int max_n = p.max_neighbors < NAVSIM_ORCA_MAX_AGENTS ? p.max_neighbors : NAVSIM_ORCA_MAX_AGENTS;
-        const PrivNeighbors nb = {agn, agd};
-        for (int k = 1; k < na; ++k)
-            insert_neighbor(nb, n_agn, max_n, k, abs_sq(position - v2((float)ag[6 * k], (float)ag[6 * k + 1])), range_sq);
-    }
-    // ---- Agent::computeNewVelocity: obstacle half-planes
-    Line lines[kMaxLines];
+    return n_obn;
+}
+
+// Agent::computeNewVelocity, the obstacle part: the half-planes of the n_obn edges listed in `nb`, written to `lines` from
+// entry 0 on -> how many.  LS: PrivLines or LdsLines.
+template <class OB, class NB, class LS>
+__device__ int obstacle_lines(const OB& ob, const NB& nb, int n_obn, V2 position, V2 velocity, float radius, float inv_tho,
+                              const LS& lines) {
     int nl = 0;
-    const float inv_tho = 1.0f / p.time_horizon_obst;
     for (int i = 0; i < n_obn; ++i) {
-        int o1 = obn[i], o2 = ob.next(o1);
+        int o1 = nb.index(i), o2 = ob.next(o1);
         const V2 p1 = ob.point(o1), p2 = ob.point(o2);
         const V2 rel1 = p1 - position, rel2 = p2 - position;
         bool covered = false;
-        for (int j = 0; j < nl; ++j)
-            if (det(inv_tho * rel1 - lines[j].point, lines[j].direction) - inv_tho * radius >= -kEps &&
-                det(inv_tho * rel2 - lines[j].point, lines[j].direction) - inv_tho * radius >= -kEps) { covered = true; break; }
+        for (int j = 0; j < nl; ++j) {
+            const Line Lj = lines.get(j);
+            if (det(inv_tho * rel1 - Lj.point, Lj.direction) - inv_tho * radius >= -kEps &&
+                det(inv_tho * rel2 - Lj.point, Lj.direction) - inv_tho * radius >= -kEps) { covered = true; break; }
+        }
         if (covered) continue;
         const float d1 = abs_sq(rel1), d2 = abs_sq(rel2), rsq = sqr(radius);
         const V2 ovec = p2 - p1;
@@ -253,15 +230,15 @@ __global__ __launch_bounds__(64) void crowd_orca_kernel(navsim_orca_params p, in
         const V2 dir1 = ob.unit_dir(o1);
         Line line;
         if (s < 0.0f && d1 <= rsq) {
-            if (convex1) { line.point = v2(0.0f, 0.0f); line.direction = normalize(v2(-rel1.y, rel1.x)); lines[nl++] = line; }
+            if (convex1) { line.point = v2(0.0f, 0.0f); line.direction = normalize(v2(-rel1.y, rel1.x)); lines.set(nl++, line); }
             continue;
         } else if (s > 1.0f && d2 <= rsq) {
             if (convex2 && det(rel2, ob.unit_dir(o2)) >= 0.0f) {
-                line.point = v2(0.0f, 0.0f); line.direction = normalize(v2(-rel2.y, rel2.x)); lines[nl++] = line;
+                line.point = v2(0.0f, 0.0f); line.direction = normalize(v2(-rel2.y, rel2.x)); lines.set(nl++, line);
             }
             continue;
         } else if (s >= 0.0f && s < 1.0f && d_line <= rsq) {
-            line.point = v2(0.0f, 0.0f); line.direction = -dir1; lines[nl++] = line;
+            line.point = v2(0.0f, 0.0f); line.direction = -dir1; lines.set(nl++, line);
             continue;
         }
         V2 left_leg, right_leg;
@@ -300,13 +277,13 @@ __global__ __launch_bounds__(64) void crowd_orca_kernel(navsim_orca_params p, in
             const V2 w = normalize(velocity - left_cut);
             line.direction = v2(w.y, -w.x);
             line.point = left_cut + (radius * inv_tho) * w;
-            lines[nl++] = line;
+            lines.set(nl++, line);
             continue;
         } else if (t > 1.0f && t_right < 0.0f) {
             const V2 w = normalize(velocity - right_cut);
             line.direction = v2(w.y, -w.x);
             line.point = right_cut + (radius * inv_tho) * w;
-            lines[nl++] = line;
+            lines.set(nl++, line);
             continue;
         }
         const float inf = __builtin_inff();
@@ -316,19 +293,61 @@ __global__ __launch_bounds__(64) void crowd_orca_kernel(navsim_orca_params p, in
         if (ds_cut <= ds_left && ds_cut <= ds_right) {
             line.direction = -dir_o1;
             line.point = left_cut + (radius * inv_tho) * v2(-line.direction.y, line.direction.x);
-            lines[nl++] = line;
+            lines.set(nl++, line);
         } else if (ds_left <= ds_right) {
             if (left_foreign) continue;
             line.direction = left_leg;
             line.point = left_cut + (radius * inv_tho) * v2(-line.direction.y, line.direction.x);
-            lines[nl++] = line;
+            lines.set(nl++, line);
         } else {
             if (right_foreign) continue;
             line.direction = -right_leg;
             line.point = right_cut + (radius * inv_tho) * v2(-line.direction.y, line.direction.x);
-            lines[nl++] = line;
+            lines.set(nl++, line);
         }
     }
+    return nl;
+}
+
+}  // namespace orca
+
+__global__ __launch_bounds__(64) void crowd_orca_kernel(navsim_orca_params p, int n_queries, int max_agents,
+                                                        const double* __restrict__ agents, const int32_t* __restrict__ n_agents,
+                                                        const double* __restrict__ pref_vel, int max_obst, int n_vert,
+                                                        const double* __restrict__ verts, const int32_t* __restrict__ n_obst,
+                                                        const int32_t* __restrict__ obst_set, const double* __restrict__ theta,
+                                                        double* __restrict__ out_vel, double* __restrict__ out_action) {
+    using namespace orca;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_queries) return;
+    const double* ag = agents + (size_t)q * max_agents * 6;
+    int na = n_agents ? n_agents[q] : max_agents;
+    na = na > max_agents ? max_agents : na;
+    if (na < 1) { out_vel[2 * q] = 0.0; out_vel[2 * q + 1] = 0.0; return; }
+    const V2 position = v2((float)ag[0], (float)ag[1]), velocity = v2((float)ag[2], (float)ag[3]);
+    const float radius = (float)ag[4], max_speed = (float)ag[5];
+    const V2 pref = v2((float)pref_vel[2 * q], (float)pref_vel[2 * q + 1]);
+    const int set = obst_set ? obst_set[q] : 0;
+    int no = max_obst ? (n_obst ? n_obst[set] : max_obst) : 0;
+    no = no > max_obst ? max_obst : no;
+    const Obstacles ob = {verts + (size_t)set * max_obst * n_vert * 2, n_vert};
+    const int n_edges = no * n_vert;
+    // ---- Agent::computeNeighbors
+    int obn[NAVSIM_ORCA_MAX_EDGES]; float obd[NAVSIM_ORCA_MAX_EDGES];
+    const PrivNeighbors obs = {obn, obd};
+    const int n_obn = obstacle_neighbors(ob, n_edges, position, sqr(p.time_horizon_obst * max_speed + radius), obs);
+    int agn[NAVSIM_ORCA_MAX_AGENTS]; float agd[NAVSIM_ORCA_MAX_AGENTS]; int n_agn = 0;
+    if (p.max_neighbors > 0) {
+        float range_sq = sqr(p.neighbor_dist);
+        const int max_n = p.max_neighbors < NAVSIM_ORCA_MAX_AGENTS ? p.max_neighbors : NAVSIM_ORCA_MAX_AGENTS;
+        const PrivNeighbors nb = {agn, agd};
+        for (int k = 1; k < na; ++k)
+            insert_neighbor(nb, n_agn, max_n, k, abs_sq(position - v2((float)ag[6 * k], (float)ag[6 * k + 1])), range_sq);
+    }
+    // ---- Agent::computeNewVelocity: obstacle half-planes
+    Line lines[kMaxLines];
+    const PrivLines ls = {lines};
+    int nl = obstacle_lines(ob, obs, n_obn, position, velocity, radius, 1.0f / p.time_horizon_obst, ls);
     const int n_obst_lines = nl;
     const float inv_th = 1.0f / p.time_horizon;
     for (int i = 0; i < n_agn; ++i) {
@@ -337,7 +356,6 @@ __global__ __launch_bounds__(64) void crowd_orca_kernel(navsim_orca_params p, in
                                  inv_th, p.time_step);
     }
     V2 nv;
-    const PrivLines ls = {lines};
     const int fail = lp2(ls, nl, max_speed, pref, false, nv);
     if (fail < nl) {
         Line proj[kMaxLines];

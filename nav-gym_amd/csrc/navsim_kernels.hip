@@ -1167,7 +1167,9 @@ int navsim_crowd_orca(const navsim_orca_params* p, int32_t n_queries, int32_t ma
     return launch_status();
 }
 
-int navsim_ped_orca(const navsim_config* c, const navsim_state* st, const navsim_ped_orca_params* p, double* ped_cmd, void* stream) {
+// navsim_ped_orca and navsim_ped_orca_walls: the refusals, the layout's LDS, one launch
+static int ped_orca_run(const navsim_config* c, const navsim_state* st, const navsim_ped_orca_params* p, int32_t max_rects,
+                        double* ped_cmd, int32_t* dropped, void* stream) {
     (void)hipGetLastError();
     if (!c || !st || !p || !ped_cmd) return NAVSIM_E_ARG;
     if (c->ped_model != NAVSIM_PED_EXTERNAL || c->n_envs < 0 || c->max_peds < 1) return NAVSIM_E_ARG;
@@ -1180,13 +1182,30 @@ int navsim_ped_orca(const navsim_config* c, const navsim_state* st, const navsim
     if (!st->n_peds || !st->ped_pose || !st->ped_vel || !st->ped_v_pref || !st->ped_waypoints || !st->ped_n_waypoints ||
         !st->ped_wp_head || (p->robot_visible && (!st->robot_pose || !st->prev_action)))
         return NAVSIM_E_ARG;
-    if (c->n_envs == 0) return NAVSIM_OK;
+    if (max_rects < 0 || max_rects > NAVSIM_PED_ORCA_MAX_RECTS) return NAVSIM_E_ARG;
+    if (max_rects > 0 && (!st->rect_index || !(p->orca.time_horizon_obst > 0.0f) || !(c->resolution > 0.0) || c->map_h < 1 ||
+                          c->map_w < 1 || (st->map_slot && c->shared_field)))
+        return NAVSIM_E_ARG;
     const int N = c->max_peds, G = ped_orca_pack(N);
-    const size_t lds = ped_orca_lds_bytes(N, ped_orca_list_len(N, p->orca.max_neighbors, p->robot_visible));
-    const int rc = allow_lds((const void*)ped_orca_kernel, lds);
+    const size_t lds = ped_orca_lds_bytes(N, ped_orca_list_len(N, p->orca.max_neighbors, p->robot_visible), max_rects);
+    if (lds > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;               // (before any device call, whatever n_envs is)
+    if (c->n_envs == 0) return NAVSIM_OK;
+    const void* kernel = max_rects > 0 ? (const void*)ped_orca_kernel<true> : (const void*)ped_orca_kernel<false>;
+    const int rc = allow_lds(kernel, lds);
     if (rc != NAVSIM_OK) return rc;
-    ped_orca_kernel<<<(c->n_envs + G - 1) / G, 64, lds, (hipStream_t)stream>>>(*c, *st, *p, ped_cmd);
+    const int grid = (c->n_envs + G - 1) / G;
+    if (max_rects > 0) ped_orca_kernel<true><<<grid, 64, lds, (hipStream_t)stream>>>(*c, *st, *p, max_rects, ped_cmd, dropped);
+    else               ped_orca_kernel<false><<<grid, 64, lds, (hipStream_t)stream>>>(*c, *st, *p, 0, ped_cmd, dropped);
     return launch_status();
+}
+
+int navsim_ped_orca(const navsim_config* c, const navsim_state* st, const navsim_ped_orca_params* p, double* ped_cmd, void* stream) {
+    return ped_orca_run(c, st, p, 0, ped_cmd, nullptr, stream);
+}
+
+int navsim_ped_orca_walls(const navsim_config* c, const navsim_state* st, const navsim_ped_orca_params* p, int32_t max_rects,
+                          double* ped_cmd, int32_t* dropped, void* stream) {
+    return ped_orca_run(c, st, p, max_rects, ped_cmd, dropped, stream);
 }
 
 int navsim_crowd_agent_step(double* pose, const double* action, double* vel, int32_t n, double time_step, void* stream) {

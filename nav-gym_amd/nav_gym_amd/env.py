@@ -19,8 +19,14 @@ and default to the reference's behaviour for num_envs == 1:
                     policy_weights = the state_dict of human_policy.pth, a path to it, or a dict of arrays),
                     'sfm' (build-defined social force), 'orca' (build-defined: reciprocal velocity obstacles among the
                     arena's pedestrians and the robot toward the current waypoint, NavSim.ped_orca in front of every step;
-                    orca_params = dict overriding sim.ped_orca_defaults, unknown keys raise ValueError; static obstacles
-                    are not ORCA obstacles; ordered like 'policy': no graphs, no pregen_pipeline), 'external' (caller
+                    orca_params = dict overriding sim.ped_orca_defaults, unknown keys raise ValueError; with the default
+                    max_obst_rects = 0 static obstacles are not ORCA obstacles, max_obst_rects = K in 1 .. 32 makes every
+                    pedestrian avoid the K nearest LISTED rectangles of its arena (NavSim.ped_orca_walls: the border ring and
+                    the boxes of outdoor maps, within time_horizon_obst * v_pref + radius; needs the packed field's rect
+                    records -- a world without them raises ValueError at construction; set time_horizon_obst = 2 or less
+                    with it: the pinned default of 5 s puts more rectangles in range than are kept and is the setting
+                    DESIGN.md section 5 lists as NOT bounded);
+                    ordered like 'policy': no graphs, no pregen_pipeline), 'external' (caller
                     supplies (v, w) per pedestrian -- the slot the reference fills with HumanPolicy) or 'none'
     action_kind     'twist' (default): action = (v, omega) like the reference (env.py:591); 'wheels': action = the
                     angular speeds (left, right) of a skid-steer base's wheel pairs in rad/s, converted on the device
@@ -240,6 +246,9 @@ class NavGymEnv(_EnvBase):
                 raise ValueError("unknown key %r in orca_params (known: %s)" % (k, ", ".join(_simmod.PED_ORCA_KEYS)))
         self.orca_params = None if orca_params is None else dict(orca_params)
         self._orca_struct = None
+        self._orca_rects = int((orca_params or {}).get("max_obst_rects", 0)) if pedestrian_model == "orca" else 0
+        if not 0 <= self._orca_rects <= 32:
+            raise ValueError("orca_params['max_obst_rects'] must be in 0 .. 32, not %r" % (self._orca_rects,))
         self.auto_reset = (self.num_envs > 1) if auto_reset is None else bool(auto_reset)
         if autoreset_mode not in ("same_step", "next_step"):
             raise ValueError("autoreset_mode must be 'same_step' or 'next_step'")
@@ -332,6 +341,14 @@ class NavGymEnv(_EnvBase):
         cfg.max_episode_steps = self.max_episode_steps or 0     # (0: no limit -- the step's plain form where it has one)
         cfg.regen_plan = int(self.plan_paths)
         cfg.regen_indoor_ratio = float(indoor_ratio)
+        # rect records (the march's shortcut around most field reads): always for fixed maps; with a new map per episode
+        # only in worlds of outdoor maps, whose records come out of the pass that writes the new field -- corridor maps
+        # would need the verified builder for a handful of maps per step, which costs more than the records save
+        self._with_rects = (cfg.field_format == abi.FIELD_U16T and self.map_size <= 1024 and
+                            (not self.randomize_maps or not cfg.regen_indoor_ratio > 0.0))
+        if self._orca_rects and not self._with_rects:
+            raise ValueError("orca_params['max_obst_rects'] > 0 needs a world with rect_index rows (the packed field, "
+                             "map_size <= 1024, and with randomize_maps outdoor maps only: indoor_ratio = 0)")
         cfg.outdoor_map_size = int(self.outdoor_map_size)
         room = (self.outdoor_map_size or self.map_size) * cfg.resolution
         cfg.min_goal_dist = float(min(min_goal_dist, 0.4 * room))
@@ -482,14 +499,9 @@ class NavGymEnv(_EnvBase):
         first = self.sim is None
         if first:
             dev = torch.device(self.device)
-            # rect records (the march's shortcut around most field reads): always for fixed maps; with a new map per episode
-            # only in worlds of outdoor maps, whose records come out of the pass that writes the new field -- corridor maps
-            # would need the verified builder for a handful of maps per step, which costs more than the records save
-            with_rects = (cfg.field_format == abi.FIELD_U16T and self.map_size <= 1024 and
-                          (not self.randomize_maps or not cfg.regen_indoor_ratio > 0.0))
             arrays = world.empty_world(cfg, device=self.device,
                                        plan_paths=self.plan_paths and cfg.ped_model != abi.PED_NONE,
-                                       rect_table=with_rects)
+                                       rect_table=self._with_rects)
             for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
                 arrays[key] = simmod.scan_threshold(cfg, torch.from_numpy(robots.footprint_array(self.robot_type, name)).to(dev))
             # every map of this world comes from navsim_regen, whose generators close their maps with a border wall
@@ -588,7 +600,10 @@ class NavGymEnv(_EnvBase):
             if self._orca_struct is None:
                 from . import sim as simmod
                 self._orca_struct = simmod.ped_orca_params(self.sim.cfg, self.orca_params, self.robot_type)
-            self.sim.ped_orca(self._orca_struct)            # the simulator's state -> ORCA -> (v, omega), one launch
+            if self._orca_rects:                            # ... with the arena's listed rectangles as obstacles
+                self.sim.ped_orca_walls(self._orca_struct, self._orca_rects)
+            else:
+                self.sim.ped_orca(self._orca_struct)        # the simulator's state -> ORCA -> (v, omega), one launch
         a = np.asarray(action, dtype=np.float64).reshape(self.num_envs, 2) if not hasattr(action, "is_cuda") else action
         path = self._step_path
         if path == "graphed":                               # step + regen + replan: one graph launch (NavSim.enable_graphs)

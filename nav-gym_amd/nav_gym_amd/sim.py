@@ -262,17 +262,18 @@ def crowd_local_map(params, free_map, robot, rotate=True):
 
 
 ORCA_KEYS = ("time_step", "neighbor_dist", "time_horizon", "time_horizon_obst", "max_neighbors")
-PED_ORCA_KEYS = ORCA_KEYS + ("ped_radius", "robot_radius", "safety_space", "robot_visible")
+PED_ORCA_KEYS = ORCA_KEYS + ("ped_radius", "robot_radius", "safety_space", "robot_visible", "max_obst_rects")
 
 
 def ped_orca_defaults(cfg, robot_type="keti"):
     """The parameters of navsim_ped_orca as a dict: orca.py:62-65's neighbourhood, the simulator's time step, discs around
-    the footprints of robots.py (the pedestrian's ~ 0.291 m), no safety space, the robot visible."""
+    the footprints of robots.py (the pedestrian's ~ 0.291 m), no safety space, the robot visible.  max_obst_rects is not a
+    field of the struct: it is navsim_ped_orca_walls's max_rects (0: static obstacles are not ORCA obstacles)."""
     from . import robots
     return dict(time_step=cfg.time_step, neighbor_dist=10.0, time_horizon=5.0, time_horizon_obst=5.0, max_neighbors=10,
                 ped_radius=robots.footprint_radius(robots.HUMAN["footprint"]),
                 robot_radius=robots.footprint_radius(robots.ROBOTS[robot_type]["footprint"]),
-                safety_space=0.0, robot_visible=1)
+                safety_space=0.0, robot_visible=1, max_obst_rects=0)
 
 
 def ped_orca_params(cfg, params=None, robot_type="keti"):
@@ -1329,21 +1330,40 @@ class NavSim(object):
                                          ws.numel(), _stream()), "navsim_ped_policy")
         return self.t["ped_cmd"], self.t["policy_prev_actions"]
 
+    def _ped_orca_struct(self, params):
+        if isinstance(params, abi.NavsimPedOrcaParams):
+            return params
+        if params is None:
+            if self._orca_default is None:
+                self._orca_default = ped_orca_params(self.cfg, None)
+            return self._orca_default
+        return ped_orca_params(self.cfg, params)
+
     def ped_orca(self, params=None):
         """navsim_ped_orca: ORCA pedestrians from the simulator's own state -> ped_cmd for a NAVSIM_PED_EXTERNAL step, one
         kernel on the simulator's stream (waypoint pop, preferred velocity, neighbours out of LDS, the linear programs).
         params: None, a dict (ped_orca_params: unknown keys raise ValueError) or a ready abi.NavsimPedOrcaParams.
         Returns ped_cmd [E,N,2] float64; rows of slots >= n_peds[e] are left as they were."""
-        if not isinstance(params, abi.NavsimPedOrcaParams):
-            if params is None and self._orca_default is not None:
-                params = self._orca_default
-            else:
-                made = ped_orca_params(self.cfg, params)
-                if params is None:
-                    self._orca_default = made
-                params = made
+        params = self._ped_orca_struct(params)
         check(self.lib.navsim_ped_orca(C.byref(self.cfg), C.byref(self.st), C.byref(params), _ptr(self.t["ped_cmd"]), _stream()),
               "navsim_ped_orca")
+        return self.t["ped_cmd"]
+
+    def ped_orca_walls(self, params=None, max_rects=8, dropped=None):
+        """navsim_ped_orca_walls: ped_orca() with the arena's listed rectangles (the list of its t['rect_index'] row) as ORCA
+        obstacles -- every pedestrian avoids the max_rects (<= 32) nearest of them within time_horizon_obst * v_pref + radius.
+        params as for ped_orca() (a dict's max_obst_rects is ignored: max_rects says it); dropped: None or an int32 [E,N]
+        tensor that receives, per live pedestrian, how many rectangles in range were not kept.  max_rects = 0 is ped_orca().
+        Returns ped_cmd [E,N,2] float64."""
+        import torch
+        params = self._ped_orca_struct(params)
+        if dropped is not None and (dropped.dtype != torch.int32 or not dropped.is_contiguous() or
+                                    tuple(dropped.shape) != (self.cfg.n_envs, self.cfg.max_peds) or
+                                    dropped.device != self.t["ped_cmd"].device):
+            raise ValueError("dropped must be a contiguous int32 [E,N] tensor on the simulator's device")
+        check(self.lib.navsim_ped_orca_walls(C.byref(self.cfg), C.byref(self.st), C.byref(params), int(max_rects),
+                                             _ptr(self.t["ped_cmd"]), None if dropped is None else _ptr(dropped), _stream()),
+              "navsim_ped_orca_walls")
         return self.t["ped_cmd"]
 
     def ped_scans(self):
