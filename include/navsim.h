@@ -941,6 +941,31 @@ int navsim_reset_obs(const navsim_config* cfg, const navsim_state* st, const nav
  * Needs the spawn tables. */
 int navsim_restart(const navsim_config* cfg, const navsim_state* st, const uint8_t* mask, void* stream);
 
+/* reset() of SOME arenas on a simulator with staged worlds (navsim_regen_stage; stage, stage_obs, mark, ready as for
+ * navsim_step_install), in ONE launch: a workgroup of 256 threads per arena.  io: what navsim_reset_obs takes (obs_prev, obs,
+ * the goal arrays).
+ *   mask[e] == 0  the arena keeps its state; its row is copied obs_prev -> obs (as navsim_reset_obs does); late[e] = 0.
+ *   mask[e] != 0  first what navsim_restart does: done_steps[e] = steps[e], episode[e] += 1, steps[e] = 0, the next start /
+ *                 goal pair.  Then ready[e] is read (acquire, device scope).  If it equals the new episode[e], the arena's
+ *                 workgroup installs the staged world exactly as the step does for an arena that finishes: the slot-table
+ *                 exchange (or the map copy without slot tables), the small rows, the staged first observation, the goal
+ *                 arrays, ped_due[e] = 0; then it requests the world after this one (barrier, fence, number, flag).
+ *                 late[e] = 0, counted in counters[NAVSIM_COUNTER_REGEN_SERVED].
+ *                 Otherwise late[e] = 1, counted in counters[NAVSIM_COUNTER_REGEN_LATE]; what is staged carries a stale
+ *                 number, so the arena is marked for staging again with episode[e] + 1.  Its world and its row are left to the
+ *                 caller: navsim_regen with io->done = late (and cfg.regen_min_steps = 0).
+ * cfg.regen_min_steps is not consulted: a reset asks for a new world whatever the length of the abandoned episode.
+ * The staged world of arena e is the world of episode[e] + 1, a function of (seed, global arena, episode number) only, and a
+ * masked reset starts exactly that episode.  So, followed by navsim_regen with io->done = late, the live state and the rows
+ * equal  navsim_restart(mask) + navsim_reset_obs(mask) + navsim_regen with io->done = mask  -- whatever the staging passes'
+ * timing (a pass may run beside the launch: the ready / mark protocol is the step's).
+ * NAVSIM_E_ARG: stage, stage_obs, mark, ready, mask, late or st->done_steps NULL; mark not 4-byte aligned; the two states differ
+ * in their optional buffers or slot tables; cfg->auto_reset == NAVSIM_AUTORESET_NONE.  NAVSIM_E_UNSUPPORTED: a field that is not
+ * packed (NAVSIM_FIELD_U16T), cfg->defer_reset_scan.  n_envs == 0: NAVSIM_OK, nothing is launched. */
+int navsim_reset_install(const navsim_config* cfg, const navsim_state* st, const navsim_step_io* io,
+                         const navsim_state* stage, const float* stage_obs, uint8_t* mark, const long long* ready,
+                         const uint8_t* mask, uint8_t* late, void* stream);
+
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);
 

@@ -774,9 +774,7 @@ __global__ __launch_bounds__(256) void regen_clear_want_kernel(const int* __rest
 
 // navsim_restart: reset() of the arenas of `mask`, part one (env.py:730-746) -- the next start / goal pair of the arena's table
 // and the next episode number: what the step does at `done` under auto-reset, as a call of its own
-__global__ __launch_bounds__(256) void restart_kernel(navsim_config c, navsim_state st, const uint8_t* __restrict__ mask) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= c.n_envs || !mask[e]) return;
+__device__ __forceinline__ void restart_arena(const navsim_config& c, const navsim_state& st, const int e) {
     const uint64_t genv = (uint64_t)(c.env_index_base + e);
     const uint64_t h = nv::hash4(c.seed, genv, (uint64_t)st.episode[e], 0x5eedULL);
     const int idx = (int)(h % (uint64_t)c.n_spawn);
@@ -787,4 +785,43 @@ __global__ __launch_bounds__(256) void restart_kernel(navsim_config c, navsim_st
     if (st.done_steps) st.done_steps[e] = (int32_t)st.steps[e];
     st.episode[e] += 1;
     st.steps[e] = 0;
+}
+__global__ __launch_bounds__(256) void restart_kernel(navsim_config c, navsim_state st, const uint8_t* __restrict__ mask) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= c.n_envs || !mask[e]) return;
+    restart_arena(c, st, e);
+}
+
+// navsim_reset_install: reset() of the arenas of `mask` on a simulator with staged worlds, one workgroup per arena.  A masked
+// arena restarts (restart_arena: it now starts episode[e] + 1) and, when the world staged for it is the one of that episode --
+// a function of (seed, global arena, episode number) only -- installs it exactly as the step does for an arena that finishes
+// (install_arena / install_publish, kernels_step.hpp).  Otherwise late[e] = 1: what is staged carries a stale number, the arena
+// asks for the world after the one it starts, and the world it starts is left to the caller's navsim_regen (io->done = late).
+// cfg.regen_min_steps is not consulted: a reset asks for a new world whatever the abandoned episode's length.
+// An arena outside the mask keeps its state; its row is carried over obs_prev -> obs like navsim_reset_obs does.
+__global__ __launch_bounds__(256) void reset_install_kernel(navsim_config c, navsim_state st, navsim_step_io io, StepInstall in,
+                                                            const uint8_t* __restrict__ mask) {
+    __shared__ int staged_s;
+    const int e = blockIdx.x, tid = threadIdx.x;
+    const int D = c.n_scan_stack * c.n_beams + NAVSIM_OBS_TAIL;
+    float* obs_row = io.obs + (size_t)e * D;
+    if (!mask[e]) {                                           // block-uniform
+        const float* obs_prev = io.obs_prev ? io.obs_prev + (size_t)e * D : nullptr;
+        if (obs_prev && obs_prev != obs_row)
+            for (int k = tid; k < D; k += 256) obs_row[k] = obs_prev[k];
+        if (tid == 0) in.late[e] = 0;
+        return;
+    }
+    if (tid == 0) {
+        restart_arena(c, st, e);
+        const bool staged = stage_ready(in.ready, e) == (long long)st.episode[e];
+        staged_s = staged;
+        in.late[e] = staged ? 0 : 1;
+        if (st.counters) atomicAdd(&st.counters[staged ? NAVSIM_COUNTER_REGEN_SERVED : NAVSIM_COUNTER_REGEN_LATE], 1ull);
+        if (!staged) stage_request(in.stage.episode, in.mark, e, st.episode[e] + 1);
+    }
+    __syncthreads();                                         // the verdict; the restart's rows before the install rewrites them
+    if (!staged_s) return;
+    install_arena<256>(c, st, io, in, e, obs_row);
+    install_publish(in, st, e);
 }

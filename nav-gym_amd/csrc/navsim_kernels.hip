@@ -1330,6 +1330,26 @@ int navsim_restart(const navsim_config* c, const navsim_state* st, const uint8_t
     return launch_status();
 }
 
+int navsim_reset_install(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, const navsim_state* stage,
+                         const float* stage_obs, uint8_t* mark, const long long* ready, const uint8_t* mask, uint8_t* late,
+                         void* stream) {
+    (void)hipGetLastError();
+    int rc = check_step_args(c, st, io, 1);
+    if (rc != NAVSIM_OK) return rc;
+    if (!stage || !stage_obs || !mark || !ready || !mask || !late || ((uintptr_t)mark & 3) != 0 || !st->done_steps) return NAVSIM_E_ARG;
+    rc = check_stage_pair(c, st, stage);                     // (auto-reset, no deferred first scan, the same optional buffers)
+    if (rc != NAVSIM_OK) return rc;
+    if (c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
+    rc = check_map_slots(st, stage);
+    if (rc != NAVSIM_OK) return rc;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    StepInstall in = {};
+    in.stage = *stage; in.stage_obs = stage_obs; in.mark = mark; in.ready = ready; in.late = late;
+    if (!st->map_slot) stage_big_buffers(c, st, stage, in.big);             // (with slot tables the maps stay where they are)
+    reset_install_kernel<<<c->n_envs, 256, 0, (hipStream_t)stream>>>(*c, *st, *io, in, mask);
+    return launch_status();
+}
+
 const char* navsim_step_kernel_name(void) { return "navsim_step_kernel"; }
 
 // test hook (declared in include/navsim.h under "test hooks")

@@ -363,6 +363,7 @@ def declare(lib, suffix=""):
         sig("navsim_regen_helper", [_P])
         sig("navsim_step_install_replan", [cfgp, stp, iop, stp, _P, _P, _P, _P, C.c_int32, _P])
         sig("navsim_step_install_next", [cfgp, stp, iop, stp, _P, _P, _P, _P, _P, C.c_int32, _P])
+        sig("navsim_reset_install", [cfgp, stp, iop, stp, _P, _P, _P, _P, _P, _P])
     sig("navsim_crowd_check", [C.POINTER(NavsimCrowdParams), i32, i32, i32, _P, _P, _P, _P, _P, _P, _P, _P, _P] + stream)
     mpp = C.POINTER(NavsimCrowdMapParams)
     sig("navsim_crowd_angular_map", [mpp, i32, i32, i32, _P, _P, _P, _P] + stream)
@@ -394,7 +395,7 @@ EXPORTS = (
     "navsim_scan_threshold", "navsim_beam_table", "navsim_ped_scans", "navsim_ped_scans_part", "navsim_ped_policy_part", "navsim_regen_workspace_bytes", "navsim_regen", "navsim_regen_swap", "navsim_regen_stage", "navsim_regen_stage_part", "navsim_step_install", "navsim_regen_helper", "navsim_step_install_replan", "navsim_step_install_next",
     "navsim_costmap", "navsim_plan", "navsim_launch_order", "navsim_replan_workspace_bytes", "navsim_replan", "navsim_ped_policy_workspace_bytes", "navsim_ped_policy", "navsim_ped_scan_policy",
     "navsim_crowd_check", "navsim_crowd_angular_map", "navsim_crowd_local_map", "navsim_crowd_orca", "navsim_crowd_agent_step", "navsim_ped_orca", "navsim_ped_orca_walls",
-    "navsim_step", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_step_kernel_name",
+    "navsim_step", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

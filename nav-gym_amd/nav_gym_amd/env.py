@@ -70,7 +70,8 @@ and default to the reference's behaviour for num_envs == 1:
                     stepped past T stays truncated until reset().  info['TimeLimit.truncated'] is a bool (num_envs == 1)
                     or a torch.bool [num_envs] view; None (default): no limit, the reference's behaviour and no such key.
     reset(mask)     reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
-                    [num_envs]; the others keep their state and their rows.  Not with the pipelined reset path.
+                    [num_envs]; the others keep their state and their rows.  On the pipelined reset path the masked arenas install
+                    their staged worlds in one launch: the same state and rows as with pregen_pipeline=0.
 
 `env.counters()` reports what the caps of the device-side reset path left unserved (arenas beyond regen_cap,
 pedestrians beyond replan_cap, routes cut at max_waypoints) since the last call.
@@ -475,15 +476,15 @@ class NavGymEnv(_EnvBase):
         finished (NavSim.regenerate_all).
         mask [num_envs] (bool / 0-1): reset only those arenas -- the reference's reset() is per environment -- the others
         keep their state and their observation rows (NavSim.reset_arenas: next start / goal pair and episode number, first
-        observation; with randomize_maps a new world each)."""
+        observation; with randomize_maps a new world each).  On the pipelined reset path (pregen_pipeline > 0) the masked
+        arenas install their staged worlds in one launch (navsim_reset_install; an arena whose world is not staged yet is
+        regenerated on the spot): the same state and rows as with pregen_pipeline=0."""
         from . import lib
         lib.require_gpu()                                 # no CPU fallback: fail before any work
         import torch
         if mask is not None:
             if self.sim is None:
                 raise RuntimeError("reset(mask) needs one reset() of every arena first")
-            if self.pregen_pipeline:
-                raise ValueError("reset(mask) is not available with the pipelined reset path (pregen_pipeline=0 for it)")
             m = torch.as_tensor(np.asarray(mask) if not hasattr(mask, "is_cuda") else mask).reshape(self.num_envs)
             if self._graphed:
                 torch.cuda.synchronize(self.sim.device)

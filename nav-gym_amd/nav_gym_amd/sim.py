@@ -440,6 +440,9 @@ class NavSim(object):
         # fallback: the arenas that finished before their world was staged (flags the step writes, navsim_regen for them)
         self.late, self.late_cfg, self.late_ws, self.late_cap = None, None, None, 0
         self.late_poll = self.lone = False
+        # reset_arenas with staged worlds: the flags navsim_reset_install writes; its fallback's workspace and cap
+        # where enable_pregen made none (rule-only worlds)
+        self.rs_late, self.rs_ws, self.rs_cap = None, None, 0
         # next-step "beside" form: the fallback on a stream of its own beside the next step's launch
         self.late2 = self.urgent = self.ev_stepped = self.ev_urgent = None
         # overlap and graphs: the re-plan inside or beside the step, the captured steps
@@ -1102,10 +1105,18 @@ class NavSim(object):
         """reset() of the arenas of `mask` (uint8 / bool [E]) alone (env.py:730-831 is per environment): navsim_restart -- the
         next start / goal pair of the arena's table, the next episode number -- then their first observations
         (navsim_reset_obs) on the same map, or with new_world=True a new world each (navsim_regen in chunks of cfg.regen_cap
-        arenas; worlds that draw a map per episode).  The other arenas keep their state and their rows."""
+        arenas; worlds that draw a map per episode).  The other arenas keep their state and their rows.
+        With enable_pregen(pipeline=P, install=True): new_world=True only, as ONE launch (navsim_reset_install) -- a masked arena
+        starts episode[e] + 1, which is the episode its staged world was generated for, and installs it; an arena whose staged
+        world is not complete is regenerated on the spot by navsim_regen (chunks of the fallback's cap).  Same state and rows as
+        without staged worlds, whatever the passes' timing.  The staging passes keep their cadence (regen() queues them): a mask
+        of more arenas than one pass stages (stage_cap) is restaged over several passes, and the arenas among them that finish
+        before that go through the fallback (counters()['regen_late']).  With the rule alone (cfg.regen_min_steps >= 4 P, no
+        fallback) an episode that starts at a reset is not covered by the rule's guarantee: an arena that finishes it before the
+        pass that restages it restarts in place, counted in regen_late."""
         import torch
         if self.pregen:
-            raise ValueError("reset_arenas is not available with enable_pregen (the staged worlds follow the episodes' own order)")
+            return self._reset_arenas_staged(mask, new_world)
         m = torch.as_tensor(mask).to(device=self.device).ne(0).to(torch.uint8).contiguous()
         check(self.lib.navsim_restart(C.byref(self.cfg), C.byref(self.st), _ptr(m), _stream()), "navsim_restart")
         self.reset_obs(m)
@@ -1123,6 +1134,59 @@ class NavSim(object):
                 chunk[idx[a:a + int(self.cfg.regen_cap)]] = 1
                 self._call_regen(cfg, ws, None, "navsim_regen (reset of some arenas)", done=chunk)
             torch.cuda.current_stream().synchronize()  # `chunk` is released on return
+        return self.obs
+
+    def _reset_arenas_staged(self, mask, new_world):
+        """reset_arenas on a simulator with staged worlds: reset_obs(mask)'s bookkeeping around navsim_reset_install, then
+        navsim_regen for the arenas the launch flagged as late."""
+        import torch
+        if not self.pg_install or self.late2 is not None:
+            raise ValueError("reset_arenas with enable_pregen needs install=True and not late_beside=True (the swap form's staged "
+                             "worlds follow the episodes' own order; the beside form keeps two flag buffers)")
+        if not new_world:
+            raise ValueError("reset_arenas(new_world=False) is not available with enable_pregen: the staged worlds are new worlds")
+        E = self.cfg.n_envs
+        m = torch.as_tensor(mask).to(device=self.device).ne(0).to(torch.uint8).contiguous()
+        keep = m == 0
+        if self.rs_late is None:
+            self.rs_late = torch.zeros(E, dtype=torch.uint8, device=self.device)
+        # what reset_obs(mask) does around its launch: the other set of outputs starts as a copy, a reset arena is not finished
+        for k, v in self.out_buf[1 - self.cur].items():
+            v.copy_(self.out_buf[self.cur][k])
+        for k in [k for k in ("done", "truncated") if k in self.out_buf[0]]:
+            self.out_buf[1 - self.cur][k].mul_(keep)
+        if self.late is not None:                       # ... and no longer waits for the step's fallback
+            self.late.mul_(keep)
+        self._flip()
+        main = torch.cuda.current_stream()
+        check(self.lib.navsim_reset_install(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), C.byref(self.stage_st),
+                                            _ptr(self.stage_obs), _ptr(self.mark), _ptr(self.ready), _ptr(m), _ptr(self.rs_late),
+                                            C.c_void_p(main.cuda_stream)), "navsim_reset_install")
+        if self.due is not None:                        # nobody was advanced; nobody of a reset arena waits for navsim_replan
+            self.due[1 - self.cur].copy_(self.due[self.cur])
+            self.due[1 - self.cur].mul_(keep)
+        self.cur = 1 - self.cur
+        idx = torch.nonzero(self.rs_late).flatten()     # (a host wait for the launch: a reset is not the per-step path)
+        if int(idx.numel()):
+            if self.late_ws is not None:                # the step's fallback: its workspace serves, on the same stream
+                ws, cap = self.late_ws, self.late_cap
+            else:
+                if self.rs_ws is None:
+                    self.rs_cap = int(min(E, max(8, E // 128)))
+                    cfg = self.cfg.copy()
+                    cfg.regen_cap = self.rs_cap
+                    self.rs_ws = torch.zeros(self.lib.navsim_regen_workspace_bytes(C.byref(cfg)), dtype=torch.uint8, device=self.device)
+                ws, cap = self.rs_ws, self.rs_cap
+            cfg = self.cfg.copy()                       # the configuration as it stands now, with the fallback's cap
+            cfg.regen_cap = cap
+            cfg.regen_min_steps = 0                     # a reset asks for a new world whatever the abandoned episode's length
+            chunk = torch.zeros_like(m)
+            for a in range(0, int(idx.numel()), cap):   # at most `cap` flags per call: nobody restarts in place
+                chunk.zero_()
+                chunk[idx[a:a + cap]] = 1
+                # (no fork: navsim_regen's helper stream belongs to the staging passes, as for the per-step fallback)
+                self._call_regen(cfg, ws, main, "navsim_regen (reset of arenas whose world was not staged)", fork=False, done=chunk)
+            main.synchronize()                          # `chunk` is released on return
         return self.obs
 
     def regenerate_all(self, new_episode=False, scratch_bytes=4 << 30):

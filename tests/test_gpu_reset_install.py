@@ -1,0 +1,316 @@
+"""GPU: reset() of some arenas on a simulator with staged worlds (navsim_reset_install, NavSim.reset_arenas after
+enable_pregen(pipeline=P, install=True), NavGymEnv.reset(mask) on the pipelined reset path).  The masked arenas install their
+staged worlds in one launch, or -- where the world is not staged -- are regenerated on the spot; either way the state and the
+rows equal the simulator without staged worlds (navsim_restart + navsim_reset_obs + navsim_regen), bit for bit."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import ref
+from nav_gym_amd import abi
+from test_gpu_autoreset import _actions, _eq, _pair, _state_eq
+from test_gpu_workspaces import _rect_pairs, _sim, gpu  # noqa: F401  (the module's fixture and world helpers)
+
+pytestmark = pytest.mark.gpu
+
+SPAWN = dict(n_spawn=6, min_goal_dist=3.0, max_goal_dist=8.0, spawn_clearance=0.9, ped_min_robot_dist=2.0, ped_min_goal_dist=4.0)
+
+
+def _world(gpu, E, size, mode, seed, n_peds=3, max_peds=4, min_steps=0, **kw):
+    cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, max_peds=max_peds, ped_model=abi.PED_SFM, auto_reset=mode, seed=seed,
+                                 field_format=abi.FIELD_U16T, regen_cap=E, regen_min_steps=min_steps,
+                                 **dict(dict(regen_plan=0, regen_indoor_ratio=0.0, **SPAWN), **kw))
+    gpu.world.lidar_full_circle(cfg, 64)
+    return cfg, gpu.world.make_maps(E, size, seed), n_peds
+
+
+def _trio(gpu, cfg, occ, n_peds, **wkw):
+    """(simulator that will stage worlds, simulator that will not, the oracle): the same world three times"""
+    u, r = _pair(gpu, cfg, occ, n_peds, **wkw)
+    p = _sim(gpu, cfg, occ, n_peds, **wkw)
+    return p, u, r
+
+
+def _state(g):
+    """every state array by arena (slot tables resolved), pedestrian routes up to their lengths, the record index by what it says"""
+    s = g.numpy_state()
+    out = {}
+    for k, v in s.items():
+        if k in ("arena_cost", "launch_order", "counters", "map_slot") or "_ws" in k:
+            continue
+        if k == "rect_index":
+            v = _rect_pairs(g.by_arena(k), g.cfg.map_h, g.cfg.map_w)
+        if k == "ped_waypoints":        # slots beyond a route's length keep whatever the buffer held
+            live = np.arange(g.cfg.max_waypoints)[None, None, :] < s["ped_n_waypoints"][..., None]
+            v = np.where(live[..., None], v, 0.0)
+        E = g.cfg.n_envs                # (a packed field is one flat blob of E equal parts)
+        out[k] = v.reshape(E, -1) if v.shape[0] == E or (v.ndim == 1 and v.size % E == 0) else v
+    return out
+
+
+def _twin_eq(gpu, p, u, what):
+    """rows, every output, every state array and the count of served arenas of the two simulators"""
+    gpu.torch.cuda.synchronize()
+    _eq(p.obs.cpu().numpy(), u.obs.cpu().numpy(), "rows %s" % what)
+    for k in u.out:
+        _eq(p.out[k].cpu().numpy(), u.out[k].cpu().numpy(), "%s %s" % (k, what))
+    sp, su = _state(p), _state(u)
+    assert set(sp) == set(su), set(sp) ^ set(su)
+    for k in su:
+        _eq(sp[k], su[k], "state %s %s" % (k, what))
+    assert p.counters()["regen_served"] == u.counters()["regen_served"], what
+
+
+def _oracle_reset(r, mask):
+    """The oracle's composition: Sim.restart(mask), then navsim_regen_cpu keyed on the mask, whatever the episodes' lengths."""
+    m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+    r.restart(m)
+    io = abi.NavsimStepIO()
+    io.obs = r.obs[r.cur].ctypes.data
+    for k, v in r.out.items():
+        setattr(io, k, v.ctypes.data)
+    io.done = m.ctypes.data
+    cfg = r.cfg.copy()
+    cfg.regen_min_steps = 0
+    cfg.regen_cap = max(int(cfg.regen_cap), int(cfg.n_envs))
+    assert ref.lib().navsim_regen_cpu(C.byref(cfg), C.byref(r.st), C.byref(io)) == 0
+    return r.obs[r.cur]
+
+
+def _reset_both(gpu, p, u, mask, what, r=None):
+    """reset_arenas(mask, new_world=True) on both simulators: equal afterwards, the unmasked arenas bit-identical to before, and
+    the simulator without staged worlds equal to the oracle's composition"""
+    gpu.torch.cuda.synchronize()
+    before, rows_before = _state(p), p.obs.cpu().numpy().copy()
+    m = gpu.torch.from_numpy(np.asarray(mask, dtype=np.uint8)).to(gpu.dev)
+    rows_p = p.reset_arenas(m, new_world=True).cpu().numpy()
+    rows_u = u.reset_arenas(m, new_world=True).cpu().numpy()
+    _eq(rows_p, rows_u, "returned rows %s" % what)
+    _twin_eq(gpu, p, u, what)
+    keep = np.asarray(mask) == 0
+    after = _state(p)
+    _eq(rows_p[keep], rows_before[keep], "rows of the unmasked arenas %s" % what)
+    for k in before:
+        if before[k].shape[0] != len(keep):
+            _eq(after[k], before[k], "state %s %s" % (k, what))
+            continue
+        _eq(after[k][keep], before[k][keep], "state %s of the unmasked arenas %s" % (k, what))
+    assert (p.t["episode"].cpu().numpy()[~keep] > 0).all()
+    if r is not None:
+        _eq(rows_u, _oracle_reset(r, mask), "rows against the oracle %s" % what)
+        _eq(u.out["done"].cpu().numpy(), r.out["done"], "done flags against the oracle %s" % what)
+        _state_eq(u, r, "against the oracle %s" % what, skip=("ped_waypoints",))
+        assert u.counters()["regen_served"] == r.counters()["regen_served"], what
+
+
+def _step_both(gpu, rng, cfg, t, p, u, r=None):
+    act = _actions(rng, cfg, t)
+    a = gpu.torch.from_numpy(act).to(gpu.dev)
+    op, outp = p.step(a)
+    ou, outu = u.step(a)
+    for k in ("reward", "done", "is_success", "is_crash", "distance"):
+        _eq(outp[k].cpu().numpy(), outu[k].cpu().numpy(), "%s at step %d" % (k, t))
+    done = outu["done"].cpu().numpy() != 0
+    p.regen(); u.regen()                   # (an arena that installed inside the step has its new world's rows and goals already)
+    _eq(p.obs.cpu().numpy(), u.obs.cpu().numpy(), "rows after regen at step %d" % t)
+    for k in u.out:
+        _eq(p.out[k].cpu().numpy(), u.out[k].cpu().numpy(), "%s after regen at step %d" % (k, t))
+    if r is not None:
+        r.step(act)
+        _eq(u.obs.cpu().numpy(), r.regen(), "rows against the oracle after regen at step %d" % t)
+    return done
+
+
+@pytest.mark.parametrize("slots", [True, False])
+@pytest.mark.parametrize("E", [24, 6])                       # 6: no multiple of 4, the last word of mark[] is padding
+@pytest.mark.parametrize("mode", [abi.AUTORESET_SAME_STEP, abi.AUTORESET_NEXT_STEP])
+@pytest.mark.parametrize("P", [1, 2])
+def test_reset_of_some_arenas_equals_the_unpipelined_path(gpu, P, mode, E, slots):
+    """48 steps of step + regen, every 6th followed by a reset of the arenas that just finished and a fifth of the others:
+    after every call the two simulators agree in rows, outputs, flags, state and the count of served arenas; the one without
+    staged worlds agrees with the oracle."""
+    cfg, occ, n_peds = _world(gpu, E, 160, mode, seed=41 + E)
+    p, u, r = _trio(gpu, cfg, occ, n_peds)
+    p.enable_pregen(pipeline=P, install=True, map_slots=slots)
+    assert ("map_slot" in p.t) == slots and p.late is not None
+    rng = np.random.default_rng(3)
+    n_masked = n_finished = 0
+    for t in range(48):
+        done = _step_both(gpu, rng, cfg, t, p, u, r)
+        if t % 6 == 5:
+            mask = done | (rng.uniform(size=E) < 0.2)
+            if t == 5:
+                mask[E - 1] = True                            # (the arena whose flag shares its word with the padding)
+            n_masked += int(mask.sum()); n_finished += int(done.sum())
+            _reset_both(gpu, p, u, mask, "after the reset at step %d" % t, r)
+    _twin_eq(gpu, p, u, "at the end")
+    c = p.counters()
+    assert n_masked >= 8 and c["regen_unserved"] == 0, (n_masked, n_finished, c)
+
+
+def test_everything_staged_means_everything_installs(gpu, monkeypatch):
+    E = 24
+    cfg, occ, n_peds = _world(gpu, E, 160, abi.AUTORESET_SAME_STEP, seed=7)
+    p, u, _ = _trio(gpu, cfg, occ, n_peds)
+    p.enable_pregen(pipeline=1, install=True)
+    calls = []
+    call_regen = p._call_regen
+    monkeypatch.setattr(p, "_call_regen", lambda *a, **k: (calls.append(a[3]), call_regen(*a, **k))[1])
+    rng = np.random.default_rng(11)
+    some = lambda: np.isin(np.arange(E), rng.choice(E, 9, replace=False))
+    for k, mask in enumerate((some(), some(), np.ones(E, bool))):
+        p.pregen_sync()
+        assert gpu.torch.equal(p.ready[:E], p.t["episode"] + 1), "round %d: not every arena's next world is staged" % k
+        c0, n0 = p.counters(), len(calls)
+        _reset_both(gpu, p, u, mask, "round %d" % k)
+        c1 = p.counters()
+        assert int(p.rs_late.sum()) == 0 and len(calls) == n0, calls[n0:]
+        assert c1["regen_late"] == c0["regen_late"] and c1["regen_served"] == c0["regen_served"] + int(mask.sum())
+        assert mask.sum() <= p.stage_cap or k == 2
+        # the worlds after these: one staging pass per regen() (P = 1), at most stage_cap arenas each
+        for _ in range(1 + E // p.stage_cap):
+            p.regen()
+
+
+def test_nothing_staged_means_everybody_is_late_and_still_correct(gpu, monkeypatch):
+    torch = gpu.torch
+    E = 24
+    cfg, occ, n_peds = _world(gpu, E, 160, abi.AUTORESET_SAME_STEP, seed=9)
+    p, u, _ = _trio(gpu, cfg, occ, n_peds)
+    p.enable_pregen(pipeline=1, install=True, fallback_cap=4)
+    calls = []
+    call_regen = p._call_regen
+    monkeypatch.setattr(p, "_call_regen", lambda *a, **k: (calls.append(a[3]), call_regen(*a, **k))[1])
+    hold = {"on": False}
+    queue = p._queue_pass
+    monkeypatch.setattr(p, "_queue_pass", lambda *a: None if hold["on"] else queue(*a))
+    rng = np.random.default_rng(5)
+    for t in range(4):
+        _step_both(gpu, rng, cfg, t, p, u)
+    mask = np.zeros(E, bool); mask[[0, 1, 2, 3, 6, 9, 12, 17, 22, 23]] = True       # ten arenas: three chunks of the fallback's four
+    n = int(mask.sum())
+    hold["on"] = True                                         # no pass is queued from here on ...
+    p.pregen_sync()                                           # ... and none is in flight
+    _reset_both(gpu, p, u, mask, "first reset, passes held")
+    for t in range(4, 6):
+        _step_both(gpu, rng, cfg, t, p, u)                    # (their regen() calls queue nothing)
+    c0, n0 = p.counters(), len(calls)
+    _reset_both(gpu, p, u, mask, "second reset, nothing staged")
+    c1 = p.counters()
+    assert int(p.rs_late.sum()) == n and c1["regen_late"] == c0["regen_late"] + n and c1["regen_unserved"] == 0, (c0, c1)
+    assert len(calls) - n0 == 3 and all("reset" in w for w in calls[n0:]), calls[n0:]
+    hold["on"] = False
+    for _ in range(2):                                        # a pass each (P = 1): the ten requests and whoever else finished
+        p.regen()
+    p.pregen_sync()
+    c0, n0 = p.counters(), len(calls)
+    _reset_both(gpu, p, u, mask, "third reset, staged again")
+    c1 = p.counters()
+    assert int(p.rs_late.sum()) == 0 and c1["regen_late"] == c0["regen_late"] and len(calls) == n0
+    # passes that take a few steps' time each, running beside the resets: whichever way an arena goes, the result is the same
+    stage_part = p.lib.navsim_regen_stage_part
+    def delayed(*a, _stage=stage_part, _p=p):
+        with torch.cuda.stream(_p.side):
+            torch.cuda._sleep(4_000_000)
+        return _stage(*a)
+    monkeypatch.setattr(p.lib, "navsim_regen_stage_part", delayed)
+    for t in range(6, 16):
+        done = _step_both(gpu, rng, cfg, t, p, u)
+        if t % 2:
+            _reset_both(gpu, p, u, done | (rng.uniform(size=E) < 0.3), "reset beside a slow pass at step %d" % t)
+    assert p.counters()["regen_unserved"] == 0
+
+
+def test_reset_of_some_arenas_in_worlds_of_corridor_maps_with_planned_starts(gpu):
+    E = 8
+    cfg, occ, n_peds = _world(gpu, E, 200, abi.AUTORESET_SAME_STEP, seed=19, regen_plan=1, regen_indoor_ratio=0.5)
+    u, r = _pair(gpu, cfg, occ, n_peds, plan_paths=True)
+    p = _sim(gpu, cfg, occ, n_peds, plan_paths=True)
+    p.enable_pregen(pipeline=2, install=True)
+    assert len(p.stage_lane) == 2 and "costmap" in p.t
+    rng = np.random.default_rng(2)
+    for t in range(24):
+        done = _step_both(gpu, rng, cfg, t, p, u)
+        if t % 6 == 5:
+            mask = done | (rng.uniform(size=E) < 0.3)
+            mask[t // 6 % E] = True
+            _reset_both(gpu, p, u, mask, "after the reset at step %d" % t)
+    _twin_eq(gpu, p, u, "at the end")
+    assert p.counters()["regen_unserved"] == 0
+
+
+def _same_tree(torch, a, b, what):
+    if isinstance(a, dict):
+        assert set(a) == set(b), what
+        for k in a:
+            _same_tree(torch, a[k], b[k], "%s[%s]" % (what, k))
+    elif isinstance(a, torch.Tensor):
+        assert torch.equal(a, b), what
+    else:
+        assert np.array_equal(np.asarray(a), np.asarray(b)), what
+
+
+@pytest.mark.parametrize("mode", ["same_step", "next_step"])
+def test_env_reset_mask_on_the_pipelined_reset_path(gpu, mode):
+    """NavGymEnv.reset(mask) with the env's default reset path (staged worlds) against pregen_pipeline=0: observation dicts,
+    rewards, done flags and info equal throughout a rollout with three masked resets, one of them of every arena."""
+    torch = gpu.torch
+    from nav_gym_amd import registry
+    E = 16
+    kw = dict(num_envs=E, map_size=160, n_beams=128, randomize_maps=True, indoor_ratio=0, plan_paths=False, pedestrian_model="sfm",
+              num_humans=3, seed=23, autoreset_mode=mode)
+    a = registry.make("NavGym-v0", **kw)
+    b = registry.make("NavGym-v0", pregen_pipeline=0, **kw)
+    _same_tree(torch, a.reset(), b.reset(), "reset()")
+    assert a.pregen_pipeline > 0 and b.pregen_pipeline == 0 and a.sim.pg_install
+    g = torch.Generator(device=gpu.dev); g.manual_seed(3)
+    acts = torch.rand((40, E, 2), generator=g, device=gpu.dev, dtype=torch.float64)
+    acts[..., 0] *= 0.5; acts[..., 1] = acts[..., 1] * 1.28 - 0.64
+    acts[::4, :, 0] = 0.5; acts[::4, :, 1] = 0.0
+    rng = np.random.default_rng(1)
+    for t in range(40):
+        oa, ra, da, ia = a.step(acts[t]); ob, rb, db, ib = b.step(acts[t])
+        _same_tree(torch, dict(o=oa, r=ra, d=da, i=ia), dict(o=ob, r=rb, d=db, i=ib), "step %d" % t)
+        if t in (9, 20, 31):
+            mask = np.ones(E, bool) if t == 20 else (da.cpu().numpy().astype(bool) | (rng.uniform(size=E) < 0.25))
+            if t == 9:
+                mask[[0, E - 1]] = True
+            ep = a.sim.t["episode"].clone()
+            _same_tree(torch, a.reset(mask), b.reset(mask), "reset(mask) after step %d" % t)
+            assert torch.equal(a.sim.t["episode"].cpu(), ep.cpu() + torch.from_numpy(mask.astype(np.int64)))
+            assert torch.equal(a.sim.t["episode"], b.sim.t["episode"])
+    ca, cb = a.counters(), b.counters()
+    assert ca["regen_served"] == cb["regen_served"] and ca["regen_unserved"] == 0, (ca, cb)
+    a.close(); b.close()
+
+
+def test_env_reset_mask_with_the_rule_alone(gpu):
+    """regen_min_steps = 4 P: no fallback objects exist (the rule makes the per-step path independent of timing); reset(mask)
+    works all the same and gives the masked arenas the worlds of their next episode numbers."""
+    torch = gpu.torch
+    from nav_gym_amd import registry
+    E = 16
+    kw = dict(num_envs=E, map_size=160, n_beams=128, randomize_maps=True, indoor_ratio=0, plan_paths=False, pedestrian_model="sfm",
+              num_humans=3, seed=29, regen_min_steps=16)
+    a = registry.make("NavGym-v0", **kw)
+    b = registry.make("NavGym-v0", pregen_pipeline=0, **kw)
+    a.reset(); b.reset()
+    assert a.pregen_pipeline == 4 and a.sim.late is None and a.sim.late_ws is None
+    act = torch.zeros((E, 2), dtype=torch.float64, device=gpu.dev); act[:, 0] = 0.1
+    mask = np.zeros(E, bool); mask[[1, 2, 5, 11, 15]] = True
+    for k in range(2):                                    # the second reset follows the first by two steps: nothing is staged for it
+        for _ in range(2):
+            a.step(act); b.step(act)
+        maps = [a.sim.occupancy(e) for e in range(E)]
+        ep = a.sim.t["episode"].clone()
+        _same_tree(torch, a.reset(mask), b.reset(mask), "reset(mask) %d" % k)
+        assert torch.equal(a.sim.t["episode"].cpu(), ep.cpu() + torch.from_numpy(mask.astype(np.int64)))
+        assert torch.equal(a.sim.t["episode"], b.sim.t["episode"])
+        assert torch.equal(a.sim.t["robot_pose"], b.sim.t["robot_pose"]) and torch.equal(a.sim.t["robot_goal"], b.sim.t["robot_goal"])
+        for e in range(E):
+            now = a.sim.occupancy(e)
+            assert np.array_equal(now, b.sim.occupancy(e)), "map of arena %d after reset %d" % (e, k)
+            assert np.array_equal(now, maps[e]) == (not mask[e]), "arena %d after reset %d" % (e, k)
+    assert a.sim.late is None and (a.sim.rs_ws is not None) == (a.counters()["regen_late"] > 0)
+    a.close(); b.close()
