@@ -85,6 +85,14 @@ __device__ __forceinline__ void sfm_pair(const navsim_config& c, double xi, doub
     fy = fv * idy + fa * idx;
 }
 
+// element idx of a wave-uniform array as a uniform base plus a 32-bit byte offset per lane (global_load / global_store with
+// an SGPR base: one shift per lane instead of a sign extension, a 64-bit shift and a 64-bit add per array).  idx *
+// sizeof(T) must fit 32 bits: true of the beam arrays ([B]) and of an arena's observation row ([S * B] floats).
+template <typename T>
+__device__ __forceinline__ T& at_off32(T* base, int idx) {
+    return *(T*)((char*)base + (unsigned)idx * (unsigned)sizeof(T));
+}
+
 // direction of a beam at robot-frame angle lin seen from heading lth (env.py:388-390, 424) through its table entry
 // (ct, st) = cos / sin(lin) and (cT, sT) = cos / sin(lth); false: the float32 rounding could not be proven, the caller
 // evaluates beam_dir(heading).  heading = fl32(lin + lth) is returned either way.
@@ -106,11 +114,14 @@ __device__ __forceinline__ void beam_dir_k(const navsim_config& c, const double*
 #ifdef NAVSIM_DIAG_CHEAP_DIR     // diagnostic build only (wrong directions): what does the exact direction cost?
     { float h = (float)c.angle_min + (float)k * (float)step + (float)lth; dx = __cosf(h); dy = __sinf(h); return; }
 #endif
-    const double lin = nv::linspace_k(c, k, step);
+    // nv::linspace_k(c, k, step) for k in [0, n_beams), its two per-lane selects as one: a single beam is its own last beam,
+    // so which end point that beam takes is a wave-uniform (scalar) choice
+    const double last = (c.n_beams == 1) ? c.angle_min : c.angle_last;
+    const double lin = (k == c.n_beams - 1) ? last : (double)k * step + c.angle_min;
     float heading = (float)(lin + lth);
     bool fast = false;
     if (tab) {
-        const double2 cs = ((const double2*)tab)[k];
+        const double2 cs = at_off32((const double2*)tab, k);
         fast = beam_dir_fast(lin, lth, cs.x, cs.y, cT, sT, heading, dx, dy);
     }
     if (!fast) nv::beam_dir(heading, dx, dy);
@@ -312,6 +323,10 @@ __device__ __forceinline__ int mask_sel(lanemask_t m, int a, int b) {
     return r;
 }
 __device__ __forceinline__ bool mask_lane(lanemask_t m) { return mask_sel(m, 1, 0) != 0; }
+// x > 0.0f of a wave-uniform x as an integer test on its bits (1 .. +inf; false for NaN, -0 and every negative value, like
+// the float compare): s_cmp on a 32-bit scalar.  The float compare of a uniform value is a VECTOR compare whose result is a
+// 64-bit lane mask, and a mask that lives across the march loop is what the register allocator spills to VGPR lanes.
+__device__ __forceinline__ bool uniform_gt0(float x) { return (unsigned)(__float_as_int(x) - 1) < 0x7F800000u; }
 
 // One probe of calc_range (env.py:425) for every lane of `active`: sample position, distance there, hit test, step.
 // Lanes that are finished or outside the map run along with their updates masked off.  A lane that hits keeps the
@@ -497,36 +512,52 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
     const int i0 = sh.i0, j0 = sh.j0;
     const float x0 = (float)i0, y0 = (float)j0;
     const bool int_range = int_range_ok(H, W);
-    const float lx = sh.lx, ly = sh.ly;
-    const int nseg = sh.nseg, ndisc = sh.ndisc;
     const unsigned uW = (unsigned)W, uH = (unsigned)H;
     const unsigned tpr = (unsigned)((W + 7) >> kRectShift);
     const float t1 = sh.t1, r_all = sh.r_all;
-    const uint64_t nkey = (noise_std > 0.0f) ? nv::noise_stream(c.seed, genv, noise_key) : 0;
-    int cr = 0, dc = 0;
-    // what happens to a finished ray (identical for every schedule)
-    auto finish = [&](int k, float dx, float dy, float rr) {
+    const bool noise_on = uniform_gt0(noise_std);
+    const uint64_t nkey = noise_on ? nv::noise_stream(c.seed, genv, noise_key) : 0;
+    float* const obs_last = obs_row + (size_t)(S - 1) * B;      // the newest row of the stack
+    // the stack fill of env.py:262-265: row j < S - 1 takes the scan too while S - 1 - j > n_hist, i.e. the first n_fill rows
+    // (n_hist is the arena's, one value per workgroup, but arrives in a vector register: made a scalar once per scan)
+    const int n_fill = __builtin_amdgcn_readfirstlane(min(max(S - 1 - n_hist, 0), S - 1));
+    // crash / discomfort votes as lane masks, combined with scalar instructions like the march's flags
+    lanemask_t crm = 0, dcm = 0;
+    // What happens to a finished ray (identical for every schedule).  EVERY lane of the wavefront runs it, outside divergent
+    // control flow -- a lane mask updated under a divergent branch would stop being one value per wave (probe_round) -- and
+    // `fin`, the lanes whose ray finishes here, predicates the votes and the stores alone.  A lane outside `fin` carries a
+    // beam index inside [0, B) (the caller clamps it), so its threshold loads stay in bounds; what it computes is dropped.
+    auto finish = [&](bool fin, lanemask_t fm, int k, float dx, float dy, float rr) {
         if (TO_LDS) {                                           // pedestrians: culled merge on the LDS copy, in metres
-            rng_lds[k] = rr * res;                              // env.py:426 (rr is r_all itself where the origin is occupied)
-            dir_lds[k] = make_float2(dx, dy);
+            if (fin) {
+                rng_lds[k] = rr * res;                          // env.py:426 (rr is r_all itself where the origin is occupied)
+                dir_lds[k] = make_float2(dx, dy);
+            }
             return;
         }
+        // No pedestrians here: TO_LDS is the kernel's PEDS at every call, and only a PEDS kernel fills sh.nseg / sh.ndisc.
+        // the beam's thresholds, asked for first: the loads are on their way while the range is clipped and noised.  (They
+        // also have to stand in the block that forms the lane offset to take the SGPR-base form: behind the stores' branch
+        // the compiler rebuilt a 64-bit address per array.)
+        const float thr_k = at_off32(thr, k), dthr_k = at_off32(dthr, k);
         rr = rr * res;                                          // env.py:426
-        for (int p = 0; p < nseg; ++p)
-            nv::seg_merge(rr, lx, ly, dx, dy, pr.seg[p][0], pr.seg[p][1], pr.seg[p][2], pr.seg[p][3]);
-        for (int p = 0; p < ndisc; ++p)
-            nv::circle_merge(rr, lx, ly, dx, dy, pr.disc[p][0], pr.disc[p][1], nv::kLegRadius);
-        rr = rr < 0.0f ? 0.0f : rr;                             // env.py:435
-        rr = rr > rmax ? rmax : rr;
-        if (noise_std > 0.0f && rr != rmax)                     // env.py:437-440
+        // env.py:435, clip(rr, 0, rmax), as one median of three: the same value as the two compare + select pairs for every
+        // rr that is neither NaN nor -0, given a lidar range rmax >= 0.  rr is neither: it is res (a map resolution, > 0)
+        // times a raw range that is sqrt_small_int of a non-negative integer or sqrtf of a sum of squares of finite cell
+        // offsets (ray_result: +0 or positive, never NaN), or r_all / `miss` (first_probe: +0 or the march limit, >= 0).
+        rr = __builtin_amdgcn_fmed3f(rr, 0.0f, rmax);
+        if (noise_on && rr != rmax)                             // env.py:437-440
             rr = rr + noise_std * nv::gauss_noise(nkey, (uint32_t)k);
-        cr |= (rr < thr[k]);
-        dc |= (rr < dthr[k]);
-        obs_row[(size_t)(S - 1) * B + k] = rr;
-        for (int j = 0; j < S - 1; ++j)
-            if (S - 1 - j > n_hist) obs_row[(size_t)j * B + k] = rr;
+        crm |= mask_flt(rr, thr_k) & fm;
+        dcm |= mask_flt(rr, dthr_k) & fm;
+        if (fin) {
+            at_off32(obs_last, k) = rr;
+            for (int j = 0; j < n_fill; ++j) at_off32(obs_row + (size_t)j * B, k) = rr;
+        }
     };
-    const float miss = (r_all >= 0.0f) ? r_all : max_range;
+    // r_all < 0.0f on its sign bit (first_probe leaves -1, +0 or the march limit): a 32-bit scalar test, see uniform_gt0
+    const bool march = __float_as_int(r_all) < 0;
+    const float miss = march ? max_range : r_all;
     // info[] of the culled merge: visible after the scan's barrier (the step's first scan: wavefront 0 has written it)
     if constexpr (TO_LDS) { if (prepare_prims) prims_prepare<BLOCK>(c, sh, pr); }
     constexpr bool kPark = step_parks(BLOCK, TO_LDS);           // compiled in only where the host ever asks for it
@@ -541,17 +572,18 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
             chunk = own_chunk++;
         }
         if (chunk * 64 >= B) break;
-        const int k = chunk * 64 + lane;
-        const bool valid = k < B;
+        const bool valid = chunk * 64 + lane < B;
+        const int k = valid ? chunk * 64 + lane : B - 1;         // lanes past the last beam run along on beam B - 1
         float dx, dy;
-        beam_dir_k(c, tab, valid ? k : B - 1, step, (double)sh.lth, sh.cT, sh.sT, dx, dy);
+        beam_dir_k(c, tab, k, step, (double)sh.lth, sh.cT, sh.sT, dx, dy);
         float t = t1;
-        lanemask_t active = mask_of(valid & (r_all < 0.0f));
+        const lanemask_t validm = mask_of(valid);
+        lanemask_t active = march ? validm : 0;
         lanemask_t hit = 0;
         if constexpr (!kPark) {
             while (active != 0)
                 probe_round<Field, RULE, RECT>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
-            if (valid) finish(k, dx, dy, ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, miss));
+            finish(valid, validm, k, dx, dy, ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, miss));
         } else {
             while ((int)__builtin_popcountll(active) > park_lanes)
                 probe_round<Field, RULE, RECT>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
@@ -570,7 +602,7 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
                     }
                 }
             }
-            if (valid & !marching) finish(k, dx, dy, ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, miss));
+            finish(valid & !marching, validm & ~active, k, dx, dy, ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, miss));
         }
     }
     // the parked rays, 64 at a time
@@ -595,12 +627,14 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
             k = __float_as_int(r.x);
             t = r.y; dx = r.z; dy = r.w;
         }
-        lanemask_t active = mask_of(valid);
+        const lanemask_t validm = mask_of(valid);
+        lanemask_t active = validm;
         lanemask_t hit = 0;
         while (active != 0)
             probe_round<Field, RULE, RECT>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
-        if (valid) finish(k, dx, dy, ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, miss));
+        finish(valid, validm, k, dx, dy, ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, miss));   // lanes past the last ray: ray g's
     }
+    int cr = (crm != 0), dc = (dcm != 0);                       // one value per wavefront; the caller ORs them over the arena
     if (TO_LDS) {
         __syncthreads();
         finish_beams<BLOCK>(c, sh, pr, tab, dir_lds, rng_lds, rng_lds, thr, dthr, obs_row, n_hist, noise_std,

@@ -18,6 +18,7 @@ namespace nv {
 constexpr float kLegRadius = 0.03f;   // CSimAgent leg radius (CMap2D, called from env.py:402)
 
 // np.linspace(angle_min, angle_max - angle_increment, n)[k]   (env.py:388-390)
+// (kernels_step.hpp beam_dir_k evaluates the same value with ONE per-lane select, for k in [0, n_beams): keep the two in step)
 __device__ __forceinline__ double linspace_k(const navsim_config& c, int k, double step) {
     if (c.n_beams == 1) return c.angle_min;
     if (k == c.n_beams - 1) return c.angle_last;
