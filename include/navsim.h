@@ -753,6 +753,18 @@ int    navsim_ped_scan_policy(const navsim_config* cfg, const navsim_state* st, 
  * for navsim_step (navsim_state.launch_order).  cost is what the step wrote to navsim_state.arena_cost. */
 int navsim_launch_order(const uint32_t* cost, int32_t* order, int32_t n, void* stream);
 
+/* navsim_step with that sort INSIDE the step's launch: one more workgroup, ahead of the arenas', sorts sort_cost [E] -- what an
+ * EARLIER launch wrote to navsim_state.arena_cost -- into sort_order [E] while the arenas step (navsim_launch_order's rule:
+ * 1024 buckets on [0, min(max, 4 mean + 1)], the costliest first, ties in unspecified order).  This launch itself writes
+ * st->arena_cost and reads st->launch_order, so the caller keeps two buffers of each and alternates them: sort_order is the
+ * launch_order of the launches that follow on the same stream.  Results are navsim_step's.
+ * NAVSIM_E_ARG, before any launch: navsim_step's refusals; sort_cost or sort_order NULL, sort_cost == st->arena_cost,
+ * sort_order == st->launch_order.  NAVSIM_E_UNSUPPORTED, nothing launched: a state with slot tables (st->map_slot), cfg->ped_split
+ * == 2, or a step whose dynamic LDS is smaller than the sort's 4.2 KB (worlds without rect index rows and without pedestrians) --
+ * the caller then sorts with navsim_launch_order and calls navsim_step. */
+int navsim_step_sorted(const navsim_config* cfg, const navsim_state* st, const navsim_step_io* io,
+                       const uint32_t* sort_cost, int32_t* sort_order, void* stream);
+
 /* ---- CrowdSim-v0: collision tests, goal test and reward / info selection of CrowdSim.step
  *      (nav_gym/src/crowd_sim/envs/crowd_sim.py:808-945, phase != 'test', border = None) -------------- */
 typedef struct navsim_crowd_params {

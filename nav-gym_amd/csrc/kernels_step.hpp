@@ -1739,6 +1739,98 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
     }
 }
 
+// navsim_launch_order: arenas by descending cost.  One workgroup: maximum, 1024-bucket histogram on the cost
+// scaled to the maximum, exclusive scan from the expensive end, scatter.  Order inside a bucket is free.
+// The same sort runs on the FRONT workgroup of a navsim_step_sorted launch (navsim_step_kernel), at the step's own block size
+// and in the launch's dynamic LDS: launch_order_sort is written for any workgroup of BLOCK threads, and both kernels call it.
+constexpr int kOrderBuckets = 1024;
+// what the sort needs of LDS: the bucket counts (which become the buckets' bases in place), the wavefronts' totals, sum and maximum
+struct OrderLds {
+    unsigned long long sum;
+    unsigned max, pad;
+    unsigned wave_tot[16];
+    unsigned hist[kOrderBuckets];
+};
+constexpr size_t kOrderLdsBytes = sizeof(OrderLds);
+// buckets span [0, min(max, 4 * mean + 1)]: one outlier (a workgroup that was held up) must not squeeze every other arena
+// into a handful of buckets.  Float arithmetic (a 64-bit integer division per arena and pass was a third of the kernel);
+// any monotone map serves as long as both passes use the same one.
+struct OrderBuckets {
+    unsigned long long m;
+    float scale;
+    __device__ __forceinline__ OrderBuckets(unsigned max, unsigned long long sum, int n) {
+        const unsigned long long cap = 4ull * (sum / (unsigned long long)n) + 1ull;
+        m = max < cap ? max : cap;
+        scale = (float)(kOrderBuckets - 1) / (float)m;
+    }
+    __device__ __forceinline__ int operator()(unsigned cst) const {                                    // 0 = costliest
+        const unsigned long long cc = cst < m ? cst : m;
+        const int b = (int)((float)cc * scale);
+        return kOrderBuckets - 1 - (b > kOrderBuckets - 1 ? kOrderBuckets - 1 : b);
+    }
+};
+// exclusive scan of the bucket counts, in place: thread t owns the 1024 / BLOCK buckets from t * (1024 / BLOCK) on; inside
+// each wavefront by shuffles, the wavefronts' totals by wavefront 0 (two barriers; the ten-step scan through LDS with its
+// twenty barriers was half of the kernel).  Barriers: the caller's in front (the counts), one at the end (the bases).
+template <int BLOCK>
+__device__ __forceinline__ void order_scan(OrderLds& s) {
+    constexpr int K = kOrderBuckets / BLOCK, WAVES = BLOCK / 64;
+    static_assert(K >= 1 && K * BLOCK == kOrderBuckets && WAVES <= 16, "one workgroup of 64 .. 1024 threads");
+    const int tid = threadIdx.x, lane = tid & 63;
+    unsigned mine = 0;
+    for (int k = 0; k < K; ++k) mine += s.hist[tid * K + k];
+    unsigned incl = mine;
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned v = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += v;
+    }
+    unsigned run = incl - mine;
+    if constexpr (WAVES > 1) {
+        if (lane == 63) s.wave_tot[tid >> 6] = incl;
+        __syncthreads();
+        if (tid < 64) {
+            const unsigned t = tid < WAVES ? s.wave_tot[tid] : 0u;
+            unsigned ti = t;
+            for (int off = 1; off < WAVES; off <<= 1) {
+                const unsigned v = __shfl_up(ti, off, 64);
+                if (tid >= off) ti += v;
+            }
+            if (tid < WAVES) s.wave_tot[tid] = ti - t;              // exclusive over the wavefronts
+        }
+        __syncthreads();
+        run += s.wave_tot[tid >> 6];
+    }
+    for (int k = 0; k < K; ++k) {
+        const unsigned h = s.hist[tid * K + k];
+        s.hist[tid * K + k] = run;
+        run += h;
+    }
+    __syncthreads();
+}
+template <int BLOCK>
+__device__ __forceinline__ void launch_order_sort(const uint32_t* __restrict__ cost, int32_t* __restrict__ order, int n, OrderLds& s) {
+    const int tid = threadIdx.x;
+    for (int b = tid; b < kOrderBuckets; b += BLOCK) s.hist[b] = 0;
+    if (tid == 0) { s.max = 1; s.sum = 0; }
+    __syncthreads();
+    unsigned mx = 0;
+    unsigned long long sm = 0;
+    for (int e = tid; e < n; e += BLOCK) { mx = cost[e] > mx ? cost[e] : mx; sm += cost[e]; }
+    atomicMax(&s.max, mx);
+    atomicAdd(&s.sum, sm);
+    __syncthreads();
+    const OrderBuckets bucket(s.max, s.sum, n);
+    for (int e = tid; e < n; e += BLOCK) atomicAdd(&s.hist[bucket(cost[e])], 1u);
+    __syncthreads();
+    order_scan<BLOCK>(s);
+    for (int e = tid; e < n; e += BLOCK) order[atomicAdd(&s.hist[bucket(cost[e])], 1u)] = e;
+}
+__global__ __launch_bounds__(1024) void launch_order_kernel(const uint32_t* __restrict__ cost, int32_t* __restrict__ order,
+                                                            int n) {
+    __shared__ OrderLds s;
+    launch_order_sort<1024>(cost, order, n, s);
+}
+
 // Kernel arguments, read WHERE THEY ARE USED (round 6).  A struct passed to a kernel by value is copied out of the kernarg
 // segment at the kernel's entry -- the compiler turns the copy into scalar loads of every field the kernel uses, all of them in
 // the entry block, ~150 scalar registers of them for step_arena, which it then spills to lanes of vector registers
@@ -1761,8 +1853,9 @@ struct StepInstallKernargs { navsim_config c; navsim_state st; navsim_step_io io
 // The `int reset_only` of navsim_step_kernel and navsim_step_install_kernel, built from a StepLaunch in ONE place (step_plan.hpp
 // step_kernel_word): bit 0 = a reset-only launch, bit 1 = ped_update_kernel has advanced the pedestrians, bits 2-3 = the part --
 // NAVSIM_STEP_ALL / NOT_DUE / DUE of navsim_step_part, or kStepPartReplan for navsim_step_replan (the host picks that form's and
-// NAVSIM_STEP_DUE's own kernels below; this one only acts on NAVSIM_STEP_NOT_DUE).
-constexpr int kStepWordResetOnly = 1, kStepWordPedsDoneBit = 1, kStepWordPartShift = 2, kStepWordPartMask = 3;
+// NAVSIM_STEP_DUE's own kernels below; this one only acts on NAVSIM_STEP_NOT_DUE), bit 4 = navsim_step_sorted: the launch
+// opens with one FRONT workgroup that sorts (navsim_step_kernel only).
+constexpr int kStepWordResetOnly = 1, kStepWordPedsDoneBit = 1, kStepWordPartShift = 2, kStepWordPartMask = 3, kStepWordSortBit = 4;
 constexpr int kStepPartReplan = 3;
 // The fused step.  One workgroup = one arena (template arguments: step_arena).
 template <int BLOCK, bool PEDS, typename Field, int RULE, int RECT, bool PINL, bool FEAT = true>
@@ -1780,14 +1873,29 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu((PEDS && 
 void navsim_step_kernel(navsim_config c_, navsim_state st_,
                                                             navsim_step_io io_, int reset_only,
                                                             const uint8_t* __restrict__ reset_mask,
-                                                            unsigned dyn_lds_bytes, int park_lanes, unsigned rect_lds_offset) {
+                                                            unsigned dyn_lds_bytes, int park_lanes, unsigned rect_lds_offset,
+                                                            const uint32_t* __restrict__ sort_cost, int32_t* __restrict__ sort_order) {
     NAVSIM_KERNARGS(StepKernargs, c_, st_, io_);
     const navsim_config& c = ka.c; const navsim_state& st = ka.st; const navsim_step_io& io = ka.io;
     const int peds_done = (reset_only >> kStepWordPedsDoneBit) & 1;
     const int part = (reset_only >> kStepWordPartShift) & kStepWordPartMask;
+    // navsim_step_sorted: the launch has one workgroup more, the FRONT one, which sorts the arenas by the costs an EARLIER
+    // launch measured (sort_cost; this launch writes st.arena_cost, another buffer) into the order the NEXT launch takes
+    // (sort_order; this launch reads st.launch_order, another buffer).  As a kernel of its own between two steps the sort
+    // held the whole chip for one workgroup's 13 us; here it runs beside the arenas, in the launch's dynamic LDS (the host
+    // checked its size).  Priority 3, like an arena's start: a chain of memory and LDS latencies with next to no vector work,
+    // which then leaves its slot to an arena early; at priority 0 the bench lines measured the same (profiles/r12_lpt/).
+    const int front = (reset_only >> kStepWordSortBit) & 1;
     reset_only &= kStepWordResetOnly;
+    if (front && blockIdx.x == 0) {
+        extern __shared__ __attribute__((aligned(16))) char dyn_lds_all[];
+        __builtin_amdgcn_s_setprio(3);
+        launch_order_sort<BLOCK>(sort_cost, sort_order, c.n_envs, *(OrderLds*)dyn_lds_all);
+        return;
+    }
     // longest-first launch order (a scheduling hint: which arena a workgroup takes never changes a result)
-    const int e = st.launch_order ? st.launch_order[blockIdx.x] : (int)blockIdx.x;
+    const int b = (int)blockIdx.x - front;
+    const int e = st.launch_order ? st.launch_order[b] : b;
     if (e < 0) return;              // navsim_regen's first-observation launch: one workgroup per list slot, -1 = empty slot
     // navsim_step_part, NAVSIM_STEP_NOT_DUE: the other launch of the pair (navsim_step_due_kernel) steps the arenas with a
     // pedestrian that waited for navsim_replan when the previous step ended
@@ -1901,62 +2009,4 @@ void navsim_step_replan_install_kernel(navsim_config c_, navsim_state st_, navsi
         }
     }
     step_arena<BLOCK, true, Field, RULE, RECT, true, true>(c, st, io, e, 0, 0, nullptr, dyn_lds_bytes, park_lanes, rect_lds_offset, &in);
-}
-
-// navsim_launch_order: arenas by descending cost.  One workgroup: maximum, 1024-bucket histogram on the cost
-// scaled to the maximum, exclusive scan from the expensive end, scatter.  Order inside a bucket is free.
-__global__ __launch_bounds__(1024) void launch_order_kernel(const uint32_t* __restrict__ cost, int32_t* __restrict__ order,
-                                                            int n) {
-    __shared__ unsigned hist[1024], base[1024], wave_tot[16];
-    __shared__ unsigned max_s;
-    __shared__ unsigned long long sum_s;
-    const int tid = threadIdx.x;
-    hist[tid] = 0;
-    if (tid == 0) { max_s = 1; sum_s = 0; }
-    __syncthreads();
-    unsigned mx = 0;
-    unsigned long long sm = 0;
-    for (int e = tid; e < n; e += 1024) { mx = cost[e] > mx ? cost[e] : mx; sm += cost[e]; }
-    atomicMax(&max_s, mx);
-    atomicAdd(&sum_s, sm);
-    __syncthreads();
-    // buckets span [0, min(max, 4 * mean)]: one outlier (a workgroup that was held up) must not squeeze every
-    // other arena into a handful of buckets
-    unsigned long long m = max_s;
-    const unsigned long long cap = 4ull * (sum_s / (unsigned long long)n) + 1ull;
-    m = m < cap ? m : cap;
-    // float arithmetic (a 64-bit integer division per arena and pass was a third of this kernel); any monotone map
-    // serves as long as both passes use the same one
-    const float scale = 1023.0f / (float)m;
-    auto bucket = [&](unsigned cst) {                                                                  // 0 = costliest
-        const unsigned long long cc = cst < m ? cst : m;
-        const int b = (int)((float)cc * scale);
-        return 1023 - (b > 1023 ? 1023 : b);
-    };
-    for (int e = tid; e < n; e += 1024) atomicAdd(&hist[bucket(cost[e])], 1u);
-    __syncthreads();
-    // exclusive scan of the 1024 bucket counts: inside each wavefront by shuffles, the 16 wavefront totals by
-    // wavefront 0 (two barriers; the ten-step scan through LDS with its twenty barriers was half of the kernel)
-    const unsigned mine = hist[tid];
-    unsigned incl = mine;
-    const int lane = tid & 63;
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wave_tot[tid >> 6] = incl;
-    __syncthreads();
-    if (tid < 64) {
-        const unsigned t = tid < 16 ? wave_tot[tid] : 0u;
-        unsigned ti = t;
-        for (int off = 1; off < 16; off <<= 1) {
-            const unsigned v = __shfl_up(ti, off, 64);
-            if (tid >= off) ti += v;
-        }
-        if (tid < 16) wave_tot[tid] = ti - t;                   // exclusive over the wavefronts
-    }
-    __syncthreads();
-    base[tid] = wave_tot[tid >> 6] + incl - mine;
-    __syncthreads();
-    for (int e = tid; e < n; e += 1024) order[atomicAdd(&base[bucket(cost[e])], 1u)] = e;
 }

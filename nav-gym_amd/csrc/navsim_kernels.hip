@@ -1234,6 +1234,26 @@ int navsim_step(const navsim_config* c, const navsim_state* st, const navsim_ste
     return dispatch_step(c, st, io, l);
 }
 
+int navsim_step_sorted(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, const uint32_t* sort_cost,
+                       int32_t* sort_order, void* stream) {
+    (void)hipGetLastError();
+    int rc = check_step_args(c, st, io, 0);
+    if (rc != NAVSIM_OK) return rc;
+    // the launch writes st->arena_cost and reads st->launch_order: the sorter's buffers are others
+    if (!sort_cost || !sort_order || (const void*)sort_cost == (const void*)st->arena_cost ||
+        (const void*)sort_order == (const void*)st->launch_order)
+        return NAVSIM_E_ARG;
+    // the front workgroup exists in navsim_step_kernel alone (a state with slot tables goes to the install kernels), behind
+    // no other launch (ped_update_kernel), and sorts in the step's own dynamic LDS
+    if (st->map_slot || c->ped_split == 2 || plan_step(c, st).lds < kOrderLdsBytes) return NAVSIM_E_UNSUPPORTED;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    StepLaunch l;
+    l.sort_cost = sort_cost;
+    l.sort_order = sort_order;
+    l.stream = (hipStream_t)stream;
+    return dispatch_step(c, st, io, l);
+}
+
 int navsim_step_part(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, int32_t part, void* stream) {
     (void)hipGetLastError();
     if (part == NAVSIM_STEP_ALL) return navsim_step(c, st, io, stream);

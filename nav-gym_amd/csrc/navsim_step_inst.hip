@@ -38,6 +38,8 @@ int launch_step_pinl(const navsim_config* c, const navsim_state* st, const navsi
     constexpr bool kPacked = !std::is_same<Field, FieldF32>::value;
     const unsigned scan = (unsigned)step_lds_scan_bytes(c, p.park);
     const int blocks = l.grid > 0 ? l.grid : c->n_envs;
+    // navsim_step_sorted's front workgroup exists in navsim_step_kernel only
+    if (l.sort_cost && (l.part != NAVSIM_STEP_ALL || l.install)) return NAVSIM_E_UNSUPPORTED;
     if constexpr (PEDS && PINL) {
         if (l.part == kStepPartReplan) {                           // navsim_step_replan: the re-plan inside the step's launch
             const size_t pl = plan_lds(c->map_h / 5, c->map_w / 5), lds = p.lds > pl ? p.lds : pl;
@@ -66,11 +68,11 @@ int launch_step_pinl(const navsim_config* c, const navsim_state* st, const navsi
         const bool feat = io->final_obs || io->reset_mask || c->auto_reset == NAVSIM_AUTORESET_NEXT_STEP ||
                           (c->max_episode_steps > 0 && !l.reset_only);
         if (!feat)
-            return launch(navsim_step_kernel<BLOCK, PEDS, Field, RULE, RECT, PINL, false>, l, blocks, BLOCK, p.lds,
-                          *c, *st, *io, step_kernel_word(l), l.mask, scan, p.park, p.rect_off);
+            return launch(navsim_step_kernel<BLOCK, PEDS, Field, RULE, RECT, PINL, false>, l, step_kernel_blocks(c, l), BLOCK, p.lds,
+                          *c, *st, *io, step_kernel_word(l), l.mask, scan, p.park, p.rect_off, l.sort_cost, l.sort_order);
     }
-    return launch(navsim_step_kernel<BLOCK, PEDS, Field, RULE, RECT, PINL, true>, l, blocks, BLOCK, p.lds,
-                  *c, *st, *io, step_kernel_word(l), l.mask, scan, p.park, p.rect_off);
+    return launch(navsim_step_kernel<BLOCK, PEDS, Field, RULE, RECT, PINL, true>, l, step_kernel_blocks(c, l), BLOCK, p.lds,
+                  *c, *st, *io, step_kernel_word(l), l.mask, scan, p.park, p.rect_off, l.sort_cost, l.sort_order);
 }
 // pedestrian variants: the form without the pedestrian phase when ped_update_kernel has run or nothing is integrated at all
 // (a reset-only launch), else -- and for every install -- the form that carries it

@@ -23,6 +23,8 @@ struct StepLaunch {
                                             // none (navsim_regen's first observations); the compact launch's; the re-plan's FRONT workgroups
     int max_queries = 0;                    // kStepPartReplan: navsim_replan's cap
     const StepInstall* install = nullptr;   // navsim_step_install: the staged worlds (the install kernels)
+    const uint32_t* sort_cost = nullptr;    // navsim_step_sorted: one FRONT workgroup ahead of the arenas' sorts these costs ...
+    int32_t* sort_order = nullptr;          // ... into this order (navsim_step_kernel only; both set or neither)
     bool prepare_only = false;              // navsim_prepare: walk down to the kernel, set what is set once per kernel (allow_lds), launch nothing
     hipStream_t stream = nullptr;
 };
@@ -146,7 +148,12 @@ int with_march_rule(int rule, F&& f) {
 
 // the `int reset_only` of navsim_step_kernel / navsim_step_install_kernel (layout: kernels_step.hpp kStepWord*)
 int step_kernel_word(const StepLaunch& l) {
-    return (l.reset_only ? kStepWordResetOnly : 0) | ((l.peds_done ? 1 : 0) << kStepWordPedsDoneBit) | (l.part << kStepWordPartShift);
+    return (l.reset_only ? kStepWordResetOnly : 0) | ((l.peds_done ? 1 : 0) << kStepWordPedsDoneBit) | (l.part << kStepWordPartShift) |
+           ((l.sort_cost ? 1 : 0) << kStepWordSortBit);
+}
+// workgroups of a navsim_step_kernel launch: one per arena (or l.grid of them), behind the front workgroup of navsim_step_sorted
+int step_kernel_blocks(const navsim_config* c, const StepLaunch& l) {
+    return (l.grid > 0 ? l.grid : c->n_envs) + (l.sort_cost ? 1 : 0);
 }
 // The record table in LDS ("map tiles staged through LDS").  Round 3 staged the 16-byte records themselves: 63.5 KB per
 // 500 x 500 arena, two 1024-thread workgroups per CU, +10-13 % for launches of up to 4 arenas per CU and a loss beyond

@@ -509,7 +509,8 @@ class NavSim(object):
             self.st.beam_table = tab.data_ptr()
         # longest-first launch order (navsim_launch_order): the step measures every arena's workgroup, every
         # few steps the arenas are re-sorted so that the slow ones start first (lpt_period = 0 disables).  8 measured
-        # against 4 / 16 / 32 / 64 in profiles/r03_lpt/: the costs drift slowly, the sort is 13 us
+        # against 4 / 16 / 32 / 64 in profiles/r03_lpt/: the costs drift slowly, the sort is 13 us.  With the sort inside the step's
+        # launch (profiles/r12_lpt/) periods 1 and 2 win 1.7 % on c2 and 2.9 % on c3 and nothing measurable on c4: 8 stays
         self.lpt_period = 8
         self._steps_launched = 0
         # only when a launch runs several generations of workgroups: with one generation everything starts
@@ -524,6 +525,13 @@ class NavSim(object):
             self.t["launch_order"] = torch.arange(self.cfg.n_envs, dtype=torch.int32, device=self.device)
             self.st.arena_cost = self.t["arena_cost"].data_ptr()
             self.st.launch_order = self.t["launch_order"].data_ptr()
+        # The sort runs INSIDE a step's launch where it can (navsim_step_sorted: a front workgroup beside the arenas'), on the
+        # costs of the step before, into the order of the steps that follow: a second buffer of each, alternated in _launch.
+        # t["arena_cost"] / t["launch_order"] always name the pair st points at.  _reorder() only marks the sort as due.
+        self._sort_pending = False
+        self._sort_spare = None                     # (cost, order): the buffers st does not point at, made on first use
+        self.sort_in_launch = hasattr(self.lib, "navsim_step_sorted")   # False: the library has no such export, or it refused
+        self.sorts_in_launch = 0                    # sorts that ran inside a step's launch
         E = self.cfg.n_envs
         D = self.cfg.n_scan_stack * self.cfg.n_beams + abi.OBS_TAIL
         self.obs_buf = [torch.zeros((E, D), dtype=torch.float32, device=self.device) for _ in range(2)]
@@ -620,9 +628,42 @@ class NavSim(object):
         # re-sort before steps 2..5 (short runs profit from the very first measured costs), then every lpt_period-th
         self._steps_launched += 1
         n = self._steps_launched
+        # (nothing is launched here: the plain step sorts inside its own launch, every other launcher calls _flush_sort first)
         if "launch_order" in self.t and self.lpt_period > 0 and (2 <= n <= 5 or n % self.lpt_period == 0):
+            self._sort_pending = True
+
+    def _flush_sort(self):
+        """A sort that is due, as a kernel of its own ahead of the launch that follows (navsim_launch_order): the launchers whose
+        kernels have no front workgroup for it, and libraries without navsim_step_sorted."""
+        if self._sort_pending:
+            self._sort_pending = False
             check(self.lib.navsim_launch_order(_ptr(self.t["arena_cost"]), _ptr(self.t["launch_order"]), self.cfg.n_envs,
                                                _stream()), "navsim_launch_order")
+
+    def _launch_sorted(self):
+        """navsim_step_sorted: the step writes the other cost buffer while the front workgroup sorts the costs of the step before
+        into the other order buffer, which the launches that follow take (stream order makes it visible to them).
+        False = not launched (NAVSIM_E_UNSUPPORTED): the caller takes the separate kernel, from now on."""
+        import torch
+        if self._sort_spare is None:
+            self._sort_spare = (torch.zeros_like(self.t["arena_cost"]), self.t["launch_order"].clone())
+        cost_next, order_next = self._sort_spare
+        cost, order = self.t["arena_cost"], self.t["launch_order"]
+        self.st.arena_cost = cost_next.data_ptr()
+        rc = self.lib.navsim_step_sorted(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), _ptr(cost), _ptr(order_next), _stream())
+        if rc == abi.E_UNSUPPORTED:
+            self.st.arena_cost = cost.data_ptr()
+            self.sort_in_launch = False
+            return False
+        if rc:
+            self.st.arena_cost = cost.data_ptr()
+            check(rc, "navsim_step_sorted")
+        self.t["arena_cost"], self.t["launch_order"] = cost_next, order_next
+        self.st.launch_order = order_next.data_ptr()
+        self._sort_spare = (cost, order)
+        self._sort_pending = False
+        self.sorts_in_launch += 1
+        return True
 
     def _set_action(self, action):
         """io.action -> the caller's tensor where it is resident in the step's own format (stream-ordered: no copy), else the
@@ -648,6 +689,9 @@ class NavSim(object):
 
     def _launch(self):
         """The step's launch on the current stream: navsim_step, or navsim_step_install behind the staging pass it may rest on."""
+        if not self.pg_install and self._sort_pending and self.sort_in_launch and self._launch_sorted():
+            return
+        self._flush_sort()
         if not self.pg_install:
             rc = self.lib.navsim_step(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), _stream())
             if rc:
@@ -1280,6 +1324,7 @@ class NavSim(object):
         if self.replan_in_step:
             if reorder:
                 self._reorder()
+            self._flush_sort()
             self._flip()
             rc = self.lib.navsim_step_replan(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), int(replan_cap), _stream())
             if rc == 0:
@@ -1295,6 +1340,7 @@ class NavSim(object):
         ws = self._replan_ws(replan_cap)
         if reorder:
             self._reorder()
+        self._flush_sort()
         for s_ in {big, chain} - {main}:            # the previous step (both parts were joined on `main`), regen, the actions
             s_.wait_stream(main)
         # the re-plan reads st.ped_due = the flags the previous step wrote: launched BEFORE the buffers flip
@@ -1463,6 +1509,7 @@ class NavSim(object):
         overlap = bool(overlap) and replan_cap > 0
         if overlap:
             self._overlap_streams()
+        self._flush_sort()                                # (a sort that is due runs now: a captured launch's buffers are frozen)
         torch.cuda.synchronize(self.device)
         cur0, self._graphs = self.cur, {}
         for p in (0, 1):
