@@ -25,7 +25,8 @@ print("render:", img.shape, img.dtype)
 import torch  # noqa: E402
 
 E = 4096
-benv = nav_gym_env.make("NavGym-v0", num_envs=E, n_beams=1081, map_size=500, pedestrian_model="sfm", num_humans=10)
+benv = nav_gym_env.make("NavGym-v0", num_envs=E, n_beams=1081, map_size=500, pedestrian_model="sfm", num_humans=10,
+                        episode_stats=True)       # info['episode'] / episode_totals(): kept on the device, one launch per step
 # (pedestrian_model="orca", orca_params=dict(max_obst_rects=8, time_horizon_obst=2.0): ORCA pedestrians that also avoid walls)
 obs = benv.reset()
 actions = torch.rand((E, 2), dtype=torch.float64, device="cuda:0")
@@ -34,16 +35,23 @@ actions[:, 1] = actions[:, 1] * 1.28 - 0.64
 for _ in range(20):
     benv.step(actions)
 torch.cuda.synchronize()
+benv.episode_totals()                                 # (reset=True: count from here)
 t0 = time.perf_counter()
 n = 200
 finished = 0
+returns = torch.zeros((), dtype=torch.float64, device="cuda:0")
 for _ in range(n):
     obs, reward, done, info = benv.step(actions)      # your batched agent here
     finished += done.sum()
+    returns += (info["episode"]["r"] * info["_episode"]).sum()      # rows of the arenas that finished in this step
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 print("%d arenas: %.2f M env-steps/s, %d episodes finished, observation %s on %s"
       % (E, E * n / dt / 1e6, int(finished), tuple(obs["observation"].shape), obs["observation"].device))
+totals = benv.episode_totals()                        # the only device -> host copy of the statistics
+print("episodes %d: success rate %.3f, crash rate %.3f, mean return %.3f, mean length %.1f"
+      % (totals["episodes"], totals["successes"] / max(totals["episodes"], 1), totals["crashes"] / max(totals["episodes"], 1),
+         float(returns) / max(totals["episodes"], 1), totals["steps"] / max(totals["episodes"], 1)))
 
 # ---- the reference's own world, batched: every registered default, a new map at every episode end ----------
 # (512 beams, 1000 x 1000 corridor / 400 x 400 outdoor maps, 5-15 pedestrians on planned routes).  For such worlds the

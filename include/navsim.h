@@ -978,6 +978,75 @@ int navsim_reset_install(const navsim_config* cfg, const navsim_state* st, const
                          const navsim_state* stage, const float* stage_obs, uint8_t* mark, const long long* ready,
                          const uint8_t* mask, uint8_t* late, void* stream);
 
+/* ---- episode statistics: what gymnasium's RecordEpisodeStatistics keeps, on the device, one launch behind the step ----------
+ * Caller-owned device arrays, all [E].  The first five are the accumulators of the episode in progress; the ep_* six are
+ * what the latest navsim_episode_stats_update published for the arenas that FINISHED in the step it followed (rows where
+ * io->done != 0; the other rows are stale).  A caller that wants the published rows to outlive the next update alternates
+ * two sets of ep_* buffers (nav_gym_amd/sim.py does, with the step's own output pairs). */
+typedef struct navsim_episode_stats {
+    /* episode in progress */
+    double*  ret;                   /* sum of the rewards of its steps */
+    int32_t* length;                /* steps */
+    double*  path_length;           /* metres travelled, from the observation tails */
+    double*  min_clearance;         /* min over steps and beams of scan - scan_threshold, metres; +inf before the first step */
+    int32_t* discomfort_steps;      /* steps with a beam inside the discomfort zone and none inside the crash zone */
+    /* episode that the latest update finished */
+    double*  ep_return;
+    int32_t* ep_length;
+    double*  ep_path_length;
+    double*  ep_min_clearance;
+    int32_t* ep_discomfort_steps;
+    uint8_t* ep_outcome;            /* NAVSIM_EPISODE_* bits */
+    unsigned long long* totals;     /* [NAVSIM_N_EPISODE_TOTALS] running totals over finished episodes; may be NULL */
+} navsim_episode_stats;
+
+#define NAVSIM_EPISODE_SUCCESS     1   /* io->is_success != 0 in the episode's last step */
+#define NAVSIM_EPISODE_CRASH       2   /* io->is_crash != 0 */
+#define NAVSIM_EPISODE_TIME_LIMIT  4   /* io->truncated given and set (cfg.max_episode_steps) */
+
+#define NAVSIM_N_EPISODE_TOTALS    5
+#define NAVSIM_EPISODE_TOTAL_EPISODES     0   /* finished episodes */
+#define NAVSIM_EPISODE_TOTAL_SUCCESSES    1
+#define NAVSIM_EPISODE_TOTAL_CRASHES      2
+#define NAVSIM_EPISODE_TOTAL_TIME_LIMITS  3
+#define NAVSIM_EPISODE_TOTAL_STEPS        4   /* steps of the finished episodes (the sum of their ep_length) */
+
+/* Call it right after navsim_step (and whatever follows the step: navsim_regen, navsim_replan) on the same stream, with the io
+ * of that step.  One launch: a wavefront per arena, four arenas per workgroup.
+ * Reads io->obs, final_obs, reward, done, is_success, is_crash, truncated (may be NULL), reset_mask, and of the state ONLY
+ * st->scan_threshold and st->scan_discomfort.  It never reads a pose: after a same-step restart the state already belongs
+ * to the next episode, and the observation's tail carries what is needed.  Per arena e, with S = n_scan_stack, B = n_beams:
+ *  1. cfg->auto_reset == NAVSIM_AUTORESET_NEXT_STEP and io->reset_mask[e] != 0: nothing of arena e is touched.  That call of
+ *     the step RESET the arena; it returned reward 0, done 0 for it, which is no step of any episode.
+ *  2. row = io->final_obs[e] if cfg->auto_reset == NAVSIM_AUTORESET_SAME_STEP and io->done[e], else io->obs[e]: the LAST
+ *     observation of the step, what the reference's step() returns (env.py:700-728).  scan = row[(S-1) B : S B], the newest
+ *     scan of the stack (_stack_scan, env.py:257-279; older slots are not read); tail = row[S B :] = prev_xy, xy, vel, yaw
+ *     (env.py:455).
+ *  3. length += 1; ret = ret + io->reward[e].
+ *  4. dx = (double)tail[2] - (double)tail[0]; dy = (double)tail[3] - (double)tail[1];
+ *     path_length = path_length + sqrt(dx * dx + dy * dy).  float64, in this order, every operation rounded on its own (no
+ *     fused multiply-add: DESIGN.md section 4).  After a crash the row is the re-scan at the REVERTED pose (env.py:700-717),
+ *     so the increment of a crash step is whatever that row's tail says -- the statistic follows the observations.
+ *  5. min_clearance = min(min_clearance, min over k of (double)scan[k] - (double)scan_threshold[k]).
+ *  6. crash_row = any k: scan[k] < scan_threshold[k]; discomfort_steps += (any k: scan[k] < scan_discomfort[k]) and not
+ *     crash_row (env.py:543-547; float32 comparisons like the reference's).
+ *  7. io->done[e] != 0: ep_outcome[e] = (is_success[e] != 0) | (is_crash[e] != 0) << 1 | (truncated && truncated[e]) << 2; the
+ *     five accumulators go to ep_*[e]; totals, when given, receive integer atomic adds (episodes + 1, the outcome's counts,
+ *     steps + length: integer sums, the same whatever the order); the accumulators return to (0, 0, 0, +inf, 0).
+ * NAVSIM_E_ARG, before anything touches the device: cfg, st, io or s NULL; any of the eleven arrays of s (totals aside),
+ * io->obs, reward, done, is_success, is_crash, st->scan_threshold or st->scan_discomfort NULL; SAME_STEP without
+ * io->final_obs; NEXT_STEP without io->reset_mask; n_envs < 0, n_beams < 1, n_scan_stack < 1.  NAVSIM_E_UNSUPPORTED: more than
+ * 8192 beams (the two threshold tables are staged in 64 KB of LDS).  n_envs == 0: NAVSIM_OK, nothing is launched.
+ * NAVSIM_AUTORESET_NONE: nothing restarts by itself, and an arena that is stepped on past its `done` may keep that flag set
+ * (the reference's step() does the same); every such call would be published as an episode of one step and counted.  The
+ * caller resets finished arenas before their next step (navsim_restart + navsim_reset_obs, with navsim_episode_stats_clear)
+ * for the rows and totals to mean episodes. */
+int navsim_episode_stats_update(const navsim_config* cfg, const navsim_state* st, const navsim_step_io* io,
+                                const navsim_episode_stats* s, void* stream);
+/* The accumulators of the arenas with mask[e] != 0 (mask NULL: of all arenas) return to (0, 0, 0, +inf, 0): what a reset() of
+ * those arenas needs.  ep_* and totals are not touched.  NAVSIM_E_ARG: cfg or s NULL, one of the eleven arrays NULL. */
+int navsim_episode_stats_clear(const navsim_config* cfg, const navsim_episode_stats* s, const uint8_t* mask, void* stream);
+
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);
 

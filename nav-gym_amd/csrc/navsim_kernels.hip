@@ -42,6 +42,7 @@ namespace {
 #include "kernels_crowd_maps.hpp"
 #include "kernels_crowd_orca.hpp"
 #include "kernels_ped_orca.hpp"
+#include "kernels_episode.hpp"
 
 }  // namespace
 #include "step_plan.hpp"
@@ -1367,6 +1368,41 @@ int navsim_reset_install(const navsim_config* c, const navsim_state* st, const n
     in.stage = *stage; in.stage_obs = stage_obs; in.mark = mark; in.ready = ready; in.late = late;
     if (!st->map_slot) stage_big_buffers(c, st, stage, in.big);             // (with slot tables the maps stay where they are)
     reset_install_kernel<<<c->n_envs, 256, 0, (hipStream_t)stream>>>(*c, *st, *io, in, mask);
+    return launch_status();
+}
+
+// navsim_episode_stats_update / _clear: the pointers both need
+static bool episode_stats_complete(const navsim_episode_stats* s) {
+    return s && s->ret && s->length && s->path_length && s->min_clearance && s->discomfort_steps && s->ep_return &&
+           s->ep_length && s->ep_path_length && s->ep_min_clearance && s->ep_discomfort_steps && s->ep_outcome;
+}
+
+int navsim_episode_stats_update(const navsim_config* c, const navsim_state* st, const navsim_step_io* io,
+                                const navsim_episode_stats* s, void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !io || !episode_stats_complete(s)) return NAVSIM_E_ARG;
+    if (c->n_envs < 0 || c->n_beams < 1 || c->n_scan_stack < 1) return NAVSIM_E_ARG;
+    if (!io->obs || !io->reward || !io->done || !io->is_success || !io->is_crash || !st->scan_threshold || !st->scan_discomfort)
+        return NAVSIM_E_ARG;
+    if (c->auto_reset == NAVSIM_AUTORESET_SAME_STEP && !io->final_obs) return NAVSIM_E_ARG;
+    if (c->auto_reset == NAVSIM_AUTORESET_NEXT_STEP && !io->reset_mask) return NAVSIM_E_ARG;
+    const size_t lds = (size_t)c->n_beams * 2 * sizeof(float);         // the two threshold tables
+    if (lds > 64 * 1024) return NAVSIM_E_UNSUPPORTED;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    EpisodeArgs a = {};
+    a.n_envs = c->n_envs; a.n_beams = c->n_beams; a.n_scan_stack = c->n_scan_stack; a.auto_reset = c->auto_reset;
+    a.obs = io->obs; a.final_obs = io->final_obs; a.reward = io->reward; a.done = io->done; a.is_success = io->is_success;
+    a.is_crash = io->is_crash; a.truncated = io->truncated; a.reset_mask = io->reset_mask;
+    a.thr = st->scan_threshold; a.dthr = st->scan_discomfort; a.s = *s;
+    episode_stats_kernel<<<(c->n_envs + kEpisodeWaves - 1) / kEpisodeWaves, 64 * kEpisodeWaves, lds, (hipStream_t)stream>>>(a);
+    return launch_status();
+}
+
+int navsim_episode_stats_clear(const navsim_config* c, const navsim_episode_stats* s, const uint8_t* mask, void* stream) {
+    (void)hipGetLastError();
+    if (!c || !episode_stats_complete(s) || c->n_envs < 0) return NAVSIM_E_ARG;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    episode_stats_clear_kernel<<<(c->n_envs + 255) / 256, 256, 0, (hipStream_t)stream>>>(c->n_envs, *s, mask);
     return launch_status();
 }
 

@@ -210,6 +210,20 @@ class NavsimStepIO(C.Structure):
     )]
 
 
+# navsim_episode_stats: the accumulators of the episode in progress, what the latest update published for the arenas that
+# finished (EPISODE_PUBLISHED: kept in pairs like everything a step returns), the running totals
+EPISODE_ACCUMULATORS = {"ret": "float64", "length": "int32", "path_length": "float64", "min_clearance": "float64",
+                        "discomfort_steps": "int32"}
+EPISODE_PUBLISHED = {"ep_return": "float64", "ep_length": "int32", "ep_path_length": "float64", "ep_min_clearance": "float64",
+                     "ep_discomfort_steps": "int32", "ep_outcome": "uint8"}
+EPISODE_TOTALS = ("episodes", "successes", "crashes", "time_limits", "steps")
+EPISODE_SUCCESS, EPISODE_CRASH, EPISODE_TIME_LIMIT = 1, 2, 4      # bits of ep_outcome
+
+
+class NavsimEpisodeStats(C.Structure):
+    _fields_ = [(name, _P) for name in tuple(EPISODE_ACCUMULATORS) + tuple(EPISODE_PUBLISHED) + ("totals",)]
+
+
 # dtype / trailing shape of every state array, in units of (E, N, B, S, K, P, H, W)
 STATE_LAYOUT = {
     "field": ("float32", ("E", "H", "W")),          # FIELD_F32; a uint8 blob for packed formats
@@ -382,6 +396,9 @@ def declare(lib, suffix=""):
         # (a library built before the export existed -- NAVSIM_LIB, A/B runs -- loads without it: NavSim falls back to navsim_launch_order)
         if hasattr(lib, "navsim_step_sorted"):
             sig("navsim_step_sorted", [cfgp, stp, iop, _P, _P, _P])
+    if not suffix and hasattr(lib, "navsim_episode_stats_update"):      # (as above: an older library of an A/B run loads without)
+        sig("navsim_episode_stats_update", [cfgp, stp, iop, C.POINTER(NavsimEpisodeStats), _P])
+        sig("navsim_episode_stats_clear", [cfgp, C.POINTER(NavsimEpisodeStats), _P, _P])
     sig("navsim_reset_obs", [cfgp, stp, iop, _P] + stream)
     sig("navsim_restart", [cfgp, stp, _P] + stream)
     return lib
@@ -399,6 +416,7 @@ EXPORTS = (
     "navsim_costmap", "navsim_plan", "navsim_launch_order", "navsim_replan_workspace_bytes", "navsim_replan", "navsim_ped_policy_workspace_bytes", "navsim_ped_policy", "navsim_ped_scan_policy",
     "navsim_crowd_check", "navsim_crowd_angular_map", "navsim_crowd_local_map", "navsim_crowd_orca", "navsim_crowd_agent_step", "navsim_ped_orca", "navsim_ped_orca_walls",
     "navsim_step", "navsim_step_sorted", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
+    "navsim_episode_stats_update", "navsim_episode_stats_clear",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

@@ -69,6 +69,17 @@ and default to the reference's behaviour for num_envs == 1:
                     terminal row; next_step: the next step() resets it (info['reset_mask']).  Without auto_reset an arena
                     stepped past T stays truncated until reset().  info['TimeLimit.truncated'] is a bool (num_envs == 1)
                     or a torch.bool [num_envs] view; None (default): no limit, the reference's behaviour and no such key.
+    episode_stats   True: step() keeps every arena's episode statistics on the device, one launch behind the step
+                    (navsim_episode_stats_update; gymnasium's RecordEpisodeStatistics) -- info['episode'] = {'r' return, 'l'
+                    length, 'path_length' metres, 'min_clearance' smallest scan - scan_threshold of the episode, 'discomfort_steps',
+                    'outcome' bit 0 success, bit 1 crash, bit 2 time limit}.  num_envs > 1: torch views [num_envs], rows valid
+                    where info['_episode'] (= done) is set, with the lifetime below; num_envs == 1: Python scalars, only in the
+                    step that ends the episode.  The terminal step counts (same_step: its row is info['final_observation'], so
+                    final_observation=False raises ValueError), the step in which next_step RESETS an arena does not, and
+                    reset() / reset(mask) start the arenas' statistics afresh.  With auto_reset=False the caller resets
+                    finished arenas (reset(mask=done)) before their next step: an arena stepped on past its `done` may keep the
+                    flag, and every such step would count as an episode of one step.  env.episode_totals() reads the running totals
+                    -- the only device -> host copy, and only when called.  False (default): nothing is launched.
     reset(mask)     reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
                     [num_envs]; the others keep their state and their rows.  On the pipelined reset path the masked arenas install
                     their staged worlds in one launch: the same state and rows as with pregen_pipeline=0.
@@ -205,7 +216,8 @@ class NavGymEnv(_EnvBase):
                  field_format=abi.FIELD_U16T, n_spawn=None, randomize_maps=False, plan_paths=True,
                  action_kind="twist", clip_actions=False, max_waypoints=64, march_rule=None, use_graphs=None,
                  regen_min_steps=0, pregen_pipeline=None, pregen_stage_cap=None, autoreset_mode="same_step",
-                 final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None):
+                 final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None,
+                 episode_stats=False):
         # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
         self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
         from . import lib
@@ -259,6 +271,10 @@ class NavGymEnv(_EnvBase):
             raise ValueError("max_episode_steps must be None or a positive int, not %r" % (max_episode_steps,))
         self.max_episode_steps = None if max_episode_steps is None else int(max_episode_steps)
         self.final_observation = bool(final_observation) and self.auto_reset and autoreset_mode == "same_step"
+        self.episode_stats = bool(episode_stats)
+        if self.episode_stats and self.auto_reset and autoreset_mode == "same_step" and not self.final_observation:
+            raise ValueError("episode_stats=True under same-step auto-reset needs final_observation=True: an episode's last "
+                             "step is read from its terminal row")
         self._num_humans_fixed = num_humans
         self._episode_batch = 0
         self.randomize_maps = bool(randomize_maps)
@@ -517,6 +533,8 @@ class NavGymEnv(_EnvBase):
                 if isinstance(w, str):
                     w = torch.load(w, map_location="cpu")
                 self.sim.set_policy(w)
+            if self.episode_stats:
+                self.sim.enable_episode_stats()
         elif "policy_prev_actions" in self.sim.t:
             self.sim.t["policy_prev_actions"].zero_()           # env.py:739
         self._episode_batch += 1
@@ -632,6 +650,8 @@ class NavGymEnv(_EnvBase):
                 self.sim.regen()
             if self._replan_behind:
                 self.sim.replan(self.replan_cap)           # ('policy', 'orca': the launch in front of the next step reads the routes)
+        if self.episode_stats:                             # one launch, behind whatever the step's path queued
+            ep = self.sim.episode_stats()
         obs = self._obs_dict()
         # the LAST observation of an episode that ended in this step (env.py:700-728 returns it with done = True): under
         # same-step auto-reset the row above already is the next episode's first one and the terminal one rides in info;
@@ -650,6 +670,8 @@ class NavGymEnv(_EnvBase):
                 info["reset_mask"] = bool(self.sim.reset_flags[0].item())
             if self.max_episode_steps is not None:
                 info["TimeLimit.truncated"] = bool(out["truncated"][0].item())
+            if self.episode_stats and done:
+                info["episode"] = {name: ep[k][0].item() for name, k in self._EPISODE_KEYS}
             return obs, float(out["reward"][0].item()), done, info
         # (views of the buffers the kernel wrote, made ONCE per buffer parity: a step of 4096 arenas is 95 us on the device, and
         #  every tensor slice or .view() costs the host 3-5 us -- round 6 measured 42 -> 36 M env-steps/s through this method
@@ -664,6 +686,8 @@ class NavGymEnv(_EnvBase):
                 v["reset"] = self.sim.reset_flags.view(self._bool)
             if self.max_episode_steps is not None:
                 v["truncated"] = out["truncated"].view(self._bool)
+            if self.episode_stats:
+                v["episode"] = {name: ep[k] for name, k in self._EPISODE_KEYS}
             self._views[self.sim.cur] = v
         info = {"is_success": out["is_success"], "is_crash": out["is_crash"], "distance": out["distance"]}
         done = v["done"]
@@ -674,7 +698,23 @@ class NavGymEnv(_EnvBase):
             info["reset_mask"] = v["reset"]
         if "truncated" in v:
             info["TimeLimit.truncated"] = v["truncated"]
+        if "episode" in v:
+            info["episode"] = v["episode"]
+            info["_episode"] = done
         return obs, out["reward"], done, info
+
+    # info['episode']: gymnasium's names for return and length, the build's own for the rest -> NavSim.episode_stats()'s rows
+    _EPISODE_KEYS = (("r", "ep_return"), ("l", "ep_length"), ("path_length", "ep_path_length"),
+                     ("min_clearance", "ep_min_clearance"), ("discomfort_steps", "ep_discomfort_steps"), ("outcome", "ep_outcome"))
+
+    def episode_totals(self, reset=True):
+        """Finished episodes since the last call (episode_stats=True): {'episodes', 'successes', 'crashes', 'time_limits',
+        'steps'} -- steps being those of the finished episodes.  The feature's only device -> host copy."""
+        if not self.episode_stats:
+            raise RuntimeError("episode_totals() needs NavGymEnv(episode_stats=True)")
+        if self.sim is None:
+            return {k: 0 for k in abi.EPISODE_TOTALS}
+        return self.sim.episode_totals(reset=reset)
 
     def counters(self, reset=True):
         """What the device-side reset path served and what its caps left waiting since the last call (abi.COUNTERS):
@@ -819,6 +859,10 @@ class NavGymEnv(_EnvBase):
             if self.sim.final_buf is not None:
                 for k, v in self.sim.final_buf[i].items():
                     sd["final.%d.%s" % (i, k)] = v.cpu().clone()
+        if self.sim.ep_acc is not None:                    # episode statistics: the episodes in progress and the totals
+            for k, v in self.sim.ep_acc.items():
+                sd["episode." + k] = v.cpu().clone()
+            sd["episode.totals"] = self.sim.ep_totals.cpu().clone()
         sd["cur"] = int(self.sim.cur)
         sd["steps_launched"] = int(self.sim._steps_launched)
         sd["episode_batch"] = int(self._episode_batch)
@@ -850,6 +894,14 @@ class NavGymEnv(_EnvBase):
                     if "final.%d.%s" % (i, k) in sd:
                         v.copy_(sd["final.%d.%s" % (i, k)])
         self.sim.cur = int(sd["cur"])
+        if self.sim.ep_acc is not None:                    # (a snapshot without them: cleared ones; with them and no feature: ignored)
+            if "episode.totals" in sd:
+                for k, v in self.sim.ep_acc.items():
+                    v.copy_(sd["episode." + k])
+                self.sim.ep_totals.copy_(sd["episode.totals"])
+            else:
+                self.sim.clear_episode_stats()
+                self.sim.ep_totals.zero_()
         if self.sim.pregen:                                # the staged worlds are not part of the snapshot: stage them again
             self.sim.restage_all(slots_from_live=True)
         self.sim._steps_launched = int(sd["steps_launched"])

@@ -451,6 +451,9 @@ class NavSim(object):
         self._graphs, self._graph_args, self._graph_cfg = {}, None, None
         # policy and orca
         self.policy_t, self.policy_w, self._scan_stream, self._orca_default = {}, None, None, None
+        # episode statistics (enable_episode_stats): the accumulators, the totals, the two sets of published rows (they flip with
+        # self.cur like out_buf) and, per parity, the arguments of navsim_episode_stats_update
+        self.ep_acc, self.ep_totals, self.ep_buf, self._ep_args = None, None, None, {}
         self.t = {}
         self.st = abi.NavsimState()
         for name, (dtype, shape) in abi.STATE_LAYOUT.items():
@@ -619,6 +622,7 @@ class NavSim(object):
         self._flip()
         check(self.lib.navsim_reset_obs(C.byref(self.cfg), C.byref(self.st), C.byref(self.io), _ptr(m), _stream()),
               "navsim_reset_obs")
+        self.clear_episode_stats(m)
         if self.due is not None:                    # a reset-only launch advances nobody: the latest flags stay the latest
             self.due[1 - self.cur].copy_(self.due[self.cur])
         self.cur = 1 - self.cur
@@ -1210,6 +1214,7 @@ class NavSim(object):
             self.due[1 - self.cur].copy_(self.due[self.cur])
             self.due[1 - self.cur].mul_(keep)
         self.cur = 1 - self.cur
+        self.clear_episode_stats(m)
         idx = torch.nonzero(self.rs_late).flatten()     # (a host wait for the launch: a reset is not the per-step path)
         if int(idx.numel()):
             if self.late_ws is not None:                # the step's fallback: its workspace serves, on the same stream
@@ -1257,6 +1262,7 @@ class NavSim(object):
             b["done"].zero_()
             if "truncated" in b:
                 b["truncated"].zero_()
+        self.clear_episode_stats()
         torch.cuda.current_stream().synchronize()          # `ws` and `done` are released on return
         return self.obs
 
@@ -1267,6 +1273,84 @@ class NavSim(object):
         if reset:
             self.t["counters"].zero_()
         return {k: int(v[i]) for i, k in enumerate(abi.COUNTERS)}
+
+    # ---- episode statistics: return, length, path, clearance, discomfort and outcome of every finished episode, kept on the
+    # device by one launch behind the step (include/navsim.h navsim_episode_stats_update)
+    def enable_episode_stats(self):
+        """Allocates the per-arena accumulators, the totals and two sets of published rows (ep_*: they flip with self.cur, so
+        the rows episode_stats() returns stay intact through the next step like everything else a step returns).  From now on
+        reset_obs(mask) / reset_arenas / regenerate_all clear the accumulators of the arenas they reset."""
+        import torch
+        if self.cfg.auto_reset == abi.AUTORESET_SAME_STEP and self.final_buf is None:
+            raise ValueError("episode statistics under same-step auto-reset read the terminal rows: NavSim(final_obs=True)")
+        if self.ep_acc is None:
+            E = self.cfg.n_envs
+            make = lambda d, n=E: torch.zeros(n, dtype=_dtype(d), device=self.device)
+            self.ep_acc = {k: make(d) for k, d in abi.EPISODE_ACCUMULATORS.items()}
+            self.ep_buf = [{k: make(d) for k, d in abi.EPISODE_PUBLISHED.items()} for _ in range(2)]
+            self.ep_totals = make("int64", len(abi.EPISODE_TOTALS))     # uint64 on the device; far below 2^63
+            self._ep_args = {}
+        self.ep_totals.zero_()
+        self.clear_episode_stats()
+
+    def _episode_struct(self, parity):
+        """navsim_episode_stats with the accumulators, the totals and the published rows of one parity."""
+        stats = abi.NavsimEpisodeStats()
+        for k, v in list(self.ep_acc.items()) + list(self.ep_buf[parity].items()):
+            setattr(stats, k, v.data_ptr())
+        stats.totals = self.ep_totals.data_ptr()
+        return stats
+
+    def _episode_args(self):
+        """(io, stats) of navsim_episode_stats_update for the current parity: the buffers of the LATEST step, taken from the
+        properties -- not from self.io, whose pointers the graph replay and the install paths do not keep current.
+        Built once per parity and kept (a ctypes struct per call costs the host as much as the launch).  That rests on an
+        invariant of this class: obs_buf, out_buf, final_buf, ep_acc, ep_buf, ep_totals, cfg and st are allocated once, in
+        __init__ / enable_episode_stats, and only ever written in place.  Whoever reallocates one of them must empty
+        self._ep_args."""
+        args = self._ep_args.get(self.cur)
+        if args is None:
+            io = abi.NavsimStepIO()
+            io.obs = self.obs.data_ptr()
+            for k in ("reward", "done", "is_success", "is_crash", "truncated"):
+                if k in self.out:
+                    setattr(io, k, self.out[k].data_ptr())
+            if self.final is not None:
+                io.final_obs = self.final["final_obs"].data_ptr()
+            if self.next_step:
+                io.reset_mask = self.reset_flags.data_ptr()
+            stats = self._episode_struct(self.cur)
+            args = self._ep_args[self.cur] = (io, stats, C.byref(io), C.byref(stats), C.byref(self.cfg), C.byref(self.st))
+        return args
+
+    def episode_stats(self):
+        """navsim_episode_stats_update behind the latest step (and its regen() / replan()) on the current stream: one launch.
+        Returns the published rows: ep_return, ep_length, ep_path_length, ep_min_clearance, ep_discomfort_steps, ep_outcome --
+        valid where that step's done flag is set, intact through the next step."""
+        if self.ep_acc is None:
+            raise RuntimeError("call enable_episode_stats() first")
+        a = self._episode_args()
+        rc = self.lib.navsim_episode_stats_update(a[4], a[5], a[2], a[3], _stream())
+        if rc:
+            check(rc, "navsim_episode_stats_update")
+        return self.ep_buf[self.cur]
+
+    def clear_episode_stats(self, mask=None):
+        """The accumulators of the masked arenas (None: all) back to "no step yet"; nothing without enable_episode_stats()."""
+        if self.ep_acc is None:
+            return
+        stats = self._episode_struct(self.cur)            # (clear touches the accumulators only: either parity's struct does)
+        check(self.lib.navsim_episode_stats_clear(C.byref(self.cfg), C.byref(stats), _ptr(mask), _stream()),
+              "navsim_episode_stats_clear")
+
+    def episode_totals(self, reset=False):
+        """The running totals over finished episodes as a dict (abi.EPISODE_TOTALS).  One device -> host copy."""
+        if self.ep_acc is None:
+            raise RuntimeError("call enable_episode_stats() first")
+        v = self.ep_totals.cpu().numpy()
+        if reset:
+            self.ep_totals.zero_()
+        return {k: int(v[i]) for i, k in enumerate(abi.EPISODE_TOTALS)}
 
     def occupancy(self, e=0):
         """uint8 [H, W] occupancy grid (1 = occupied) of arena e, read back from its distance field
