@@ -308,6 +308,7 @@ typedef unsigned long long lanemask_t;
 __device__ __forceinline__ lanemask_t mask_of(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 __device__ __forceinline__ lanemask_t mask_ult(unsigned a, unsigned b) { return __builtin_amdgcn_uicmp(a, b, 36); }   // ICMP_ULT
 __device__ __forceinline__ lanemask_t mask_eq(unsigned a, unsigned b) { return __builtin_amdgcn_uicmp(a, b, 32); }    // ICMP_EQ
+__device__ __forceinline__ lanemask_t mask_ne(unsigned a, unsigned b) { return __builtin_amdgcn_uicmp(a, b, 33); }    // ICMP_NE
 __device__ __forceinline__ lanemask_t mask_flt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 4); }         // FCMP_OLT
 // lane bit of m set ? a : b.  Pass masks that a SCALAR instruction produced (an and / or / andn2 of comparison
 // masks, as everywhere below): the compiler's hazard recognizer does not look into the asm, and a v_cndmask that
@@ -334,7 +335,11 @@ __device__ __forceinline__ bool uniform_gt0(float x) { return (unsigned)(__float
 // RECT: 0 = the field alone; 1 = the tile's two-rectangle record from global memory; 2 = from the INDEX form of the arena's
 // table staged in LDS (kernels_rect.hpp: `rects` then points at the LDS copy of the arena's row -- list[256], then two
 // list indices per tile; round 4.  Round 3 staged the 16-byte records themselves, 63.5 KB per arena: two workgroups per CU).
-template <typename Field, int RULE, int RECT>
+// ONE (RECT = 2): a round computes the second rectangle's distance only when a live lane needs it (below).
+#ifndef NAVSIM_PROBE_ONE_RECT           // leave-one-out builds (profiles/r14_probe/): 0 = every round evaluates both rectangles
+#define NAVSIM_PROBE_ONE_RECT 1
+#endif
+template <typename Field, int RULE, int RECT, bool ONE = false>
 __device__ __forceinline__ void probe_round(const Field& field, const char* __restrict__ rects, unsigned tpr,
                                             float x0, float y0, float dx, float dy, unsigned uW, unsigned uH,
                                             float max_range, float& t, lanemask_t& active, lanemask_t& hit) {
@@ -369,6 +374,7 @@ __device__ __forceinline__ void probe_round(const Field& field, const char* __re
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         u32x4 rec;
         lanemask_t inval;
+        lanemask_t two = 0;                                             // (ONE) the live lanes whose tile names two rectangles
         if constexpr (RECT == 2) {
             // the arena's row in LDS: ds_read_u16 of the tile's index pair, then the two rectangles (ds_read_b64 each; most
             // lanes of a wavefront name the same few list entries: broadcast reads)
@@ -383,9 +389,14 @@ __device__ __forceinline__ void probe_round(const Field& field, const char* __re
             lds_u8* row = (lds_u8*)rects;
             const unsigned ia = row[kRectListLen * 8 + tile * 2u], ib = row[kRectListLen * 8 + 1 + tile * 2u];
             const u32x2 ra = *(lds_u2*)(row + ia * 8u);
-            const u32x2 rb = *(lds_u2*)(row + ib * 8u);
+            // (ONE: read as volatile, which is what keeps the compiler from sinking the read behind the branch on `two` below)
+            typedef __attribute__((address_space(3))) const volatile u32x2 lds_u2_pinned;
+            u32x2 rb;
+            if constexpr (ONE) rb = *(lds_u2_pinned*)(row + ib * 8u);
+            else rb = *(lds_u2*)(row + ib * 8u);
             rec.x = ra.x; rec.y = ra.y; rec.z = rb.x; rec.w = rb.y;
             inval = live & mask_eq(ia, 0xFFu);                       // no index: both bytes are 0xFF
+            if constexpr (ONE) two = live & mask_ne(ia, ib);
         } else {
             // The load is written out: after a compiler-generated global_load_dwordx4 the register allocator moved three
             // of the four loaded dwords to other registers before using them (3 of 42 vector instructions per probe).
@@ -400,8 +411,21 @@ __device__ __forceinline__ void probe_round(const Field& field, const char* __re
                          : "=&v"(rec), "=&s"(base) : "v"(off), "s"(rects) : "memory");
             inval = live & mask_eq(rec.x & 0xFFFFu, (unsigned)kRectInvalid);
         }
-        const int da = rect_dist2(rec.x, rec.y, cell), db = rect_dist2(rec.z, rec.w, cell);
-        const int d2 = da < db ? da : db;
+        int d2 = rect_dist2(rec.x, rec.y, cell);
+        // ONE: the second rectangle's distance only when a LIVE lane's tile has a second rectangle.  rect_tiles_kernel writes a
+        // one-rectangle tile's record as the same rectangle twice, so its index pair has ia == ib and db reproduces da; a tile
+        // without an index has both bytes 0xFF, counts as equal, and takes its distance from the field below as before.  In a
+        // round that skips db EVERY lane keeps da: for a live lane that is min(da, db) of one rectangle twice, and what a lane
+        // that is not live computes is masked off like all its results -- which is why only live lanes vote (modelled, c2:
+        // 0.44 of the rounds skip, 0.38 if all 64 lanes voted; profiles/r14_probe/).  A scalar branch around straight-line
+        // code, like `inval` below.  rb's ds_read stays IN FRONT of the branch, beside ra's: behind it a round that needs db
+        // waits a second LDS latency (measured: c2 +1.0 % that way, +1.4 % this way; profiles/r14_probe/ab.txt).
+        bool both = true;
+        if constexpr (ONE && RECT == 2) both = two != 0;
+        if (both) {                                                     // wave-uniform branch (ONE), or no branch at all
+            const int db = rect_dist2(rec.z, rec.w, cell);
+            d2 = d2 < db ? d2 : db;
+        }
         occ = live & mask_eq((unsigned)d2, 0u);
         d = Field::sqrt_d2(d2);
         if (inval != 0) {                                               // wave-uniform branch
@@ -561,6 +585,9 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
     // info[] of the culled merge: visible after the scan's barrier (the step's first scan: wavefront 0 has written it)
     if constexpr (TO_LDS) { if (prepare_prims) prims_prepare<BLOCK>(c, sh, pr); }
     constexpr bool kPark = step_parks(BLOCK, TO_LDS);           // compiled in only where the host ever asks for it
+    // probe_round's one-rectangle rounds: not in the pedestrian variants (TO_LDS is the kernel's PEDS at every call), where the
+    // branch cost c3 1.2 % (profiles/r14_probe/loo_ab.txt)
+    constexpr bool kOne = NAVSIM_PROBE_ONE_RECT != 0 && RECT == 2 && !TO_LDS;
     int own_chunk = 0;                                    // one wavefront per arena: no counter needed
     const int lane = (int)threadIdx.x & 63;
     for (;;) {
@@ -582,11 +609,11 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
         lanemask_t hit = 0;
         if constexpr (!kPark) {
             while (active != 0)
-                probe_round<Field, RULE, RECT>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
+                probe_round<Field, RULE, RECT, kOne>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
             finish(valid, validm, k, dx, dy, ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, miss));
         } else {
             while ((int)__builtin_popcountll(active) > park_lanes)
-                probe_round<Field, RULE, RECT>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
+                probe_round<Field, RULE, RECT, kOne>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
             const bool marching = mask_lane(active);
             if (active != 0) {                                   // park what is still marching
                 int base = 0;
@@ -631,7 +658,7 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
         lanemask_t active = validm;
         lanemask_t hit = 0;
         while (active != 0)
-            probe_round<Field, RULE, RECT>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
+            probe_round<Field, RULE, RECT, kOne>(field, (const char*)rects, tpr, x0, y0, dx, dy, uW, uH, max_range, t, active, hit);
         finish(valid, validm, k, dx, dy, ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, miss));   // lanes past the last ray: ray g's
     }
     int cr = (crm != 0), dc = (dcm != 0);                       // one value per wavefront; the caller ORs them over the arena
