@@ -1047,6 +1047,61 @@ int navsim_episode_stats_update(const navsim_config* cfg, const navsim_state* st
  * those arenas needs.  ep_* and totals are not touched.  NAVSIM_E_ARG: cfg or s NULL, one of the eleven arrays NULL. */
 int navsim_episode_stats_clear(const navsim_config* cfg, const navsim_episode_stats* s, const uint8_t* mask, void* stream);
 
+/* ---- observed pedestrians: the K nearest pedestrians the robot has in line of sight, in its frame, from one launch ------------
+ * What the SARL / CADRL / attention family of crowd-navigation policies takes as input: per arena a list of observed humans --
+ * position and velocity in the robot's frame, sorted by distance, an entry only for a human the robot can actually see.
+ * BUILD-DEFINED, all of it: the reference's NavGym-v0 has no such observation (env.py:455-461 returns the lidar stack and a
+ * 7-float tail).  In particular: the line of sight starts at the scan's INTEGER origin cell (env.py:386, 419) while d comes from
+ * the float64 pose -- the two can be up to a cell apart; only one or three rays are cast per pedestrian, so partial occlusion
+ * between them is not seen; other pedestrians and the robot's own body do not occlude. */
+typedef struct navsim_ped_observe_params {
+    double  ped_radius;     /* metres, >= 0 */
+    double  sensor_range;   /* metres, finite, >= 0: a pedestrian is in range iff d - ped_radius <= sensor_range */
+    int32_t max_obs;        /* K, 1 .. NAVSIM_MAX_PEDS: rows kept per arena */
+    int32_t rays;           /* 1 or 3: lines of sight tried per pedestrian */
+    int32_t occlusion;      /* 0: every pedestrian in range (and in the field of view) counts as seen; no march */
+    int32_t fov;            /* 1: the relative bearing must lie in [cfg.angle_min, cfg.angle_last] */
+} navsim_ped_observe_params;
+
+typedef struct navsim_ped_observation {
+    float*   state;    /* [E,K,5] x, y, vx, vy in the robot's frame, d */
+    int32_t* index;    /* [E,K]   pedestrian index of the row, -1 = unused row */
+    int32_t* count;    /* [E]     pedestrians SEEN (may exceed K: the cap is observable) */
+    uint8_t* visible;  /* [E,N]   1 = pedestrian i is seen; may be NULL */
+} navsim_ped_observation;
+
+/* One launch (a wavefront per arena, four arenas per workgroup) that reads st->robot_pose, n_peds, ped_pose, ped_vel and the
+ * distance field of the arena's map slot (cfg.shared_field, st->map_slot, st->field_overflow; both field formats), and writes
+ * EVERY element of `out`.  Call it behind the step (and whatever follows it: navsim_regen, navsim_replan) on the same stream.
+ * Per arena e, everything float64 in exactly this order, every operation rounded on its own (no fused multiply-add: DESIGN.md
+ * section 4); nv:: are the functions of navmath.hpp / navmath_ref.h; N = cfg.max_peds, K = p->max_obs:
+ *  1. skip && skip[e]: count = 0, every row of state 0, every index -1, visible 0.  The arena is done.
+ *  2. n = min(n_peds[e], N); (rx, ry, th) = robot_pose[e]; c = nv::cos(th), s = nv::sin(th);
+ *     (i0, j0) = xy_to_ij_f32((float)rx, (float)ry): the integer cell the robot's own scan starts from (env.py:386, 419).
+ *  3. pedestrian i < n: ax = px_i - rx, ay = py_i - ry, d = sqrt(ax*ax + ay*ay); x = c*ax + s*ay, y = c*ay - s*ax; with
+ *     ped_vel, vxr = c*vx + s*vy, vyr = c*vy - s*vx.  in_range = (d - ped_radius <= sensor_range).
+ *     in_fov = !fov || (cfg.angle_min <= b && b <= cfg.angle_last), b = nv::atan2(y, x).
+ *  4. line of sight: seen = 1 when !occlusion or d <= ped_radius.  Otherwise ux = ax/d, uy = ay/d, and ray k = 0 .. rays-1
+ *     with the offsets o = (0, +ped_radius, -ped_radius) -- the centre, then the two silhouette points -- is cast at
+ *     tx = ax - o_k*uy, ty = ay + o_k*ux: heading = (float)nv::atan2(ty, tx), (dx, dy) = beam_dir(heading) (navsim_cast_static's),
+ *     r = the restatement of range_libc's calc_range that navsim_cast_static runs, on the field of the arena's map slot, from
+ *     ((float)i0, (float)j0) along (dx, dy) with max_range = (float)((int64)H*W) and cfg.march_rule -- the general form with its
+ *     bounds test: a ray that leaves the map returns max_range.  r_m = (double)(r * (float)cfg.resolution), the float32 product
+ *     of env.py:426.  reach = sqrt(tx*tx + ty*ty) - (k == 0 ? ped_radius : 0).  Ray k is clear iff r_m >= reach; seen = any
+ *     ray clear.  (The kernel stops a ray at floor(reach / resolution) + 4 cells -- at most floor((sensor_range + 2 ped_radius) /
+ *     resolution) + 4 for a pedestrian in range -- where every outcome is `clear`; kernels_ped_observe.hpp writes the bound out;
+ *     the result is the one of H*W.)
+ *  5. visible[e,i] = in_range && in_fov && seen; entries i >= n are 0.  count[e] = the number of set entries.
+ *  6. the seen pedestrians in ascending (d, i) order -- equal d: the lower index first -- give the first min(count, K) rows:
+ *     state[e,row] = ((float)x, (float)y, (float)vxr, (float)vyr, (float)d), index[e,row] = i.  Every further row is 0 / -1.
+ * NAVSIM_E_ARG, before anything touches the device: cfg, st, p or out NULL; out->state, index or count NULL; st->robot_pose,
+ * n_peds, ped_pose, ped_vel or field NULL; cfg.ped_model == NAVSIM_PED_NONE; max_obs outside 1 .. NAVSIM_MAX_PEDS; rays not 1
+ * or 3; ped_radius or sensor_range negative or not finite; n_envs < 0; max_peds outside 1 .. NAVSIM_MAX_PEDS; map_h or map_w
+ * < 1; a march_rule that is none of NAVSIM_MARCH_*; st->map_slot with cfg.shared_field.  NAVSIM_E_UNSUPPORTED: a field_format
+ * that is neither NAVSIM_FIELD_F32 nor NAVSIM_FIELD_U16T.  n_envs == 0: NAVSIM_OK, nothing is launched. */
+int navsim_ped_observe(const navsim_config* cfg, const navsim_state* st, const navsim_ped_observe_params* p,
+                       const uint8_t* skip, const navsim_ped_observation* out, void* stream);
+
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);
 

@@ -20,6 +20,7 @@
 //   kernels_pedscan.hpp  pedestrian scans (+ ped_scan_lds_bytes, host side), CrowdSim collision block, beam table, test hooks
 //   kernels_crowd_maps.hpp  CrowdSim local maps;  kernels_crowd_orca.hpp  CrowdSim pedestrians (ORCA, Agent.step)
 //   kernels_ped_orca.hpp  NavGym pedestrians driven by ORCA from the simulator's state (navsim_ped_orca)
+//   kernels_episode.hpp  episode statistics behind the step;  kernels_ped_observe.hpp  the K nearest pedestrians in line of sight
 //   step_plan.hpp        launch geometry of the fused step, the descriptors of a launch and the march-rule dispatch (shared by this
 //                        file and navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
 // Host code of this file, ahead of the C ABI: dispatch_step and the argument checks; the workspaces (Carver and one layout
@@ -43,6 +44,7 @@ namespace {
 #include "kernels_crowd_orca.hpp"
 #include "kernels_ped_orca.hpp"
 #include "kernels_episode.hpp"
+#include "kernels_ped_observe.hpp"
 
 }  // namespace
 #include "step_plan.hpp"
@@ -437,6 +439,20 @@ int launch_ped_scan_features(const navsim_config* c, const navsim_state* st, int
                                                                                   ws.cv2t, w->cv2_b, ws.feat);
         return NAVSIM_OK;
     });
+}
+
+// navsim_ped_observe: one kernel per (field type, cfg.march_rule) -- nine forms.  NAVSIM_MARCH_F64 keeps its float64 form here
+// (kernels_field.hpp's float32-only evaluation would be a tenth and an eleventh form for a kernel that marches a few rays).
+template <typename F>
+int launch_ped_observe(const navsim_config* c, const navsim_state* st, const PedObserveArgs& a, hipStream_t s) {
+    const int grid = (c->n_envs + kObserveWaves - 1) / kObserveWaves, block = 64 * kObserveWaves;
+    switch (c->march_rule) {
+        case NAVSIM_MARCH_F64:     ped_observe_kernel<F, NAVSIM_MARCH_F64><<<grid, block, 0, s>>>(*c, *st, a); break;
+        case NAVSIM_MARCH_F32:     ped_observe_kernel<F, NAVSIM_MARCH_F32><<<grid, block, 0, s>>>(*c, *st, a); break;
+        case NAVSIM_MARCH_F32_FMA: ped_observe_kernel<F, NAVSIM_MARCH_F32_FMA><<<grid, block, 0, s>>>(*c, *st, a); break;
+        default: return NAVSIM_E_ARG;
+    }
+    return launch_status();
 }
 
 }  // namespace
@@ -1404,6 +1420,28 @@ int navsim_episode_stats_clear(const navsim_config* c, const navsim_episode_stat
     if (c->n_envs == 0) return NAVSIM_OK;
     episode_stats_clear_kernel<<<(c->n_envs + 255) / 256, 256, 0, (hipStream_t)stream>>>(c->n_envs, *s, mask);
     return launch_status();
+}
+
+int navsim_ped_observe(const navsim_config* c, const navsim_state* st, const navsim_ped_observe_params* p, const uint8_t* skip,
+                       const navsim_ped_observation* out, void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !p || !out || !out->state || !out->index || !out->count) return NAVSIM_E_ARG;
+    if (!st->robot_pose || !st->n_peds || !st->ped_pose || !st->ped_vel || !st->field) return NAVSIM_E_ARG;
+    if (c->ped_model == NAVSIM_PED_NONE) return NAVSIM_E_ARG;
+    if (p->max_obs < 1 || p->max_obs > NAVSIM_MAX_PEDS || (p->rays != 1 && p->rays != 3)) return NAVSIM_E_ARG;
+    if (!(p->ped_radius >= 0.0) || !(p->sensor_range >= 0.0) || std::isinf(p->ped_radius) || std::isinf(p->sensor_range)) return NAVSIM_E_ARG;
+    if (c->n_envs < 0 || c->max_peds < 1 || c->max_peds > NAVSIM_MAX_PEDS || c->map_h < 1 || c->map_w < 1) return NAVSIM_E_ARG;
+    if (c->march_rule < NAVSIM_MARCH_F64 || c->march_rule > NAVSIM_MARCH_F32_FMA) return NAVSIM_E_ARG;
+    if (st->map_slot && c->shared_field) return NAVSIM_E_ARG;
+    if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    PedObserveArgs a = {};
+    a.p = *p; a.out = *out; a.skip = skip;
+    a.max_range = (float)((long long)c->map_h * c->map_w);
+    hipStream_t s = (hipStream_t)stream;
+    if (c->field_format == NAVSIM_FIELD_F32) return launch_ped_observe<FieldF32>(c, st, a, s);
+    if (st->field_overflow) return launch_ped_observe<FieldU16T>(c, st, a, s);
+    return launch_ped_observe<FieldU16TN>(c, st, a, s);
 }
 
 const char* navsim_step_kernel_name(void) { return "navsim_step_kernel"; }

@@ -195,6 +195,19 @@ class NavsimPedOrcaParams(C.Structure):
                 ("safety_space", C.c_double), ("robot_visible", C.c_int32)]
 
 
+# navsim_ped_observe: the rule's parameters, and the four output arrays (dtype, trailing shape behind E; K = max_obs, N = max_peds)
+class NavsimPedObserveParams(C.Structure):
+    _fields_ = [("ped_radius", C.c_double), ("sensor_range", C.c_double), ("max_obs", C.c_int32), ("rays", C.c_int32),
+                ("occlusion", C.c_int32), ("fov", C.c_int32)]
+
+
+PED_OBSERVATION = {"state": ("float32", ("K", 5)), "index": ("int32", ("K",)), "count": ("int32", ()), "visible": ("uint8", ("N",))}
+
+
+class NavsimPedObservation(C.Structure):
+    _fields_ = [(name, _P) for name in PED_OBSERVATION]
+
+
 ORCA_MAX_AGENTS = 64
 ORCA_MAX_EDGES = 128
 CROWD_MAX_VERTS = 8
@@ -399,6 +412,8 @@ def declare(lib, suffix=""):
     if not suffix and hasattr(lib, "navsim_episode_stats_update"):      # (as above: an older library of an A/B run loads without)
         sig("navsim_episode_stats_update", [cfgp, stp, iop, C.POINTER(NavsimEpisodeStats), _P])
         sig("navsim_episode_stats_clear", [cfgp, C.POINTER(NavsimEpisodeStats), _P, _P])
+    if not suffix and hasattr(lib, "navsim_ped_observe"):               # (likewise; the oracle has no twin of it)
+        sig("navsim_ped_observe", [cfgp, stp, C.POINTER(NavsimPedObserveParams), _P, C.POINTER(NavsimPedObservation), _P])
     sig("navsim_reset_obs", [cfgp, stp, iop, _P] + stream)
     sig("navsim_restart", [cfgp, stp, _P] + stream)
     return lib
@@ -416,7 +431,7 @@ EXPORTS = (
     "navsim_costmap", "navsim_plan", "navsim_launch_order", "navsim_replan_workspace_bytes", "navsim_replan", "navsim_ped_policy_workspace_bytes", "navsim_ped_policy", "navsim_ped_scan_policy",
     "navsim_crowd_check", "navsim_crowd_angular_map", "navsim_crowd_local_map", "navsim_crowd_orca", "navsim_crowd_agent_step", "navsim_ped_orca", "navsim_ped_orca_walls",
     "navsim_step", "navsim_step_sorted", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
-    "navsim_episode_stats_update", "navsim_episode_stats_clear",
+    "navsim_episode_stats_update", "navsim_episode_stats_clear", "navsim_ped_observe",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

@@ -80,6 +80,19 @@ and default to the reference's behaviour for num_envs == 1:
                     finished arenas (reset(mask=done)) before their next step: an arena stepped on past its `done` may keep the
                     flag, and every such step would count as an episode of one step.  env.episode_totals() reads the running totals
                     -- the only device -> host copy, and only when called.  False (default): nothing is launched.
+    observe_humans  K (1 .. the world's pedestrian cap): the K nearest pedestrians the robot has in line of sight, one launch behind
+                    the step (navsim_ped_observe; the list SARL / CADRL-style policies take) -- info['humans'] = {'state' [E,K,5]
+                    x, y, vx, vy in the robot's frame and the distance d, nearest first; 'index' [E,K] the pedestrian of the row,
+                    -1 = unused row; 'count' [E] pedestrians seen, which may exceed K; 'visible' [E,N] bool}.  A pedestrian is
+                    seen when it is within sensor_range, inside the lidar's field of view and one of `rays` lines of sight (its
+                    centre, its two silhouette points) crosses no wall of the arena's map; other pedestrians do not occlude.
+                    observe_params overrides ped_radius, sensor_range, rays (1 | 3), occlusion, fov.  The rows describe the state
+                    the returned observation row describes: after a same-step restart the new episode's first state
+                    (info['final_observation'] carries no humans: a terminal copy is a follow-up); under next-step auto-reset
+                    an arena whose `done` is set has restarted already, and its rows are empty (count 0, index -1) until the
+                    step that resets it.  env.observed_humans() returns the same dict, also after reset() / reset(mask).
+                    num_envs > 1: torch views with the lifetime below; num_envs == 1: NumPy arrays without the leading axis,
+                    from one device -> host copy.  Needs a pedestrian model; None (default): nothing is allocated or launched.
     reset(mask)     reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
                     [num_envs]; the others keep their state and their rows.  On the pipelined reset path the masked arenas install
                     their staged worlds in one launch: the same state and rows as with pregen_pipeline=0.
@@ -217,7 +230,7 @@ class NavGymEnv(_EnvBase):
                  action_kind="twist", clip_actions=False, max_waypoints=64, march_rule=None, use_graphs=None,
                  regen_min_steps=0, pregen_pipeline=None, pregen_stage_cap=None, autoreset_mode="same_step",
                  final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None,
-                 episode_stats=False):
+                 episode_stats=False, observe_humans=None, observe_params=None):
         # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
         self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
         from . import lib
@@ -394,6 +407,25 @@ class NavGymEnv(_EnvBase):
             cfg.n_beams = spec["n_angles"]
             cfg.angle_min = spec["angle_min"]
             cfg.angle_last = spec["angle_max"] - spec["angle_increment"]
+        # observed pedestrians (navsim_ped_observe): K rows per arena, one launch behind the step
+        if observe_params is not None and observe_humans is None:
+            raise ValueError("observe_params needs observe_humans=K")
+        for k in (observe_params or {}):
+            if k not in _simmod.PED_OBSERVE_KEYS or k == "max_obs":
+                raise ValueError("unknown key %r in observe_params (known: %s; max_obs is observe_humans)"
+                                 % (k, ", ".join(x for x in _simmod.PED_OBSERVE_KEYS if x != "max_obs")))
+        if observe_humans is not None:
+            if not (isinstance(observe_humans, numbers.Integral) and not isinstance(observe_humans, bool) and
+                    1 <= observe_humans <= cfg.max_peds):
+                raise ValueError("observe_humans must be None or an int in 1 .. %d (the world's pedestrian cap), not %r"
+                                 % (cfg.max_peds, observe_humans))
+            if cfg.ped_model == abi.PED_NONE:
+                raise ValueError("observe_humans needs pedestrians: pedestrian_model=%r with at most %d of them has none"
+                                 % (pedestrian_model, nh_hi))
+        self.observe_humans = None if observe_humans is None else int(observe_humans)
+        self.observe_params = None if observe_params is None else dict(observe_params)
+        self._humans_np = None                              # num_envs == 1: the latest rows as NumPy arrays
+        self._human_views = {}                              # per buffer parity: the views info['humans'] hands out
         self.cfg = cfg
         self.sim = None
         self._choose_reset_path(pregen_pipeline, plain_cap=cfg.regen_cap)      # (without the pipeline: the library's default cap)
@@ -509,6 +541,8 @@ class NavGymEnv(_EnvBase):
                 self.sim.t["policy_prev_actions"].mul_((m.to(self.sim.device) == 0).to(self.sim.t["policy_prev_actions"].dtype)[:, None, None])
             self._map_info = None
             self._humans_of_episode = None
+            if self.observe_humans:
+                self._observe()
             return self._obs_dict()
         self._bool = torch.bool
         from . import sim as simmod
@@ -535,6 +569,8 @@ class NavGymEnv(_EnvBase):
                 self.sim.set_policy(w)
             if self.episode_stats:
                 self.sim.enable_episode_stats()
+            if self.observe_humans:
+                self.sim.enable_ped_observe(dict(self.observe_params or {}, max_obs=self.observe_humans))
         elif "policy_prev_actions" in self.sim.t:
             self.sim.t["policy_prev_actions"].zero_()           # env.py:739
         self._episode_batch += 1
@@ -565,6 +601,8 @@ class NavGymEnv(_EnvBase):
             self._choose_step_path()
         self._map_info = None                             # read back from the device when somebody asks (map_info)
         self._humans_of_episode = None
+        if self.observe_humans:
+            self._observe()
         return self._obs_dict()
 
     @property
@@ -652,6 +690,8 @@ class NavGymEnv(_EnvBase):
                 self.sim.replan(self.replan_cap)           # ('policy', 'orca': the launch in front of the next step reads the routes)
         if self.episode_stats:                             # one launch, behind whatever the step's path queued
             ep = self.sim.episode_stats()
+        if self.observe_humans:                            # likewise: the state the returned rows describe
+            humans = self._observe()
         obs = self._obs_dict()
         # the LAST observation of an episode that ended in this step (env.py:700-728 returns it with done = True): under
         # same-step auto-reset the row above already is the next episode's first one and the terminal one rides in info;
@@ -672,6 +712,8 @@ class NavGymEnv(_EnvBase):
                 info["TimeLimit.truncated"] = bool(out["truncated"][0].item())
             if self.episode_stats and done:
                 info["episode"] = {name: ep[k][0].item() for name, k in self._EPISODE_KEYS}
+            if self.observe_humans:
+                info["humans"] = humans
             return obs, float(out["reward"][0].item()), done, info
         # (views of the buffers the kernel wrote, made ONCE per buffer parity: a step of 4096 arenas is 95 us on the device, and
         #  every tensor slice or .view() costs the host 3-5 us -- round 6 measured 42 -> 36 M env-steps/s through this method
@@ -701,7 +743,36 @@ class NavGymEnv(_EnvBase):
         if "episode" in v:
             info["episode"] = v["episode"]
             info["_episode"] = done
+        if self.observe_humans:
+            info["humans"] = humans
         return obs, out["reward"], done, info
+
+    def _observe(self):
+        """navsim_ped_observe behind whatever was queued: the observed pedestrians of the state the current observation rows
+        describe.  Next-step auto-reset: an arena whose `done` is set has its state restarted already while its row is the
+        terminal one -- it is skipped (empty rows) until the call that resets it.  The views are made once per buffer parity."""
+        next_step = self.auto_reset and self.autoreset_mode == "next_step"
+        out = self.sim.ped_observe(skip=self.sim.out["done"] if next_step else None)
+        if self.num_envs == 1:
+            h = self.sim.ped_observation_host()
+            self._humans_np = {"state": h["state"][0], "index": h["index"][0], "count": int(h["count"][0]),
+                               "visible": h["visible"][0].astype(bool)}
+            return self._humans_np
+        v = self._human_views.get(self.sim.cur)
+        if v is None:
+            v = self._human_views[self.sim.cur] = {"state": out["state"], "index": out["index"], "count": out["count"],
+                                                   "visible": out["visible"].view(self._bool)}
+        return v
+
+    def observed_humans(self):
+        """What info['humans'] of the latest step() holds (observe_humans=K); valid after reset() and reset(mask) too: {'state'
+        [E,K,5] x, y, vx, vy in the robot's frame and the distance, nearest first; 'index' [E,K] the pedestrian of the row, -1 =
+        unused; 'count' [E] pedestrians seen, which may exceed K; 'visible' [E,N] bool}."""
+        if not self.observe_humans:
+            raise RuntimeError("observed_humans() needs NavGymEnv(observe_humans=K)")
+        if self.sim is None or self.sim.ped_obs_buf is None:
+            raise RuntimeError("call reset() before observed_humans()")
+        return self._humans_np if self.num_envs == 1 else self._human_views[self.sim.cur]
 
     # info['episode']: gymnasium's names for return and length, the build's own for the rest -> NavSim.episode_stats()'s rows
     _EPISODE_KEYS = (("r", "ep_return"), ("l", "ep_length"), ("path_length", "ep_path_length"),
@@ -908,6 +979,8 @@ class NavGymEnv(_EnvBase):
         self._episode_batch = int(sd["episode_batch"])
         self._map_info = None
         self._humans_of_episode = None
+        if self.observe_humans:                            # (no part of the snapshot: a function of the state just loaded)
+            self._observe()
         torch.cuda.synchronize(self.sim.device)
         self._obs_dict()
 

@@ -291,6 +291,44 @@ def ped_orca_params(cfg, params=None, robot_type="keti"):
     return p
 
 
+PED_OBSERVE_KEYS = ("ped_radius", "sensor_range", "max_obs", "rays", "occlusion", "fov")
+
+
+def ped_observe_defaults(cfg, robot_type="keti"):
+    """The parameters of navsim_ped_observe as a dict: the pedestrian disc ped_orca_defaults uses, the lidar's range and field
+    of view, three lines of sight per pedestrian, a row for every pedestrian the arena can hold."""
+    return dict(ped_radius=ped_orca_defaults(cfg, robot_type)["ped_radius"], sensor_range=cfg.range_max, max_obs=cfg.max_peds,
+                rays=3, occlusion=1, fov=1)
+
+
+def ped_observe_params(cfg, params=None, robot_type="keti"):
+    """abi.NavsimPedObserveParams of ped_observe_defaults(cfg) overridden by the dict `params`; an unknown key raises ValueError."""
+    d = ped_observe_defaults(cfg, robot_type)
+    for k, v in (params or {}).items():
+        if k not in d:
+            raise ValueError("unknown observation parameter %r (known: %s)" % (k, ", ".join(PED_OBSERVE_KEYS)))
+        d[k] = v
+    p = abi.NavsimPedObserveParams()
+    p.ped_radius, p.sensor_range = float(d["ped_radius"]), float(d["sensor_range"])
+    p.max_obs, p.rays = int(d["max_obs"]), int(d["rays"])
+    p.occlusion, p.fov = int(bool(d["occlusion"])), int(bool(d["fov"]))
+    return p
+
+
+def ped_observation_layout(E, K, N):
+    """Where navsim_ped_observation's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in
+    abi.PED_OBSERVATION's order, each start rounded up to 16 bytes, and a last entry whose end byte is the blob's size."""
+    sym = {"K": K, "N": N}
+    out, at = [], 0
+    for k, (d, shape) in abi.PED_OBSERVATION.items():
+        full = (E,) + tuple(sym[s] if isinstance(s, str) else s for s in shape)
+        n = int(np.prod(full)) * np.dtype(d).itemsize
+        out.append((k, d, at, at + n, full))
+        at = (at + n + 15) // 16 * 16
+    out.append((None, None, at, max(at, 16), None))
+    return out
+
+
 def crowd_orca(params, agents, pref_vel, verts=None, n_agents=None, n_obst=None, obst_set=None, theta=None):
     """navsim_crowd_orca: ORCA.predict (orca.py:85-135) for Q pedestrians: agents [Q,A,6] (agent 0 = the pedestrian),
     pref_vel [Q,2], verts [S,O,V,2] CCW polygons -> (new velocity [Q,2], ActionRot (v, r) [Q,2]), float64 tensors."""
@@ -454,6 +492,9 @@ class NavSim(object):
         # episode statistics (enable_episode_stats): the accumulators, the totals, the two sets of published rows (they flip with
         # self.cur like out_buf) and, per parity, the arguments of navsim_episode_stats_update
         self.ep_acc, self.ep_totals, self.ep_buf, self._ep_args = None, None, None, {}
+        # observed pedestrians (enable_ped_observe): the parameters, two sets of outputs (they flip with self.cur as well) and, per
+        # parity, the arguments of navsim_ped_observe
+        self.obs_params, self.ped_obs_buf, self._ped_obs_args = None, None, {}
         self.t = {}
         self.st = abi.NavsimState()
         for name, (dtype, shape) in abi.STATE_LAYOUT.items():
@@ -1351,6 +1392,50 @@ class NavSim(object):
         if reset:
             self.ep_totals.zero_()
         return {k: int(v[i]) for i, k in enumerate(abi.EPISODE_TOTALS)}
+
+    # ---- observed pedestrians: the K nearest pedestrians in the robot's line of sight, in its frame, from one launch behind the
+    # step (include/navsim.h navsim_ped_observe)
+    def enable_ped_observe(self, params=None):
+        """Allocates two sets of outputs (state [E,K,5], index [E,K], count [E], visible [E,N]: they flip with self.cur, so what
+        ped_observe() returned stays intact through the next step like everything else a step returns).  params: an
+        abi.NavsimPedObserveParams, a dict of overrides of ped_observe_defaults(cfg), or None."""
+        import torch
+        if self.cfg.ped_model == abi.PED_NONE:
+            raise ValueError("observed pedestrians need a pedestrian model")
+        p = params if isinstance(params, abi.NavsimPedObserveParams) else ped_observe_params(self.cfg, params)
+        if not 1 <= p.max_obs <= abi.MAX_PEDS:
+            raise ValueError("max_obs must lie in 1..%d, not %d" % (abi.MAX_PEDS, p.max_obs))
+        self.obs_params = p
+        # one allocation per set, the four arrays carved out of it in abi.PED_OBSERVATION's order (4-byte types first): a caller
+        # that wants them on the host copies the blob once (ped_observation_host)
+        self._ped_obs_layout = ped_observation_layout(self.cfg.n_envs, p.max_obs, self.cfg.max_peds)
+        total = self._ped_obs_layout[-1][3]
+        self.ped_obs_blob = [torch.zeros(total, dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self.ped_obs_buf = [{k: blob[lo:hi].view(_dtype(d)).view(shape) for k, d, lo, hi, shape in self._ped_obs_layout[:-1]}
+                            for blob in self.ped_obs_blob]
+        self._ped_obs_args = {}
+
+    def ped_observation_host(self):
+        """The current set of ped_observe()'s outputs as NumPy arrays, from ONE device -> host copy."""
+        blob = self.ped_obs_blob[self.cur].cpu().numpy()
+        return {k: blob[lo:hi].view(d).reshape(shape) for k, d, lo, hi, shape in self._ped_obs_layout[:-1]}
+
+    def ped_observe(self, skip=None):
+        """navsim_ped_observe of the current state on the current stream: one launch.  skip: uint8 / bool [E], arenas whose rows
+        come back empty (None: none).  Returns the current set {'state', 'index', 'count', 'visible'}, intact through the next
+        step."""
+        if self.ped_obs_buf is None:
+            raise RuntimeError("call enable_ped_observe() first")
+        a = self._ped_obs_args.get(self.cur)
+        if a is None:                                     # (built once per parity: every buffer behind it is allocated once)
+            out = abi.NavsimPedObservation()
+            for k, v in self.ped_obs_buf[self.cur].items():
+                setattr(out, k, v.data_ptr())
+            a = self._ped_obs_args[self.cur] = (out, C.byref(out), C.byref(self.obs_params), C.byref(self.cfg), C.byref(self.st))
+        rc = self.lib.navsim_ped_observe(a[3], a[4], a[2], _ptr(skip), a[1], _stream())
+        if rc:
+            check(rc, "navsim_ped_observe")
+        return self.ped_obs_buf[self.cur]
 
     def occupancy(self, e=0):
         """uint8 [H, W] occupancy grid (1 = occupied) of arena e, read back from its distance field
