@@ -70,3 +70,15 @@ for _ in range(100):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 print("reference defaults, %d arenas: %.2f M env-steps/s (pregen_pipeline=%d); %s" % (E, E * 100 / dt / 1e6, renv.pregen_pipeline, renv.counters()))
+
+# ---- the path to the goal on that world: its corridors make the straight line point through walls ---------------------------
+# goal_path=True keeps a distance-to-goal field per arena on the device (rebuilt whenever an arena gets a new goal or map) and
+# returns, two launches behind the step, the PATH distance and a sub-goal 2 m down the path in the robot's frame.
+genv = nav_gym_env.make("NavGym-v0", num_envs=64, map_size="reference", randomize_maps=True, goal_path=True)
+genv.reset()
+obs, reward, done, info = genv.step(actions[:64].contiguous())
+g = info["goal_path"]
+for e in range(4):
+    print("arena %d: straight line %.2f m, path %.2f m, sub-goal (%.2f, %.2f) m in the robot's frame, status %d"
+          % (e, float(info["distance"][e]), float(g["distance"][e]), float(g["subgoal"][e, 0]), float(g["subgoal"][e, 1]), int(g["status"][e])))
+print("fields rebuilt so far: %d" % genv.sim.goal_path_rebuilds())

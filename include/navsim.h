@@ -1102,6 +1102,97 @@ typedef struct navsim_ped_observation {
 int navsim_ped_observe(const navsim_config* cfg, const navsim_state* st, const navsim_ped_observe_params* p,
                        const uint8_t* skip, const navsim_ped_observation* out, void* stream);
 
+/* ---- goal path: a distance-to-goal field per arena, and from it the robot's path distance and a steering sub-goal ---------------
+ * What a policy, a reward shaper, a curriculum or an evaluation ("success weighted by path length") reads where the straight line
+ * to the goal (info['distance']) points through walls.  BUILD-DEFINED, all of it: the reference plans the spawn path on its
+ * costmap and throws it away (env.py:366-383); it has no field and no sub-goal.  Everything below is integer arithmetic or
+ * float64 with every operation rounded on its own (no fused multiply-add: DESIGN.md section 4).
+ *
+ * THE NAVIGATION GRID of an arena.  Hc = map_h / 5, Wc = map_w / 5 (integer division): the costmap's cells.  Nav cell (ic, jc),
+ * 0 <= ic < Wc along x (the field's column), 0 <= jc < Hc along y (the field's row), is SAMPLED at map cell (5 ic + 2, 5 jc + 2):
+ * d = the float32 distance, in cells, that the field of the arena's map slot holds there (cfg.shared_field, st->map_slot,
+ * st->field_overflow; identical in NAVSIM_FIELD_F32 and NAVSIM_FIELD_U16T, the overflow plane included).  With
+ * hard = (float)(hard_clearance / resolution) and clear = (float)(clearance / resolution), float32 comparisons:
+ *   d < hard: IMPASSABLE;   hard <= d < clear: in the BAND, multiplier m = band_cost;   otherwise CLEAR, m = 1.
+ * Cells outside the grid are impassable.  hard_clearance >= 3 resolution is required: the sample lies at most 2.83 cells from every
+ * cell of its 5 x 5 block, so every nav cell whose block holds an occupied cell is impassable -- a wall one cell thick does not leak.
+ * The nav cell OF A POSITION (x, y): (i, j) = xy_to_ij_f32((float)x, (float)y), the scan's origin cell (env.py:386, 419);
+ * (ic, jc) = (min(i / 5, Wc - 1), min(j / 5, Hc - 1)).
+ *
+ * THE FIELD.  dist [Hc, Wc] uint16 per arena (element jc Wc + ic), in map cells: a straight hop weighs 5, a diagonal hop 7;
+ * 0xFFFF = impassable, unreachable, or farther than 65534.  The GOAL CELL is the nav cell of st->robot_goal[e]; it has
+ * dist = 0 whatever its class.  A neighbour n of a cell is ADMISSIBLE when it lies in the grid and is passable (not impassable)
+ * or the goal cell, and -- for a diagonal hop -- the two cells orthogonally adjacent to both are passable or the goal cell as
+ * well (no corner is cut).  Every other passable cell c holds
+ *     dist[c] = min(0xFFFF, min over admissible neighbours n of dist[n] + w(direction) m(c)),
+ * an impassable cell that is not the goal cell holds 0xFFFF.  With positive weights these equations have exactly one solution, the
+ * cost of the cheapest path saturated at 0xFFFF, so the field does not depend on the order in which cells are relaxed.
+ *
+ * NEIGHBOUR ORDER k = 0 .. 7, (d ic, d jc): (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (+1,-1) (-1,+1) (-1,-1); w = 5 for k < 4, else 7. */
+typedef struct navsim_goal_path_params {
+    double  hard_clearance;   /* metres, finite, >= 3 cfg.resolution */
+    double  clearance;        /* metres, finite, >= hard_clearance */
+    double  lookahead;        /* metres, finite, >= 0: how far down the field the sub-goal lies */
+    int32_t band_cost;        /* 1 .. 16: the multiplier of a hop that leaves a band cell */
+} navsim_goal_path_params;
+
+typedef struct navsim_goal_field {
+    uint16_t* dist;                  /* [E,Hc,Wc] */
+    int64_t*  key;                   /* [E,3] (episode, bits of gx, bits of gy) the arena's field was built for; the caller
+                                        initialises key[e,0] = -1: never built */
+    unsigned long long* rebuilds;    /* [1] fields rebuilt so far (atomic adds); may be NULL */
+} navsim_goal_field;
+
+typedef struct navsim_goal_path_out {
+    float*   distance;   /* [E]   metres */
+    float*   subgoal;    /* [E,2] the target in the robot's frame, metres */
+    uint8_t* status;     /* [E]   0 = skipped, else NAVSIM_GOAL_PATH_* */
+} navsim_goal_path_out;
+
+#define NAVSIM_GOAL_PATH_OK                 1   /* the robot stands on the field; distance is a path length */
+#define NAVSIM_GOAL_PATH_REACHED_GOAL_CELL  2   /* or'ed to OK: the walk ended on the goal cell, the sub-goal IS the goal */
+#define NAVSIM_GOAL_PATH_OFF_FIELD          4   /* the robot's nav cell holds 0xFFFF: straight-line values */
+
+/* Bytes of navsim_goal_field.dist: n_envs (map_h / 5) (map_w / 5) uint16.  0: cfg NULL, n_envs < 0, map_h / 5 < 1 or map_w / 5 < 1. */
+size_t navsim_goal_field_bytes(const navsim_config* cfg);
+
+/* TWO launches, whatever the number of arenas that rebuild (kernels_goal_path.hpp): the first tests every arena's key and
+ * rebuilds the stale fields, one 1024-thread workgroup per field with the grid in LDS; the second answers the query of every
+ * arena, eight lanes an arena, without LDS.  No device-to-host copy, nothing that blocks; every loop in both kernels has a
+ * stated bound.  Call it behind the step (and whatever follows it: navsim_regen, navsim_replan) on the same stream.  It reads
+ * st->robot_pose, robot_goal, episode and the distance field, and writes EVERY element of `out`.  Per arena e:
+ *  1. skip && skip[e]: distance = 0, subgoal = (0, 0), status = 0.  Nothing of the arena is rebuilt or read; its key stays.
+ *  2. rebuild: iff (rebuild && rebuild[e]) or key[e] != (st->episode[e], the 64 bits of gx, the 64 bits of gy) the arena's
+ *     field is rebuilt as above from its map and (gx, gy) = robot_goal[e]; key[e] is recorded and *rebuilds += 1.
+ *     Every in-launch restart advances episode[e] (the step's restart from the spawn table, navsim_step_install*, navsim_regen
+ *     behind the step -- it serves arenas the step restarted --, navsim_regen_swap, navsim_reset_install, navsim_restart), so the
+ *     key follows them; a caller that changes a map or a goal WITHOUT a new episode number (a reset of every arena that starts
+ *     the numbers again, a state loaded from a snapshot) passes rebuild for those arenas.
+ *  3. (rx, ry, th) = robot_pose[e]; the robot's nav cell r as above.  dist[r] == 0xFFFF: status = OFF_FIELD, target = the goal
+ *     (gx, gy), rem = 0; continue at 6.
+ *  4. the walk: cur = r, walked = 0, L = lookahead_cells = (int)min(floor(lookahead / resolution), 1048576.0).  At most
+ *     min(L / 5, Hc Wc) times: stop if cur is the goal cell; among the admissible neighbours n_k of cur take the one with the
+ *     least (dist[n_k] + w_k, k) -- ties go to the lower k of the neighbour order; stop if there is none (which a field built by
+ *     step 2 never shows) or if walked + w_k > L; else cur = n_k, walked += w_k.  On a field of step 2 dist falls at every hop
+ *     (dist[n_k] <= dist[cur] - 5 m(cur) + 2), so the walk needs no more than L / 5 hops and never returns to a cell.
+ *  5. the target: cur is the goal cell: (gx, gy) itself, rem = 0, status = OK | REACHED_GOAL_CELL.  Otherwise the centre of cur,
+ *     (origin_x + ((double)(5 ic) + 2.5) * resolution, origin_y + ((double)(5 jc) + 2.5) * resolution), rem = dist[cur], status = OK.
+ *  6. dx = tx - rx, dy = ty - ry; distance = (float)(sqrt(dx*dx + dy*dy) + (double)rem * resolution);
+ *     c = nv::cos(th), s = nv::sin(th); subgoal = ((float)(c*dx + s*dy), (float)(c*dy - s*dx)).
+ *  7. consequence: distance is the length in metres (5 / 7 chamfer metric: between 1 % below and 8 % above the Euclidean length
+ *     between two cells) of the cheapest path where that path keeps `clearance` from the walls; it OVERSTATES it by (band_cost - 1) times
+ *     the part that runs inside the band; it equals the straight-line distance, bit for bit what step 3 would give, once the goal
+ *     cell lies within the look-ahead.
+ * NAVSIM_E_ARG, before anything touches the device: cfg, st, p, field or out NULL; field->dist or key, out->distance, subgoal or
+ * status NULL (rebuilds may be NULL); st->robot_pose, robot_goal, episode or field NULL; a parameter that is not finite;
+ * hard_clearance < 3 resolution; clearance < hard_clearance; band_cost outside 1 .. 16; lookahead < 0; n_envs < 0; map_h / 5 < 1
+ * or map_w / 5 < 1; st->map_slot with cfg.shared_field.  NAVSIM_E_UNSUPPORTED: a field_format that is neither NAVSIM_FIELD_F32
+ * nor NAVSIM_FIELD_U16T; a grid whose 3 (Hc + 2) (Wc + 2) bytes do not fit the LDS of one workgroup (160 KB less 8 KB: 200 x 200
+ * nav cells, the reference's 1000 x 1000 maps, take 122.4 KB).  n_envs == 0: NAVSIM_OK, nothing is launched. */
+int navsim_goal_path(const navsim_config* cfg, const navsim_state* st, const navsim_goal_path_params* p,
+                     const uint8_t* rebuild, const uint8_t* skip, const navsim_goal_field* field,
+                     const navsim_goal_path_out* out, void* stream);
+
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);
 
@@ -1118,6 +1209,11 @@ int navsim_debug_math(int32_t fn, const double* x, const double* x2, double* out
 /* batch_xy_to_ij (env.py:1228-1253) exactly as the scan evaluates it: xy [n,2] float64 in, ij [n,2] int32 out;
  * as_f32 = 1 rounds the inputs to float32 first and divides in float32 (the lidar origin, env.py:386, 419). */
 int navsim_debug_xy_to_ij(const navsim_config* cfg, const double* xy, int32_t as_f32, int32_t* ij, int32_t n, void* stream);
+/* navsim_goal_path's rebuilds, from now on and on this thread, record the relaxation sweeps each took: sweeps [E] device int32,
+ * entry e written when arena e's field is rebuilt; NULL (the default) turns the record off.  The library keeps the POINTER: the
+ * array must stay allocated (and hold the cfg.n_envs of every later call) until the hook is set to NULL again -- set it to NULL
+ * before freeing the array.  Always NAVSIM_OK. */
+int navsim_debug_goal_path_sweeps(int32_t* sweeps);
 
 /* The spawn loops' acceptance rules (env.py:366-383, 748-762, 786-793) on SUPPLIED candidates -- the very device
  * functions navsim_regen's samplers call -- so that tests can compare them with the decisions the reference's own

@@ -169,16 +169,20 @@ __device__ __forceinline__ void xy_to_ij(double x, double y, const navsim_config
     i = (int)fi;
     j = (int)fj;
 }
-// same with float32 inputs (the scan origin, env.py:419): float32 arithmetic (NumPy >= 2 scalars)
-__device__ __forceinline__ void xy_to_ij_f32(float x, float y, const navsim_config& c, int& i, int& j) {
-    float fi = (x - (float)c.origin_x) / (float)c.resolution;
-    float fj = (y - (float)c.origin_y) / (float)c.resolution;
-    if (fi >= (float)c.map_h) fi = (float)(c.map_h - 1);
-    if (fj >= (float)c.map_w) fj = (float)(c.map_w - 1);
+// same with float32 inputs (the scan origin, env.py:419): float32 arithmetic (NumPy >= 2 scalars).  On its operands -- ox, oy,
+// res = (float)cfg.origin_x, (float)cfg.origin_y, (float)cfg.resolution -- for a kernel that does not carry a navsim_config
+__device__ __forceinline__ void xy_to_ij_f32(float x, float y, float ox, float oy, float res, int map_h, int map_w, int& i, int& j) {
+    float fi = (x - ox) / res;
+    float fj = (y - oy) / res;
+    if (fi >= (float)map_h) fi = (float)(map_h - 1);
+    if (fj >= (float)map_w) fj = (float)(map_w - 1);
     if (fi < 0.0f) fi = 0.0f;
     if (fj < 0.0f) fj = 0.0f;
     i = (int)fi;
     j = (int)fj;
+}
+__device__ __forceinline__ void xy_to_ij_f32(float x, float y, const navsim_config& c, int& i, int& j) {
+    xy_to_ij_f32(x, y, (float)c.origin_x, (float)c.origin_y, (float)c.resolution, c.map_h, c.map_w, i, j);
 }
 
 // _update_dist_travelled (env.py:237-255) for one pedestrian

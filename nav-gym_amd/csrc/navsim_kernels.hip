@@ -21,6 +21,7 @@
 //   kernels_crowd_maps.hpp  CrowdSim local maps;  kernels_crowd_orca.hpp  CrowdSim pedestrians (ORCA, Agent.step)
 //   kernels_ped_orca.hpp  NavGym pedestrians driven by ORCA from the simulator's state (navsim_ped_orca)
 //   kernels_episode.hpp  episode statistics behind the step;  kernels_ped_observe.hpp  the K nearest pedestrians in line of sight
+//   kernels_goal_path.hpp  distance-to-goal field per arena, the robot's path distance and steering sub-goal (navsim_goal_path)
 //   step_plan.hpp        launch geometry of the fused step, the descriptors of a launch and the march-rule dispatch (shared by this
 //                        file and navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
 // Host code of this file, ahead of the C ABI: dispatch_step and the argument checks; the workspaces (Carver and one layout
@@ -45,6 +46,7 @@ namespace {
 #include "kernels_ped_orca.hpp"
 #include "kernels_episode.hpp"
 #include "kernels_ped_observe.hpp"
+#include "kernels_goal_path.hpp"
 
 }  // namespace
 #include "step_plan.hpp"
@@ -452,6 +454,33 @@ int launch_ped_observe(const navsim_config* c, const navsim_state* st, const Ped
         case NAVSIM_MARCH_F32_FMA: ped_observe_kernel<F, NAVSIM_MARCH_F32_FMA><<<grid, block, 0, s>>>(*c, *st, a); break;
         default: return NAVSIM_E_ARG;
     }
+    return launch_status();
+}
+
+// navsim_goal_path: the grid of one rebuilding workgroup in LDS -- 2 bytes of dist (the array rounded up to 16) + 1 byte of class
+// per cell of the padded grid (kernels_goal_path.hpp)
+size_t goal_lds_bytes(int Hc, int Wc) {
+    const size_t cells = (size_t)(Hc + 2) * (Wc + 2);
+    return ((cells * 2 + 15) & ~(size_t)15) + ((cells + 15) & ~(size_t)15);
+}
+constexpr size_t kGoalLdsMax = kLdsPerCu - 8 * 1024;       // the kernel's static LDS (the list: 4 KB) and headroom
+
+thread_local int32_t* g_goal_sweeps = nullptr;      // navsim_debug_goal_path_sweeps
+
+template <typename F>
+int launch_goal_path(const navsim_config* c, const navsim_state* st, const GoalFieldArgs& f, const GoalPathArgs& a, hipStream_t s) {
+    const size_t lds = goal_lds_bytes(a.Hc, a.Wc);
+    if (allow_lds((const void*)goal_field_kernel<F>, lds) != NAVSIM_OK) return NAVSIM_E_UNSUPPORTED;
+    // workgroups of launch 1: as many as are resident at once (LDS and the 2048 threads of a compute unit), at most one per arena
+    // -- and no fewer than E / 1024: a workgroup tests its arenas' keys one per thread
+    const size_t fit = kLdsPerCu / (lds + 4 * 1024 + 64);
+    long g = (long)device_cu_count() * (fit >= 2 ? 2 : 1);
+    const long least = ((long)c->n_envs + kGoalBlock - 1) / kGoalBlock;
+    g = g < least ? least : g;
+    const int grid = (int)(g < (long)c->n_envs ? g : (long)c->n_envs);
+    goal_field_kernel<F><<<grid, kGoalBlock, lds, s>>>(f);
+    const int per = kGoalWaves * 8;                        // arenas per workgroup of launch 2
+    goal_query_kernel<F><<<(c->n_envs + per - 1) / per, 64 * kGoalWaves, 0, s>>>(*c, *st, a);
     return launch_status();
 }
 
@@ -1442,6 +1471,52 @@ int navsim_ped_observe(const navsim_config* c, const navsim_state* st, const nav
     if (c->field_format == NAVSIM_FIELD_F32) return launch_ped_observe<FieldF32>(c, st, a, s);
     if (st->field_overflow) return launch_ped_observe<FieldU16T>(c, st, a, s);
     return launch_ped_observe<FieldU16TN>(c, st, a, s);
+}
+
+size_t navsim_goal_field_bytes(const navsim_config* c) {
+    if (!c || c->n_envs < 0 || c->map_h / 5 < 1 || c->map_w / 5 < 1) return 0;
+    return (size_t)c->n_envs * (size_t)(c->map_h / 5) * (size_t)(c->map_w / 5) * sizeof(uint16_t);
+}
+
+int navsim_goal_path(const navsim_config* c, const navsim_state* st, const navsim_goal_path_params* p, const uint8_t* rebuild,
+                     const uint8_t* skip, const navsim_goal_field* field, const navsim_goal_path_out* out, void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !p || !field || !out) return NAVSIM_E_ARG;
+    if (!field->dist || !field->key || !out->distance || !out->subgoal || !out->status) return NAVSIM_E_ARG;
+    if (!st->robot_pose || !st->robot_goal || !st->episode || !st->field) return NAVSIM_E_ARG;
+    if (!std::isfinite(p->hard_clearance) || !std::isfinite(p->clearance) || !std::isfinite(p->lookahead)) return NAVSIM_E_ARG;
+    if (!(c->resolution > 0.0) || !std::isfinite(c->resolution)) return NAVSIM_E_ARG;
+    if (p->hard_clearance < 3.0 * c->resolution || p->clearance < p->hard_clearance) return NAVSIM_E_ARG;
+    if (p->band_cost < 1 || p->band_cost > 16 || p->lookahead < 0.0) return NAVSIM_E_ARG;
+    if (c->n_envs < 0 || c->map_h / 5 < 1 || c->map_w / 5 < 1) return NAVSIM_E_ARG;
+    if (st->map_slot && c->shared_field) return NAVSIM_E_ARG;
+    if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
+    GoalPathArgs a = {};
+    a.Hc = c->map_h / 5; a.Wc = c->map_w / 5;
+    if ((long long)a.Hc * a.Wc > (1ll << 26) || goal_lds_bytes(a.Hc, a.Wc) > kGoalLdsMax) return NAVSIM_E_UNSUPPORTED;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    a.field = *field; a.out = *out; a.skip = skip;
+    a.hard = (float)(p->hard_clearance / c->resolution);
+    const double look = floor(p->lookahead / c->resolution);
+    a.lookahead_cells = (int)(look < 1048576.0 ? look : 1048576.0);
+    GoalFieldArgs f = {};
+    f.field = st->field; f.overflow = st->field_overflow; f.map_slot = st->map_slot;
+    f.robot_goal = st->robot_goal; f.episode = st->episode;
+    f.out = *field; f.rebuild = rebuild; f.skip = skip; f.sweeps = g_goal_sweeps;
+    f.ox = (float)c->origin_x; f.oy = (float)c->origin_y; f.res = (float)c->resolution;
+    f.hard = a.hard;
+    f.clear = (float)(p->clearance / c->resolution);
+    f.band_cost = p->band_cost;
+    f.n_envs = c->n_envs; f.map_h = c->map_h; f.map_w = c->map_w; f.shared_field = c->shared_field; f.Hc = a.Hc; f.Wc = a.Wc;
+    hipStream_t s = (hipStream_t)stream;
+    if (c->field_format == NAVSIM_FIELD_F32) return launch_goal_path<FieldF32>(c, st, f, a, s);
+    if (st->field_overflow) return launch_goal_path<FieldU16T>(c, st, f, a, s);
+    return launch_goal_path<FieldU16TN>(c, st, f, a, s);
+}
+
+int navsim_debug_goal_path_sweeps(int32_t* sweeps) {
+    g_goal_sweeps = sweeps;
+    return NAVSIM_OK;
 }
 
 const char* navsim_step_kernel_name(void) { return "navsim_step_kernel"; }

@@ -208,6 +208,25 @@ class NavsimPedObservation(C.Structure):
     _fields_ = [(name, _P) for name in PED_OBSERVATION]
 
 
+# navsim_goal_path: the rule's parameters, the field with its keys, and the three output arrays (dtype, trailing shape behind E)
+class NavsimGoalPathParams(C.Structure):
+    _fields_ = [("hard_clearance", C.c_double), ("clearance", C.c_double), ("lookahead", C.c_double), ("band_cost", C.c_int32)]
+
+
+class NavsimGoalField(C.Structure):
+    _fields_ = [("dist", _P), ("key", _P), ("rebuilds", _P)]
+
+
+GOAL_PATH_OUT = {"distance": ("float32", ()), "subgoal": ("float32", (2,)), "status": ("uint8", ())}
+
+
+class NavsimGoalPathOut(C.Structure):
+    _fields_ = [(name, _P) for name in GOAL_PATH_OUT]
+
+
+GOAL_PATH_OK, GOAL_PATH_REACHED_GOAL_CELL, GOAL_PATH_OFF_FIELD = 1, 2, 4
+GOAL_FIELD_INF = 0xFFFF
+
 ORCA_MAX_AGENTS = 64
 ORCA_MAX_EDGES = 128
 CROWD_MAX_VERTS = 8
@@ -414,6 +433,11 @@ def declare(lib, suffix=""):
         sig("navsim_episode_stats_clear", [cfgp, C.POINTER(NavsimEpisodeStats), _P, _P])
     if not suffix and hasattr(lib, "navsim_ped_observe"):               # (likewise; the oracle has no twin of it)
         sig("navsim_ped_observe", [cfgp, stp, C.POINTER(NavsimPedObserveParams), _P, C.POINTER(NavsimPedObservation), _P])
+    if not suffix and hasattr(lib, "navsim_goal_path"):                 # (likewise)
+        sig("navsim_goal_path", [cfgp, stp, C.POINTER(NavsimGoalPathParams), _P, _P, C.POINTER(NavsimGoalField),
+                                 C.POINTER(NavsimGoalPathOut), _P])
+        sig("navsim_goal_field_bytes", [cfgp], C.c_size_t)
+        sig("navsim_debug_goal_path_sweeps", [_P])
     sig("navsim_reset_obs", [cfgp, stp, iop, _P] + stream)
     sig("navsim_restart", [cfgp, stp, _P] + stream)
     return lib
@@ -432,6 +456,7 @@ EXPORTS = (
     "navsim_crowd_check", "navsim_crowd_angular_map", "navsim_crowd_local_map", "navsim_crowd_orca", "navsim_crowd_agent_step", "navsim_ped_orca", "navsim_ped_orca_walls",
     "navsim_step", "navsim_step_sorted", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
     "navsim_episode_stats_update", "navsim_episode_stats_clear", "navsim_ped_observe",
+    "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

@@ -93,6 +93,20 @@ and default to the reference's behaviour for num_envs == 1:
                     step that resets it.  env.observed_humans() returns the same dict, also after reset() / reset(mask).
                     num_envs > 1: torch views with the lifetime below; num_envs == 1: NumPy arrays without the leading axis,
                     from one device -> host copy.  Needs a pedestrian model; None (default): nothing is allocated or launched.
+    goal_path       True: a distance-to-goal field per arena on the 5 x 5-cell navigation grid (the costmap's cells), rebuilt on the
+                    device whenever the arena gets a new goal or map, and from it the robot's PATH distance and a steering
+                    sub-goal -- two launches behind the step (navsim_goal_path), no copy: info['goal_path'] = {'distance' [E]
+                    metres along the cheapest path that keeps its clearance from the walls (info['distance'] is the straight
+                    line, which points through them); 'subgoal' [E,2] a point `lookahead` metres down that path, in the robot's
+                    frame -- the goal itself once it is that near; 'status' [E] uint8: 1 on the field, 3 = the sub-goal is the
+                    goal, 4 = the robot stands on no passable cell and the values are the straight line's, 0 = skipped}.
+                    goal_path_params overrides hard_clearance (0.3 m), clearance (0.75 m), band_cost (3), lookahead (2.0 m).  The
+                    row describes the state the returned observation row describes: after a SAME-STEP restart that is the NEW
+                    episode (new goal, new field) -- a reward shaper masks its progress term with `done`; under next-step
+                    auto-reset an arena whose `done` is set has restarted already and its row is skipped (all 0) until the step
+                    that resets it.  env.goal_path() returns the same dict, also after reset() / reset(mask); env.goal_field() the
+                    uint16 [E, H/5, W/5] fields on the device.  num_envs > 1: torch views with the lifetime below; num_envs == 1:
+                    NumPy scalars and arrays from one device -> host copy.  False (default): nothing is allocated or launched.
     reset(mask)     reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
                     [num_envs]; the others keep their state and their rows.  On the pipelined reset path the masked arenas install
                     their staged worlds in one launch: the same state and rows as with pregen_pipeline=0.
@@ -230,7 +244,7 @@ class NavGymEnv(_EnvBase):
                  action_kind="twist", clip_actions=False, max_waypoints=64, march_rule=None, use_graphs=None,
                  regen_min_steps=0, pregen_pipeline=None, pregen_stage_cap=None, autoreset_mode="same_step",
                  final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None,
-                 episode_stats=False, observe_humans=None, observe_params=None):
+                 episode_stats=False, observe_humans=None, observe_params=None, goal_path=False, goal_path_params=None):
         # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
         self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
         from . import lib
@@ -426,6 +440,16 @@ class NavGymEnv(_EnvBase):
         self.observe_params = None if observe_params is None else dict(observe_params)
         self._humans_np = None                              # num_envs == 1: the latest rows as NumPy arrays
         self._human_views = {}                              # per buffer parity: the views info['humans'] hands out
+        # goal path (navsim_goal_path): the field per arena, the path distance and the sub-goal, two launches behind the step
+        if goal_path_params is not None and not goal_path:
+            raise ValueError("goal_path_params needs goal_path=True")
+        for k in (goal_path_params or {}):
+            if k not in _simmod.GOAL_PATH_KEYS:
+                raise ValueError("unknown key %r in goal_path_params (known: %s)" % (k, ", ".join(_simmod.GOAL_PATH_KEYS)))
+        self.goal_path_on = bool(goal_path)
+        self.goal_path_params = None if goal_path_params is None else dict(goal_path_params)
+        self._goal_np = None                                # num_envs == 1: the latest row as NumPy scalars / arrays
+        self._goal_views = {}                               # per buffer parity: the views info['goal_path'] hands out
         self.cfg = cfg
         self.sim = None
         self._choose_reset_path(pregen_pipeline, plain_cap=cfg.regen_cap)      # (without the pipeline: the library's default cap)
@@ -543,6 +567,8 @@ class NavGymEnv(_EnvBase):
             self._humans_of_episode = None
             if self.observe_humans:
                 self._observe()
+            if self.goal_path_on:                         # (restarted: the key says so; a new map with the old number would not)
+                self._goal_path(rebuild=m.to(self.sim.device).ne(0).to(torch.uint8).contiguous())
             return self._obs_dict()
         self._bool = torch.bool
         from . import sim as simmod
@@ -571,6 +597,9 @@ class NavGymEnv(_EnvBase):
                 self.sim.enable_episode_stats()
             if self.observe_humans:
                 self.sim.enable_ped_observe(dict(self.observe_params or {}, max_obs=self.observe_humans))
+            if self.goal_path_on:
+                self.sim.enable_goal_path(self.goal_path_params)
+                self._goal_all = torch.ones(self.num_envs, dtype=torch.uint8, device=dev)
         elif "policy_prev_actions" in self.sim.t:
             self.sim.t["policy_prev_actions"].zero_()           # env.py:739
         self._episode_batch += 1
@@ -603,6 +632,8 @@ class NavGymEnv(_EnvBase):
         self._humans_of_episode = None
         if self.observe_humans:
             self._observe()
+        if self.goal_path_on:                             # every arena: a reset() may start the episode numbers again
+            self._goal_path(rebuild=self._goal_all)
         return self._obs_dict()
 
     @property
@@ -692,6 +723,8 @@ class NavGymEnv(_EnvBase):
             ep = self.sim.episode_stats()
         if self.observe_humans:                            # likewise: the state the returned rows describe
             humans = self._observe()
+        if self.goal_path_on:                              # likewise; the keys decide what is rebuilt
+            goal = self._goal_path()
         obs = self._obs_dict()
         # the LAST observation of an episode that ended in this step (env.py:700-728 returns it with done = True): under
         # same-step auto-reset the row above already is the next episode's first one and the terminal one rides in info;
@@ -714,6 +747,8 @@ class NavGymEnv(_EnvBase):
                 info["episode"] = {name: ep[k][0].item() for name, k in self._EPISODE_KEYS}
             if self.observe_humans:
                 info["humans"] = humans
+            if self.goal_path_on:
+                info["goal_path"] = goal
             return obs, float(out["reward"][0].item()), done, info
         # (views of the buffers the kernel wrote, made ONCE per buffer parity: a step of 4096 arenas is 95 us on the device, and
         #  every tensor slice or .view() costs the host 3-5 us -- round 6 measured 42 -> 36 M env-steps/s through this method
@@ -745,6 +780,8 @@ class NavGymEnv(_EnvBase):
             info["_episode"] = done
         if self.observe_humans:
             info["humans"] = humans
+        if self.goal_path_on:
+            info["goal_path"] = goal
         return obs, out["reward"], done, info
 
     def _observe(self):
@@ -763,6 +800,40 @@ class NavGymEnv(_EnvBase):
             v = self._human_views[self.sim.cur] = {"state": out["state"], "index": out["index"], "count": out["count"],
                                                    "visible": out["visible"].view(self._bool)}
         return v
+
+    def _goal_path(self, rebuild=None):
+        """navsim_goal_path behind whatever was queued, on the same stream: the path distance and the sub-goal of the state the
+        current observation rows describe.  Same-step auto-reset: the row of an arena that finished describes its NEW episode,
+        like the observation beside it (a shaper masks with `done`).  Next-step auto-reset: an arena whose `done` is set has its
+        state restarted already while its row is the terminal one -- it is skipped (neither rebuilt nor read, all 0) until the
+        call that resets it.  The views are made once per buffer parity."""
+        next_step = self.auto_reset and self.autoreset_mode == "next_step"
+        out = self.sim.goal_path(rebuild=rebuild, skip=self.sim.out["done"] if next_step else None)
+        if self.num_envs == 1:
+            h = self.sim.goal_path_host()
+            self._goal_np = {"distance": h["distance"][0], "subgoal": h["subgoal"][0], "status": h["status"][0]}
+            return self._goal_np
+        v = self._goal_views.get(self.sim.cur)
+        if v is None:
+            v = self._goal_views[self.sim.cur] = {"distance": out["distance"], "subgoal": out["subgoal"], "status": out["status"]}
+        return v
+
+    def goal_path(self):
+        """What info['goal_path'] of the latest step() holds (goal_path=True); valid after reset() and reset(mask) too:
+        {'distance' [E] float32 metres, 'subgoal' [E,2] float32 in the robot's frame, 'status' [E] uint8}."""
+        if not self.goal_path_on:
+            raise RuntimeError("goal_path() needs NavGymEnv(goal_path=True)")
+        if self.sim is None or self.sim.goal_buf is None:
+            raise RuntimeError("call reset() before goal_path()")
+        return self._goal_np if self.num_envs == 1 else self._goal_views[self.sim.cur]
+
+    def goal_field(self):
+        """The distance-to-goal fields on the device (goal_path=True): uint16 [E, H/5, W/5], NavSim.goal_field()."""
+        if not self.goal_path_on:
+            raise RuntimeError("goal_field() needs NavGymEnv(goal_path=True)")
+        if self.sim is None or self.sim.goal_buf is None:
+            raise RuntimeError("call reset() before goal_field()")
+        return self.sim.goal_field()
 
     def observed_humans(self):
         """What info['humans'] of the latest step() holds (observe_humans=K); valid after reset() and reset(mask) too: {'state'
@@ -981,6 +1052,8 @@ class NavGymEnv(_EnvBase):
         self._humans_of_episode = None
         if self.observe_humans:                            # (no part of the snapshot: a function of the state just loaded)
             self._observe()
+        if self.goal_path_on:                              # (likewise, and its keys know nothing of the state just loaded)
+            self._goal_path(rebuild=self._goal_all)
         torch.cuda.synchronize(self.sim.device)
         self._obs_dict()
 

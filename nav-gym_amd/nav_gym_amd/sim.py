@@ -315,6 +315,41 @@ def ped_observe_params(cfg, params=None, robot_type="keti"):
     return p
 
 
+GOAL_PATH_KEYS = ("hard_clearance", "clearance", "band_cost", "lookahead")
+
+
+def goal_path_defaults(cfg):
+    """The parameters of navsim_goal_path as a dict: cells closer than 0.3 m to a wall are impassable (never below the three
+    map cells the rule requires), cells closer than 0.75 m cost three times their length, the sub-goal lies 2 m down the field."""
+    return dict(hard_clearance=max(0.3, 3.0 * cfg.resolution), clearance=max(0.75, 3.0 * cfg.resolution), band_cost=3, lookahead=2.0)
+
+
+def goal_path_params(cfg, params=None):
+    """abi.NavsimGoalPathParams of goal_path_defaults(cfg) overridden by the dict `params`; an unknown key raises ValueError."""
+    d = goal_path_defaults(cfg)
+    for k, v in (params or {}).items():
+        if k not in d:
+            raise ValueError("unknown goal-path parameter %r (known: %s)" % (k, ", ".join(GOAL_PATH_KEYS)))
+        d[k] = v
+    p = abi.NavsimGoalPathParams()
+    p.hard_clearance, p.clearance, p.lookahead = float(d["hard_clearance"]), float(d["clearance"]), float(d["lookahead"])
+    p.band_cost = int(d["band_cost"])
+    return p
+
+
+def goal_path_layout(E):
+    """Where navsim_goal_path_out's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in
+    abi.GOAL_PATH_OUT's order, each start rounded up to 16 bytes, and a last entry whose end byte is the blob's size."""
+    out, at = [], 0
+    for k, (d, shape) in abi.GOAL_PATH_OUT.items():
+        full = (E,) + tuple(shape)
+        n = int(np.prod(full)) * np.dtype(d).itemsize
+        out.append((k, d, at, at + n, full))
+        at = (at + n + 15) // 16 * 16
+    out.append((None, None, at, max(at, 16), None))
+    return out
+
+
 def ped_observation_layout(E, K, N):
     """Where navsim_ped_observation's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in
     abi.PED_OBSERVATION's order, each start rounded up to 16 bytes, and a last entry whose end byte is the blob's size."""
@@ -495,6 +530,10 @@ class NavSim(object):
         # observed pedestrians (enable_ped_observe): the parameters, two sets of outputs (they flip with self.cur as well) and, per
         # parity, the arguments of navsim_ped_observe
         self.obs_params, self.ped_obs_buf, self._ped_obs_args = None, None, {}
+        # goal path (enable_goal_path): the parameters, the field [E,Hc,Wc] with its keys and rebuild counter, two sets of outputs
+        # (they flip with self.cur) and, per parity, the arguments of navsim_goal_path
+        self.goal_params, self.goal_dist, self.goal_key, self.goal_rebuilds = None, None, None, None
+        self.goal_buf, self._goal_args = None, {}
         self.t = {}
         self.st = abi.NavsimState()
         for name, (dtype, shape) in abi.STATE_LAYOUT.items():
@@ -1436,6 +1475,69 @@ class NavSim(object):
         if rc:
             check(rc, "navsim_ped_observe")
         return self.ped_obs_buf[self.cur]
+
+    # ---- goal path: a distance-to-goal field per arena on the 5 x 5-cell navigation grid, the robot's path distance and a steering
+    # sub-goal read from it -- two launches behind the step (include/navsim.h navsim_goal_path)
+    def enable_goal_path(self, params=None):
+        """Allocates the field (uint16 [E, H/5, W/5]), its keys (int64 [E,3], -1 = never built), the rebuild counter and two sets
+        of outputs (distance [E], subgoal [E,2], status [E]: they flip with self.cur like everything a step returns).  params: an
+        abi.NavsimGoalPathParams, a dict of overrides of goal_path_defaults(cfg), or None."""
+        import torch
+        cfg = self.cfg
+        p = params if isinstance(params, abi.NavsimGoalPathParams) else goal_path_params(cfg, params)
+        nbytes = self.lib.navsim_goal_field_bytes(C.byref(cfg))
+        if nbytes == 0 and cfg.n_envs > 0:
+            raise ValueError("the goal path needs maps of at least 5 x 5 cells")
+        self.goal_params = p
+        self.goal_dist = torch.full((cfg.n_envs, cfg.map_h // 5, cfg.map_w // 5), abi.GOAL_FIELD_INF - 65536, dtype=torch.int16,
+                                    device=self.device).view(torch.uint16)
+        self.goal_key = torch.full((cfg.n_envs, 3), -1, dtype=torch.int64, device=self.device)
+        self.goal_rebuilds = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._goal_layout = goal_path_layout(cfg.n_envs)
+        total = self._goal_layout[-1][3]
+        self.goal_blob = [torch.zeros(total, dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self.goal_buf = [{k: blob[lo:hi].view(_dtype(d)).view(shape) for k, d, lo, hi, shape in self._goal_layout[:-1]}
+                         for blob in self.goal_blob]
+        self._goal_field = abi.NavsimGoalField(dist=self.goal_dist.data_ptr(), key=self.goal_key.data_ptr(),
+                                               rebuilds=self.goal_rebuilds.data_ptr())
+        self._goal_args = {}
+
+    def goal_path(self, rebuild=None, skip=None):
+        """navsim_goal_path of the current state on the current stream: two launches, no copy.  rebuild: uint8 / bool [E], arenas
+        whose field is rebuilt whatever their key says (None: the keys alone decide -- every in-launch restart changes them);
+        skip: uint8 / bool [E], arenas that are neither rebuilt nor read and come back (0, (0, 0), 0).  Returns the current set
+        {'distance', 'subgoal', 'status'}, intact through the next step."""
+        if self.goal_buf is None:
+            raise RuntimeError("call enable_goal_path() first")
+        a = self._goal_args.get(self.cur)
+        if a is None:                                     # (built once per parity: every buffer behind it is allocated once)
+            out = abi.NavsimGoalPathOut()
+            for k, v in self.goal_buf[self.cur].items():
+                setattr(out, k, v.data_ptr())
+            a = self._goal_args[self.cur] = (out, C.byref(out), C.byref(self.goal_params), C.byref(self.cfg), C.byref(self.st),
+                                             C.byref(self._goal_field))
+        rc = self.lib.navsim_goal_path(a[3], a[4], a[2], _ptr(rebuild), _ptr(skip), a[5], a[1], _stream())
+        if rc:
+            check(rc, "navsim_goal_path")
+        return self.goal_buf[self.cur]
+
+    def goal_path_host(self):
+        """The current set of goal_path()'s outputs as NumPy arrays, from ONE device -> host copy."""
+        blob = self.goal_blob[self.cur].cpu().numpy()
+        return {k: blob[lo:hi].view(d).reshape(shape) for k, d, lo, hi, shape in self._goal_layout[:-1]}
+
+    def goal_field(self):
+        """The distance-to-goal fields on the device: uint16 [E, H/5, W/5] in map cells (5 a straight hop, 7 a diagonal one),
+        0xFFFF = impassable, unreachable or farther than 65534; as of each arena's latest rebuild."""
+        if self.goal_buf is None:
+            raise RuntimeError("call enable_goal_path() first")
+        return self.goal_dist
+
+    def goal_path_rebuilds(self):
+        """Fields rebuilt since enable_goal_path().  One device -> host copy."""
+        if self.goal_buf is None:
+            raise RuntimeError("call enable_goal_path() first")
+        return int(self.goal_rebuilds.item())
 
     def occupancy(self, e=0):
         """uint8 [H, W] occupancy grid (1 = occupied) of arena e, read back from its distance field
