@@ -82,3 +82,20 @@ for e in range(4):
     print("arena %d: straight line %.2f m, path %.2f m, sub-goal (%.2f, %.2f) m in the robot's frame, status %d"
           % (e, float(info["distance"][e]), float(g["distance"][e]), float(g["subgoal"][e, 0]), float(g["subgoal"][e, 1]), int(g["status"][e])))
 print("fields rebuilt so far: %d" % genv.sim.goal_path_rebuilds())
+
+# ---- a baseline controller on the same batch: the dynamic-window local planner ------------------------------------------------
+# local_planner='dwa' returns, one launch behind the step (and behind the goal path, whose sub-goal it then steers for), the
+# action a classical planner would take in every arena: candidates around the last twist rolled out against the arena's distance
+# field and its pedestrians.  Feeding it back drives the batch without a policy.
+penv = nav_gym_env.make("NavGym-v0", num_envs=64, map_size=400, indoor_ratio=0.0, min_goal_dist=3.0, max_goal_dist=8.0,
+                        goal_path=True, local_planner="dwa")
+penv.reset()
+plan = penv.planner_action()                               # valid after reset() too
+successes = crashes = 0
+for _ in range(150):
+    obs, reward, done, info = penv.step(plan["action"])    # a float64 [E,2] tensor on the device, read in place
+    successes += int(((info["is_success"] > 0) & done).sum())
+    crashes += int(((info["is_crash"] > 0) & done).sum())
+    plan = info["planner"]
+print("planner-driven, 64 arenas x 150 steps: %d successes, %d crashes; now %d arenas blocked, clearance of arena 0 %.2f m"
+      % (successes, crashes, int((plan["status"] == 2).sum()), float(plan["clearance"][0])))

@@ -1193,6 +1193,94 @@ int navsim_goal_path(const navsim_config* cfg, const navsim_state* st, const nav
                      const uint8_t* rebuild, const uint8_t* skip, const navsim_goal_field* field,
                      const navsim_goal_path_out* out, void* stream);
 
+/* ---- local planner: a dynamic-window action per arena from one launch ------------------------------------------------------------
+ * A classical baseline controller on the batch (a number to beat, an expert for demonstrations, a per-candidate cost surface, a
+ * check that an arena is solvable): every arena forms a window of reachable twists around the twist its last step integrated,
+ * rolls each candidate out with the step's own kinematics, tests a disc model of the robot's body against the arena's distance
+ * field and against pedestrians moved at constant velocity, scores the admissible candidates and returns the best as an action.
+ * BUILD-DEFINED, all of it: the reference has ORCA as a robot policy of its other simulator only, NavGym-v0 has no controller. */
+#define NAVSIM_DWA_MAX_DISCS 4
+typedef struct navsim_dwa_params {
+    double  acc_lin, acc_rot;          /* >= 0: the window is prev twist +- acc * cfg.time_step */
+    double  body_radius;               /* >= 0 */
+    double  body_offset[NAVSIM_DWA_MAX_DISCS];  /* disc centres on the body's x axis, metres from the pose origin */
+    double  ped_radius, margin, clearance_cap;  /* >= 0 */
+    double  w_progress, w_heading, w_clearance, w_speed;   /* finite */
+    int32_t n_discs;                   /* 1 .. 4 */
+    int32_t n_v, n_w;                  /* 1 .. 16, 1 .. 32: C = n_v n_w candidates, index c = iv n_w + iw */
+    int32_t horizon;                   /* T, 1 .. 32 steps of cfg.time_step */
+    int32_t use_peds;                  /* 0: pedestrians ignored (always so with NAVSIM_PED_NONE) */
+} navsim_dwa_params;
+
+#define NAVSIM_DWA_OK      1   /* the chosen candidate is admissible */
+#define NAVSIM_DWA_BLOCKED 2   /* no candidate is admissible: the chosen one violates the margin last */
+
+typedef struct navsim_dwa_out {
+    double*  twist;      /* [E,2] chosen (v, omega) */
+    double*  action;     /* [E,2] the same in cfg.action_kind's form (WHEELS: wl = (v - omega track / 2) / r, wr = (v + omega track / 2) / r) */
+    float*   clearance;  /* [E]   the chosen candidate's minclr (below), metres */
+    int32_t* best;       /* [E]   chosen candidate index */
+    uint8_t* status;     /* [E]   0 skipped, NAVSIM_DWA_OK 1, NAVSIM_DWA_BLOCKED 2 */
+    double*  scores;     /* [E,C] or NULL: score of every candidate, -inf where inadmissible */
+    int32_t* first_hit;  /* [E,C] or NULL: 0 = admissible, else the step k of the first violation */
+} navsim_dwa_out;
+
+/* ONE launch (a workgroup per arena, a lane per candidate; kernels_dwa.hpp), no device-to-host copy, nothing that blocks.  Call it
+ * behind the step (and whatever follows it: navsim_regen, navsim_replan, navsim_goal_path -- whose out->subgoal is this call's
+ * `subgoal`) on the same stream.  It reads st->robot_pose, robot_goal, prev_action, the distance field of the arena's map slot
+ * (cfg.shared_field, st->map_slot, st->field_overflow; both field formats) and, with pedestrians, n_peds, ped_pose and ped_vel; it
+ * writes EVERY element of `out`.  Everything is float64 in exactly this order, every operation rounded on its own (no fused
+ * multiply-add: DESIGN.md section 4); nv:: are the functions of navmath.hpp / navsim_device.hpp (navmath_ref.h); dt = cfg.time_step,
+ * N = cfg.max_peds, T = p->horizon, C = n_v n_w.  Per arena e:
+ *  1. skip && skip[e]: twist, action, clearance and best are 0, status is 0, the arena's rows of scores / first_hit are 0.
+ *     Nothing of the arena is read.
+ *  2. the window.  (v0, w0) = st->prev_action[e]: the twist the last step integrated.  The step stores it in TWIST form whatever
+ *     cfg.action_kind is -- after the wheel conversion, cfg.clamp_action and cfg.min_turning_radius (include/navsim.h
+ *     NAVSIM_ACTION_WHEELS: "the twist after conversion and clamp is what the step integrates"), (0, 0) at the start of an episode
+ *     -- so nothing is converted back.
+ *     vlo = max(linvel_lo, v0 - acc_lin * dt), vhi = min(linvel_hi, v0 + acc_lin * dt); if vlo > vhi both become
+ *     min(max(v0, linvel_lo), linvel_hi).  wlo, whi alike from w0, acc_rot and rotvel_lo, rotvel_hi.
+ *     v_iv = n_v == 1 ? vhi : vlo + (vhi - vlo) * ((double)iv / (double)(n_v - 1)), iv = 0 .. n_v - 1;
+ *     w_iw = n_w == 1 ? whi : wlo + (whi - wlo) * ((double)iw / (double)(n_w - 1)), iw = 0 .. n_w - 1.
+ *     Candidate c = iv n_w + iw is the twist (v_iv, w_iw).
+ *  3. the target.  (rx, ry, th) = robot_pose[e].  subgoal == NULL: (tx, ty) = robot_goal[e].  Otherwise, with
+ *     (s, c) = nv::sincos(th) and (sx, sy) = subgoal[e] widened to float64: tx = rx + (c*sx - s*sy), ty = ry + (s*sx + c*sy).
+ *     dx = tx - rx, dy = ty - ry, d0 = sqrt(dx*dx + dy*dy).
+ *  4. the rollout of candidate c.  p = robot_pose[e], minclr = clearance_cap, hit = 0.  For k = 1 .. T:
+ *     nv::set_vel(p, v, w, dt, cfg.axle_offset, nullptr) (the step's integration, env.py:664), then (sk, ck) = nv::sincos(p[2]).
+ *     For disc j < n_discs: cx = p[0] + body_offset[j] * ck, cy = p[1] + body_offset[j] * sk.
+ *       static clearance: (i, j) = nv::xy_to_ij(cx, cy) (batch_xy_to_ij on float64 inputs, env.py:1228-1253), then
+ *       i = min(i, map_w - 1), j = min(j, map_h - 1) -- xy_to_ij clips x by map_h and y by map_w, which differ on a map that is
+ *       not square --; cs = (double)field.at(i, j) * resolution - body_radius, field.at = the float32 distance in cells the
+ *       field of the arena's map slot holds for column i, row j.
+ *       pedestrian clearance, when use_peds and cfg.ped_model != NAVSIM_PED_NONE, for every pedestrian q < min(n_peds[e], N):
+ *       tk = (double)k * dt, ex = (ped_pose[e,q,0] + ped_vel[e,q,0] * tk) - cx, ey = (ped_pose[e,q,1] + ped_vel[e,q,1] * tk) - cy,
+ *       cp = sqrt(ex*ex + ey*ey) - (ped_radius + body_radius).
+ *     clr_k = the least of all cs and cp of step k.  clr_k < margin: hit = k and the rollout stops.  Otherwise
+ *     minclr = min(minclr, clr_k).
+ *  5. the score of an admissible candidate (hit == 0).  With p the pose after step T and (sT, cT) = nv::sincos(p[2]):
+ *     gx = tx - p[0], gy = ty - p[1], dT = sqrt(gx*gx + gy*gy), align = dT > 0 ? (cT*gx + sT*gy) / dT : 1,
+ *     score = ((w_progress * (d0 - dT) + w_heading * align) + w_clearance * minclr) + w_speed * v.
+ *  6. the choice.  The admissible candidate with the greatest score wins, ties go to the lowest c: status = NAVSIM_DWA_OK.  No
+ *     candidate admissible: the one with the greatest hit wins, ties to the lowest c: status = NAVSIM_DWA_BLOCKED.
+ *     twist = its (v, w); action = twist under NAVSIM_ACTION_TWIST, ((v - w * wheel_track / 2) / wheel_radius,
+ *     (v + w * wheel_track / 2) / wheel_radius) under NAVSIM_ACTION_WHEELS; clearance = (float)minclr -- of a blocked candidate
+ *     the least clearance of the steps before its hit --; best = c.
+ *  7. scores[e,c] = the score, -inf where hit != 0; first_hit[e,c] = hit -- of every candidate, when the arrays are given.
+ * (The kernel takes each step's minima over float32 field values and over squared distances and converts once: sqrt, the product
+ * with resolution and the subtraction of a constant are monotone and correctly rounded, so the results are the rule's bit for bit.)
+ * NAVSIM_E_ARG, before anything touches the device: cfg, st, p or out NULL; out->twist, action, clearance, best or status NULL
+ * (scores and first_hit may be NULL); st->robot_pose, robot_goal, prev_action or field NULL; st->n_peds, ped_pose or ped_vel NULL
+ * with use_peds set and a pedestrian model on (then also max_peds outside 1 .. NAVSIM_MAX_PEDS); a parameter that is not finite;
+ * acc_lin, acc_rot, body_radius, ped_radius, margin or clearance_cap negative; n_discs outside 1 .. 4, n_v outside 1 .. 16, n_w
+ * outside 1 .. 32, horizon outside 1 .. 32; n_envs < 0; map_h or map_w < 1; resolution or time_step not finite or not positive;
+ * an action_kind that is none of NAVSIM_ACTION_*, NAVSIM_ACTION_WHEELS with a wheel_radius that is not positive; st->map_slot with
+ * cfg.shared_field.  NAVSIM_E_UNSUPPORTED: a field_format that is neither NAVSIM_FIELD_F32 nor NAVSIM_FIELD_U16T.
+ * n_envs == 0: NAVSIM_OK, nothing is launched. */
+int navsim_dwa(const navsim_config* cfg, const navsim_state* st, const navsim_dwa_params* p,
+               const float* subgoal /* [E,2] robot frame, or NULL */, const uint8_t* skip,
+               const navsim_dwa_out* out, void* stream);
+
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);
 

@@ -22,6 +22,7 @@
 //   kernels_ped_orca.hpp  NavGym pedestrians driven by ORCA from the simulator's state (navsim_ped_orca)
 //   kernels_episode.hpp  episode statistics behind the step;  kernels_ped_observe.hpp  the K nearest pedestrians in line of sight
 //   kernels_goal_path.hpp  distance-to-goal field per arena, the robot's path distance and steering sub-goal (navsim_goal_path)
+//   kernels_dwa.hpp  local planner: a dynamic-window action per arena (navsim_dwa)
 //   step_plan.hpp        launch geometry of the fused step, the descriptors of a launch and the march-rule dispatch (shared by this
 //                        file and navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
 // Host code of this file, ahead of the C ABI: dispatch_step and the argument checks; the workspaces (Carver and one layout
@@ -47,6 +48,7 @@ namespace {
 #include "kernels_episode.hpp"
 #include "kernels_ped_observe.hpp"
 #include "kernels_goal_path.hpp"
+#include "kernels_dwa.hpp"
 
 }  // namespace
 #include "step_plan.hpp"
@@ -481,6 +483,15 @@ int launch_goal_path(const navsim_config* c, const navsim_state* st, const GoalF
     goal_field_kernel<F><<<grid, kGoalBlock, lds, s>>>(f);
     const int per = kGoalWaves * 8;                        // arenas per workgroup of launch 2
     goal_query_kernel<F><<<(c->n_envs + per - 1) / per, 64 * kGoalWaves, 0, s>>>(*c, *st, a);
+    return launch_status();
+}
+
+// navsim_dwa: a workgroup per arena, a lane per candidate; the pedestrians of every step in dynamic LDS (kernels_dwa.hpp)
+template <typename F>
+int launch_dwa(const navsim_config* c, const navsim_state* st, const DwaArgs& a, hipStream_t s) {
+    const int C = a.p.n_v * a.p.n_w, block = 64 * ((C + 63) / 64);
+    const size_t lds = a.use_peds ? (size_t)a.p.horizon * c->max_peds * sizeof(double2) : 0;
+    dwa_kernel<F><<<c->n_envs, block, lds, s>>>(*c, *st, a);
     return launch_status();
 }
 
@@ -1517,6 +1528,40 @@ int navsim_goal_path(const navsim_config* c, const navsim_state* st, const navsi
 int navsim_debug_goal_path_sweeps(int32_t* sweeps) {
     g_goal_sweeps = sweeps;
     return NAVSIM_OK;
+}
+
+int navsim_dwa(const navsim_config* c, const navsim_state* st, const navsim_dwa_params* p, const float* subgoal, const uint8_t* skip,
+               const navsim_dwa_out* out, void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !p || !out) return NAVSIM_E_ARG;
+    if (!out->twist || !out->action || !out->clearance || !out->best || !out->status) return NAVSIM_E_ARG;
+    if (!st->robot_pose || !st->robot_goal || !st->prev_action || !st->field) return NAVSIM_E_ARG;
+    const bool use_peds = p->use_peds != 0 && c->ped_model != NAVSIM_PED_NONE;
+    if (use_peds && (!st->n_peds || !st->ped_pose || !st->ped_vel || c->max_peds < 1 || c->max_peds > NAVSIM_MAX_PEDS)) return NAVSIM_E_ARG;
+    const double nonneg[] = {p->acc_lin, p->acc_rot, p->body_radius, p->ped_radius, p->margin, p->clearance_cap};
+    for (double x : nonneg)
+        if (!std::isfinite(x) || x < 0.0) return NAVSIM_E_ARG;
+    const double finite[] = {p->w_progress, p->w_heading, p->w_clearance, p->w_speed, p->body_offset[0], p->body_offset[1],
+                             p->body_offset[2], p->body_offset[3], c->linvel_lo, c->linvel_hi, c->rotvel_lo, c->rotvel_hi,
+                             c->axle_offset, c->origin_x, c->origin_y};
+    for (double x : finite)
+        if (!std::isfinite(x)) return NAVSIM_E_ARG;
+    if (p->n_discs < 1 || p->n_discs > NAVSIM_DWA_MAX_DISCS || p->n_v < 1 || p->n_v > 16 || p->n_w < 1 || p->n_w > 32) return NAVSIM_E_ARG;
+    if (p->horizon < 1 || p->horizon > 32) return NAVSIM_E_ARG;
+    if (c->n_envs < 0 || c->map_h < 1 || c->map_w < 1) return NAVSIM_E_ARG;
+    if (!(c->resolution > 0.0) || !std::isfinite(c->resolution) || !(c->time_step > 0.0) || !std::isfinite(c->time_step)) return NAVSIM_E_ARG;
+    if (c->action_kind != NAVSIM_ACTION_TWIST && c->action_kind != NAVSIM_ACTION_WHEELS) return NAVSIM_E_ARG;
+    if (c->action_kind == NAVSIM_ACTION_WHEELS && (!(c->wheel_radius > 0.0) || !std::isfinite(c->wheel_radius) || !std::isfinite(c->wheel_track)))
+        return NAVSIM_E_ARG;
+    if (st->map_slot && c->shared_field) return NAVSIM_E_ARG;
+    if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    DwaArgs a = {};
+    a.p = *p; a.out = *out; a.subgoal = subgoal; a.skip = skip; a.use_peds = use_peds ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (c->field_format == NAVSIM_FIELD_F32) return launch_dwa<FieldF32>(c, st, a, s);
+    if (st->field_overflow) return launch_dwa<FieldU16T>(c, st, a, s);
+    return launch_dwa<FieldU16TN>(c, st, a, s);
 }
 
 const char* navsim_step_kernel_name(void) { return "navsim_step_kernel"; }

@@ -227,6 +227,28 @@ class NavsimGoalPathOut(C.Structure):
 GOAL_PATH_OK, GOAL_PATH_REACHED_GOAL_CELL, GOAL_PATH_OFF_FIELD = 1, 2, 4
 GOAL_FIELD_INF = 0xFFFF
 
+# navsim_dwa: the rule's parameters and the output arrays (dtype, trailing shape behind E; C = n_v n_w candidates)
+DWA_MAX_DISCS = 4
+
+
+class NavsimDwaParams(C.Structure):
+    _fields_ = [("acc_lin", C.c_double), ("acc_rot", C.c_double), ("body_radius", C.c_double),
+                ("body_offset", C.c_double * DWA_MAX_DISCS), ("ped_radius", C.c_double), ("margin", C.c_double),
+                ("clearance_cap", C.c_double), ("w_progress", C.c_double), ("w_heading", C.c_double), ("w_clearance", C.c_double),
+                ("w_speed", C.c_double), ("n_discs", C.c_int32), ("n_v", C.c_int32), ("n_w", C.c_int32), ("horizon", C.c_int32),
+                ("use_peds", C.c_int32)]
+
+
+DWA_OUT = {"twist": ("float64", (2,)), "action": ("float64", (2,)), "clearance": ("float32", ()), "best": ("int32", ()),
+           "status": ("uint8", ()), "scores": ("float64", ("C",)), "first_hit": ("int32", ("C",))}
+
+
+class NavsimDwaOut(C.Structure):
+    _fields_ = [(name, _P) for name in DWA_OUT]
+
+
+DWA_OK, DWA_BLOCKED = 1, 2
+
 ORCA_MAX_AGENTS = 64
 ORCA_MAX_EDGES = 128
 CROWD_MAX_VERTS = 8
@@ -438,6 +460,8 @@ def declare(lib, suffix=""):
                                  C.POINTER(NavsimGoalPathOut), _P])
         sig("navsim_goal_field_bytes", [cfgp], C.c_size_t)
         sig("navsim_debug_goal_path_sweeps", [_P])
+    if not suffix and hasattr(lib, "navsim_dwa"):                       # (likewise)
+        sig("navsim_dwa", [cfgp, stp, C.POINTER(NavsimDwaParams), _P, _P, C.POINTER(NavsimDwaOut), _P])
     sig("navsim_reset_obs", [cfgp, stp, iop, _P] + stream)
     sig("navsim_restart", [cfgp, stp, _P] + stream)
     return lib
@@ -456,7 +480,7 @@ EXPORTS = (
     "navsim_crowd_check", "navsim_crowd_angular_map", "navsim_crowd_local_map", "navsim_crowd_orca", "navsim_crowd_agent_step", "navsim_ped_orca", "navsim_ped_orca_walls",
     "navsim_step", "navsim_step_sorted", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
     "navsim_episode_stats_update", "navsim_episode_stats_clear", "navsim_ped_observe",
-    "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps",
+    "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps", "navsim_dwa",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

@@ -107,6 +107,21 @@ and default to the reference's behaviour for num_envs == 1:
                     that resets it.  env.goal_path() returns the same dict, also after reset() / reset(mask); env.goal_field() the
                     uint16 [E, H/5, W/5] fields on the device.  num_envs > 1: torch views with the lifetime below; num_envs == 1:
                     NumPy scalars and arrays from one device -> host copy.  False (default): nothing is allocated or launched.
+    local_planner   'dwa': a dynamic-window local planner on the device, one launch behind the step (navsim_dwa; behind
+                    navsim_goal_path with goal_path=True, whose sub-goal is then its target -- otherwise the goal itself): every
+                    arena forms a window of twists it can reach from the twist of its last step, rolls each candidate out with the
+                    step's kinematics against its distance field (two discs over the threshold footprint) and its pedestrians
+                    (moved at constant velocity), and picks the admissible candidate with the best score --
+                    info['planner'] = {'action' [E,2] float64 in action_kind's form: feed it to the next step(); 'twist' [E,2] the
+                    same as (v, omega); 'clearance' [E] metres; 'best' [E] the candidate's index; 'status' [E] uint8: 1 = ok, 2 =
+                    blocked (no admissible candidate: the one that violates the margin last), 0 = skipped}.  A classical baseline
+                    on the same batch: a number to beat, an expert for demonstrations, a check that an arena is solvable.
+                    local_planner_params overrides sim.dwa_defaults (acc_lin, acc_rot, body_radius, body_offset, ped_radius,
+                    margin, clearance_cap, the four weights, n_v, n_w, horizon, use_peds).  The row describes the state the returned
+                    observation row describes; under next-step auto-reset an arena whose `done` is set is skipped (all 0) until
+                    the step that resets it.  env.planner_action() returns the same dict, also after reset() / reset(mask).
+                    num_envs > 1: torch views with the lifetime below; num_envs == 1: NumPy values from one device -> host copy.
+                    None (default): nothing is allocated or launched.
     reset(mask)     reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
                     [num_envs]; the others keep their state and their rows.  On the pipelined reset path the masked arenas install
                     their staged worlds in one launch: the same state and rows as with pregen_pipeline=0.
@@ -244,7 +259,8 @@ class NavGymEnv(_EnvBase):
                  action_kind="twist", clip_actions=False, max_waypoints=64, march_rule=None, use_graphs=None,
                  regen_min_steps=0, pregen_pipeline=None, pregen_stage_cap=None, autoreset_mode="same_step",
                  final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None,
-                 episode_stats=False, observe_humans=None, observe_params=None, goal_path=False, goal_path_params=None):
+                 episode_stats=False, observe_humans=None, observe_params=None, goal_path=False, goal_path_params=None,
+                 local_planner=None, local_planner_params=None):
         # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
         self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
         from . import lib
@@ -450,6 +466,18 @@ class NavGymEnv(_EnvBase):
         self.goal_path_params = None if goal_path_params is None else dict(goal_path_params)
         self._goal_np = None                                # num_envs == 1: the latest row as NumPy scalars / arrays
         self._goal_views = {}                               # per buffer parity: the views info['goal_path'] hands out
+        # local planner (navsim_dwa): an action per arena, one launch behind the step (and behind the goal path)
+        if local_planner not in (None, "dwa"):
+            raise ValueError("local_planner must be None or 'dwa', not %r" % (local_planner,))
+        if local_planner_params is not None and local_planner is None:
+            raise ValueError("local_planner_params needs local_planner='dwa'")
+        for k in (local_planner_params or {}):
+            if k not in _simmod.DWA_KEYS:
+                raise ValueError("unknown key %r in local_planner_params (known: %s)" % (k, ", ".join(_simmod.DWA_KEYS)))
+        self.local_planner = local_planner
+        self.local_planner_params = None if local_planner_params is None else dict(local_planner_params)
+        self._planner_np = None                             # num_envs == 1: the latest row as NumPy values
+        self._planner_views = {}                            # per buffer parity: the views info['planner'] hands out
         self.cfg = cfg
         self.sim = None
         self._choose_reset_path(pregen_pipeline, plain_cap=cfg.regen_cap)      # (without the pipeline: the library's default cap)
@@ -569,6 +597,8 @@ class NavGymEnv(_EnvBase):
                 self._observe()
             if self.goal_path_on:                         # (restarted: the key says so; a new map with the old number would not)
                 self._goal_path(rebuild=m.to(self.sim.device).ne(0).to(torch.uint8).contiguous())
+            if self.local_planner:
+                self._plan()
             return self._obs_dict()
         self._bool = torch.bool
         from . import sim as simmod
@@ -600,6 +630,8 @@ class NavGymEnv(_EnvBase):
             if self.goal_path_on:
                 self.sim.enable_goal_path(self.goal_path_params)
                 self._goal_all = torch.ones(self.num_envs, dtype=torch.uint8, device=dev)
+            if self.local_planner:
+                self.sim.enable_dwa(self.local_planner_params, robot_type=self.robot_type)
         elif "policy_prev_actions" in self.sim.t:
             self.sim.t["policy_prev_actions"].zero_()           # env.py:739
         self._episode_batch += 1
@@ -634,6 +666,8 @@ class NavGymEnv(_EnvBase):
             self._observe()
         if self.goal_path_on:                             # every arena: a reset() may start the episode numbers again
             self._goal_path(rebuild=self._goal_all)
+        if self.local_planner:
+            self._plan()
         return self._obs_dict()
 
     @property
@@ -725,6 +759,8 @@ class NavGymEnv(_EnvBase):
             humans = self._observe()
         if self.goal_path_on:                              # likewise; the keys decide what is rebuilt
             goal = self._goal_path()
+        if self.local_planner:                             # behind the goal path: its sub-goal is the planner's target
+            plan = self._plan()
         obs = self._obs_dict()
         # the LAST observation of an episode that ended in this step (env.py:700-728 returns it with done = True): under
         # same-step auto-reset the row above already is the next episode's first one and the terminal one rides in info;
@@ -749,6 +785,8 @@ class NavGymEnv(_EnvBase):
                 info["humans"] = humans
             if self.goal_path_on:
                 info["goal_path"] = goal
+            if self.local_planner:
+                info["planner"] = plan
             return obs, float(out["reward"][0].item()), done, info
         # (views of the buffers the kernel wrote, made ONCE per buffer parity: a step of 4096 arenas is 95 us on the device, and
         #  every tensor slice or .view() costs the host 3-5 us -- round 6 measured 42 -> 36 M env-steps/s through this method
@@ -782,6 +820,8 @@ class NavGymEnv(_EnvBase):
             info["humans"] = humans
         if self.goal_path_on:
             info["goal_path"] = goal
+        if self.local_planner:
+            info["planner"] = plan
         return obs, out["reward"], done, info
 
     def _observe(self):
@@ -817,6 +857,35 @@ class NavGymEnv(_EnvBase):
         if v is None:
             v = self._goal_views[self.sim.cur] = {"distance": out["distance"], "subgoal": out["subgoal"], "status": out["status"]}
         return v
+
+    _PLANNER_KEYS = ("action", "twist", "clearance", "best", "status")
+
+    def _plan(self):
+        """navsim_dwa behind whatever was queued (the goal path included: the sub-goal of the current buffer set is its target;
+        without goal_path the arena's goal), on the same stream: the planner's action for the state the current observation rows
+        describe.  Next-step auto-reset: an arena whose `done` is set is skipped (all 0) until the call that resets it.  The
+        views are made once per buffer parity."""
+        next_step = self.auto_reset and self.autoreset_mode == "next_step"
+        sub = self.sim.goal_buf[self.sim.cur]["subgoal"] if self.goal_path_on else None
+        out = self.sim.dwa(subgoal=sub, skip=self.sim.out["done"] if next_step else None)
+        if self.num_envs == 1:
+            h = self.sim.dwa_host()
+            self._planner_np = {k: h[k][0] for k in self._PLANNER_KEYS}
+            return self._planner_np
+        v = self._planner_views.get(self.sim.cur)
+        if v is None:
+            v = self._planner_views[self.sim.cur] = {k: out[k] for k in self._PLANNER_KEYS}
+        return v
+
+    def planner_action(self):
+        """What info['planner'] of the latest step() holds (local_planner='dwa'); valid after reset() and reset(mask) too:
+        {'action' [E,2] float64 in action_kind's form, 'twist' [E,2] float64 (v, omega), 'clearance' [E] float32 metres, 'best' [E]
+        int32, 'status' [E] uint8}."""
+        if not self.local_planner:
+            raise RuntimeError("planner_action() needs NavGymEnv(local_planner='dwa')")
+        if self.sim is None or self.sim.dwa_buf is None:
+            raise RuntimeError("call reset() before planner_action()")
+        return self._planner_np if self.num_envs == 1 else self._planner_views[self.sim.cur]
 
     def goal_path(self):
         """What info['goal_path'] of the latest step() holds (goal_path=True); valid after reset() and reset(mask) too:
@@ -1054,6 +1123,8 @@ class NavGymEnv(_EnvBase):
             self._observe()
         if self.goal_path_on:                              # (likewise, and its keys know nothing of the state just loaded)
             self._goal_path(rebuild=self._goal_all)
+        if self.local_planner:                             # (likewise)
+            self._plan()
         torch.cuda.synchronize(self.sim.device)
         self._obs_dict()
 

@@ -350,6 +350,65 @@ def goal_path_layout(E):
     return out
 
 
+DWA_KEYS = ("acc_lin", "acc_rot", "body_radius", "body_offset", "ped_radius", "margin", "clearance_cap", "w_progress", "w_heading",
+            "w_clearance", "w_speed", "n_v", "n_w", "horizon", "use_peds")
+
+
+def dwa_defaults(cfg, robot_type="keti"):
+    """The parameters of navsim_dwa as a dict: two discs that cover the robot's threshold footprint (robots.py) -- at the centres
+    of the two halves of its x extent, radius the half-diagonal of a half --, a 0.1 m margin, 0.3 m pedestrian discs, clearance
+    counted up to 1 m, 1.0 m/s^2 and 3.2 rad/s^2, 5 x 9 candidates rolled out over 8 steps, weights 1 / 0.2 / 0.3 / 0.1 for
+    progress, heading, clearance and speed.  body_offset is a sequence of 1 .. 4 disc centres (n_discs is its length)."""
+    from . import robots
+    fp = np.asarray(robots.ROBOTS[robot_type]["threshold_footprint"], np.float64)
+    x_lo, x_hi, half_y = float(fp[:, 0].min()), float(fp[:, 0].max()), float(np.abs(fp[:, 1]).max())
+    quarter = (x_hi - x_lo) / 4.0
+    return dict(acc_lin=1.0, acc_rot=3.2, body_radius=float(np.hypot(quarter, half_y)), body_offset=(x_lo + quarter, x_hi - quarter),
+                ped_radius=0.3, margin=0.1, clearance_cap=1.0, w_progress=1.0, w_heading=0.2, w_clearance=0.3, w_speed=0.1,
+                n_v=5, n_w=9, horizon=8, use_peds=1)
+
+
+def dwa_params(cfg, params=None, robot_type="keti"):
+    """abi.NavsimDwaParams of dwa_defaults(cfg) overridden by the dict `params`; an unknown key raises ValueError."""
+    d = dwa_defaults(cfg, robot_type)
+    for k, v in (params or {}).items():
+        if k not in d:
+            raise ValueError("unknown planner parameter %r (known: %s)" % (k, ", ".join(DWA_KEYS)))
+        d[k] = v
+    offs = [float(x) for x in np.atleast_1d(np.asarray(d["body_offset"], np.float64))]
+    if not 1 <= len(offs) <= abi.DWA_MAX_DISCS:
+        raise ValueError("body_offset holds 1 .. %d disc centres, not %d" % (abi.DWA_MAX_DISCS, len(offs)))
+    p = abi.NavsimDwaParams()
+    for k in DWA_KEYS:
+        if k == "body_offset":
+            for i, x in enumerate(offs):
+                p.body_offset[i] = x
+        elif k in ("n_v", "n_w", "horizon"):
+            setattr(p, k, int(d[k]))
+        elif k == "use_peds":
+            p.use_peds = int(bool(d[k]))
+        else:
+            setattr(p, k, float(d[k]))
+    p.n_discs = len(offs)
+    return p
+
+
+def dwa_layout(E, C_, scores=False):
+    """Where navsim_dwa_out's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in abi.DWA_OUT's
+    order (the two per-candidate arrays only with scores=True), each start rounded up to 16 bytes, and a last entry whose end
+    byte is the blob's size."""
+    out, at = [], 0
+    for k, (d, shape) in abi.DWA_OUT.items():
+        if "C" in shape and not scores:
+            continue
+        full = (E,) + tuple(C_ if s == "C" else s for s in shape)
+        n = int(np.prod(full)) * np.dtype(d).itemsize
+        out.append((k, d, at, at + n, full))
+        at = (at + n + 15) // 16 * 16
+    out.append((None, None, at, max(at, 16), None))
+    return out
+
+
 def ped_observation_layout(E, K, N):
     """Where navsim_ped_observation's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in
     abi.PED_OBSERVATION's order, each start rounded up to 16 bytes, and a last entry whose end byte is the blob's size."""
@@ -534,6 +593,8 @@ class NavSim(object):
         # (they flip with self.cur) and, per parity, the arguments of navsim_goal_path
         self.goal_params, self.goal_dist, self.goal_key, self.goal_rebuilds = None, None, None, None
         self.goal_buf, self._goal_args = None, {}
+        # local planner (enable_dwa): the parameters, two sets of outputs (they flip with self.cur) and navsim_dwa's arguments
+        self.dwa_params, self.dwa_buf, self.dwa_blob, self._dwa_args = None, None, None, {}
         self.t = {}
         self.st = abi.NavsimState()
         for name, (dtype, shape) in abi.STATE_LAYOUT.items():
@@ -1538,6 +1599,47 @@ class NavSim(object):
         if self.goal_buf is None:
             raise RuntimeError("call enable_goal_path() first")
         return int(self.goal_rebuilds.item())
+
+    # ---- local planner: a dynamic-window action per arena -- candidates rolled out against the distance field and the pedestrians,
+    # the best one returned -- one launch behind the step (include/navsim.h navsim_dwa)
+    def enable_dwa(self, params=None, scores=False, robot_type="keti"):
+        """Allocates two sets of outputs (twist [E,2], action [E,2], clearance [E], best [E], status [E]; with scores=True also
+        scores [E,C] and first_hit [E,C], every candidate's values: they flip with self.cur like everything a step returns).
+        params: an abi.NavsimDwaParams, a dict of overrides of dwa_defaults(cfg, robot_type), or None."""
+        import torch
+        p = params if isinstance(params, abi.NavsimDwaParams) else dwa_params(self.cfg, params, robot_type)
+        if not (1 <= p.n_v <= 16 and 1 <= p.n_w <= 32 and 1 <= p.horizon <= 32):
+            raise ValueError("n_v must lie in 1..16, n_w in 1..32, horizon in 1..32, not %d, %d, %d" % (p.n_v, p.n_w, p.horizon))
+        self.dwa_params = p
+        self._dwa_layout = dwa_layout(self.cfg.n_envs, p.n_v * p.n_w, scores=scores)
+        total = self._dwa_layout[-1][3]
+        self.dwa_blob = [torch.zeros(total, dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self.dwa_buf = [{k: blob[lo:hi].view(_dtype(d)).view(shape) for k, d, lo, hi, shape in self._dwa_layout[:-1]}
+                        for blob in self.dwa_blob]
+        self._dwa_args = {}
+
+    def dwa(self, subgoal=None, skip=None):
+        """navsim_dwa of the current state on the current stream: one launch, no copy.  subgoal: float32 [E,2] targets in the
+        robot's frame (goal_path()'s 'subgoal'; None: the arena's goal); skip: uint8 / bool [E], arenas that are not read and come
+        back all 0.  Returns the current set {'twist', 'action', 'clearance', 'best', 'status'[, 'scores', 'first_hit']}, intact
+        through the next step."""
+        if self.dwa_buf is None:
+            raise RuntimeError("call enable_dwa() first")
+        a = self._dwa_args.get(self.cur)
+        if a is None:                                     # (built once per parity: every buffer behind it is allocated once)
+            out = abi.NavsimDwaOut()
+            for k, v in self.dwa_buf[self.cur].items():
+                setattr(out, k, v.data_ptr())
+            a = self._dwa_args[self.cur] = (out, C.byref(out), C.byref(self.dwa_params), C.byref(self.cfg), C.byref(self.st))
+        rc = self.lib.navsim_dwa(a[3], a[4], a[2], _ptr(subgoal), _ptr(skip), a[1], _stream())
+        if rc:
+            check(rc, "navsim_dwa")
+        return self.dwa_buf[self.cur]
+
+    def dwa_host(self):
+        """The current set of dwa()'s outputs as NumPy arrays, from ONE device -> host copy."""
+        blob = self.dwa_blob[self.cur].cpu().numpy()
+        return {k: blob[lo:hi].view(d).reshape(shape) for k, d, lo, hi, shape in self._dwa_layout[:-1]}
 
     def occupancy(self, e=0):
         """uint8 [H, W] occupancy grid (1 = occupied) of arena e, read back from its distance field

@@ -1,0 +1,369 @@
+"""GPU: the local planner (include/navsim.h navsim_dwa; NavGymEnv(local_planner='dwa')) against the NumPy specification of
+tests/dwa_spec.py, bit for bit -- twist, action, clearance and scores as raw bits, best, status, first_hit: single calls on raw
+states at the shapes where the kernel's mapping changes (45 candidates, 512, one), both field formats, every way an arena finds
+its map, pedestrians on and off, a skip mask, a sub-goal, wheel actions, a closed loop through NavGymEnv under every reset path,
+and the refusals.  Every output is pre-filled with a sentinel: the call writes every element."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import dwa_spec as spec
+import ref
+from nav_gym_amd import abi
+from test_gpu_autoreset import gpu, _t, _eq  # noqa: F401  (gpu: the module's fixture)
+
+pytestmark = pytest.mark.gpu
+
+KEYS = spec.KEYS
+BITS = dict(twist=np.uint64, action=np.uint64, scores=np.uint64, clearance=np.uint32)
+
+
+def _params(gpu, cfg, params):
+    return gpu.sim.dwa_params(cfg, params)
+
+
+def _call(gpu, cfg, st, params, subgoal=None, skip=None, want_rc=0, n_out=None, with_scores=True, n_cand=None):
+    """navsim_dwa into sentinel-filled outputs (n_out rows; None: cfg.n_envs) -> NumPy arrays."""
+    p = _params(gpu, cfg, params) if isinstance(params, dict) else params
+    torch, E = gpu.torch, cfg.n_envs if n_out is None else n_out
+    Cn = p.n_v * p.n_w if n_cand is None else n_cand
+    out = dict(twist=torch.full((E, 2), 777.0, dtype=torch.float64, device=gpu.dev),
+               action=torch.full((E, 2), 777.0, dtype=torch.float64, device=gpu.dev),
+               clearance=torch.full((E,), 777.0, dtype=torch.float32, device=gpu.dev),
+               best=torch.full((E,), 7777, dtype=torch.int32, device=gpu.dev),
+               status=torch.full((E,), 77, dtype=torch.uint8, device=gpu.dev),
+               scores=torch.full((E, Cn), 777.0, dtype=torch.float64, device=gpu.dev),
+               first_hit=torch.full((E, Cn), 7777, dtype=torch.int32, device=gpu.dev))
+    o = abi.NavsimDwaOut(**{k: (v.data_ptr() if with_scores or k not in ("scores", "first_hit") else None) for k, v in out.items()})
+    t_sub = None if subgoal is None else _t(gpu, np.asarray(subgoal, np.float32))
+    t_skip = None if skip is None else _t(gpu, np.asarray(skip, np.uint8))
+    rc = gpu.lib.load().navsim_dwa(C.byref(cfg), C.byref(st), C.byref(p), None if subgoal is None else t_sub.data_ptr(),
+                                   None if skip is None else t_skip.data_ptr(), C.byref(o), None)
+    assert rc == want_rc, rc
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def _untouched(dev, keys=KEYS):
+    for k in keys:
+        assert (dev[k] == (7777 if k in ("best", "first_hit") else (77 if k == "status" else 777.0))).all(), k
+
+
+def _same(dev, want, what, keys=KEYS):
+    for k in keys:
+        a, b = dev[k], want[k]
+        assert a.dtype == b.dtype and a.shape == b.shape, (what, k, a.dtype, a.shape, b.dtype, b.shape)
+        if k in BITS:
+            a, b = a.view(BITS[k]), b.view(BITS[k])
+        _eq(a, b, "%s: %s" % (what, k))
+
+
+def _device_state(gpu, cfg, occ, w, overflow=False, map_slot=None, peds=True):
+    """navsim_state over device copies of the world `w` and the field of `occ` [M,H,W] in cfg.field_format (overflow: whether the
+    packed field must saturate somewhere; None: as it comes).  -> (st, keepalive)"""
+    occ_t = _t(gpu, occ)
+    keep = {k: _t(gpu, np.asarray(w[k], np.float64)) for k in ("robot_pose", "robot_goal", "prev_action")}
+    if peds:
+        keep.update(n_peds=_t(gpu, np.asarray(w["n_peds"], np.int32)), ped_pose=_t(gpu, np.asarray(w["ped_pose"], np.float64)),
+                    ped_vel=_t(gpu, np.asarray(w["ped_vel"], np.float64)))
+    if cfg.field_format == abi.FIELD_F32:
+        keep["field"] = gpu.sim.build_dt(occ_t)
+    else:
+        keep["field"], plane, nsat = gpu.sim.build_field(occ_t, abi.FIELD_U16T)
+        assert overflow is None or (nsat > 0) == overflow, nsat
+        if nsat > 0:
+            keep["field_overflow"] = plane
+    if map_slot is not None:
+        keep["map_slot"] = _t(gpu, np.asarray(map_slot, np.int32))
+    st = abi.NavsimState()
+    for k, v in keep.items():
+        setattr(st, k, v.data_ptr())
+    return st, keep
+
+
+_WORLDS = {}
+
+
+def _world(key):
+    """A shared world with its float32 fields and the specification's answer under the world's own parameters, computed once."""
+    if key not in _WORLDS:
+        (E, N, size, seed), params = getattr(spec, key), getattr(spec, key + "_PARAMS")
+        occ, w = spec.random_world(E, N, size, seed)
+        fields = ref.build_dt(occ)
+        _WORLDS[key] = (occ, w, fields, params, spec.plan(spec.config(E, size, N), fields, w, params))
+    return _WORLDS[key]
+
+
+# ---- a. single calls -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", [abi.FIELD_F32, abi.FIELD_U16T])
+def test_base_world_equals_the_spec(gpu, fmt):
+    """E = 5, 100 x 100 maps, six pedestrians, 5 x 9 = 45 candidates (19 idle lanes), T = 6: defaults, a skip mask, a sub-goal
+    against NULL, pedestrians switched off, and the call without the per-candidate arrays."""
+    occ, w, fields, params, want = _world("BASE")
+    E, N, size, _ = spec.BASE
+    cfg = spec.config(E, size, N, field_format=fmt)
+    st, keep = _device_state(gpu, cfg, occ, w)
+    _same(_call(gpu, cfg, st, params), want, "base")
+    dev = _call(gpu, cfg, st, params, with_scores=False)
+    _same(dev, want, "without scores", keys=KEYS[:5])
+    _untouched(dev, ("scores", "first_hit"))
+    skip = np.array([0, 1, 0, 0, 1], np.uint8)
+    _same(_call(gpu, cfg, st, params, skip=skip), spec.plan(cfg, fields, w, params, skip=skip), "skip")
+    rng = np.random.default_rng(3)
+    sub = rng.uniform(-2.0, 2.0, (E, 2)).astype(np.float32)
+    with_sub = spec.plan(cfg, fields, w, params, subgoal=sub)
+    assert (with_sub["scores"] != want["scores"]).any()
+    _same(_call(gpu, cfg, st, params, subgoal=sub), with_sub, "sub-goal")
+    off = dict(params, use_peds=0)
+    want_off = spec.plan(cfg, fields, w, off)
+    assert (want_off["first_hit"] != want["first_hit"]).any()
+    _same(_call(gpu, cfg, st, off), want_off, "use_peds = 0")
+    for what, p in (("default body", dict(n_v=5, n_w=9, horizon=6)),
+                    ("four discs, other weights", dict(params, body_offset=(0.2, 0.0, -0.2, -0.4), body_radius=0.15, margin=0.0,
+                                                       w_progress=-1.0, w_heading=2.0, w_clearance=0.0, w_speed=-0.5, clearance_cap=0.4)),
+                    ("all weights zero", dict(params, w_progress=0.0, w_heading=0.0, w_clearance=0.0, w_speed=0.0))):
+        _same(_call(gpu, cfg, st, p), spec.plan(cfg, fields, w, p), what)
+
+
+def test_the_maxima(gpu):
+    """16 x 32 = 512 candidates (eight wavefronts), T = 32, N = 64 (32 KB of pedestrian positions in LDS), E = 3."""
+    occ, w, fields, params, want = _world("MAXIMA")
+    E, N, size, _ = spec.MAXIMA
+    cfg = spec.config(E, size, N, field_format=abi.FIELD_U16T)
+    st, keep = _device_state(gpu, cfg, occ, w)
+    _same(_call(gpu, cfg, st, params), want, "maxima")
+    ragged = dict(w, n_peds=np.array([64, 0, 33], np.int32))
+    st, keep = _device_state(gpu, cfg, occ, ragged)
+    _same(_call(gpu, cfg, st, params), spec.plan(cfg, fields, ragged, params), "ragged counts")
+
+
+def test_one_candidate_and_no_pedestrians(gpu):
+    """C = 1; max_peds = 1 with a count of 0; NAVSIM_PED_NONE with the pedestrian arrays absent."""
+    occ, w, fields, params, _ = _world("BASE")
+    E, N, size, _ = spec.BASE
+    cfg = spec.config(E, size, N, field_format=abi.FIELD_U16T)
+    st, keep = _device_state(gpu, cfg, occ, w)
+    for nv, nw in ((1, 1), (1, 9), (5, 1), (16, 4), (3, 32)):
+        p = dict(params, n_v=nv, n_w=nw)
+        _same(_call(gpu, cfg, st, p), spec.plan(cfg, fields, w, p), "%d x %d" % (nv, nw))
+    zero = dict(w, n_peds=np.zeros(E, np.int32))
+    st, keep = _device_state(gpu, cfg, occ, zero)
+    want = spec.plan(cfg, fields, zero, params)
+    _same(_call(gpu, cfg, st, params), want, "N = 0")
+    none = spec.config(E, size, 0, field_format=abi.FIELD_U16T)
+    assert none.ped_model == abi.PED_NONE
+    st, keep = _device_state(gpu, none, occ, w, peds=False)
+    _same(_call(gpu, none, st, params), want, "NAVSIM_PED_NONE")
+
+
+@pytest.mark.parametrize("fmt", [abi.FIELD_F32, abi.FIELD_U16T])
+def test_shared_field_and_permuted_map_slots(gpu, fmt):
+    E, N, size, seed = spec.BASE
+    occ, w = spec.random_world(E, N, size, seed + 50, shared=True)
+    cfg = spec.config(E, size, N, field_format=fmt, shared_field=1)
+    st, keep = _device_state(gpu, cfg, occ[:1], w)
+    want = spec.plan(cfg, ref.build_dt(occ[:1]), w, spec.BASE_PARAMS)
+    assert (want["first_hit"] != 0).any() and (want["first_hit"] == 0).any()
+    _same(_call(gpu, cfg, st, spec.BASE_PARAMS), want, "shared field")
+    occ, w, fields, params, want = _world("BASE")
+    perm = np.array([3, 0, 4, 1, 2])
+    stored = np.empty_like(occ); stored[perm] = occ                            # arena e's map lies in slot perm[e]
+    cfg = spec.config(E, size, N, field_format=fmt)
+    st, keep = _device_state(gpu, cfg, stored, w, map_slot=perm)
+    _same(spec.plan(cfg, ref.build_dt(stored), w, params, map_slot=perm), want, "the specification's own slot table")
+    _same(_call(gpu, cfg, st, params), want, "permuted slots")
+
+
+def test_saturated_packed_field_with_its_overflow_plane(gpu):
+    """A 560 x 560 hall: its middle lies further than 255 cells from every wall, which the packed field stores saturated -- the
+    static clearance there comes from the float32 overflow plane.  With clearance_cap = 20 m the chosen clearance IS that value."""
+    size = 560
+    occ = np.ones((1, size, size), np.uint8)
+    occ[0, 5:size - 5, 5:size - 5] = 0
+    fields = ref.build_dt(occ)
+    assert fields.max() >= 270.0
+    w = dict(robot_pose=np.array([[14.0, 14.1, 1.0], [3.0, 4.0, -2.0], [13.0, 15.0, 4.0]]), robot_goal=np.array([[25.0, 24.0], [14.0, 14.0], [2.0, 2.0]]),
+             prev_action=np.array([[0.3, 0.1], [0.5, 0.0], [0.0, -0.3]]))
+    p = dict(spec.BASE_PARAMS, clearance_cap=20.0, w_clearance=1.0)
+    for fmt in (abi.FIELD_U16T, abi.FIELD_F32):
+        cfg = spec.config(3, size, 0, field_format=fmt, shared_field=1)
+        st, keep = _device_state(gpu, cfg, occ, w, overflow=(fmt == abi.FIELD_U16T), peds=False)
+        want = spec.plan(cfg, fields, w, p)
+        assert want["clearance"][0] > 255 * 0.05 and want["clearance"][1] < 4.0 and (want["status"] == spec.OK).all()
+        _same(_call(gpu, cfg, st, p), want, "format %d" % fmt)
+
+
+@pytest.mark.parametrize("fmt", [abi.FIELD_F32, abi.FIELD_U16T])
+@pytest.mark.parametrize("rows,size", [(85, 330)])
+def test_map_that_is_not_square(gpu, rows, size, fmt):
+    """map_h = 85, map_w = 330: xy_to_ij clips x by map_h and y by map_w (env.py:1228-1253), the rule clamps the cell into the
+    map after it -- robots beyond x = 85 cells read column 84, in the specification as on the device, and nothing reads outside
+    the field."""
+    E, N = 6, 4
+    occ, w = spec.random_world(E, N, size, 7120, n_obstacles=16, rows=rows)
+    assert occ.shape == (E, rows, size)
+    cfg = spec.config(E, size, N, map_h=rows, map_w=size, field_format=fmt)
+    st, keep = _device_state(gpu, cfg, occ, w, overflow=None)
+    want = spec.plan(cfg, ref.build_dt(occ), w, spec.BASE_PARAMS)
+    assert (w["robot_pose"][:, 0] > rows * 0.05).any() and (want["first_hit"] != 0).any() and (want["first_hit"] == 0).any()
+    _same(_call(gpu, cfg, st, spec.BASE_PARAMS), want, "%d x %d cells" % (rows, size))
+    tall = np.ascontiguousarray(occ.transpose(0, 2, 1))                         # 330 rows x 85 columns
+    wt = dict(w, robot_pose=w["robot_pose"][:, [1, 0, 2]].copy(), robot_goal=w["robot_goal"][:, ::-1].copy())
+    wt["ped_pose"] = w["ped_pose"][:, :, [1, 0, 2]].copy()
+    cfg = spec.config(E, size, N, map_h=size, map_w=rows, field_format=fmt)
+    st, keep = _device_state(gpu, cfg, tall, wt, overflow=None)
+    _same(_call(gpu, cfg, st, spec.BASE_PARAMS), spec.plan(cfg, ref.build_dt(tall), wt, spec.BASE_PARAMS), "%d x %d cells" % (size, rows))
+
+
+def test_wheel_actions(gpu):
+    occ, w, fields, params, twist = _world("BASE")
+    E, N, size, _ = spec.BASE
+    cfg = spec.config(E, size, N, field_format=abi.FIELD_U16T, action_kind=abi.ACTION_WHEELS)
+    st, keep = _device_state(gpu, cfg, occ, w)
+    want = spec.plan(cfg, fields, w, params)
+    _eq(want["twist"], twist["twist"], "prev_action is a twist whatever the action's form")
+    assert (want["action"] != want["twist"]).any()
+    v, om = want["twist"][:, 0], want["twist"][:, 1]
+    r, track = cfg.wheel_radius, cfg.wheel_track
+    assert np.allclose(r * (want["action"][:, 0] + want["action"][:, 1]) * 0.5, v, atol=1e-12)
+    assert np.allclose(r * (want["action"][:, 1] - want["action"][:, 0]) / track, om, atol=1e-12)
+    _same(_call(gpu, cfg, st, params), want, "wheels")
+
+
+# ---- b. refusals -----------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_device_alone(gpu):
+    occ, w, fields, params, want = _world("BASE")
+    E, N, size, _ = spec.BASE
+    cfg = spec.config(E, size, N, field_format=abi.FIELD_U16T)
+    st, keep = _device_state(gpu, cfg, occ, w)
+
+    def refused(rc, c=cfg, s=st, **p):
+        _untouched(_call(gpu, c, s, dict(params, **p), want_rc=rc, n_out=E))
+
+    nan, inf = float("nan"), float("inf")
+    for p in (dict(acc_lin=nan), dict(acc_rot=-1.0), dict(body_radius=inf), dict(ped_radius=-0.1), dict(margin=nan),
+              dict(clearance_cap=-1.0), dict(w_progress=inf), dict(w_heading=nan), dict(w_clearance=-inf), dict(w_speed=nan),
+              dict(body_offset=(0.0, nan))):
+        refused(abi.E_ARG, **p)
+    for k, bad in (("n_w", 33), ("n_w", 0), ("horizon", 0), ("horizon", 33)):
+        p2 = _params(gpu, cfg, params); setattr(p2, k, bad)
+        _untouched(_call(gpu, cfg, st, p2, want_rc=abi.E_ARG, n_cand=45))
+    for k, bad in (("n_v", 0), ("n_v", 17), ("n_discs", 0), ("n_discs", 5), ("horizon", -1)):
+        p2 = _params(gpu, cfg, params); setattr(p2, k, bad)
+        _untouched(_call(gpu, cfg, st, p2, want_rc=abi.E_ARG, n_cand=45))        # (the buffers are sized by a valid count)
+    for k, bad in (("n_envs", -1), ("map_h", 0), ("map_w", 0), ("max_peds", 65), ("action_kind", 5)):
+        c2 = cfg.copy(); setattr(c2, k, bad)
+        refused(abi.E_ARG, c=c2)
+    for k in ("robot_pose", "robot_goal", "prev_action", "field", "n_peds", "ped_pose", "ped_vel"):
+        s2 = abi.NavsimState()
+        for name, v in keep.items():
+            setattr(s2, name, None if name == k else v.data_ptr())
+        refused(abi.E_ARG, s=s2)
+    shared = cfg.copy(); shared.shared_field = 1
+    s2, keep2 = _device_state(gpu, cfg, occ, w, map_slot=np.arange(E))
+    refused(abi.E_ARG, c=shared, s=s2)
+    fmt = cfg.copy(); fmt.field_format = 9
+    refused(abi.E_UNSUPPORTED, c=fmt)
+    _same(_call(gpu, cfg, st, params), want, "and then the call goes through")
+
+
+# ---- c. closed loop through NavGymEnv ----------------------------------------------------------------------------------------------
+def _env(**kw):
+    import nav_gym_amd
+    from nav_gym_amd import registry
+    ranges = dict(nav_gym_amd.DEFAULT_KWARGS["env_param_range"], obstacle_number=([4, 4], "int"), obstacle_width=([0.3, 0.5], "float"),
+                  num_humans=([3, 3], "int"))
+    base = dict(num_envs=16, map_size=100, n_beams=64, seed=7, plan_paths=False, min_goal_dist=2.0, max_goal_dist=4.0,
+                indoor_ratio=0.0, pedestrian_model="sfm", max_episode_steps=9, local_planner="dwa",
+                local_planner_params=dict(spec.SMALL, horizon=6), env_param_range=ranges)
+    base.update(kw)
+    return registry.make("NavGym-v0", **base)
+
+
+def _from_device_state(env, skip=None):
+    """The specification on the environment's state read back from the device (the maps through their occupancy); with
+    goal_path=True the target is the sub-goal the device's goal path returned (that call has its own test)."""
+    sim = env.sim
+    names = ["robot_pose", "robot_goal", "prev_action"] + (["n_peds", "ped_pose", "ped_vel"] if sim.cfg.ped_model != abi.PED_NONE else [])
+    s = sim.numpy_state(*names)
+    occ = np.stack([sim.occupancy(e) for e in range(env.num_envs)])
+    sub = env.goal_path()["subgoal"] if env.goal_path_on else None
+    if sub is not None:
+        sub = (sub if isinstance(sub, np.ndarray) else sub.cpu().numpy()).reshape(env.num_envs, 2)
+    return spec.plan(sim.cfg, ref.build_dt(occ), s, dict(env.local_planner_params or {}), subgoal=sub, skip=skip)
+
+
+def _check(env, h, what, skip=None):
+    dev = {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in h.items()}
+    want = _from_device_state(env, skip=skip)
+    _same(dev, want, what, keys=KEYS[:5])
+    return want
+
+
+@pytest.mark.parametrize("path", ["same_step", "next_step", "reset_mask", "goal_path"])
+def test_closed_loop_through_the_env(gpu, path):
+    """16 arenas, 60 steps driven by the planner's own action, episodes of at most 9 steps: after every step info['planner']
+    equals the specification on the state read back, and last step's dict is still intact."""
+    kw = dict(same_step={}, next_step=dict(autoreset_mode="next_step"), reset_mask=dict(auto_reset=False),
+              goal_path=dict(goal_path=True, pedestrian_model="none"))[path]
+    env = _env(**kw)
+    E = env.num_envs
+    env.reset()
+    plan = env.planner_action()
+    _check(env, plan, "after reset()")
+    assert set(plan) == {"action", "twist", "clearance", "best", "status"}
+    ptrs, prev, moved, blocked, skipped, resets = set(), None, 0, 0, 0, 0
+    for t in range(60):
+        _, _, done, info = env.step(plan["action"])
+        plan = info["planner"]
+        assert plan is env.planner_action()
+        ptrs.add(plan["action"].data_ptr())
+        done = done.cpu().numpy().astype(np.uint8)
+        want = _check(env, plan, "step %d" % t, skip=done if path == "next_step" else None)
+        moved += int((want["twist"][:, 0] > 0).sum())
+        blocked += int((want["status"] == spec.BLOCKED).sum())
+        skipped += int((want["status"] == 0).sum())
+        resets += int(done.sum())
+        if prev is not None:                                                     # the pair lifetime: last step's rows are intact
+            for k in prev[1]:
+                _eq(prev[0][k].cpu().numpy(), prev[1][k], "step %d's %s after step %d" % (t - 1, k, t))
+        prev = (plan, {k: plan[k].cpu().numpy().copy() for k in plan})
+        if path == "reset_mask" and done.any():
+            env.reset(mask=done.astype(bool))
+            plan = env.planner_action()
+            ptrs.add(plan["action"].data_ptr())                                  # (where every step ends an episode somewhere, the
+            _check(env, plan, "after reset(mask) at step %d" % t)                #  steps see one set and the resets the other)
+            prev = None                                                          # (a reset takes a set of buffers like a step does)
+    print(path, dict(moved=moved, blocked=blocked, skipped=skipped, resets=resets))
+    assert len(ptrs) == 2 and moved > 60 and resets >= E and (path != "next_step" or skipped > 0)
+    env.close()
+
+
+def test_single_environment_returns_numpy(gpu):
+    env = _env(num_envs=1)
+    env.reset()
+    plan = env.planner_action()
+    for t in range(3):
+        _, _, done, info = env.step(plan["action"])
+        plan = info["planner"]
+        assert plan is env.planner_action()
+        assert isinstance(plan["action"], np.ndarray) and plan["action"].shape == (2,) and plan["action"].dtype == np.float64
+        assert isinstance(plan["clearance"], np.float32) and isinstance(plan["best"], np.int32) and isinstance(plan["status"], np.uint8)
+        want = _from_device_state(env)
+        for k in KEYS[:5]:
+            a, b = np.asarray(plan[k]), want[k][0]
+            assert a.tobytes() == np.asarray(b).tobytes(), k
+    env.close()
+
+
+def test_off_by_default(gpu):
+    env = _env(local_planner=None, local_planner_params=None)
+    env.reset()
+    _, _, _, info = env.step(np.zeros((16, 2)))
+    assert "planner" not in info and env.sim.dwa_buf is None and env.sim.dwa_blob is None and env.sim.dwa_params is None
+    with pytest.raises(RuntimeError):
+        env.planner_action()
+    with pytest.raises(RuntimeError):
+        env.sim.dwa()
+    env.close()
