@@ -128,11 +128,15 @@ __device__ __forceinline__ void beam_dir_k(const navsim_config& c, const double*
 }
 
 // the t = 0 sample of calc_range is the origin cell for every beam: take it once per scan
+// xy_to_ij clips the x index against map_h and the y index against map_w (env.py:1244-1247), so on a square map the origin
+// cell lies in the map; on a non-square map a pose outside the map can keep a column >= map_w or a row >= map_h, and
+// calc_range's first sample then leaves the map: every beam returns max_range, and the field is not read
 template <int RULE, typename Field>
-__device__ __forceinline__ void first_probe(const Field& field, int i0, int j0, float max_range,
+__device__ __forceinline__ void first_probe(const Field& field, int map_h, int map_w, int i0, int j0, float max_range,
                                             float& t1, float& r_all) {
     t1 = 0.0f; r_all = -1.0f;
-    typename Field::raw_t raw0 = field.load(i0, j0);               // origin is clipped into the map
+    if (i0 >= map_w || j0 >= map_h) { r_all = max_range; return; } // (never negative: xy_to_ij clips at 0)
+    typename Field::raw_t raw0 = field.load(i0, j0);
     if (field.occupied(raw0)) { r_all = 0.0f; return; }            // sqrtf(0): starts inside an obstacle
     t1 = march_step<RULE>(field.decode(raw0, i0, j0));
     if (!(t1 < max_range)) r_all = max_range;
@@ -1435,7 +1439,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
             sh.lx = (float)sh.rp[0]; sh.ly = (float)sh.rp[1]; sh.lth = (float)sh.rp[2];   // env.py:386
             nv::xy_to_ij_f32(sh.lx, sh.ly, c, sh.i0, sh.j0);                              // env.py:419
             sh.sT = sT; sh.cT = cT;                            // sincos((double)sh.lth): sh.rp[2] is th_new
-            first_probe<RULE>(field, sh.i0, sh.j0, (float)((long long)c.map_h * c.map_w), sh.t1, sh.r_all);
+            first_probe<RULE>(field, c.map_h, c.map_w, sh.i0, sh.j0, (float)((long long)c.map_h * c.map_w), sh.t1, sh.r_all);
             sh.step_key = (unsigned long long)st.episode[e] * 0x100000000ULL +
                           (unsigned long long)(reset_only ? 0 : st.steps[e]) * 2ULL;
             sh.rescan_key = sh.step_key + 1;
@@ -1641,7 +1645,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
                     sh.lx = (float)sh.rp[0]; sh.ly = (float)sh.rp[1]; sh.lth = (float)sh.rp[2];
                     nv::xy_to_ij_f32(sh.lx, sh.ly, c, sh.i0, sh.j0);
                     nv::sincos((double)sh.lth, sh.sT, sh.cT);
-                    first_probe<RULE>(field, sh.i0, sh.j0, (float)((long long)c.map_h * c.map_w), sh.t1, sh.r_all);
+                    first_probe<RULE>(field, c.map_h, c.map_w, sh.i0, sh.j0, (float)((long long)c.map_h * c.map_w), sh.t1, sh.r_all);
                 }
             }
         }
@@ -1680,7 +1684,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
                     sh.lx = (float)at[0]; sh.ly = (float)at[1]; sh.lth = (float)at[2];
                     nv::xy_to_ij_f32(sh.lx, sh.ly, c, sh.i0, sh.j0);
                     nv::sincos((double)sh.lth, sh.sT, sh.cT);
-                    first_probe<RULE>(field, sh.i0, sh.j0, (float)((long long)c.map_h * c.map_w), sh.t1, sh.r_all);
+                    first_probe<RULE>(field, c.map_h, c.map_w, sh.i0, sh.j0, (float)((long long)c.map_h * c.map_w), sh.t1, sh.r_all);
                 }
                 __syncthreads();
                 if (pass == 1 && sh.respawn) n_hist = 0;

@@ -427,9 +427,10 @@ def test_step_rollout_with_split_pedestrian_kernel(gpu, ped_model, N, n_peds):
 # NAVSIM_FUZZ_SEEDS=n widens the sweep for a one-off run (profiles/r03_soak/fuzz_4000.txt: 4000 seeds at the final kernels)
 @pytest.mark.parametrize("seed", list(range(101, 101 + int(os.environ.get("NAVSIM_FUZZ_SEEDS", "16")))))
 def test_step_fuzzed_configurations(gpu, seed):
-    """Random launch shapes: map size (incl. odd), beam count and field of view, stack depth, pedestrian
-    count and model, field format, arena count (which also moves the threads-per-arena heuristic), robot
-    type, turning radius.  Eight steps each, every output and the final state against the oracle."""
+    """Random launch shapes: map height and width (incl. odd, drawn separately) and origin, beam count and field of view,
+    stack depth, pedestrian count and model, field format, arena count (which also moves the threads-per-arena heuristic),
+    robot type, turning radius.  Eight steps each, every output and the final state against the oracle.
+    (The width and the origin are drawn behind every other draw, so a seed keeps the configuration it always had.)"""
     rng = np.random.default_rng(seed)
     size = int(rng.choice([97, 128, 200, 253, 320]))
     E = int(rng.choice([1, 3, 17, 40]))
@@ -451,9 +452,13 @@ def test_step_fuzzed_configurations(gpu, seed):
     if rng.random() < 0.5:
         from nav_gym_amd import robots
         cfg.axle_offset = robots.ROBOTS["husky"]["axle_offset"]
-    occ = gpu.world.make_maps(E, size, seed)
     n_peds = 0 if ped_model == abi.PED_NONE else int(rng.integers(0, N + 1))
-    goal = (1.0, 3.0) if size < 200 else (2.0, 5.0)
+    width = int(rng.choice([97, 128, 200, 253, 320]))
+    cfg.map_w = width
+    cfg.origin_x, cfg.origin_y = [(0.0, 0.0), (-16.0, 32.0), (-7.3, 12.9)][int(rng.integers(0, 3))]
+    occ = np.ascontiguousarray(gpu.world.make_maps(E, max(size, width), seed)[:, :size, :width])
+    occ[:, size - 5:, :] = 1; occ[:, :, width - 5:] = 1          # the border wall along the cut
+    goal = (1.0, 3.0) if min(size, width) < 200 else (2.0, 5.0)
     for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=n_peds, steps=8, seed=seed,
                                                      min_goal_dist=goal[0], max_goal_dist=goal[1], robot_clearance=0.5):
         for k in rout:

@@ -97,6 +97,9 @@ CASES = [
     ("install_replan_without_pedestrians", "square", ("navsim_step_install_replan",) + INSTALL + (8, None), dict(cfg=NO_PEDS), ARG),
     ("install_replan_block_below_plan_words", "tall", ("navsim_step_install_replan",) + INSTALL + (8, None),
      dict(cfg=dict(step_block=64)), UNSUPPORTED),
+    # the lone form (NEXT_STEP without a fallback: an arena regenerates its own world inside the launch) draws square maps only
+    ("install_lone_not_square", "tall", ("navsim_step_install", "stage", "stage_obs", "mark", "ready", None, None),
+     dict(cfg=dict(auto_reset=abi.AUTORESET_NEXT_STEP, regen_min_steps=0, step_block=256), costmap=None), UNSUPPORTED),
     # navsim_prepare launches nothing whatever it is given; a form the configuration cannot use is skipped without an error
     ("prepare_all_forms", "square", ("navsim_prepare",), {}, OK),
     ("prepare_no_part_replan_install_lone", "square", ("navsim_prepare",),
