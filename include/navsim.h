@@ -1281,6 +1281,57 @@ int navsim_dwa(const navsim_config* cfg, const navsim_state* st, const navsim_dw
                const float* subgoal /* [E,2] robot frame, or NULL */, const uint8_t* skip,
                const navsim_dwa_out* out, void* stream);
 
+/* ---- egocentric local map: wall and pedestrian grids per arena in the robot's frame, one launch -------------------------------------
+ * What a CNN policy over a local costmap, a DRL-VO style pedestrian "kinematic map" or the local-map half of the reference's
+ * SOADRL networks (crowd_nav/policy/network_om.py) reads: a G x G picture around the robot, rotated with it, of the clearance to
+ * the walls, the clearance to the nearest pedestrian and the velocity of the pedestrian that covers a cell.  BUILD-DEFINED, all
+ * of it (navsim_crowd_local_map serves only the other simulator's binary CrowdSim.map). */
+#define NAVSIM_LOCAL_MAP_MAX 128
+typedef struct navsim_local_map_params {
+    double  cell;        /* metres per grid cell, finite, > 0 */
+    double  ahead;       /* metres the window's centre lies ahead of the pose origin on the body's x axis, finite */
+    double  cap;         /* metres, finite, > 0: clearances saturate here */
+    double  ped_radius;  /* metres, finite, >= 0 */
+    int32_t size;        /* G, 1 .. NAVSIM_LOCAL_MAP_MAX (128) */
+    int32_t channels;    /* C: 1 walls; 2 + pedestrian clearance; 4 + the covering pedestrian's velocity */
+} navsim_local_map_params;
+
+/* ONE launch (arena x strip of cells, four cells and one 16-byte store per lane and channel where G % 4 == 0;
+ * kernels_local_map.hpp), no device-to-host copy, nothing that blocks, no allocation.  Call it behind the step (and whatever
+ * follows it: navsim_regen, navsim_replan; navsim_ped_observe when its `visible` array is this call's) on the same stream.  It
+ * reads st->robot_pose, the distance field of the arena's map slot (cfg.shared_field, st->map_slot, st->field_overflow; both field
+ * formats) and, with channels > 1, n_peds and ped_pose (channels == 4: ped_vel); it writes EVERY element of out [E,C,G,G] float32,
+ * out[e, ch, r, q].  Everything is float64 in exactly this order, every operation rounded on its own (no fused multiply-add:
+ * DESIGN.md section 4); nv:: are the functions of navmath.hpp / navsim_device.hpp (navmath_ref.h); G = p->size, C = p->channels,
+ * N = cfg.max_peds; min / max as written: min(a, b) = a < b ? a : b, max(a, b) = a > b ? a : b.  Per arena e:
+ *  1. skip && skip[e]: every element of the arena's block out[e] is 0.  Nothing of the arena is read.
+ *  2. the pose.  (rx, ry, th) = robot_pose[e], (s, c) = nv::sincos(th).
+ *  3. the centre of cell (r, q), r counting FORWARD along the body's x axis and q to the LEFT along its y axis:
+ *     u = (((double)r + 0.5) - (double)G * 0.5) * cell + ahead,  v = (((double)q + 0.5) - (double)G * 0.5) * cell,
+ *     wx = rx + (c*u - s*v),  wy = ry + (s*u + c*v).
+ *  4. channel 0, the wall clearance.  fi = (float)((wx - origin_x) / resolution), fj = (float)((wy - origin_y) / resolution):
+ *     the float32 quotients of nv::xy_to_ij, before its clipping.  The cell is INSIDE iff 0 <= fi && fi < (float)map_w &&
+ *     0 <= fj && fj < (float)map_h -- the field has map_w columns for i and map_h rows for j, the addressing of navsim_dwa step 4
+ *     (which clamps i by map_w and j by map_h).  On a map that is not square this DELIBERATELY differs from xy_to_ij's own
+ *     clipping, which clips x by map_h and y by map_w (env.py:1244-1247): a picture of the map shows the map that is stored.
+ *     Inside: (i, j) = ((int)fi, (int)fj), value = (float)min((double)field.at(i, j) * resolution, cap), field.at = the float32
+ *     distance in cells the field of the arena's map slot holds for column i, row j.  Outside: 0 -- the world ends in a wall.
+ *  5. channel 1 (C >= 2), the pedestrian clearance.  Of the pedestrians i < min(n_peds[e], N) -- with `visible` given only those
+ *     with visible[e*N + i] != 0 --: ex = ped_pose[e,i,0] - wx, ey = ped_pose[e,i,1] - wy, d2 = ex*ex + ey*ey; the NEAREST one has
+ *     the least (d2, i).  No pedestrian: value = (float)cap.  Otherwise value = (float)min(max(sqrt(d2) - ped_radius, 0), cap).
+ *  6. channels 2 and 3 (C == 4), the velocity.  Where the nearest pedestrian covers the cell, sqrt(d2) <= ped_radius, its velocity
+ *     (vx, vy) = ped_vel[e,i] in the robot's frame: (float)(c*vx + s*vy) and (float)(c*vy - s*vx).  Elsewhere both are 0.
+ * (The kernel finds the nearest pedestrian over squared distances and takes one sqrt: the rule's own order.)
+ * NAVSIM_E_ARG, before anything touches the device: cfg, st, p or out NULL; st->robot_pose or st->field NULL; channels none of 1,
+ * 2, 4; size outside 1 .. NAVSIM_LOCAL_MAP_MAX; cell or cap not finite or not positive; ahead not finite; ped_radius not finite or
+ * negative; channels > 1 with cfg.ped_model == NAVSIM_PED_NONE, with st->n_peds, ped_pose or ped_vel NULL or with max_peds outside
+ * 1 .. NAVSIM_MAX_PEDS; st->map_slot with cfg.shared_field; n_envs < 0; map_h or map_w < 1; resolution not finite or not positive;
+ * origin_x or origin_y not finite.  NAVSIM_E_UNSUPPORTED: a field_format that is neither NAVSIM_FIELD_F32 nor NAVSIM_FIELD_U16T.
+ * n_envs == 0: NAVSIM_OK, nothing is launched.  `visible` is not read with channels == 1. */
+int navsim_local_map(const navsim_config* cfg, const navsim_state* st, const navsim_local_map_params* p,
+                     const uint8_t* visible /* [E,N] or NULL */, const uint8_t* skip /* [E] or NULL */,
+                     float* out /* [E,C,G,G] */, void* stream);
+
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);
 

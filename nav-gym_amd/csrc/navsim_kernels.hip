@@ -23,6 +23,7 @@
 //   kernels_episode.hpp  episode statistics behind the step;  kernels_ped_observe.hpp  the K nearest pedestrians in line of sight
 //   kernels_goal_path.hpp  distance-to-goal field per arena, the robot's path distance and steering sub-goal (navsim_goal_path)
 //   kernels_dwa.hpp  local planner: a dynamic-window action per arena (navsim_dwa)
+//   kernels_local_map.hpp  egocentric local map: wall and pedestrian grids per arena in the robot's frame (navsim_local_map)
 //   step_plan.hpp        launch geometry of the fused step, the descriptors of a launch and the march-rule dispatch (shared by this
 //                        file and navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
 // Host code of this file, ahead of the C ABI: dispatch_step and the argument checks; the workspaces (Carver and one layout
@@ -49,6 +50,7 @@ namespace {
 #include "kernels_ped_observe.hpp"
 #include "kernels_goal_path.hpp"
 #include "kernels_dwa.hpp"
+#include "kernels_local_map.hpp"
 
 }  // namespace
 #include "step_plan.hpp"
@@ -492,6 +494,20 @@ int launch_dwa(const navsim_config* c, const navsim_state* st, const DwaArgs& a,
     const int C = a.p.n_v * a.p.n_w, block = 64 * ((C + 63) / 64);
     const size_t lds = a.use_peds ? (size_t)a.p.horizon * c->max_peds * sizeof(double2) : 0;
     dwa_kernel<F><<<c->n_envs, block, lds, s>>>(*c, *st, a);
+    return launch_status();
+}
+
+// navsim_local_map: arena x strip of cells, four cells and one 16-byte store per thread and channel where the grid and the
+// output's alignment allow (kernels_local_map.hpp)
+template <typename F>
+int launch_local_map(const navsim_config* c, const navsim_state* st, const LocalMapArgs& a, hipStream_t s) {
+    const int cells = a.p.size * a.p.size;
+    const bool vec = a.p.size % 4 == 0 && ((uintptr_t)a.out & 15u) == 0;
+    const int items = vec ? cells / 4 : cells;
+    const int block = items <= 64 ? 64 : (items <= 128 ? 128 : kLocalMapBlock);
+    const dim3 grid((unsigned)c->n_envs, (unsigned)((items + block - 1) / block));
+    if (vec) local_map_kernel<F, 4><<<grid, block, 0, s>>>(*c, *st, a);
+    else     local_map_kernel<F, 1><<<grid, block, 0, s>>>(*c, *st, a);
     return launch_status();
 }
 
@@ -1562,6 +1578,32 @@ int navsim_dwa(const navsim_config* c, const navsim_state* st, const navsim_dwa_
     if (c->field_format == NAVSIM_FIELD_F32) return launch_dwa<FieldF32>(c, st, a, s);
     if (st->field_overflow) return launch_dwa<FieldU16T>(c, st, a, s);
     return launch_dwa<FieldU16TN>(c, st, a, s);
+}
+
+int navsim_local_map(const navsim_config* c, const navsim_state* st, const navsim_local_map_params* p, const uint8_t* visible,
+                     const uint8_t* skip, float* out, void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !p || !out) return NAVSIM_E_ARG;
+    if (!st->robot_pose || !st->field) return NAVSIM_E_ARG;
+    if (p->channels != 1 && p->channels != 2 && p->channels != 4) return NAVSIM_E_ARG;
+    if (p->size < 1 || p->size > NAVSIM_LOCAL_MAP_MAX) return NAVSIM_E_ARG;
+    if (!std::isfinite(p->cell) || !(p->cell > 0.0) || !std::isfinite(p->cap) || !(p->cap > 0.0)) return NAVSIM_E_ARG;
+    if (!std::isfinite(p->ahead) || !std::isfinite(p->ped_radius) || p->ped_radius < 0.0) return NAVSIM_E_ARG;
+    if (p->channels > 1 && (c->ped_model == NAVSIM_PED_NONE || !st->n_peds || !st->ped_pose || !st->ped_vel || c->max_peds < 1 ||
+                            c->max_peds > NAVSIM_MAX_PEDS))
+        return NAVSIM_E_ARG;
+    if (st->map_slot && c->shared_field) return NAVSIM_E_ARG;
+    if (c->n_envs < 0 || c->map_h < 1 || c->map_w < 1) return NAVSIM_E_ARG;
+    if (!(c->resolution > 0.0) || !std::isfinite(c->resolution) || !std::isfinite(c->origin_x) || !std::isfinite(c->origin_y))
+        return NAVSIM_E_ARG;
+    if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    LocalMapArgs a = {};
+    a.p = *p; a.visible = p->channels > 1 ? visible : nullptr; a.skip = skip; a.out = out;
+    hipStream_t s = (hipStream_t)stream;
+    if (c->field_format == NAVSIM_FIELD_F32) return launch_local_map<FieldF32>(c, st, a, s);
+    if (st->field_overflow) return launch_local_map<FieldU16T>(c, st, a, s);
+    return launch_local_map<FieldU16TN>(c, st, a, s);
 }
 
 const char* navsim_step_kernel_name(void) { return "navsim_step_kernel"; }

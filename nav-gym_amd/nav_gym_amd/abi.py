@@ -249,6 +249,15 @@ class NavsimDwaOut(C.Structure):
 
 DWA_OK, DWA_BLOCKED = 1, 2
 
+# navsim_local_map: the rule's parameters; the output is one float32 array [E, channels, size, size]
+LOCAL_MAP_MAX = 128
+
+
+class NavsimLocalMapParams(C.Structure):
+    _fields_ = [("cell", C.c_double), ("ahead", C.c_double), ("cap", C.c_double), ("ped_radius", C.c_double),
+                ("size", C.c_int32), ("channels", C.c_int32)]
+
+
 ORCA_MAX_AGENTS = 64
 ORCA_MAX_EDGES = 128
 CROWD_MAX_VERTS = 8
@@ -462,6 +471,8 @@ def declare(lib, suffix=""):
         sig("navsim_debug_goal_path_sweeps", [_P])
     if not suffix and hasattr(lib, "navsim_dwa"):                       # (likewise)
         sig("navsim_dwa", [cfgp, stp, C.POINTER(NavsimDwaParams), _P, _P, C.POINTER(NavsimDwaOut), _P])
+    if not suffix and hasattr(lib, "navsim_local_map"):                 # (likewise)
+        sig("navsim_local_map", [cfgp, stp, C.POINTER(NavsimLocalMapParams), _P, _P, _P, _P])
     sig("navsim_reset_obs", [cfgp, stp, iop, _P] + stream)
     sig("navsim_restart", [cfgp, stp, _P] + stream)
     return lib
@@ -480,7 +491,7 @@ EXPORTS = (
     "navsim_crowd_check", "navsim_crowd_angular_map", "navsim_crowd_local_map", "navsim_crowd_orca", "navsim_crowd_agent_step", "navsim_ped_orca", "navsim_ped_orca_walls",
     "navsim_step", "navsim_step_sorted", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
     "navsim_episode_stats_update", "navsim_episode_stats_clear", "navsim_ped_observe",
-    "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps", "navsim_dwa",
+    "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps", "navsim_dwa", "navsim_local_map",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

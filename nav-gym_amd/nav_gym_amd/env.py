@@ -122,6 +122,19 @@ and default to the reference's behaviour for num_envs == 1:
                     the step that resets it.  env.planner_action() returns the same dict, also after reset() / reset(mask).
                     num_envs > 1: torch views with the lifetime below; num_envs == 1: NumPy values from one device -> host copy.
                     None (default): nothing is allocated or launched.
+    observe_local_map  G (1 .. 128): an egocentric grid map per arena, one launch behind the step (navsim_local_map; what a CNN
+                    policy over a local costmap or a DRL-VO style pedestrian map reads) -- info['local_map'] = float32
+                    [E, C, G, G] in the robot's frame, row r counting forward along the body's x axis and column q to its left,
+                    the window's centre `ahead` metres in front of the pose origin: channel 0 the clearance to the walls (metres,
+                    saturated at `cap`, 0 outside the map), channel 1 the clearance to the nearest pedestrian's disc, channels 2
+                    and 3 the robot-frame velocity of the pedestrian that covers the cell (0 elsewhere).  local_map_params
+                    overrides sim.local_map_defaults (cell 0.1 m, ahead 0, cap 2 m, ped_radius 0.3 m, channels 4 with a
+                    pedestrian model and 1 without); visible_only=True (needs observe_humans) counts only the pedestrians that
+                    launch found in line of sight.  The map describes the state the returned observation row describes; under
+                    next-step auto-reset an arena whose `done` is set is skipped (all 0) until the step that resets it;
+                    info['final_observation'] carries no map.  env.local_map() returns the same tensor, also after reset() /
+                    reset(mask).  num_envs > 1: a torch tensor with the lifetime below; num_envs == 1: a NumPy array [C, G, G]
+                    from one device -> host copy.  None (default): nothing is allocated or launched.
     reset(mask)     reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
                     [num_envs]; the others keep their state and their rows.  On the pipelined reset path the masked arenas install
                     their staged worlds in one launch: the same state and rows as with pregen_pipeline=0.
@@ -260,7 +273,7 @@ class NavGymEnv(_EnvBase):
                  regen_min_steps=0, pregen_pipeline=None, pregen_stage_cap=None, autoreset_mode="same_step",
                  final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None,
                  episode_stats=False, observe_humans=None, observe_params=None, goal_path=False, goal_path_params=None,
-                 local_planner=None, local_planner_params=None):
+                 local_planner=None, local_planner_params=None, observe_local_map=None, local_map_params=None):
         # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
         self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
         from . import lib
@@ -478,6 +491,29 @@ class NavGymEnv(_EnvBase):
         self.local_planner_params = None if local_planner_params is None else dict(local_planner_params)
         self._planner_np = None                             # num_envs == 1: the latest row as NumPy values
         self._planner_views = {}                            # per buffer parity: the views info['planner'] hands out
+        # local map (navsim_local_map): a G x G grid per arena in the robot's frame, one launch behind the step
+        if local_map_params is not None and observe_local_map is None:
+            raise ValueError("local_map_params needs observe_local_map=G")
+        for k in (local_map_params or {}):
+            if k not in _simmod.LOCAL_MAP_KEYS and k != "visible_only":
+                raise ValueError("unknown key %r in local_map_params (known: %s, visible_only; the size is observe_local_map)"
+                                 % (k, ", ".join(_simmod.LOCAL_MAP_KEYS)))
+        if observe_local_map is not None:
+            if not (isinstance(observe_local_map, numbers.Integral) and not isinstance(observe_local_map, bool) and
+                    1 <= observe_local_map <= abi.LOCAL_MAP_MAX):
+                raise ValueError("observe_local_map must be None or an int in 1 .. %d, not %r" % (abi.LOCAL_MAP_MAX, observe_local_map))
+            channels = (local_map_params or {}).get("channels", _simmod.local_map_defaults(cfg)["channels"])
+            if channels not in (1, 2, 4):
+                raise ValueError("local_map_params: channels must be 1, 2 or 4, not %r" % (channels,))
+            if channels > 1 and cfg.ped_model == abi.PED_NONE:
+                raise ValueError("local_map_params: channels=%d needs pedestrians: pedestrian_model=%r with at most %d of them "
+                                 "has none" % (channels, pedestrian_model, nh_hi))
+            if (local_map_params or {}).get("visible_only") and self.observe_humans is None:
+                raise ValueError("local_map_params: visible_only=True needs observe_humans=K")
+        self.observe_local_map = None if observe_local_map is None else int(observe_local_map)
+        self.local_map_params = None if local_map_params is None else dict(local_map_params)
+        self._local_map_visible = bool((local_map_params or {}).get("visible_only"))
+        self._local_map_np = None                           # num_envs == 1: the latest map as a NumPy array
         self.cfg = cfg
         self.sim = None
         self._choose_reset_path(pregen_pipeline, plain_cap=cfg.regen_cap)      # (without the pipeline: the library's default cap)
@@ -599,6 +635,8 @@ class NavGymEnv(_EnvBase):
                 self._goal_path(rebuild=m.to(self.sim.device).ne(0).to(torch.uint8).contiguous())
             if self.local_planner:
                 self._plan()
+            if self.observe_local_map:
+                self._local_map()
             return self._obs_dict()
         self._bool = torch.bool
         from . import sim as simmod
@@ -632,6 +670,9 @@ class NavGymEnv(_EnvBase):
                 self._goal_all = torch.ones(self.num_envs, dtype=torch.uint8, device=dev)
             if self.local_planner:
                 self.sim.enable_dwa(self.local_planner_params, robot_type=self.robot_type)
+            if self.observe_local_map:
+                self.sim.enable_local_map(self.observe_local_map, {k: v for k, v in (self.local_map_params or {}).items()
+                                                                   if k != "visible_only"})
         elif "policy_prev_actions" in self.sim.t:
             self.sim.t["policy_prev_actions"].zero_()           # env.py:739
         self._episode_batch += 1
@@ -668,6 +709,8 @@ class NavGymEnv(_EnvBase):
             self._goal_path(rebuild=self._goal_all)
         if self.local_planner:
             self._plan()
+        if self.observe_local_map:
+            self._local_map()
         return self._obs_dict()
 
     @property
@@ -761,6 +804,8 @@ class NavGymEnv(_EnvBase):
             goal = self._goal_path()
         if self.local_planner:                             # behind the goal path: its sub-goal is the planner's target
             plan = self._plan()
+        if self.observe_local_map:                         # behind navsim_ped_observe: its visible array may be this call's
+            local = self._local_map()
         obs = self._obs_dict()
         # the LAST observation of an episode that ended in this step (env.py:700-728 returns it with done = True): under
         # same-step auto-reset the row above already is the next episode's first one and the terminal one rides in info;
@@ -787,6 +832,8 @@ class NavGymEnv(_EnvBase):
                 info["goal_path"] = goal
             if self.local_planner:
                 info["planner"] = plan
+            if self.observe_local_map:
+                info["local_map"] = local
             return obs, float(out["reward"][0].item()), done, info
         # (views of the buffers the kernel wrote, made ONCE per buffer parity: a step of 4096 arenas is 95 us on the device, and
         #  every tensor slice or .view() costs the host 3-5 us -- round 6 measured 42 -> 36 M env-steps/s through this method
@@ -822,6 +869,8 @@ class NavGymEnv(_EnvBase):
             info["goal_path"] = goal
         if self.local_planner:
             info["planner"] = plan
+        if self.observe_local_map:
+            info["local_map"] = local
         return obs, out["reward"], done, info
 
     def _observe(self):
@@ -876,6 +925,27 @@ class NavGymEnv(_EnvBase):
         if v is None:
             v = self._planner_views[self.sim.cur] = {k: out[k] for k in self._PLANNER_KEYS}
         return v
+
+    def _local_map(self):
+        """navsim_local_map behind whatever was queued (navsim_ped_observe included: with visible_only the `visible` array of the
+        current buffer set is the pedestrians that count), on the same stream: the map of the state the current observation rows
+        describe.  Next-step auto-reset: an arena whose `done` is set is skipped (all 0) until the call that resets it."""
+        next_step = self.auto_reset and self.autoreset_mode == "next_step"
+        vis = self.sim.ped_obs_buf[self.sim.cur]["visible"] if self._local_map_visible else None
+        out = self.sim.local_map(skip=self.sim.out["done"] if next_step else None, visible=vis)
+        if self.num_envs == 1:
+            self._local_map_np = out[0].cpu().numpy()
+            return self._local_map_np
+        return out
+
+    def local_map(self):
+        """What info['local_map'] of the latest step() holds (observe_local_map=G); valid after reset() and reset(mask) too:
+        float32 [E, C, G, G] in the robot's frame (num_envs == 1: a NumPy array [C, G, G])."""
+        if not self.observe_local_map:
+            raise RuntimeError("local_map() needs NavGymEnv(observe_local_map=G)")
+        if self.sim is None or self.sim.local_map_buf is None:
+            raise RuntimeError("call reset() before local_map()")
+        return self._local_map_np if self.num_envs == 1 else self.sim.local_map_buf[self.sim.cur]
 
     def planner_action(self):
         """What info['planner'] of the latest step() holds (local_planner='dwa'); valid after reset() and reset(mask) too:
@@ -1125,6 +1195,8 @@ class NavGymEnv(_EnvBase):
             self._goal_path(rebuild=self._goal_all)
         if self.local_planner:                             # (likewise)
             self._plan()
+        if self.observe_local_map:                         # (likewise)
+            self._local_map()
         torch.cuda.synchronize(self.sim.device)
         self._obs_dict()
 

@@ -409,6 +409,31 @@ def dwa_layout(E, C_, scores=False):
     return out
 
 
+LOCAL_MAP_KEYS = ("cell", "ahead", "cap", "ped_radius", "channels")
+
+
+def local_map_defaults(cfg):
+    """The parameters of navsim_local_map as a dict (the grid's size apart, which is asked for): 0.1 m cells around the pose
+    origin, clearances counted up to 2 m, 0.3 m pedestrian discs; four channels -- walls, pedestrian clearance, the covering
+    pedestrian's velocity -- in a world with a pedestrian model, the wall channel alone in one without."""
+    return dict(cell=0.1, ahead=0.0, cap=2.0, ped_radius=0.3, channels=1 if cfg.ped_model == abi.PED_NONE else 4)
+
+
+def local_map_params(cfg, params=None, size=None):
+    """abi.NavsimLocalMapParams of local_map_defaults(cfg) overridden by the dict `params`, with `size` cells a side; an unknown
+    key raises ValueError."""
+    d = local_map_defaults(cfg)
+    for k, v in (params or {}).items():
+        if k not in d:
+            raise ValueError("unknown local map parameter %r (known: %s)" % (k, ", ".join(LOCAL_MAP_KEYS)))
+        d[k] = v
+    p = abi.NavsimLocalMapParams()
+    for k in LOCAL_MAP_KEYS:
+        setattr(p, k, int(d[k]) if k == "channels" else float(d[k]))
+    p.size = 0 if size is None else int(size)
+    return p
+
+
 def ped_observation_layout(E, K, N):
     """Where navsim_ped_observation's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in
     abi.PED_OBSERVATION's order, each start rounded up to 16 bytes, and a last entry whose end byte is the blob's size."""
@@ -595,6 +620,8 @@ class NavSim(object):
         self.goal_buf, self._goal_args = None, {}
         # local planner (enable_dwa): the parameters, two sets of outputs (they flip with self.cur) and navsim_dwa's arguments
         self.dwa_params, self.dwa_buf, self.dwa_blob, self._dwa_args = None, None, None, {}
+        # local map (enable_local_map): the parameters and two output tensors (they flip with self.cur)
+        self.local_map_params, self.local_map_buf, self._local_map_args = None, None, None
         self.t = {}
         self.st = abi.NavsimState()
         for name, (dtype, shape) in abi.STATE_LAYOUT.items():
@@ -1640,6 +1667,35 @@ class NavSim(object):
         """The current set of dwa()'s outputs as NumPy arrays, from ONE device -> host copy."""
         blob = self.dwa_blob[self.cur].cpu().numpy()
         return {k: blob[lo:hi].view(d).reshape(shape) for k, d, lo, hi, shape in self._dwa_layout[:-1]}
+
+    # ---- egocentric local map: wall and pedestrian grids per arena in the robot's frame, one launch behind the step
+    # (include/navsim.h navsim_local_map)
+    def enable_local_map(self, size, params=None):
+        """Allocates two outputs float32 [E, C, size, size] (they flip with self.cur like everything a step returns).  params: an
+        abi.NavsimLocalMapParams (its own size counts), a dict of overrides of local_map_defaults(cfg), or None."""
+        import torch
+        p = params if isinstance(params, abi.NavsimLocalMapParams) else local_map_params(self.cfg, params, size)
+        if not 1 <= p.size <= abi.LOCAL_MAP_MAX:
+            raise ValueError("the local map's size must lie in 1 .. %d, not %d" % (abi.LOCAL_MAP_MAX, p.size))
+        if p.channels not in (1, 2, 4):
+            raise ValueError("the local map has 1, 2 or 4 channels, not %d" % p.channels)
+        self.local_map_params = p
+        self.local_map_buf = [torch.zeros((self.cfg.n_envs, p.channels, p.size, p.size), dtype=torch.float32, device=self.device)
+                              for _ in range(2)]
+        self._local_map_args = (C.byref(self.cfg), C.byref(self.st), C.byref(p))
+
+    def local_map(self, skip=None, visible=None):
+        """navsim_local_map of the current state on the current stream: one launch, no copy, no allocation.  skip: uint8 / bool
+        [E], arenas that are not read and come back all 0; visible: uint8 / bool [E,N], the pedestrians that count
+        (ped_observe()'s 'visible'; None: all of them).  Returns the current tensor [E, C, G, G], intact through the next step."""
+        if self.local_map_buf is None:
+            raise RuntimeError("call enable_local_map() first")
+        a = self._local_map_args
+        out = self.local_map_buf[self.cur]
+        rc = self.lib.navsim_local_map(a[0], a[1], a[2], _ptr(visible), _ptr(skip), out.data_ptr(), _stream())
+        if rc:
+            check(rc, "navsim_local_map")
+        return out
 
     def occupancy(self, e=0):
         """uint8 [H, W] occupancy grid (1 = occupied) of arena e, read back from its distance field

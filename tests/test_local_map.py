@@ -1,0 +1,354 @@
+"""CPU: the egocentric local map (include/navsim.h navsim_local_map) -- the specification of tests/local_map_spec.py against a
+plain per-cell loop, orientation scenes whose pictures are worked out by hand from the rule's words, the population of the worlds
+the device test uses, the entry's place in the C ABI, its argument refusals and the keywords on NavGymEnv.  The device against
+that specification is tests/test_gpu_local_map.py."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import dwa_spec
+import local_map_spec as spec
+import ref
+from nav_gym_amd import abi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---- the specification against a plain loop ---------------------------------------------------------------------------------------
+def _sincos(th):
+    x = np.array([th], np.float64)
+    return np.float64(ref.math_fn(spec.SIN, x)[0]), np.float64(ref.math_fn(spec.COS, x)[0])
+
+
+def _loop(cfg, fields, w, p, G, visible=None, skip=None):
+    """The header's steps, one cell and one pedestrian at a time, on NumPy float64 / float32 scalars."""
+    f8, f4 = np.float64, np.float32
+    E, N, C_ = cfg.n_envs, cfg.max_peds, p["channels"]
+    out = np.full((E, C_, G, G), np.nan, np.float32)
+    for e in range(E):
+        if skip is not None and skip[e]:
+            out[e] = 0
+            continue
+        rx, ry, th = (f8(x) for x in w["robot_pose"][e])
+        s, c = _sincos(th)
+        for r in range(G):
+            for q in range(G):
+                u = ((f8(r) + f8(0.5)) - f8(G) * f8(0.5)) * f8(p["cell"]) + f8(p["ahead"])
+                v = ((f8(q) + f8(0.5)) - f8(G) * f8(0.5)) * f8(p["cell"])
+                wx, wy = rx + (c * u - s * v), ry + (s * u + c * v)
+                fi, fj = f4((wx - f8(cfg.origin_x)) / f8(cfg.resolution)), f4((wy - f8(cfg.origin_y)) / f8(cfg.resolution))
+                if f4(0) <= fi < f4(cfg.map_w) and f4(0) <= fj < f4(cfg.map_h):
+                    out[e, 0, r, q] = f4(min(f8(fields[e][int(fj), int(fi)]) * f8(cfg.resolution), f8(p["cap"])))
+                else:
+                    out[e, 0, r, q] = 0
+                if C_ == 1:
+                    continue
+                best = None
+                for i in range(min(int(w["n_peds"][e]), N)):
+                    if visible is not None and not visible[e][i]:
+                        continue
+                    ex, ey = f8(w["ped_pose"][e, i, 0]) - wx, f8(w["ped_pose"][e, i, 1]) - wy
+                    d2 = ex * ex + ey * ey
+                    if best is None or d2 < best[0]:
+                        best = (d2, i)
+                if best is None:
+                    out[e, 1:, r, q] = 0
+                    out[e, 1, r, q] = f4(p["cap"])
+                    continue
+                d = np.sqrt(best[0])
+                out[e, 1, r, q] = f4(min(max(d - f8(p["ped_radius"]), f8(0)), f8(p["cap"])))
+                if C_ == 4:
+                    vx, vy = f8(w["ped_vel"][e, best[1], 0]), f8(w["ped_vel"][e, best[1], 1])
+                    cover = d <= f8(p["ped_radius"])
+                    out[e, 2, r, q] = f4(c * vx + s * vy) if cover else 0
+                    out[e, 3, r, q] = f4(c * vy - s * vx) if cover else 0
+    return out
+
+
+def test_spec_equals_a_plain_loop():
+    """E = 2, G = 5: what a vectorisation slip (a transposed broadcast, a wrong axis of argmin) would change."""
+    E, N, size = 2, 3, 60
+    occ, w = dwa_spec.random_world(E, N, size, 8301)
+    w["robot_pose"][1, :2] = (0.1, 2.9)                                         # a window that leaves the map
+    w["ped_pose"][0, 0, :2] = w["robot_pose"][0, :2] + (0.2, 0.1)               # a pedestrian over the window
+    cfg = spec.config(E, size, N)
+    fields = ref.build_dt(occ)
+    vis = np.array([[1, 0, 1], [0, 1, 1]], np.uint8)
+    for p, kw in ((dict(cell=0.2, ahead=0.3, cap=0.5, ped_radius=0.3, channels=4), {}),
+                  (dict(cell=0.2, ahead=0.3, cap=0.5, ped_radius=0.3, channels=4), dict(visible=vis)),
+                  (dict(cell=0.07, ahead=0.0, cap=2.0, ped_radius=0.0, channels=2), dict(skip=[0, 1])),
+                  (dict(cell=0.5, ahead=-0.4, cap=1.0, ped_radius=0.3, channels=1), {})):
+        a, b = spec.local_map(cfg, fields, w, p, 5, **kw), _loop(cfg, fields, w, p, 5, **kw)
+        assert a.dtype == b.dtype == np.float32 and a.shape == b.shape == (E, p["channels"], 5, 5)
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (p, kw)
+    a, info = spec.local_map(cfg, fields, w, dict(cell=0.2, ahead=0.3, cap=0.5, ped_radius=0.3, channels=4), 5, detail=True)
+    assert info["covered"].any() and not info["inside"].all() and info["inside"].any()
+
+
+# ---- orientation scenes: the pictures below are worked out from the rule's words, not from the specification's code ---------------
+# A 6 m hall (120 x 120 cells of 0.05 m, a 3-cell border).  A wall 0.1 m thick at y in [4.0, 4.1) (rows 80, 81) and a pillar of
+# 0.1 m x 0.1 m at x in [2.0, 2.1), y in [3.0, 3.1) (columns 40, 41, rows 60, 61).  The robot stands at (3.02, 3.01); G = 30 cells
+# of 0.1 m: the centre of cell (r, q) lies (r - 14.5) / 10 m ahead and (q - 14.5) / 10 m to the left of it.
+SCENE_G, SCENE_POSE = 30, (3.02, 3.01)
+SCENE = dict(cell=0.1, ahead=0.0, cap=5.0, ped_radius=0.3)
+
+
+def _scene_map():
+    return dwa_spec.hall([(0, dwa_spec.HALL, 80, 82), (40, 42, 60, 62)])
+
+
+def _clear_of_boundaries(th, ahead=0.0):
+    """No cell centre within 1e-6 map cells of a cell boundary (plain Python floats and math.sin / cos: not the rule's code)."""
+    for r in range(SCENE_G):
+        for q in range(SCENE_G):
+            u, v = (r - 14.5) * 0.1 + ahead, (q - 14.5) * 0.1
+            x = SCENE_POSE[0] + math.cos(th) * u - math.sin(th) * v
+            y = SCENE_POSE[1] + math.sin(th) * u + math.cos(th) * v
+            for t in (x / 0.05, y / 0.05):
+                assert abs(t - round(t)) > 1e-6, (r, q, t)
+
+
+def _scene(th, channels=1, peds=(), vels=(), **params):
+    _clear_of_boundaries(th, params.get("ahead", 0.0))
+    w = dwa_spec.scene(SCENE_POSE + (th,), (0.0, 0.0), peds=peds, vels=vels)
+    cfg = spec.config(1, dwa_spec.HALL, len(peds))
+    return spec.local_map(cfg, ref.build_dt(_scene_map()[None]), w, dict(SCENE, channels=channels, **params), SCENE_G)[0]
+
+
+def _zeros(plane):
+    return set(map(tuple, np.argwhere(plane == 0)))
+
+
+def test_wall_to_the_left_at_heading_zero():
+    """Heading 0: forward is +x, left is +y.  The wall's face is 0.99 m to the left: the centres 1.05 m to the left, q = 15 + 10,
+    lie in it (y = 4.06), those at q = 24 (3.96) and q = 26 (4.16) do not -- one zero column.  The pillar is behind: x = 2.07 is
+    0.95 m back, r = 5; y = 3.06 is 0.05 m to the left, q = 15."""
+    m = _scene(0.0)
+    assert m.shape == (1, SCENE_G, SCENE_G)
+    assert _zeros(m[0]) == {(r, 25) for r in range(SCENE_G)} | {(5, 15)}
+    assert m[0, 15, 24] == np.float32(0.05) and m[0, 15, 26] == np.float32(0.1)         # y = 3.96: row 79, one cell from row 80;
+                                                                                        # y = 4.16: row 83, two cells from row 81
+    assert m[0, 15, 15] == pytest.approx(0.9, abs=0.08)                                 # the robot's own cell: the wall, 0.94 m
+
+
+def test_wall_ahead_at_heading_half_pi():
+    """Heading pi / 2: forward is +y, left is -x.  The same wall is now 0.99 m AHEAD -- a zero row r = 25 -- and the pillar, at
+    x = 2.07, lies 0.95 m to the LEFT, q = 24, level with the robot, r = 15.  A mirrored map would show it at q = 5, a transposed
+    one the wall as a column."""
+    m = _scene(math.pi / 2)
+    assert _zeros(m[0]) == {(25, q) for q in range(SCENE_G)} | {(15, 24)}
+    m = _scene(math.pi)                                                                  # and facing -x: the wall to the RIGHT,
+    assert _zeros(m[0]) == {(r, 4) for r in range(SCENE_G)} | {(24, 14)}                 # the pillar 0.95 m ahead, 0.05 m right
+
+
+def test_pedestrian_straight_ahead_carries_its_velocity():
+    """A pedestrian 1 m straight ahead covers the cells whose centres lie within 0.3 m of it: ((r - 24.5)^2 + (q - 14.5)^2) / 100
+    <= 0.09, around r = G / 2 + 1 / cell = 25 (no centre lies on the circle: 36 is no sum of two odd squares)."""
+    disc = {(r, q) for r in range(SCENE_G) for q in range(SCENE_G) if (2 * r - 49) ** 2 + (2 * q - 29) ** 2 <= 36}
+    assert len(disc) == 32 and (24, 14) in disc and (25, 15) in disc and (21, 14) not in disc
+    m = _scene(0.0, 4, peds=[(4.02, 3.01)], vels=[(0.3, -0.2)])
+    for ch in (2, 3):
+        assert set(map(tuple, np.argwhere(m[ch] != 0))) == disc
+    assert _zeros(m[1]) == disc
+    assert all(m[2][rq] == np.float32(0.3) and m[3][rq] == np.float32(-0.2) for rq in disc)       # heading 0: the world's axes
+    assert m[1, 15, 15] == pytest.approx(math.hypot(0.95, 0.05) - 0.3, abs=1e-6)
+    # heading pi / 2, the pedestrian 1 m along +y with the same world velocity: forward speed vy, leftward speed -vx
+    m = _scene(math.pi / 2, 4, peds=[(3.02, 4.01)], vels=[(0.3, -0.2)])
+    for ch in (2, 3):
+        assert set(map(tuple, np.argwhere(m[ch] != 0))) == disc
+    assert all(abs(m[2][rq] + 0.2) < 1e-6 and abs(m[3][rq] + 0.3) < 1e-6 for rq in disc)
+    # two channels: the clearance without the velocity
+    m2, m4 = (_scene(0.0, ch, peds=[(4.02, 3.01)], vels=[(0.3, -0.2)]) for ch in (2, 4))
+    assert m2.shape == (2, SCENE_G, SCENE_G) and np.array_equal(m2, m4[:2])
+
+
+def test_ahead_shifts_the_picture_by_whole_rows():
+    """ahead = 0.5 m with 0.1 m cells: row r of the shifted map is row r + 5 of the other."""
+    kw = dict(peds=[(4.02, 3.01)], vels=[(0.3, -0.2)])
+    a, b = _scene(0.0, 4, **kw), _scene(0.0, 4, ahead=0.5, **kw)
+    assert np.array_equal(b[0, :-5], a[0, 5:])                                  # field cells: the same cell, the same float
+    assert np.allclose(b[1:, :-5], a[1:, 5:], atol=1e-6) and (b[2, :-5] != 0).any()
+    assert _zeros(b[0]) == {(r, 25) for r in range(SCENE_G)} | {(0, 15)}         # the pillar: 0.95 m back is now row 0
+    c = _scene(0.0, 1, ahead=-0.5)
+    assert np.array_equal(c[0, 5:], a[0, :-5])
+
+
+# ---- the shared worlds ------------------------------------------------------------------------------------------------------------
+def test_population_of_the_device_tests_worlds():
+    """What the device comparison needs to mean something, on the specification alone: every branch of the rule is taken."""
+    E, N, size, _ = spec.BASE
+    occ, w = spec.base_world()
+    cfg = spec.config(E, size, N)
+    fields = ref.build_dt(occ)
+    seen = dict(outside=0, wall_zero=0, wall_cap=0, ped_cap=0, covered=0, tied=0, tied_covered=0)
+    for G, cell, ahead, ch in spec.CALLS:
+        m, info = spec.local_map(cfg, fields, w, spec.call_params(cell, ahead, 4), G, detail=True)
+        seen["outside"] += int((~info["inside"]).sum())
+        seen["wall_zero"] += int((info["inside"] & (m[:, 0] == 0)).sum())
+        seen["wall_cap"] += int((m[:, 0] == np.float32(spec.CAP)).sum())
+        seen["ped_cap"] += int((m[:, 1] == np.float32(spec.CAP)).sum())
+        seen["covered"] += int(info["covered"].sum())
+        seen["tied"] += int(info["tied"].sum())
+        seen["tied_covered"] += int((info["tied"] & info["covered"]).sum())
+        assert not (~info["inside"] & (m[:, 0] != 0)).any()
+        if G == 1:
+            assert ch == 4
+    print(seen)
+    assert all(v > 0 for v in seen.values()), seen
+    # the tie decides what the device must write: the two pedestrians' velocities differ, the lower index wins
+    m, info = spec.local_map(cfg, fields, w, spec.call_params(0.1, 0.0, 4), spec.TIE_G, detail=True)
+    h = spec.TIE_G // 2
+    assert info["tied"][spec.TIE_ARENA, h, h] and info["covered"][spec.TIE_ARENA, h, h]
+    assert (m[spec.TIE_ARENA, 2, h, h], m[spec.TIE_ARENA, 3, h, h]) == (np.float32(0.5), np.float32(-0.25))
+    # arenas without pedestrians, and slots behind the count that hold poses and would change the picture if counted
+    assert (w["n_peds"] == 0).any() and info["counted"].tolist() == w["n_peds"].tolist()
+    full = dict(w, n_peds=np.full(E, N, np.int32))
+    big = spec.call_params(0.1, 0.0, 4)
+    assert np.abs(w["ped_pose"][w["n_peds"] < N]).sum() > 0
+    a, b = spec.local_map(cfg, fields, w, big, 64), spec.local_map(cfg, fields, full, big, 64)
+    for e in range(E):
+        assert np.array_equal(a[e], b[e]) == (w["n_peds"][e] == N), e
+    assert (a[1, 1] == np.float32(spec.CAP)).all() and not a[1, 2:].any()         # n_peds == 0: cap and no velocity
+    # the one-cell call outside the map
+    out, info = spec.local_map(cfg, fields, w, spec.call_params(0.1, -2.0, 4), 1, detail=True)
+    assert not info["inside"][0].any() and out[0, 0, 0, 0] == 0 and info["inside"][1:].any()
+
+
+# ---- C ABI ------------------------------------------------------------------------------------------------------------------------
+def _struct_fields(header, name):
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), header, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = []
+    for decl in body.split(";"):
+        if decl.strip():
+            names += [re.match(r"\s*(\w+)", part).group(1) for part in decl.strip().split(None, 1)[1].split(",")]
+    return names
+
+
+def test_symbol_and_structure_in_header_library_and_exports():
+    from nav_gym_amd import lib
+    L = lib.load()
+    header = open(os.path.join(ROOT, "include", "navsim.h")).read()
+    assert abi.ABI_VERSION == 7 and L.navsim_abi_version() == 7
+    assert C.sizeof(abi.NavsimConfig) == 624 == L.navsim_sizeof_config()         # no structure changed its size
+    assert C.sizeof(abi.NavsimState) == L.navsim_sizeof_state() and C.sizeof(abi.NavsimStepIO) == L.navsim_sizeof_step_io()
+    assert re.search(r"\bint navsim_local_map\(", header) and "navsim_local_map" in abi.EXPORTS and hasattr(L, "navsim_local_map")
+    fields = _struct_fields(header, "navsim_local_map_params")
+    assert fields == ["cell", "ahead", "cap", "ped_radius", "size", "channels"]
+    assert [n for n, _ in abi.NavsimLocalMapParams._fields_] == fields
+    assert C.sizeof(abi.NavsimLocalMapParams) == 4 * 8 + 2 * 4
+    assert [getattr(abi.NavsimLocalMapParams, n).offset for n in fields] == [0, 8, 16, 24, 32, 36]
+    assert re.search(r"#define NAVSIM_LOCAL_MAP_MAX\s+128\b", header) and abi.LOCAL_MAP_MAX == 128
+    for step in range(1, 7):                                                     # the rule stands in numbered steps
+        assert re.search(r"^ \*  %d\. " % step, header[header.index("navsim_local_map_params;"):], re.M), step
+
+
+def test_argument_refusals_without_gpu():
+    """Every refusal is decided before anything touches the device: they come back on a machine without one."""
+    from nav_gym_amd import lib, sim
+    L = lib.load()
+    one = (C.c_double * 64)()
+    ptr = C.addressof(one)
+    cfg = lib.default_config(n_envs=2, map_h=100, map_w=100, max_peds=4, ped_model=abi.PED_EXTERNAL)
+    base = ("robot_pose", "field")
+    peds = ("n_peds", "ped_pose", "ped_vel")
+
+    def state(skip=(), **extra):
+        st = abi.NavsimState()
+        for k in base + peds + tuple(extra):
+            setattr(st, k, None if k in skip else ptr)
+        return st
+
+    def params(**kw):
+        p = sim.local_map_params(cfg, None, 16)
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    ref_ = lambda x: None if x is None else C.byref(x)
+    call = lambda c=cfg, s=state(), p=params(), o=ptr: L.navsim_local_map(ref_(c), ref_(s), ref_(p), None, None, o, None)
+    assert call(c=None) == call(s=None) == call(p=None) == call(o=None) == abi.E_ARG
+    for k in base:
+        assert call(s=state(skip=(k,))) == abi.E_ARG, k
+    for k in peds:
+        for ch in (2, 4):
+            assert call(s=state(skip=(k,)), p=params(channels=ch)) == abi.E_ARG, (k, ch)
+    for bad in (0, 3, 5, 8, -1):
+        assert call(p=params(channels=bad)) == abi.E_ARG, bad
+    for bad in (0, -1, 129):
+        assert call(p=params(size=bad)) == abi.E_ARG, bad
+    nan, inf = float("nan"), float("inf")
+    for k, bads in (("cell", (nan, inf, 0.0, -0.1)), ("cap", (nan, inf, 0.0, -1.0)), ("ahead", (nan, inf, -inf)),
+                    ("ped_radius", (nan, inf, -0.01))):
+        for bad in bads:
+            assert call(p=params(**{k: bad})) == abi.E_ARG, (k, bad)
+    for k, bad in (("n_envs", -1), ("map_h", 0), ("map_w", 0), ("max_peds", 0), ("max_peds", 65), ("resolution", 0.0),
+                   ("resolution", nan), ("resolution", -0.05), ("ped_model", abi.PED_NONE)):
+        c2 = cfg.copy(); setattr(c2, k, bad)
+        assert call(c=c2) == abi.E_ARG, (k, bad)
+    shared = cfg.copy(); shared.shared_field = 1
+    assert call(c=shared, s=state(map_slot=1)) == abi.E_ARG
+    fmt = cfg.copy(); fmt.field_format = 7
+    assert call(c=fmt) == abi.E_UNSUPPORTED
+    # nothing to do is not an error and launches nothing -- at the bounds of what is accepted, and with the pedestrian arrays
+    # absent where they are not read
+    empty = cfg.copy(); empty.n_envs = 0
+    assert call(c=empty) == abi.OK
+    assert call(c=empty, p=params(size=128, ped_radius=0.0, ahead=-3.0)) == call(c=empty, p=params(size=1, channels=2)) == abi.OK
+    assert call(c=empty, p=params(channels=1), s=state(skip=peds)) == abi.OK
+    none = empty.copy(); none.ped_model = abi.PED_NONE; none.max_peds = 0
+    assert call(c=none, p=params(channels=1), s=state(skip=peds)) == abi.OK
+    assert call(c=none, p=params(channels=2)) == abi.E_ARG
+
+
+# ---- host wiring ------------------------------------------------------------------------------------------------------------------
+def test_parameter_defaults_and_unknown_keys():
+    from nav_gym_amd import lib, sim
+    cfg = lib.default_config(ped_model=abi.PED_SFM)
+    d = sim.local_map_defaults(cfg)
+    assert d == spec.DEFAULT == dict(cell=0.1, ahead=0.0, cap=2.0, ped_radius=0.3, channels=4) and tuple(d) == sim.LOCAL_MAP_KEYS
+    assert sim.local_map_defaults(lib.default_config(ped_model=abi.PED_NONE))["channels"] == 1
+    p = sim.local_map_params(cfg, dict(cell=0.05, channels=2, ahead=1), 48)
+    assert (p.cell, p.ahead, p.cap, p.ped_radius, p.size, p.channels) == (0.05, 1.0, 2.0, 0.3, 48, 2)
+    with pytest.raises(ValueError, match="cell, ahead, cap, ped_radius, channels"):
+        sim.local_map_params(cfg, dict(resolution=0.1), 16)
+
+
+def test_env_keywords():
+    import copy
+    import pickle
+    import nav_gym_env
+    from nav_gym_amd import registry
+    kw = dict(observe_local_map=32, local_map_params=dict(cell=0.05, ahead=0.5))
+    env = nav_gym_env.make("NavGym-v0", num_envs=3, **kw)
+    assert env.observe_local_map == 32 and env.local_map_params == dict(cell=0.05, ahead=0.5)
+    for twin in (pickle.loads(pickle.dumps(env)), copy.deepcopy(env)):
+        assert twin.observe_local_map == 32 and twin.local_map_params == dict(cell=0.05, ahead=0.5) and twin.num_envs == 3
+    with pytest.raises(RuntimeError, match="reset"):
+        env.local_map()                                    # before reset()
+    with pytest.raises(ValueError, match="needs observe_local_map=G"):             # parameters without the feature
+        nav_gym_env.make("NavGym-v0", num_envs=3, local_map_params=dict(cell=0.05))
+    with pytest.raises(ValueError, match="cell, ahead, cap, ped_radius, channels, visible_only"):
+        nav_gym_env.make("NavGym-v0", num_envs=3, observe_local_map=16, local_map_params=dict(size=4))
+    for bad in (0, 129, 16.0, True, "16"):
+        with pytest.raises(ValueError, match="an int in 1 .. 128"):
+            nav_gym_env.make("NavGym-v0", num_envs=3, observe_local_map=bad)
+    with pytest.raises(ValueError, match="channels must be 1, 2 or 4"):
+        nav_gym_env.make("NavGym-v0", num_envs=3, observe_local_map=16, local_map_params=dict(channels=3))
+    with pytest.raises(ValueError, match="needs pedestrians"):
+        nav_gym_env.make("NavGym-v0", num_envs=3, observe_local_map=16, pedestrian_model="none", local_map_params=dict(channels=2))
+    with pytest.raises(ValueError, match="visible_only=True needs observe_humans"):
+        nav_gym_env.make("NavGym-v0", num_envs=3, observe_local_map=16, local_map_params=dict(visible_only=True))
+    ok = nav_gym_env.make("NavGym-v0", num_envs=3, observe_local_map=16, observe_humans=2, local_map_params=dict(visible_only=True))
+    assert ok.observe_local_map == 16 and ok.observe_humans == 2
+    walls = nav_gym_env.make("NavGym-v0", num_envs=3, observe_local_map=1, pedestrian_model="none")
+    assert walls.observe_local_map == 1
+    plain = nav_gym_env.make("NavGym-v0", num_envs=3)
+    assert plain.observe_local_map is None and plain.local_map_params is None
+    with pytest.raises(RuntimeError, match="observe_local_map=G"):
+        plain.local_map()
+    assert "observe_local_map" not in registry.spec("NavGym-v0")["kwargs"] and "local_map_params" not in registry.spec("NavGym-v0")["kwargs"]
