@@ -1495,9 +1495,7 @@ int navsim_ped_observe(const navsim_config* c, const navsim_state* st, const nav
     a.p = *p; a.out = *out; a.skip = skip;
     a.max_range = (float)((long long)c->map_h * c->map_w);
     hipStream_t s = (hipStream_t)stream;
-    if (c->field_format == NAVSIM_FIELD_F32) return launch_ped_observe<FieldF32>(c, st, a, s);
-    if (st->field_overflow) return launch_ped_observe<FieldU16T>(c, st, a, s);
-    return launch_ped_observe<FieldU16TN>(c, st, a, s);
+    return with_field(c, st, [&](auto field) { return launch_ped_observe<typename decltype(field)::type>(c, st, a, s); });
 }
 
 size_t navsim_goal_field_bytes(const navsim_config* c) {
@@ -1536,9 +1534,7 @@ int navsim_goal_path(const navsim_config* c, const navsim_state* st, const navsi
     f.band_cost = p->band_cost;
     f.n_envs = c->n_envs; f.map_h = c->map_h; f.map_w = c->map_w; f.shared_field = c->shared_field; f.Hc = a.Hc; f.Wc = a.Wc;
     hipStream_t s = (hipStream_t)stream;
-    if (c->field_format == NAVSIM_FIELD_F32) return launch_goal_path<FieldF32>(c, st, f, a, s);
-    if (st->field_overflow) return launch_goal_path<FieldU16T>(c, st, f, a, s);
-    return launch_goal_path<FieldU16TN>(c, st, f, a, s);
+    return with_field(c, st, [&](auto field) { return launch_goal_path<typename decltype(field)::type>(c, st, f, a, s); });
 }
 
 int navsim_debug_goal_path_sweeps(int32_t* sweeps) {
@@ -1575,9 +1571,7 @@ int navsim_dwa(const navsim_config* c, const navsim_state* st, const navsim_dwa_
     DwaArgs a = {};
     a.p = *p; a.out = *out; a.subgoal = subgoal; a.skip = skip; a.use_peds = use_peds ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
-    if (c->field_format == NAVSIM_FIELD_F32) return launch_dwa<FieldF32>(c, st, a, s);
-    if (st->field_overflow) return launch_dwa<FieldU16T>(c, st, a, s);
-    return launch_dwa<FieldU16TN>(c, st, a, s);
+    return with_field(c, st, [&](auto field) { return launch_dwa<typename decltype(field)::type>(c, st, a, s); });
 }
 
 int navsim_local_map(const navsim_config* c, const navsim_state* st, const navsim_local_map_params* p, const uint8_t* visible,
@@ -1601,9 +1595,7 @@ int navsim_local_map(const navsim_config* c, const navsim_state* st, const navsi
     LocalMapArgs a = {};
     a.p = *p; a.visible = p->channels > 1 ? visible : nullptr; a.skip = skip; a.out = out;
     hipStream_t s = (hipStream_t)stream;
-    if (c->field_format == NAVSIM_FIELD_F32) return launch_local_map<FieldF32>(c, st, a, s);
-    if (st->field_overflow) return launch_local_map<FieldU16T>(c, st, a, s);
-    return launch_local_map<FieldU16TN>(c, st, a, s);
+    return with_field(c, st, [&](auto field) { return launch_local_map<typename decltype(field)::type>(c, st, a, s); });
 }
 
 const char* navsim_step_kernel_name(void) { return "navsim_step_kernel"; }

@@ -103,11 +103,11 @@ int launch_step_field(const navsim_config* c, const navsim_state* st, const navs
 template <int BLOCK, bool PEDS>
 int launch_step_family(const navsim_config* c, const navsim_state* st, const navsim_step_io* io, const StepLaunch& l,
                        const StepPlan& p) {
-    if (c->field_format == NAVSIM_FIELD_U16T && !st->field_overflow)           // no saturated cell anywhere
-        return launch_step_field<BLOCK, PEDS, FieldU16TN>(c, st, io, l, p);
-    if (c->field_format == NAVSIM_FIELD_U16T)
-        return launch_step_field<BLOCK, PEDS, FieldU16T>(c, st, io, l, p);
-    return launch_step_rule<BLOCK, PEDS, FieldF32, 0>(c, st, io, l, p);
+    return with_field(c, st, [&](auto field) {
+        typedef typename decltype(field)::type Field;
+        if constexpr (std::is_same<Field, FieldF32>::value) return launch_step_rule<BLOCK, PEDS, Field, 0>(c, st, io, l, p);   // (no record table)
+        else return launch_step_field<BLOCK, PEDS, Field>(c, st, io, l, p);
+    });
 }
 
 }  // namespace

@@ -146,6 +146,20 @@ int with_march_rule(int rule, F&& f) {
 #endif
 }
 
+// f(field_tag<Field>) for the field type that reads this world's distance field: float32 planes, packed tiles with the
+// float32 plane behind saturated cells, or packed tiles alone (no saturated cell anywhere).  The one place the field's format
+// becomes a template argument, for the step and the launches behind it alike (`typename decltype(tag)::type`).
+// Precondition: the caller has refused every cfg.field_format but NAVSIM_FIELD_F32 and NAVSIM_FIELD_U16T (each entry point
+// returns NAVSIM_E_UNSUPPORTED for another one before it gets here): whatever is not U16T is taken for float32.
+template <typename Field>
+struct field_tag { typedef Field type; };
+template <typename F>
+int with_field(const navsim_config* c, const navsim_state* st, F&& f) {
+    if (c->field_format != NAVSIM_FIELD_U16T) return f(field_tag<FieldF32>{});
+    if (st->field_overflow) return f(field_tag<FieldU16T>{});
+    return f(field_tag<FieldU16TN>{});
+}
+
 // the `int reset_only` of navsim_step_kernel / navsim_step_install_kernel (layout: kernels_step.hpp kStepWord*)
 int step_kernel_word(const StepLaunch& l) {
     return (l.reset_only ? kStepWordResetOnly : 0) | ((l.peds_done ? 1 : 0) << kStepWordPedsDoneBit) | (l.part << kStepWordPartShift) |

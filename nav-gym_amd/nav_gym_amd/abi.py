@@ -258,6 +258,8 @@ class NavsimLocalMapParams(C.Structure):
                 ("size", C.c_int32), ("channels", C.c_int32)]
 
 
+LOCAL_MAP_OUT = {"map": ("float32", ("C", "G", "G"))}       # (dtype, trailing shape behind E; C = channels, G = size)
+
 ORCA_MAX_AGENTS = 64
 ORCA_MAX_EDGES = 128
 CROWD_MAX_VERTS = 8

@@ -154,7 +154,9 @@ Pickling (env.py:30, 56-78: the reference is an EzPickle): `pickle.dumps(env)` s
 arguments; the copy is a fresh environment that has not been reset().  `state_dict()` / `load_state_dict()` move the
 simulation state itself.  When `gym` is importable the class is a gym.Env (`unwrapped`, `spec`, `reward_range`).
 """
+import collections
 import numbers
+import operator
 import warnings
 
 import numpy as np
@@ -213,6 +215,21 @@ DEFAULT_KWARGS = {                       # nav_gym_env/__init__.py:6-38
         scan_noise_std=([0., 0.05], 'float'),
     ),
 }
+
+
+# one launch behind the step as NavGymEnv runs it: the key in info, the record in NavSim.products, the bound method that makes the
+# call (skip, rebuild), the arrays handed out and, where the rows need more than that, what finishes them
+_Product = collections.namedtuple("_Product", "key record launch keys finish")
+
+
+def _check_params(name, params, on, needs, known, hint=""):
+    """A feature's dict of overrides (the constructor argument `name`) asks for the feature (`on`; `needs` is how to ask for
+    it) and holds `known` keys only."""
+    if params is not None and not on:
+        raise ValueError("%s needs %s" % (name, needs))
+    for k in (params or {}):
+        if k not in known:
+            raise ValueError("unknown key %r in %s (known: %s%s)" % (k, name, ", ".join(known), hint))
 
 
 class _AgentView(object):
@@ -451,12 +468,8 @@ class NavGymEnv(_EnvBase):
             cfg.angle_min = spec["angle_min"]
             cfg.angle_last = spec["angle_max"] - spec["angle_increment"]
         # observed pedestrians (navsim_ped_observe): K rows per arena, one launch behind the step
-        if observe_params is not None and observe_humans is None:
-            raise ValueError("observe_params needs observe_humans=K")
-        for k in (observe_params or {}):
-            if k not in _simmod.PED_OBSERVE_KEYS or k == "max_obs":
-                raise ValueError("unknown key %r in observe_params (known: %s; max_obs is observe_humans)"
-                                 % (k, ", ".join(x for x in _simmod.PED_OBSERVE_KEYS if x != "max_obs")))
+        _check_params("observe_params", observe_params, observe_humans is not None, "observe_humans=K",
+                      [k for k in _simmod.PED_OBSERVE_KEYS if k != "max_obs"], hint="; max_obs is observe_humans")
         if observe_humans is not None:
             if not (isinstance(observe_humans, numbers.Integral) and not isinstance(observe_humans, bool) and
                     1 <= observe_humans <= cfg.max_peds):
@@ -467,37 +480,20 @@ class NavGymEnv(_EnvBase):
                                  % (pedestrian_model, nh_hi))
         self.observe_humans = None if observe_humans is None else int(observe_humans)
         self.observe_params = None if observe_params is None else dict(observe_params)
-        self._humans_np = None                              # num_envs == 1: the latest rows as NumPy arrays
-        self._human_views = {}                              # per buffer parity: the views info['humans'] hands out
         # goal path (navsim_goal_path): the field per arena, the path distance and the sub-goal, two launches behind the step
-        if goal_path_params is not None and not goal_path:
-            raise ValueError("goal_path_params needs goal_path=True")
-        for k in (goal_path_params or {}):
-            if k not in _simmod.GOAL_PATH_KEYS:
-                raise ValueError("unknown key %r in goal_path_params (known: %s)" % (k, ", ".join(_simmod.GOAL_PATH_KEYS)))
+        _check_params("goal_path_params", goal_path_params, goal_path, "goal_path=True", _simmod.GOAL_PATH_KEYS)
         self.goal_path_on = bool(goal_path)
         self.goal_path_params = None if goal_path_params is None else dict(goal_path_params)
-        self._goal_np = None                                # num_envs == 1: the latest row as NumPy scalars / arrays
-        self._goal_views = {}                               # per buffer parity: the views info['goal_path'] hands out
+        self._goal_all = None                               # the goal path's rebuild mask of a reset(): every arena
         # local planner (navsim_dwa): an action per arena, one launch behind the step (and behind the goal path)
         if local_planner not in (None, "dwa"):
             raise ValueError("local_planner must be None or 'dwa', not %r" % (local_planner,))
-        if local_planner_params is not None and local_planner is None:
-            raise ValueError("local_planner_params needs local_planner='dwa'")
-        for k in (local_planner_params or {}):
-            if k not in _simmod.DWA_KEYS:
-                raise ValueError("unknown key %r in local_planner_params (known: %s)" % (k, ", ".join(_simmod.DWA_KEYS)))
+        _check_params("local_planner_params", local_planner_params, local_planner is not None, "local_planner='dwa'", _simmod.DWA_KEYS)
         self.local_planner = local_planner
         self.local_planner_params = None if local_planner_params is None else dict(local_planner_params)
-        self._planner_np = None                             # num_envs == 1: the latest row as NumPy values
-        self._planner_views = {}                            # per buffer parity: the views info['planner'] hands out
         # local map (navsim_local_map): a G x G grid per arena in the robot's frame, one launch behind the step
-        if local_map_params is not None and observe_local_map is None:
-            raise ValueError("local_map_params needs observe_local_map=G")
-        for k in (local_map_params or {}):
-            if k not in _simmod.LOCAL_MAP_KEYS and k != "visible_only":
-                raise ValueError("unknown key %r in local_map_params (known: %s, visible_only; the size is observe_local_map)"
-                                 % (k, ", ".join(_simmod.LOCAL_MAP_KEYS)))
+        _check_params("local_map_params", local_map_params, observe_local_map is not None, "observe_local_map=G",
+                      _simmod.LOCAL_MAP_KEYS + ("visible_only",), hint="; the size is observe_local_map")
         if observe_local_map is not None:
             if not (isinstance(observe_local_map, numbers.Integral) and not isinstance(observe_local_map, bool) and
                     1 <= observe_local_map <= abi.LOCAL_MAP_MAX):
@@ -513,7 +509,15 @@ class NavGymEnv(_EnvBase):
         self.observe_local_map = None if observe_local_map is None else int(observe_local_map)
         self.local_map_params = None if local_map_params is None else dict(local_map_params)
         self._local_map_visible = bool((local_map_params or {}).get("visible_only"))
-        self._local_map_np = None                           # num_envs == 1: the latest map as a NumPy array
+        # the launches behind the step (and behind reset() / reset(mask) / load_state_dict), in the order they run -- the planner
+        # reads the goal path's sub-goal, the local map the observer's `visible`.  _run_products() runs them; its latest result
+        # and, per buffer parity, the views it handed out
+        self._products = [row for on, row in (
+            (self.observe_humans, _Product("humans", "ped_observe", self._observe, tuple(abi.PED_OBSERVATION), self._humans_row)),
+            (self.goal_path_on, _Product("goal_path", "goal_path", self._goal_path, tuple(abi.GOAL_PATH_OUT), None)),
+            (self.local_planner, _Product("planner", "dwa", self._plan, self._PLANNER_KEYS, None)),
+            (self.observe_local_map, _Product("local_map", "local_map", self._local_map, ("map",), operator.itemgetter("map")))) if on]
+        self._product_out, self._product_views = {}, {}
         self.cfg = cfg
         self.sim = None
         self._choose_reset_path(pregen_pipeline, plain_cap=cfg.regen_cap)      # (without the pipeline: the library's default cap)
@@ -629,14 +633,8 @@ class NavGymEnv(_EnvBase):
                 self.sim.t["policy_prev_actions"].mul_((m.to(self.sim.device) == 0).to(self.sim.t["policy_prev_actions"].dtype)[:, None, None])
             self._map_info = None
             self._humans_of_episode = None
-            if self.observe_humans:
-                self._observe()
-            if self.goal_path_on:                         # (restarted: the key says so; a new map with the old number would not)
-                self._goal_path(rebuild=m.to(self.sim.device).ne(0).to(torch.uint8).contiguous())
-            if self.local_planner:
-                self._plan()
-            if self.observe_local_map:
-                self._local_map()
+            # (the goal path of the restarted arenas: their key says so; a new map with the old number would not)
+            self._run_products(rebuild=m.to(self.sim.device).ne(0).to(torch.uint8).contiguous() if self.goal_path_on else None)
             return self._obs_dict()
         self._bool = torch.bool
         from . import sim as simmod
@@ -703,14 +701,7 @@ class NavGymEnv(_EnvBase):
             self._choose_step_path()
         self._map_info = None                             # read back from the device when somebody asks (map_info)
         self._humans_of_episode = None
-        if self.observe_humans:
-            self._observe()
-        if self.goal_path_on:                             # every arena: a reset() may start the episode numbers again
-            self._goal_path(rebuild=self._goal_all)
-        if self.local_planner:
-            self._plan()
-        if self.observe_local_map:
-            self._local_map()
+        self._run_products(rebuild=self._goal_all)        # (every arena's goal path: a reset() may start the episode numbers again)
         return self._obs_dict()
 
     @property
@@ -798,14 +789,8 @@ class NavGymEnv(_EnvBase):
                 self.sim.replan(self.replan_cap)           # ('policy', 'orca': the launch in front of the next step reads the routes)
         if self.episode_stats:                             # one launch, behind whatever the step's path queued
             ep = self.sim.episode_stats()
-        if self.observe_humans:                            # likewise: the state the returned rows describe
-            humans = self._observe()
-        if self.goal_path_on:                              # likewise; the keys decide what is rebuilt
-            goal = self._goal_path()
-        if self.local_planner:                             # behind the goal path: its sub-goal is the planner's target
-            plan = self._plan()
-        if self.observe_local_map:                         # behind navsim_ped_observe: its visible array may be this call's
-            local = self._local_map()
+        products = self._run_products()                    # likewise: the state the returned rows describe (the goal path's keys
+        #                                                    decide what is rebuilt)
         obs = self._obs_dict()
         # the LAST observation of an episode that ended in this step (env.py:700-728 returns it with done = True): under
         # same-step auto-reset the row above already is the next episode's first one and the terminal one rides in info;
@@ -826,14 +811,7 @@ class NavGymEnv(_EnvBase):
                 info["TimeLimit.truncated"] = bool(out["truncated"][0].item())
             if self.episode_stats and done:
                 info["episode"] = {name: ep[k][0].item() for name, k in self._EPISODE_KEYS}
-            if self.observe_humans:
-                info["humans"] = humans
-            if self.goal_path_on:
-                info["goal_path"] = goal
-            if self.local_planner:
-                info["planner"] = plan
-            if self.observe_local_map:
-                info["local_map"] = local
+            info.update(products)
             return obs, float(out["reward"][0].item()), done, info
         # (views of the buffers the kernel wrote, made ONCE per buffer parity: a step of 4096 arenas is 95 us on the device, and
         #  every tensor slice or .view() costs the host 3-5 us -- round 6 measured 42 -> 36 M env-steps/s through this method
@@ -863,126 +841,92 @@ class NavGymEnv(_EnvBase):
         if "episode" in v:
             info["episode"] = v["episode"]
             info["_episode"] = done
-        if self.observe_humans:
-            info["humans"] = humans
-        if self.goal_path_on:
-            info["goal_path"] = goal
-        if self.local_planner:
-            info["planner"] = plan
-        if self.observe_local_map:
-            info["local_map"] = local
+        info.update(products)
         return obs, out["reward"], done, info
 
-    def _observe(self):
-        """navsim_ped_observe behind whatever was queued: the observed pedestrians of the state the current observation rows
-        describe.  Next-step auto-reset: an arena whose `done` is set has its state restarted already while its row is the
-        terminal one -- it is skipped (empty rows) until the call that resets it.  The views are made once per buffer parity."""
-        next_step = self.auto_reset and self.autoreset_mode == "next_step"
-        out = self.sim.ped_observe(skip=self.sim.out["done"] if next_step else None)
-        if self.num_envs == 1:
-            h = self.sim.ped_observation_host()
-            self._humans_np = {"state": h["state"][0], "index": h["index"][0], "count": int(h["count"][0]),
-                               "visible": h["visible"][0].astype(bool)}
-            return self._humans_np
-        v = self._human_views.get(self.sim.cur)
-        if v is None:
-            v = self._human_views[self.sim.cur] = {"state": out["state"], "index": out["index"], "count": out["count"],
-                                                   "visible": out["visible"].view(self._bool)}
+    def _run_products(self, rebuild=None):
+        """The enabled launches behind whatever was queued, on the same stream and in the constructor's order: the products of the
+        state the current observation rows describe.  rebuild: the goal path's mask of arenas whose field is rebuilt whatever its
+        key says.  Same-step auto-reset: the row of an arena that finished describes its NEW episode, like the observation beside
+        it (a shaper masks with `done`).  Next-step auto-reset: an arena whose `done` is set has its state restarted already
+        while its row is the terminal one -- every product skips it (empty rows, all 0) until the call that resets it.
+        Returns {info key: value}: dicts of views of the current buffer set, made ONCE per buffer parity (env.step's comment has
+        the host cost of a view); num_envs == 1: arena 0's rows as NumPy values, from one device -> host copy per product."""
+        sim, one = self.sim, self.num_envs == 1
+        cur = sim.cur
+        skip = sim.out["done"] if self.auto_reset and self.autoreset_mode == "next_step" else None
+        for p in self._products:
+            p.launch(skip, rebuild)
+        res = None if one else self._product_views.get(cur)
+        if res is None:
+            res = {}
+            for p in self._products:
+                o = sim.products[p.record].host(cur) if one else sim.products[p.record].buf[cur]
+                v = {k: o[k][0] if one else o[k] for k in p.keys}
+                res[p.key] = v if p.finish is None else p.finish(v)
+            if not one:
+                self._product_views[cur] = res
+        self._product_out = res
+        return res
+
+    # what differs per product: its call with its inputs, and what its rows still need
+    def _observe(self, skip, rebuild):
+        self.sim.ped_observe(skip=skip)
+
+    def _humans_row(self, v):
+        if self.num_envs == 1:                            # (NumPy rows: the count an int, `visible` of dtype bool)
+            v["count"], v["visible"] = int(v["count"]), v["visible"].astype(bool)
+        else:
+            v["visible"] = v["visible"].view(self._bool)
         return v
 
-    def _goal_path(self, rebuild=None):
-        """navsim_goal_path behind whatever was queued, on the same stream: the path distance and the sub-goal of the state the
-        current observation rows describe.  Same-step auto-reset: the row of an arena that finished describes its NEW episode,
-        like the observation beside it (a shaper masks with `done`).  Next-step auto-reset: an arena whose `done` is set has its
-        state restarted already while its row is the terminal one -- it is skipped (neither rebuilt nor read, all 0) until the
-        call that resets it.  The views are made once per buffer parity."""
-        next_step = self.auto_reset and self.autoreset_mode == "next_step"
-        out = self.sim.goal_path(rebuild=rebuild, skip=self.sim.out["done"] if next_step else None)
-        if self.num_envs == 1:
-            h = self.sim.goal_path_host()
-            self._goal_np = {"distance": h["distance"][0], "subgoal": h["subgoal"][0], "status": h["status"][0]}
-            return self._goal_np
-        v = self._goal_views.get(self.sim.cur)
-        if v is None:
-            v = self._goal_views[self.sim.cur] = {"distance": out["distance"], "subgoal": out["subgoal"], "status": out["status"]}
-        return v
+    def _goal_path(self, skip, rebuild):
+        self.sim.goal_path(rebuild=rebuild, skip=skip)
 
     _PLANNER_KEYS = ("action", "twist", "clearance", "best", "status")
 
-    def _plan(self):
-        """navsim_dwa behind whatever was queued (the goal path included: the sub-goal of the current buffer set is its target;
-        without goal_path the arena's goal), on the same stream: the planner's action for the state the current observation rows
-        describe.  Next-step auto-reset: an arena whose `done` is set is skipped (all 0) until the call that resets it.  The
-        views are made once per buffer parity."""
-        next_step = self.auto_reset and self.autoreset_mode == "next_step"
-        sub = self.sim.goal_buf[self.sim.cur]["subgoal"] if self.goal_path_on else None
-        out = self.sim.dwa(subgoal=sub, skip=self.sim.out["done"] if next_step else None)
-        if self.num_envs == 1:
-            h = self.sim.dwa_host()
-            self._planner_np = {k: h[k][0] for k in self._PLANNER_KEYS}
-            return self._planner_np
-        v = self._planner_views.get(self.sim.cur)
-        if v is None:
-            v = self._planner_views[self.sim.cur] = {k: out[k] for k in self._PLANNER_KEYS}
-        return v
+    def _plan(self, skip, rebuild):                      # (the goal path's sub-goal of the current buffer set is the target; without
+        sim = self.sim                                    # goal_path the arena's goal)
+        sim.dwa(subgoal=sim.products["goal_path"].buf[sim.cur]["subgoal"] if self.goal_path_on else None, skip=skip)
 
-    def _local_map(self):
-        """navsim_local_map behind whatever was queued (navsim_ped_observe included: with visible_only the `visible` array of the
-        current buffer set is the pedestrians that count), on the same stream: the map of the state the current observation rows
-        describe.  Next-step auto-reset: an arena whose `done` is set is skipped (all 0) until the call that resets it."""
-        next_step = self.auto_reset and self.autoreset_mode == "next_step"
-        vis = self.sim.ped_obs_buf[self.sim.cur]["visible"] if self._local_map_visible else None
-        out = self.sim.local_map(skip=self.sim.out["done"] if next_step else None, visible=vis)
-        if self.num_envs == 1:
-            self._local_map_np = out[0].cpu().numpy()
-            return self._local_map_np
-        return out
+    def _local_map(self, skip, rebuild):                 # (visible_only: the observer's `visible` of the current buffer set is the
+        sim = self.sim                                    # pedestrians that count)
+        sim.local_map(skip=skip, visible=sim.products["ped_observe"].buf[sim.cur]["visible"] if self._local_map_visible else None)
+
+    def _latest(self, key, on, what, needs):
+        """What info[key] of the latest step() holds; valid after reset() and reset(mask) too."""
+        if not on:
+            raise RuntimeError("%s() needs NavGymEnv(%s)" % (what, needs))
+        if self.sim is None:
+            raise RuntimeError("call reset() before %s()" % what)
+        return self._product_out[key]
 
     def local_map(self):
         """What info['local_map'] of the latest step() holds (observe_local_map=G); valid after reset() and reset(mask) too:
         float32 [E, C, G, G] in the robot's frame (num_envs == 1: a NumPy array [C, G, G])."""
-        if not self.observe_local_map:
-            raise RuntimeError("local_map() needs NavGymEnv(observe_local_map=G)")
-        if self.sim is None or self.sim.local_map_buf is None:
-            raise RuntimeError("call reset() before local_map()")
-        return self._local_map_np if self.num_envs == 1 else self.sim.local_map_buf[self.sim.cur]
+        return self._latest("local_map", self.observe_local_map, "local_map", "observe_local_map=G")
 
     def planner_action(self):
         """What info['planner'] of the latest step() holds (local_planner='dwa'); valid after reset() and reset(mask) too:
         {'action' [E,2] float64 in action_kind's form, 'twist' [E,2] float64 (v, omega), 'clearance' [E] float32 metres, 'best' [E]
         int32, 'status' [E] uint8}."""
-        if not self.local_planner:
-            raise RuntimeError("planner_action() needs NavGymEnv(local_planner='dwa')")
-        if self.sim is None or self.sim.dwa_buf is None:
-            raise RuntimeError("call reset() before planner_action()")
-        return self._planner_np if self.num_envs == 1 else self._planner_views[self.sim.cur]
+        return self._latest("planner", self.local_planner, "planner_action", "local_planner='dwa'")
 
     def goal_path(self):
         """What info['goal_path'] of the latest step() holds (goal_path=True); valid after reset() and reset(mask) too:
         {'distance' [E] float32 metres, 'subgoal' [E,2] float32 in the robot's frame, 'status' [E] uint8}."""
-        if not self.goal_path_on:
-            raise RuntimeError("goal_path() needs NavGymEnv(goal_path=True)")
-        if self.sim is None or self.sim.goal_buf is None:
-            raise RuntimeError("call reset() before goal_path()")
-        return self._goal_np if self.num_envs == 1 else self._goal_views[self.sim.cur]
+        return self._latest("goal_path", self.goal_path_on, "goal_path", "goal_path=True")
 
     def goal_field(self):
         """The distance-to-goal fields on the device (goal_path=True): uint16 [E, H/5, W/5], NavSim.goal_field()."""
-        if not self.goal_path_on:
-            raise RuntimeError("goal_field() needs NavGymEnv(goal_path=True)")
-        if self.sim is None or self.sim.goal_buf is None:
-            raise RuntimeError("call reset() before goal_field()")
+        self._latest("goal_path", self.goal_path_on, "goal_field", "goal_path=True")
         return self.sim.goal_field()
 
     def observed_humans(self):
         """What info['humans'] of the latest step() holds (observe_humans=K); valid after reset() and reset(mask) too: {'state'
         [E,K,5] x, y, vx, vy in the robot's frame and the distance, nearest first; 'index' [E,K] the pedestrian of the row, -1 =
         unused; 'count' [E] pedestrians seen, which may exceed K; 'visible' [E,N] bool}."""
-        if not self.observe_humans:
-            raise RuntimeError("observed_humans() needs NavGymEnv(observe_humans=K)")
-        if self.sim is None or self.sim.ped_obs_buf is None:
-            raise RuntimeError("call reset() before observed_humans()")
-        return self._humans_np if self.num_envs == 1 else self._human_views[self.sim.cur]
+        return self._latest("humans", self.observe_humans, "observed_humans", "observe_humans=K")
 
     # info['episode']: gymnasium's names for return and length, the build's own for the rest -> NavSim.episode_stats()'s rows
     _EPISODE_KEYS = (("r", "ep_return"), ("l", "ep_length"), ("path_length", "ep_path_length"),
@@ -1189,14 +1133,8 @@ class NavGymEnv(_EnvBase):
         self._episode_batch = int(sd["episode_batch"])
         self._map_info = None
         self._humans_of_episode = None
-        if self.observe_humans:                            # (no part of the snapshot: a function of the state just loaded)
-            self._observe()
-        if self.goal_path_on:                              # (likewise, and its keys know nothing of the state just loaded)
-            self._goal_path(rebuild=self._goal_all)
-        if self.local_planner:                             # (likewise)
-            self._plan()
-        if self.observe_local_map:                         # (likewise)
-            self._local_map()
+        # (no part of the snapshot: functions of the state just loaded, of which the goal path's keys know nothing)
+        self._run_products(rebuild=self._goal_all)
         torch.cuda.synchronize(self.sim.device)
         self._obs_dict()
 

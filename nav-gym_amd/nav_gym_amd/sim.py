@@ -261,6 +261,41 @@ def crowd_local_map(params, free_map, robot, rotate=True):
     return out
 
 
+def _overridden(d, params, noun, keys):
+    """The dict of defaults `d` with the overrides `params` (a dict or None) applied; a key that `d` does not have raises
+    ValueError naming the `noun` and the `keys` a caller may give."""
+    for k, v in (params or {}).items():
+        if k not in d:
+            raise ValueError("unknown %s parameter %r (known: %s)" % (noun, k, ", ".join(keys)))
+        d[k] = v
+    return d
+
+
+def _set_fields(p, d, keys, flags=()):
+    """d[k] into the ctypes struct p for every k of keys, as the field's type asks: an int (0 / 1 for the flags) or a float."""
+    kinds = dict(p._fields_)
+    for k in keys:
+        setattr(p, k, int(bool(d[k])) if k in flags else int(d[k]) if kinds[k] is C.c_int32 else float(d[k]))
+    return p
+
+
+def blob_layout(table, E, sym=None, omit=()):
+    """Where the arrays of an output table lie in one byte blob.  table: {name: (dtype, trailing shape behind E)} as abi states
+    them, a str in a shape being an extent that `sym` resolves; names in `omit` are left out.  Returns [(name, dtype, first byte,
+    end byte, shape), ...] in the table's order, each start rounded up to 16 bytes, and a last entry (None, None, start, end, None)
+    whose end byte is the blob's size: at least 16."""
+    out, at = [], 0
+    for k, (d, shape) in table.items():
+        if k in omit:
+            continue
+        full = (E,) + tuple(sym[s] if isinstance(s, str) else s for s in shape)
+        n = int(np.prod(full)) * np.dtype(d).itemsize
+        out.append((k, d, at, at + n, full))
+        at = (at + n + 15) // 16 * 16
+    out.append((None, None, at, max(at, 16), None))
+    return out
+
+
 ORCA_KEYS = ("time_step", "neighbor_dist", "time_horizon", "time_horizon_obst", "max_neighbors")
 PED_ORCA_KEYS = ORCA_KEYS + ("ped_radius", "robot_radius", "safety_space", "robot_visible", "max_obst_rects")
 
@@ -278,17 +313,10 @@ def ped_orca_defaults(cfg, robot_type="keti"):
 
 def ped_orca_params(cfg, params=None, robot_type="keti"):
     """abi.NavsimPedOrcaParams of ped_orca_defaults(cfg) overridden by the dict `params`; an unknown key raises ValueError."""
-    d = ped_orca_defaults(cfg, robot_type)
-    for k, v in (params or {}).items():
-        if k not in d:
-            raise ValueError("unknown ORCA parameter %r (known: %s)" % (k, ", ".join(PED_ORCA_KEYS)))
-        d[k] = v
+    d = _overridden(ped_orca_defaults(cfg, robot_type), params, "ORCA", PED_ORCA_KEYS)
     p = abi.NavsimPedOrcaParams()
-    for k in ORCA_KEYS:
-        setattr(p.orca, k, int(d[k]) if k == "max_neighbors" else float(d[k]))
-    p.ped_radius, p.robot_radius, p.safety_space = float(d["ped_radius"]), float(d["robot_radius"]), float(d["safety_space"])
-    p.robot_visible = int(bool(d["robot_visible"]))
-    return p
+    _set_fields(p.orca, d, ORCA_KEYS)
+    return _set_fields(p, d, ("ped_radius", "robot_radius", "safety_space", "robot_visible"), flags=("robot_visible",))
 
 
 PED_OBSERVE_KEYS = ("ped_radius", "sensor_range", "max_obs", "rays", "occlusion", "fov")
@@ -303,16 +331,8 @@ def ped_observe_defaults(cfg, robot_type="keti"):
 
 def ped_observe_params(cfg, params=None, robot_type="keti"):
     """abi.NavsimPedObserveParams of ped_observe_defaults(cfg) overridden by the dict `params`; an unknown key raises ValueError."""
-    d = ped_observe_defaults(cfg, robot_type)
-    for k, v in (params or {}).items():
-        if k not in d:
-            raise ValueError("unknown observation parameter %r (known: %s)" % (k, ", ".join(PED_OBSERVE_KEYS)))
-        d[k] = v
-    p = abi.NavsimPedObserveParams()
-    p.ped_radius, p.sensor_range = float(d["ped_radius"]), float(d["sensor_range"])
-    p.max_obs, p.rays = int(d["max_obs"]), int(d["rays"])
-    p.occlusion, p.fov = int(bool(d["occlusion"])), int(bool(d["fov"]))
-    return p
+    d = _overridden(ped_observe_defaults(cfg, robot_type), params, "observation", PED_OBSERVE_KEYS)
+    return _set_fields(abi.NavsimPedObserveParams(), d, PED_OBSERVE_KEYS, flags=("occlusion", "fov"))
 
 
 GOAL_PATH_KEYS = ("hard_clearance", "clearance", "band_cost", "lookahead")
@@ -326,28 +346,14 @@ def goal_path_defaults(cfg):
 
 def goal_path_params(cfg, params=None):
     """abi.NavsimGoalPathParams of goal_path_defaults(cfg) overridden by the dict `params`; an unknown key raises ValueError."""
-    d = goal_path_defaults(cfg)
-    for k, v in (params or {}).items():
-        if k not in d:
-            raise ValueError("unknown goal-path parameter %r (known: %s)" % (k, ", ".join(GOAL_PATH_KEYS)))
-        d[k] = v
-    p = abi.NavsimGoalPathParams()
-    p.hard_clearance, p.clearance, p.lookahead = float(d["hard_clearance"]), float(d["clearance"]), float(d["lookahead"])
-    p.band_cost = int(d["band_cost"])
-    return p
+    d = _overridden(goal_path_defaults(cfg), params, "goal-path", GOAL_PATH_KEYS)
+    return _set_fields(abi.NavsimGoalPathParams(), d, GOAL_PATH_KEYS)
 
 
 def goal_path_layout(E):
     """Where navsim_goal_path_out's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in
     abi.GOAL_PATH_OUT's order, each start rounded up to 16 bytes, and a last entry whose end byte is the blob's size."""
-    out, at = [], 0
-    for k, (d, shape) in abi.GOAL_PATH_OUT.items():
-        full = (E,) + tuple(shape)
-        n = int(np.prod(full)) * np.dtype(d).itemsize
-        out.append((k, d, at, at + n, full))
-        at = (at + n + 15) // 16 * 16
-    out.append((None, None, at, max(at, 16), None))
-    return out
+    return blob_layout(abi.GOAL_PATH_OUT, E)
 
 
 DWA_KEYS = ("acc_lin", "acc_rot", "body_radius", "body_offset", "ped_radius", "margin", "clearance_cap", "w_progress", "w_heading",
@@ -370,26 +376,12 @@ def dwa_defaults(cfg, robot_type="keti"):
 
 def dwa_params(cfg, params=None, robot_type="keti"):
     """abi.NavsimDwaParams of dwa_defaults(cfg) overridden by the dict `params`; an unknown key raises ValueError."""
-    d = dwa_defaults(cfg, robot_type)
-    for k, v in (params or {}).items():
-        if k not in d:
-            raise ValueError("unknown planner parameter %r (known: %s)" % (k, ", ".join(DWA_KEYS)))
-        d[k] = v
+    d = _overridden(dwa_defaults(cfg, robot_type), params, "planner", DWA_KEYS)
     offs = [float(x) for x in np.atleast_1d(np.asarray(d["body_offset"], np.float64))]
     if not 1 <= len(offs) <= abi.DWA_MAX_DISCS:
         raise ValueError("body_offset holds 1 .. %d disc centres, not %d" % (abi.DWA_MAX_DISCS, len(offs)))
-    p = abi.NavsimDwaParams()
-    for k in DWA_KEYS:
-        if k == "body_offset":
-            for i, x in enumerate(offs):
-                p.body_offset[i] = x
-        elif k in ("n_v", "n_w", "horizon"):
-            setattr(p, k, int(d[k]))
-        elif k == "use_peds":
-            p.use_peds = int(bool(d[k]))
-        else:
-            setattr(p, k, float(d[k]))
-    p.n_discs = len(offs)
+    p = _set_fields(abi.NavsimDwaParams(), d, [k for k in DWA_KEYS if k != "body_offset"], flags=("use_peds",))
+    p.body_offset[:len(offs)], p.n_discs = offs, len(offs)
     return p
 
 
@@ -397,16 +389,7 @@ def dwa_layout(E, C_, scores=False):
     """Where navsim_dwa_out's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in abi.DWA_OUT's
     order (the two per-candidate arrays only with scores=True), each start rounded up to 16 bytes, and a last entry whose end
     byte is the blob's size."""
-    out, at = [], 0
-    for k, (d, shape) in abi.DWA_OUT.items():
-        if "C" in shape and not scores:
-            continue
-        full = (E,) + tuple(C_ if s == "C" else s for s in shape)
-        n = int(np.prod(full)) * np.dtype(d).itemsize
-        out.append((k, d, at, at + n, full))
-        at = (at + n + 15) // 16 * 16
-    out.append((None, None, at, max(at, 16), None))
-    return out
+    return blob_layout(abi.DWA_OUT, E, {"C": C_}, omit=() if scores else [k for k, (_, shape) in abi.DWA_OUT.items() if "C" in shape])
 
 
 LOCAL_MAP_KEYS = ("cell", "ahead", "cap", "ped_radius", "channels")
@@ -422,14 +405,8 @@ def local_map_defaults(cfg):
 def local_map_params(cfg, params=None, size=None):
     """abi.NavsimLocalMapParams of local_map_defaults(cfg) overridden by the dict `params`, with `size` cells a side; an unknown
     key raises ValueError."""
-    d = local_map_defaults(cfg)
-    for k, v in (params or {}).items():
-        if k not in d:
-            raise ValueError("unknown local map parameter %r (known: %s)" % (k, ", ".join(LOCAL_MAP_KEYS)))
-        d[k] = v
-    p = abi.NavsimLocalMapParams()
-    for k in LOCAL_MAP_KEYS:
-        setattr(p, k, int(d[k]) if k == "channels" else float(d[k]))
+    d = _overridden(local_map_defaults(cfg), params, "local map", LOCAL_MAP_KEYS)
+    p = _set_fields(abi.NavsimLocalMapParams(), d, LOCAL_MAP_KEYS)
     p.size = 0 if size is None else int(size)
     return p
 
@@ -437,15 +414,7 @@ def local_map_params(cfg, params=None, size=None):
 def ped_observation_layout(E, K, N):
     """Where navsim_ped_observation's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in
     abi.PED_OBSERVATION's order, each start rounded up to 16 bytes, and a last entry whose end byte is the blob's size."""
-    sym = {"K": K, "N": N}
-    out, at = [], 0
-    for k, (d, shape) in abi.PED_OBSERVATION.items():
-        full = (E,) + tuple(sym[s] if isinstance(s, str) else s for s in shape)
-        n = int(np.prod(full)) * np.dtype(d).itemsize
-        out.append((k, d, at, at + n, full))
-        at = (at + n + 15) // 16 * 16
-    out.append((None, None, at, max(at, 16), None))
-    return out
+    return blob_layout(abi.PED_OBSERVATION, E, {"K": K, "N": N})
 
 
 def crowd_orca(params, agents, pref_vel, verts=None, n_agents=None, n_obst=None, obst_set=None, theta=None):
@@ -572,6 +541,35 @@ def concurrent_stream(device, priority=0, tries=8, beside=None):
     return best
 
 
+class _StepProduct(object):
+    """What one enable_* call of NavSim makes for a launch behind the step (observed pedestrians, goal path, local planner, local
+    map): the parameters, two sets of outputs -- they flip with NavSim.cur, so what a call returned stays intact through the next
+    step like everything else a step returns -- and the arguments of the call, built here once: every buffer behind them is
+    allocated once and only ever written in place.
+    params: the rule's ctypes struct.  layout: blob_layout()'s list; each set is ONE allocation (blob[i]) with the arrays carved
+    out of it (buf[i]: {name: tensor}), so that a caller who wants them on the host copies once (host()).
+    cfg, st, par: byrefs of the simulator's config and state and of params.  out[i]: the call's output argument for set i -- the
+    byref of an out_type filled with buf[i]'s pointers (struct[i]) or, without an out_type, the pointer of the blob itself (a
+    layout of one array).  extra: further device state of the product ({name: tensor}) that the call takes through one more
+    struct, extra_struct, whose byref is extra_ref."""
+
+    def __init__(self, sim, params, layout, out_type=None, extra=None, extra_struct=None):
+        import torch
+        self.params, self.layout = params, layout
+        self.blob = [torch.zeros(layout[-1][3], dtype=torch.uint8, device=sim.device) for _ in range(2)]
+        self.buf = [{k: blob[lo:hi].view(_dtype(d)).view(shape) for k, d, lo, hi, shape in layout[:-1]} for blob in self.blob]
+        self.cfg, self.st, self.par = C.byref(sim.cfg), C.byref(sim.st), C.byref(params)
+        self.struct = [out_type(**{k: v.data_ptr() for k, v in buf.items()}) if out_type else None for buf in self.buf]
+        self.out = [C.byref(s) if out_type else C.c_void_p(blob.data_ptr()) for s, blob in zip(self.struct, self.blob)]
+        self.extra, self.extra_struct = extra or {}, extra_struct
+        self.extra_ref = None if extra_struct is None else C.byref(extra_struct)
+
+    def host(self, cur):
+        """Set cur's arrays as NumPy arrays, from ONE device -> host copy."""
+        blob = self.blob[cur].cpu().numpy()
+        return {k: blob[lo:hi].view(d).reshape(shape) for k, d, lo, hi, shape in self.layout[:-1]}
+
+
 class NavSim(object):
     """E arenas resident on one GPU.  `arrays` maps navsim_state field names to numpy arrays or
     torch tensors (host or device); missing optional fields stay NULL."""
@@ -611,17 +609,9 @@ class NavSim(object):
         # episode statistics (enable_episode_stats): the accumulators, the totals, the two sets of published rows (they flip with
         # self.cur like out_buf) and, per parity, the arguments of navsim_episode_stats_update
         self.ep_acc, self.ep_totals, self.ep_buf, self._ep_args = None, None, None, {}
-        # observed pedestrians (enable_ped_observe): the parameters, two sets of outputs (they flip with self.cur as well) and, per
-        # parity, the arguments of navsim_ped_observe
-        self.obs_params, self.ped_obs_buf, self._ped_obs_args = None, None, {}
-        # goal path (enable_goal_path): the parameters, the field [E,Hc,Wc] with its keys and rebuild counter, two sets of outputs
-        # (they flip with self.cur) and, per parity, the arguments of navsim_goal_path
-        self.goal_params, self.goal_dist, self.goal_key, self.goal_rebuilds = None, None, None, None
-        self.goal_buf, self._goal_args = None, {}
-        # local planner (enable_dwa): the parameters, two sets of outputs (they flip with self.cur) and navsim_dwa's arguments
-        self.dwa_params, self.dwa_buf, self.dwa_blob, self._dwa_args = None, None, None, {}
-        # local map (enable_local_map): the parameters and two output tensors (they flip with self.cur)
-        self.local_map_params, self.local_map_buf, self._local_map_args = None, None, None
+        # the other launches behind the step: 'ped_observe', 'goal_path', 'dwa', 'local_map' -> the _StepProduct its enable_* call
+        # made (parameters, two sets of outputs, the call's arguments; the goal path's field, keys and rebuild counter as its extra)
+        self.products = {}
         self.t = {}
         self.st = abi.NavsimState()
         for name, (dtype, shape) in abi.STATE_LAYOUT.items():
@@ -1520,49 +1510,55 @@ class NavSim(object):
             self.ep_totals.zero_()
         return {k: int(v[i]) for i, k in enumerate(abi.EPISODE_TOTALS)}
 
+    # ---- the launches behind the step that follow: each enable_* call leaves one _StepProduct in self.products
+    def _product(self, name):
+        """The record of an enabled product.  (The four call methods ask the dict themselves first, `self.products.get(name) or
+        self._product(name)`: per step the guard is a function call only when it raises.)"""
+        p = self.products.get(name)
+        if p is None:
+            raise RuntimeError("call enable_%s() first" % name)
+        return p
+
+    # the two parameter structs that callers outside this class read by name (a specification run beside the device's call takes
+    # the struct the call uses): read-only views of the records, None while the product is not enabled
+    @property
+    def obs_params(self):
+        p = self.products.get("ped_observe")
+        return p and p.params
+
+    @property
+    def local_map_params(self):
+        p = self.products.get("local_map")
+        return p and p.params
+
     # ---- observed pedestrians: the K nearest pedestrians in the robot's line of sight, in its frame, from one launch behind the
     # step (include/navsim.h navsim_ped_observe)
     def enable_ped_observe(self, params=None):
         """Allocates two sets of outputs (state [E,K,5], index [E,K], count [E], visible [E,N]: they flip with self.cur, so what
         ped_observe() returned stays intact through the next step like everything else a step returns).  params: an
         abi.NavsimPedObserveParams, a dict of overrides of ped_observe_defaults(cfg), or None."""
-        import torch
         if self.cfg.ped_model == abi.PED_NONE:
             raise ValueError("observed pedestrians need a pedestrian model")
         p = params if isinstance(params, abi.NavsimPedObserveParams) else ped_observe_params(self.cfg, params)
         if not 1 <= p.max_obs <= abi.MAX_PEDS:
             raise ValueError("max_obs must lie in 1..%d, not %d" % (abi.MAX_PEDS, p.max_obs))
-        self.obs_params = p
-        # one allocation per set, the four arrays carved out of it in abi.PED_OBSERVATION's order (4-byte types first): a caller
-        # that wants them on the host copies the blob once (ped_observation_host)
-        self._ped_obs_layout = ped_observation_layout(self.cfg.n_envs, p.max_obs, self.cfg.max_peds)
-        total = self._ped_obs_layout[-1][3]
-        self.ped_obs_blob = [torch.zeros(total, dtype=torch.uint8, device=self.device) for _ in range(2)]
-        self.ped_obs_buf = [{k: blob[lo:hi].view(_dtype(d)).view(shape) for k, d, lo, hi, shape in self._ped_obs_layout[:-1]}
-                            for blob in self.ped_obs_blob]
-        self._ped_obs_args = {}
+        # (the four arrays in abi.PED_OBSERVATION's order: 4-byte types first)
+        self.products["ped_observe"] = _StepProduct(self, p, ped_observation_layout(self.cfg.n_envs, p.max_obs, self.cfg.max_peds),
+                                                    abi.NavsimPedObservation)
 
     def ped_observation_host(self):
         """The current set of ped_observe()'s outputs as NumPy arrays, from ONE device -> host copy."""
-        blob = self.ped_obs_blob[self.cur].cpu().numpy()
-        return {k: blob[lo:hi].view(d).reshape(shape) for k, d, lo, hi, shape in self._ped_obs_layout[:-1]}
+        return self._product("ped_observe").host(self.cur)
 
     def ped_observe(self, skip=None):
         """navsim_ped_observe of the current state on the current stream: one launch.  skip: uint8 / bool [E], arenas whose rows
         come back empty (None: none).  Returns the current set {'state', 'index', 'count', 'visible'}, intact through the next
         step."""
-        if self.ped_obs_buf is None:
-            raise RuntimeError("call enable_ped_observe() first")
-        a = self._ped_obs_args.get(self.cur)
-        if a is None:                                     # (built once per parity: every buffer behind it is allocated once)
-            out = abi.NavsimPedObservation()
-            for k, v in self.ped_obs_buf[self.cur].items():
-                setattr(out, k, v.data_ptr())
-            a = self._ped_obs_args[self.cur] = (out, C.byref(out), C.byref(self.obs_params), C.byref(self.cfg), C.byref(self.st))
-        rc = self.lib.navsim_ped_observe(a[3], a[4], a[2], _ptr(skip), a[1], _stream())
+        p, cur = self.products.get("ped_observe") or self._product("ped_observe"), self.cur
+        rc = self.lib.navsim_ped_observe(p.cfg, p.st, p.par, _ptr(skip), p.out[cur], _stream())
         if rc:
             check(rc, "navsim_ped_observe")
-        return self.ped_obs_buf[self.cur]
+        return p.buf[cur]
 
     # ---- goal path: a distance-to-goal field per arena on the 5 x 5-cell navigation grid, the robot's path distance and a steering
     # sub-goal read from it -- two launches behind the step (include/navsim.h navsim_goal_path)
@@ -1576,56 +1572,36 @@ class NavSim(object):
         nbytes = self.lib.navsim_goal_field_bytes(C.byref(cfg))
         if nbytes == 0 and cfg.n_envs > 0:
             raise ValueError("the goal path needs maps of at least 5 x 5 cells")
-        self.goal_params = p
-        self.goal_dist = torch.full((cfg.n_envs, cfg.map_h // 5, cfg.map_w // 5), abi.GOAL_FIELD_INF - 65536, dtype=torch.int16,
-                                    device=self.device).view(torch.uint16)
-        self.goal_key = torch.full((cfg.n_envs, 3), -1, dtype=torch.int64, device=self.device)
-        self.goal_rebuilds = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._goal_layout = goal_path_layout(cfg.n_envs)
-        total = self._goal_layout[-1][3]
-        self.goal_blob = [torch.zeros(total, dtype=torch.uint8, device=self.device) for _ in range(2)]
-        self.goal_buf = [{k: blob[lo:hi].view(_dtype(d)).view(shape) for k, d, lo, hi, shape in self._goal_layout[:-1]}
-                         for blob in self.goal_blob]
-        self._goal_field = abi.NavsimGoalField(dist=self.goal_dist.data_ptr(), key=self.goal_key.data_ptr(),
-                                               rebuilds=self.goal_rebuilds.data_ptr())
-        self._goal_args = {}
+        field = dict(dist=torch.full((cfg.n_envs, cfg.map_h // 5, cfg.map_w // 5), abi.GOAL_FIELD_INF - 65536, dtype=torch.int16,
+                                     device=self.device).view(torch.uint16),
+                     key=torch.full((cfg.n_envs, 3), -1, dtype=torch.int64, device=self.device),
+                     rebuilds=torch.zeros(1, dtype=torch.int64, device=self.device))
+        self.products["goal_path"] = _StepProduct(self, p, goal_path_layout(cfg.n_envs), abi.NavsimGoalPathOut, extra=field,
+                                                  extra_struct=abi.NavsimGoalField(**{k: v.data_ptr() for k, v in field.items()}))
 
     def goal_path(self, rebuild=None, skip=None):
         """navsim_goal_path of the current state on the current stream: two launches, no copy.  rebuild: uint8 / bool [E], arenas
         whose field is rebuilt whatever their key says (None: the keys alone decide -- every in-launch restart changes them);
         skip: uint8 / bool [E], arenas that are neither rebuilt nor read and come back (0, (0, 0), 0).  Returns the current set
         {'distance', 'subgoal', 'status'}, intact through the next step."""
-        if self.goal_buf is None:
-            raise RuntimeError("call enable_goal_path() first")
-        a = self._goal_args.get(self.cur)
-        if a is None:                                     # (built once per parity: every buffer behind it is allocated once)
-            out = abi.NavsimGoalPathOut()
-            for k, v in self.goal_buf[self.cur].items():
-                setattr(out, k, v.data_ptr())
-            a = self._goal_args[self.cur] = (out, C.byref(out), C.byref(self.goal_params), C.byref(self.cfg), C.byref(self.st),
-                                             C.byref(self._goal_field))
-        rc = self.lib.navsim_goal_path(a[3], a[4], a[2], _ptr(rebuild), _ptr(skip), a[5], a[1], _stream())
+        p, cur = self.products.get("goal_path") or self._product("goal_path"), self.cur
+        rc = self.lib.navsim_goal_path(p.cfg, p.st, p.par, _ptr(rebuild), _ptr(skip), p.extra_ref, p.out[cur], _stream())
         if rc:
             check(rc, "navsim_goal_path")
-        return self.goal_buf[self.cur]
+        return p.buf[cur]
 
     def goal_path_host(self):
         """The current set of goal_path()'s outputs as NumPy arrays, from ONE device -> host copy."""
-        blob = self.goal_blob[self.cur].cpu().numpy()
-        return {k: blob[lo:hi].view(d).reshape(shape) for k, d, lo, hi, shape in self._goal_layout[:-1]}
+        return self._product("goal_path").host(self.cur)
 
     def goal_field(self):
         """The distance-to-goal fields on the device: uint16 [E, H/5, W/5] in map cells (5 a straight hop, 7 a diagonal one),
         0xFFFF = impassable, unreachable or farther than 65534; as of each arena's latest rebuild."""
-        if self.goal_buf is None:
-            raise RuntimeError("call enable_goal_path() first")
-        return self.goal_dist
+        return self._product("goal_path").extra["dist"]
 
     def goal_path_rebuilds(self):
         """Fields rebuilt since enable_goal_path().  One device -> host copy."""
-        if self.goal_buf is None:
-            raise RuntimeError("call enable_goal_path() first")
-        return int(self.goal_rebuilds.item())
+        return int(self._product("goal_path").extra["rebuilds"].item())
 
     # ---- local planner: a dynamic-window action per arena -- candidates rolled out against the distance field and the pedestrians,
     # the best one returned -- one launch behind the step (include/navsim.h navsim_dwa)
@@ -1633,69 +1609,48 @@ class NavSim(object):
         """Allocates two sets of outputs (twist [E,2], action [E,2], clearance [E], best [E], status [E]; with scores=True also
         scores [E,C] and first_hit [E,C], every candidate's values: they flip with self.cur like everything a step returns).
         params: an abi.NavsimDwaParams, a dict of overrides of dwa_defaults(cfg, robot_type), or None."""
-        import torch
         p = params if isinstance(params, abi.NavsimDwaParams) else dwa_params(self.cfg, params, robot_type)
         if not (1 <= p.n_v <= 16 and 1 <= p.n_w <= 32 and 1 <= p.horizon <= 32):
             raise ValueError("n_v must lie in 1..16, n_w in 1..32, horizon in 1..32, not %d, %d, %d" % (p.n_v, p.n_w, p.horizon))
-        self.dwa_params = p
-        self._dwa_layout = dwa_layout(self.cfg.n_envs, p.n_v * p.n_w, scores=scores)
-        total = self._dwa_layout[-1][3]
-        self.dwa_blob = [torch.zeros(total, dtype=torch.uint8, device=self.device) for _ in range(2)]
-        self.dwa_buf = [{k: blob[lo:hi].view(_dtype(d)).view(shape) for k, d, lo, hi, shape in self._dwa_layout[:-1]}
-                        for blob in self.dwa_blob]
-        self._dwa_args = {}
+        self.products["dwa"] = _StepProduct(self, p, dwa_layout(self.cfg.n_envs, p.n_v * p.n_w, scores=scores), abi.NavsimDwaOut)
 
     def dwa(self, subgoal=None, skip=None):
         """navsim_dwa of the current state on the current stream: one launch, no copy.  subgoal: float32 [E,2] targets in the
         robot's frame (goal_path()'s 'subgoal'; None: the arena's goal); skip: uint8 / bool [E], arenas that are not read and come
         back all 0.  Returns the current set {'twist', 'action', 'clearance', 'best', 'status'[, 'scores', 'first_hit']}, intact
         through the next step."""
-        if self.dwa_buf is None:
-            raise RuntimeError("call enable_dwa() first")
-        a = self._dwa_args.get(self.cur)
-        if a is None:                                     # (built once per parity: every buffer behind it is allocated once)
-            out = abi.NavsimDwaOut()
-            for k, v in self.dwa_buf[self.cur].items():
-                setattr(out, k, v.data_ptr())
-            a = self._dwa_args[self.cur] = (out, C.byref(out), C.byref(self.dwa_params), C.byref(self.cfg), C.byref(self.st))
-        rc = self.lib.navsim_dwa(a[3], a[4], a[2], _ptr(subgoal), _ptr(skip), a[1], _stream())
+        p, cur = self.products.get("dwa") or self._product("dwa"), self.cur
+        rc = self.lib.navsim_dwa(p.cfg, p.st, p.par, _ptr(subgoal), _ptr(skip), p.out[cur], _stream())
         if rc:
             check(rc, "navsim_dwa")
-        return self.dwa_buf[self.cur]
+        return p.buf[cur]
 
     def dwa_host(self):
         """The current set of dwa()'s outputs as NumPy arrays, from ONE device -> host copy."""
-        blob = self.dwa_blob[self.cur].cpu().numpy()
-        return {k: blob[lo:hi].view(d).reshape(shape) for k, d, lo, hi, shape in self._dwa_layout[:-1]}
+        return self._product("dwa").host(self.cur)
 
     # ---- egocentric local map: wall and pedestrian grids per arena in the robot's frame, one launch behind the step
     # (include/navsim.h navsim_local_map)
     def enable_local_map(self, size, params=None):
         """Allocates two outputs float32 [E, C, size, size] (they flip with self.cur like everything a step returns).  params: an
         abi.NavsimLocalMapParams (its own size counts), a dict of overrides of local_map_defaults(cfg), or None."""
-        import torch
         p = params if isinstance(params, abi.NavsimLocalMapParams) else local_map_params(self.cfg, params, size)
         if not 1 <= p.size <= abi.LOCAL_MAP_MAX:
             raise ValueError("the local map's size must lie in 1 .. %d, not %d" % (abi.LOCAL_MAP_MAX, p.size))
         if p.channels not in (1, 2, 4):
             raise ValueError("the local map has 1, 2 or 4 channels, not %d" % p.channels)
-        self.local_map_params = p
-        self.local_map_buf = [torch.zeros((self.cfg.n_envs, p.channels, p.size, p.size), dtype=torch.float32, device=self.device)
-                              for _ in range(2)]
-        self._local_map_args = (C.byref(self.cfg), C.byref(self.st), C.byref(p))
+        # (a layout of one array, at the start of its allocation: navsim_local_map picks its four-cell kernel by out's alignment)
+        self.products["local_map"] = _StepProduct(self, p, blob_layout(abi.LOCAL_MAP_OUT, self.cfg.n_envs, {"C": p.channels, "G": p.size}))
 
     def local_map(self, skip=None, visible=None):
         """navsim_local_map of the current state on the current stream: one launch, no copy, no allocation.  skip: uint8 / bool
         [E], arenas that are not read and come back all 0; visible: uint8 / bool [E,N], the pedestrians that count
         (ped_observe()'s 'visible'; None: all of them).  Returns the current tensor [E, C, G, G], intact through the next step."""
-        if self.local_map_buf is None:
-            raise RuntimeError("call enable_local_map() first")
-        a = self._local_map_args
-        out = self.local_map_buf[self.cur]
-        rc = self.lib.navsim_local_map(a[0], a[1], a[2], _ptr(visible), _ptr(skip), out.data_ptr(), _stream())
+        p, cur = self.products.get("local_map") or self._product("local_map"), self.cur
+        rc = self.lib.navsim_local_map(p.cfg, p.st, p.par, _ptr(visible), _ptr(skip), p.out[cur], _stream())
         if rc:
             check(rc, "navsim_local_map")
-        return out
+        return p.buf[cur]["map"]
 
     def occupancy(self, e=0):
         """uint8 [H, W] occupancy grid (1 = occupied) of arena e, read back from its distance field

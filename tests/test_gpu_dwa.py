@@ -361,7 +361,7 @@ def test_off_by_default(gpu):
     env = _env(local_planner=None, local_planner_params=None)
     env.reset()
     _, _, _, info = env.step(np.zeros((16, 2)))
-    assert "planner" not in info and env.sim.dwa_buf is None and env.sim.dwa_blob is None and env.sim.dwa_params is None
+    assert "planner" not in info and env.sim.products == {}
     with pytest.raises(RuntimeError):
         env.planner_action()
     with pytest.raises(RuntimeError):

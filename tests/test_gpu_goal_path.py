@@ -435,7 +435,7 @@ def test_off_by_default(gpu):
     env = _env(goal_path=False)
     env.reset()
     _, _, _, info = env.step(np.zeros((16, 2)))
-    assert "goal_path" not in info and env.sim.goal_buf is None and env.sim.goal_dist is None and env.sim.goal_key is None
+    assert "goal_path" not in info and env.sim.products == {}
     with pytest.raises(RuntimeError):
         env.goal_path()
     with pytest.raises(RuntimeError):

@@ -442,7 +442,7 @@ def test_feature_off_allocates_and_reports_nothing(gpu):
     env = _env(observe_local_map=None, local_map_params=None)
     env.reset()
     _, _, _, info = env.step(_drive(8, 0))
-    assert "local_map" not in info and env.sim.local_map_buf is None and env.sim.local_map_params is None
+    assert "local_map" not in info and env.sim.products == {}
     with pytest.raises(RuntimeError):
         env.local_map()
     with pytest.raises(RuntimeError):

@@ -356,5 +356,5 @@ def test_feature_off_allocates_and_reports_nothing(gpu):
     env = _env(observe_humans=None)
     env.reset()
     _, _, _, info = env.step(_drive(6))
-    assert "humans" not in info and env.sim.ped_obs_buf is None
+    assert "humans" not in info and env.sim.products == {}
     env.close()
