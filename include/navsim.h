@@ -100,7 +100,11 @@ typedef struct navsim_config {
     double origin_x, origin_y;
     double time_step;        /* __init__.py:8 */
     double angle_min;        /* first beam angle in the robot frame (keti_robot.py:45) */
-    double angle_last;       /* last beam angle = angle_max - angle_increment (env.py:388-390) */
+    double angle_last;       /* last beam angle = angle_max - angle_increment (env.py:388-390).  With pedestrians
+                              * (ped_model != NAVSIM_PED_NONE) angle_last - angle_min > 2 pi is NAVSIM_E_UNSUPPORTED from every
+                              * step and reset entry, before anything is launched: the bearing-culled merge of pedestrians
+                              * into the scan visits the 2 pi aliases of a bearing up to one turn.  Exactly 2 pi, a reversed
+                              * lidar (angle_last < angle_min) and, without pedestrians, any field of view are served. */
     double range_max;        /* keti_robot.py:47 */
     double axle_offset;      /* 0.14474 for KetiRobot (keti_robot.py:72-90); 0 = plain unicycle */
     double min_turning_radius;   /* env.py:595-600 */
@@ -129,7 +133,8 @@ typedef struct navsim_config {
 
     /* pedestrian lidar (human.py:12-16) and the robot as pedestrians see it (env.py:404-405):
      * only used by navsim_ped_scans */
-    double ped_angle_min, ped_angle_last, ped_range_max;
+    double ped_angle_min, ped_angle_last, ped_range_max;   /* ped_angle_last - ped_angle_min > 2 pi: NAVSIM_E_UNSUPPORTED from
+                                                            * navsim_ped_scans(_part) and navsim_ped_scan_policy (as angle_last) */
     int32_t ped_n_beams;
     int32_t regen_plan;               /* navsim_regen: 1 = sample on the costmap and keep only start/goal pairs
                                          joined by a path (env.py:342-383), pedestrians get path waypoints */

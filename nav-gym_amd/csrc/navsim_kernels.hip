@@ -91,6 +91,9 @@ int dispatch_step(const navsim_config* c, const navsim_state* st, const navsim_s
     // (a NAVSIM_STEP_DUE launch and the front of the re-plan are the ordinary step on other workgroups: their grid does not change the plan)
     const StepPlan p = plan_step(c, st, l.part == NAVSIM_STEP_DUE || l.part == kStepPartReplan ? 0 : l.grid);
     const bool peds = c->ped_model != NAVSIM_PED_NONE;
+    // the culled merge of pedestrian primitives walks the 2 pi aliases m <= 1 of a bearing (kernels_step.hpp
+    // merge_prims_culled_core): a field of view above 2 pi has beams that need m = 2, and is refused where anything is merged
+    if (peds && c->angle_last - c->angle_min > nv::kTwoPi) return NAVSIM_E_UNSUPPORTED;
     const bool split = peds && !l.reset_only && ped_split_on(c);               // pedestrians ahead of the step (ped_split_on)
     // a state with slot tables (navsim_state.map_slot): only the INSTALL instantiations look a map up through the table -- every
     // launch goes to them, with nothing to install unless navsim_step_install says so
@@ -811,6 +814,7 @@ int navsim_ped_scans_part(const navsim_config* c, const navsim_state* st, float*
         !st->field || c->ped_n_beams < 1 || c->max_peds < 1) return NAVSIM_E_ARG;
     if (e0 < 0 || n_e < 0 || (long)e0 + n_e > c->n_envs) return NAVSIM_E_ARG;
     if (c->max_peds > NAVSIM_MAX_PEDS || c->ped_n_beams > 4096) return NAVSIM_E_UNSUPPORTED;
+    if (c->ped_angle_last - c->ped_angle_min > nv::kTwoPi) return NAVSIM_E_UNSUPPORTED;     // the culled merge: dispatch_step
     if (n_e == 0) return NAVSIM_OK;
     hipStream_t s = (hipStream_t)stream;
     int rc = NAVSIM_E_UNSUPPORTED;
@@ -1138,6 +1142,7 @@ static int ped_policy_run(const navsim_config* c, const navsim_state* st, const 
         if (c->ped_model == NAVSIM_PED_NONE || !st->robot_pose || !st->field) return NAVSIM_E_ARG;
         if (c->max_peds > NAVSIM_MAX_PEDS) return NAVSIM_E_UNSUPPORTED;
         if (c->field_format != NAVSIM_FIELD_U16T && c->field_format != NAVSIM_FIELD_F32) return NAVSIM_E_UNSUPPORTED;
+        if (c->ped_angle_last - c->ped_angle_min > nv::kTwoPi) return NAVSIM_E_UNSUPPORTED;
     }
     const size_t P_all = (size_t)c->n_envs * (size_t)c->max_peds;
     if (p_count < 0) p_count = (long)P_all - p_begin;

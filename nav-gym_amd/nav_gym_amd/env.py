@@ -459,6 +459,11 @@ class NavGymEnv(_EnvBase):
             cfg.robot_seen_footprint[i] = float(v)
         if lidar is not None:                         # (angle_min, angle_last, n_beams)
             cfg.angle_min, cfg.angle_last, cfg.n_beams = float(lidar[0]), float(lidar[1]), int(lidar[2])
+            # the step refuses it (include/navsim.h angle_last): pedestrians are merged into the scan by bearing, one turn at most
+            if cfg.ped_model != abi.PED_NONE and cfg.angle_last - cfg.angle_min > 2.0 * np.pi:
+                raise ValueError("lidar=(%r, %r, ...) spans more than 2*pi, which worlds with pedestrians do not support "
+                                 "(pedestrian_model=%r); use pedestrian_model='none' or num_humans=0, or a lidar of at most "
+                                 "one turn" % (lidar[0], lidar[1], pedestrian_model))
         elif n_beams is not None and int(n_beams) == 1081:
             world.lidar_1081(cfg)
         elif n_beams is not None:

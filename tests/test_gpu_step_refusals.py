@@ -72,6 +72,7 @@ def worlds(gpu):
 INSTALL = ("stage", "stage_obs", "mark", "ready", "late")          # navsim_step_install's arguments behind io
 F32 = dict(cfg=dict(field_format=abi.FIELD_F32), field="field_f32")
 NO_PEDS = dict(ped_model=abi.PED_NONE)
+WIDE = dict(angle_min=-3.5, angle_last=3.5)                        # 7 rad > 2 pi
 
 CASES = [
     # navsim_step_part
@@ -110,6 +111,19 @@ CASES = [
     ("prepare_map_slot_without_pedestrians", "square", ("navsim_prepare",), dict(cfg=NO_PEDS, map_slot="map_slot"), OK),
     # (a state with slot tables has no navsim_step_part form, and navsim_prepare says so instead of skipping it)
     ("prepare_map_slot_with_pedestrians", "square", ("navsim_prepare",), dict(map_slot="map_slot"), UNSUPPORTED),
+    # a lidar wider than one turn in a world with pedestrians (include/navsim.h angle_last): refused by dispatch_step, which
+    # every step and reset entry passes through, ahead of ped_update_kernel; without pedestrians the same lidar is served
+    # (tests/test_gpu_ped_edge_scenes.py runs it against the oracle)
+    ("step_lidar_above_one_turn", "square", ("navsim_step", None), dict(cfg=WIDE), UNSUPPORTED),
+    ("step_lidar_far_above_one_turn", "square", ("navsim_step", None), dict(cfg=dict(angle_min=-3.2, angle_last=6.2)), UNSUPPORTED),
+    ("step_lidar_above_one_turn_ped_split", "square", ("navsim_step", None), dict(cfg=dict(WIDE, ped_split=2)), UNSUPPORTED),
+    ("step_lidar_above_one_turn_external", "square", ("navsim_step", None), dict(cfg=dict(WIDE, ped_model=abi.PED_EXTERNAL)), UNSUPPORTED),
+    ("step_part_lidar_above_one_turn", "square", ("navsim_step_part", abi.STEP_DUE, None), dict(cfg=WIDE), UNSUPPORTED),
+    ("step_replan_lidar_above_one_turn", "square", ("navsim_step_replan", 8, None), dict(cfg=WIDE), UNSUPPORTED),
+    ("step_install_lidar_above_one_turn", "square", ("navsim_step_install",) + INSTALL + (None,), dict(cfg=WIDE), UNSUPPORTED),
+    ("reset_obs_lidar_above_one_turn", "square", ("navsim_reset_obs", None, None), dict(cfg=WIDE), UNSUPPORTED),
+    ("prepare_lidar_above_one_turn", "square", ("navsim_prepare",), dict(cfg=WIDE), UNSUPPORTED),
+    ("prepare_lidar_above_one_turn_without_pedestrians", "square", ("navsim_prepare",), dict(cfg=dict(WIDE, **NO_PEDS)), OK),
 ]
 
 
@@ -119,3 +133,30 @@ def test_refusal_code_and_nothing_launched(gpu, worlds, world, call, changes, co
     rc = w.call(*call, **changes)
     assert rc == code, "%s returned %d" % (call[0], rc)
     assert w.unchanged(gpu.torch), "%s wrote to the outputs or the state" % call[0]
+
+
+def test_pedestrian_scan_entries_refuse_a_lidar_above_one_turn(gpu):
+    """include/navsim.h ped_angle_last: navsim_ped_scans, navsim_ped_scans_part and navsim_ped_scan_policy return
+    NAVSIM_E_UNSUPPORTED for ped_angle_last - ped_angle_min > 2 pi and write nothing.  (Exactly 2 pi is served:
+    tests/test_gpu_ped_edge_scenes.py runs it against the oracle.)"""
+    torch = gpu.torch
+    w = _World(gpu, SIDE)
+    g = w.g
+    g.set_policy({k: torch.zeros(abi.POLICY_SHAPES[k]) for k in abi.POLICY_FIELDS})
+    ws = g.t["policy_ws"]
+    ws.zero_()
+    scans = torch.full((E, N, g.cfg.ped_n_beams), 7.0, dtype=torch.float32, device=gpu.dev)
+    prev, cmd = g.t["policy_prev_actions"], g.t["ped_cmd"]
+    extra = [scans, ws, prev] + list(g.policy_t.values())
+    before = [t.clone() for t in extra]
+    P = lambda t: C.c_void_p(t.data_ptr())
+    c = g.cfg.copy()
+    c.ped_angle_min, c.ped_angle_last = -3.5, 3.5
+    calls = dict(
+        navsim_ped_scans=lambda c: g.lib.navsim_ped_scans(C.byref(c), C.byref(g.st), P(scans), None),
+        navsim_ped_scans_part=lambda c: g.lib.navsim_ped_scans_part(C.byref(c), C.byref(g.st), P(scans), 0, E, None),
+        navsim_ped_scan_policy=lambda c: g.lib.navsim_ped_scan_policy(C.byref(c), C.byref(g.st), C.byref(g.policy_w), P(scans), P(prev),
+                                                                      P(cmd), P(ws), ws.numel(), None))
+    for name, call in calls.items():
+        assert call(c) == UNSUPPORTED, name
+        assert w.unchanged(torch) and all(torch.equal(a, b) for a, b in zip(extra, before)), "%s wrote something" % name

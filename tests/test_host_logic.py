@@ -237,6 +237,24 @@ def test_env_fallbacks_are_announced_once():
         assert not [x for x in w if issubclass(x.category, RuntimeWarning)]
 
 
+def test_env_refuses_a_lidar_wider_than_one_turn_with_pedestrians():
+    """include/navsim.h angle_last: the step returns NAVSIM_E_UNSUPPORTED for angle_last - angle_min > 2 pi in a world with
+    pedestrians, so the constructor says so.  Exactly 2 pi, a reversed lidar, and any width without pedestrians are taken."""
+    import nav_gym_env
+    from nav_gym_amd import abi
+    mk = lambda **kw: nav_gym_env.make("NavGym-v0", num_envs=2, map_size=200, **kw)
+    for lidar in ((-3.5, 3.5, 90), (-3.2, 6.2, 90), (0.0, float(np.nextafter(2 * np.pi, 7.0)), 8)):
+        for model in ("sfm", "external", "orca"):
+            with pytest.raises(ValueError, match="2\\*pi"):
+                mk(lidar=lidar, pedestrian_model=model)
+        for kw in (dict(pedestrian_model="none"), dict(num_humans=0)):
+            env = mk(lidar=lidar, **kw)
+            assert env.cfg.ped_model == abi.PED_NONE and (env.cfg.angle_min, env.cfg.angle_last, env.cfg.n_beams) == lidar
+    for lidar in ((-np.pi, np.pi, 90), (0.0, 2 * np.pi, 8), (1.0, -1.0, 33), (-0.75 * np.pi, 0.75 * np.pi, 1081)):
+        env = mk(lidar=lidar)
+        assert env.cfg.ped_model == abi.PED_SFM and (env.cfg.angle_min, env.cfg.angle_last) == lidar[:2]
+
+
 def test_env_picks_the_pipelined_reset_path_where_it_pays():
     """NavGymEnv(pregen_pipeline=None), worlds with a new map per episode: 8 where the reset is heavy -- corridor maps with planned
     starts, the reference's own kind --, 4 otherwise, 0 where the pipeline is not available; an explicit value wins.  With
