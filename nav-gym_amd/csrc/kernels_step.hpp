@@ -26,8 +26,44 @@ struct StepShared {
     int pair_done;                // pedestrian phase: wavefronts that have written their share of the pair table (ped_pair_share)
     int term;                     // io.final_obs of an arena that restarts in this step: 1 = its rows are scan A's, 2 = a scan of their own
                                   // (crash: the re-scan at the reverted pose, env.py:707-723); sits in what was padding
+    int vote;                     // scan A: crash (bit 0) and discomfort (bit 1) ORed over the arena's wavefronts (vote_flags); in padding
+    double lin_step;              // nv::linspace_step(c) and ...
+    float march_lim;              // ... march_limit(map, range_max, resolution): functions of the configuration alone, two float64
+                                  // divisions that every wavefront evaluated in every scan; now two lanes of phase 0, once per step
     double wave_ratio[kMaxWaves];
 };
+#ifndef NAVSIM_STEP_CONSTS_LDS          // leave-one-out builds (profiles/r20_scan_fixed/): 0 = every wavefront divides for itself
+#define NAVSIM_STEP_CONSTS_LDS 1
+#endif
+#ifndef NAVSIM_STEP_VOTE_LDS            // ... 0 = two __syncthreads_or
+#define NAVSIM_STEP_VOTE_LDS 1
+#endif
+// The two values of a scan that depend on the configuration alone, as the fused step's scans and merges read them: what phase 0
+// published in StepShared (step_consts_publish: the same operations on the same operands, so the same values).  The
+// stand-alone kernels (cast_static, ped_scan, regen_commit) call nv::linspace_step / march_limit themselves.
+__device__ __forceinline__ double scan_lin_step(const navsim_config& c, const StepShared& sh) {
+    if constexpr (NAVSIM_STEP_CONSTS_LDS) return sh.lin_step;
+    else return nv::linspace_step(c);
+}
+__device__ __forceinline__ float scan_march_limit(const navsim_config& c, const StepShared& sh) {
+    if constexpr (NAVSIM_STEP_CONSTS_LDS) return sh.march_lim;
+    else return march_limit(c.map_h, c.map_w, c.range_max, c.resolution);
+}
+// Phase 0, lanes l0 = 3 and 4 (which = 0 / 1): ONE float64 division serves both quotients, each on its own lane --
+// (angle_last - angle_min) / (n_beams - 1) and range_max / resolution -- and the lane finishes its value as
+// nv::linspace_step / march_limit do.  A lane's work costs the wavefront the same issue slots whether one lane or five are live.
+__device__ __forceinline__ void step_consts_publish(const navsim_config& c, StepShared& sh, int which) {
+    const double num = which ? c.range_max : c.angle_last - c.angle_min;
+    const double den = which ? c.resolution : (double)(c.n_beams - 1);
+    const double q = num / den;
+    if (which) {
+        const float full = (float)((long long)c.map_h * c.map_w);
+        const float lim = (float)(floor(q) + 4.0);
+        sh.march_lim = lim < full ? lim : full;
+    } else {
+        sh.lin_step = (c.n_beams > 1) ? q : 0.0;
+    }
+}
 // Pedestrian scratch of the pedestrian variants of the kernel, carved out of dynamic LDS behind the scan's
 // dir / rng area and sized by cfg.max_peds (N), not by the compiled maximum: 144 N + 32 bytes, so that a
 // 20-pedestrian world still fits 8 arenas per CU (the static 64-pedestrian layout allowed 7).
@@ -100,12 +136,21 @@ __device__ __forceinline__ bool beam_dir_fast(double lin, double lth, double ct,
                                               float& heading, float& dx, float& dy) {
     const double ang = lin + lth;
     heading = (float)ang;
-    // heading = lin + lth + delta EXACTLY: (heading - ang) is exact (Sterbenz), and the rounding error of the
-    // float64 sum is recovered by TwoSum
-    const double bb = ang - lin;
-    const double eps = (lin - (ang - bb)) + (lth - bb);
-    const double delta = ((double)heading - ang) + eps;
-    return nv::beam_dir_from_table(ct, st, cT, sT, delta, dx, dy);
+    if constexpr (nv::kDirTwoSum) {
+        // heading = lin + lth + delta EXACTLY: (heading - ang) is exact (Sterbenz), and the rounding error of the
+        // float64 sum is recovered by TwoSum
+        const double bb = ang - lin;
+        const double eps = (lin - (ang - bb)) + (lth - bb);
+        const double delta = ((double)heading - ang) + eps;
+        return nv::beam_dir_from_table(ct, st, cT, sT, delta, dx, dy);
+    } else {
+        // heading = ang + delta exactly (Sterbenz); the rounding error of the sum is paid for by the margin, which holds for
+        // |ang| < 64 (navsim_device.hpp [D]): beyond, and for a NaN, the candidate is declined.  |ang| on its high word: an
+        // integer and + compare instead of a float64 compare.
+        const double delta = (double)heading - ang;
+        const unsigned mag = (unsigned)__double2hiint(ang) & 0x7FFFFFFFu;
+        return nv::beam_dir_from_table(ct, st, cT, sT, delta, dx, dy) & (mag < nv::kDirHi64);
+    }
 }
 // direction of beam k: table fast path with proven rounding, else full sincos
 __device__ __forceinline__ void beam_dir_k(const navsim_config& c, const double* __restrict__ tab, int k,
@@ -241,12 +286,12 @@ __host__ __device__ inline float prim_cull_range(double range_max) { return (flo
 template <int BLOCK>
 __device__ __forceinline__ void prims_prepare(const navsim_config& c, const StepShared& sh, const Prims pr) {
     prim_in_range<BLOCK>(sh.nseg + sh.ndisc, sh.nseg, sh.lx, sh.ly, prim_cull_range(c.range_max), pr,
-                         (float)nv::linspace_step(c), (float)(c.angle_min + (double)sh.lth));
+                         (float)scan_lin_step(c, sh), (float)(c.angle_min + (double)sh.lth));
 }
 template <int BLOCK>
 __device__ __forceinline__ void merge_prims_culled(const navsim_config& c, const StepShared& sh, const Prims pr,
                                                    const float2* __restrict__ dir, float* __restrict__ rng) {
-    merge_prims_culled_core<BLOCK>(c.n_beams, sh.lx, sh.ly, (float)nv::linspace_step(c), sh.nseg, sh.ndisc, pr, dir, rng);
+    merge_prims_culled_core<BLOCK>(c.n_beams, sh.lx, sh.ly, (float)scan_lin_step(c, sh), sh.nseg, sh.ndisc, pr, dir, rng);
 }
 
 // raw ranges (cells) -> metres, pedestrians, clip, noise, crash / discomfort flags, observation row
@@ -262,7 +307,7 @@ __device__ __forceinline__ void finish_beams(const navsim_config& c, const StepS
     const int B = c.n_beams, S = c.n_scan_stack;
     const float res = (float)c.resolution;
     const float rmax = (float)c.range_max;
-    const double step = nv::linspace_step(c);
+    const double step = scan_lin_step(c, sh);
     const float lx = sh.lx, ly = sh.ly;
     const int nseg = sh.nseg, ndisc = sh.ndisc;
     const float r_all = sh.r_all;
@@ -533,10 +578,10 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
                                                 uint64_t noise_key, uint64_t genv,
                                                 int& crash, int& discomfort, bool prepare_prims = true) {
     const int B = c.n_beams, S = c.n_scan_stack, H = c.map_h, W = c.map_w;
-    const float max_range = march_limit(H, W, c.range_max, c.resolution);
+    const float max_range = scan_march_limit(c, sh);
     const float res = (float)c.resolution;
     const float rmax = (float)c.range_max;
-    const double step = nv::linspace_step(c);
+    const double step = scan_lin_step(c, sh);
     const int i0 = sh.i0, j0 = sh.j0;
     const float x0 = (float)i0, y0 = (float)j0;
     const bool int_range = int_range_ok(H, W);
@@ -673,6 +718,33 @@ __device__ __forceinline__ void scan_beams_pred(const navsim_config& c, StepShar
     }
     crash = cr;
     discomfort = dc;
+}
+
+// Scan A's crash / discomfort flags ORed over the arena's wavefronts: one lane per wavefront ORs its two bits into sh.vote,
+// ONE barrier, every wavefront reads the word.  (__syncthreads_or, twice, was a DPP reduction over the wave, an LDS round
+// trip and three barriers PER CALL -- for inputs that are one value per wavefront already.)
+// Without pedestrians the flags come out of the scan as one scalar per wavefront (crm / dcm); the pedestrian variants take
+// them per lane from finish_beams and a ballot makes them one.  A 64-thread workgroup is one wavefront: no LDS, no barrier.
+// sh.vote is zeroed by phase 0, whose barrier stands between that store and every OR.  Only scan A votes: the second scans of
+// a step (crash revert, restart, terminal row) drop their flags, so the word is neither zeroed nor written again in the
+// step -- thread 0 re-arming it with next_chunk in phase 4 would race the wavefronts that have not read it yet.
+template <int BLOCK, bool PEDS>
+__device__ __forceinline__ void vote_flags(StepShared& sh, int& crash, int& discomfort) {
+    if constexpr (!NAVSIM_STEP_VOTE_LDS) {
+        crash = __syncthreads_or(crash);
+        discomfort = __syncthreads_or(discomfort);
+    } else {
+        int v;
+        if constexpr (PEDS) v = (int)(mask_of(crash != 0) != 0) | ((int)(mask_of(discomfort != 0) != 0) << 1);
+        else v = (crash != 0) | ((discomfort != 0) << 1);
+        if constexpr (BLOCK > 64) {
+            if (v != 0 && ((int)threadIdx.x & 63) == 0) atomicOr(&sh.vote, v);
+            __syncthreads();
+            v = __builtin_amdgcn_readfirstlane(sh.vote);
+        }
+        crash = v & 1;
+        discomfort = (v >> 1) & 1;
+    }
 }
 
 // ---- pieces of phase 1 for ONE pedestrian (env.py:617-693 with the build-defined social force or external commands),
@@ -1366,8 +1438,10 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
     // Its three sincos -- the robot's old heading, its new heading, the float32 lidar heading -- depend on the old heading and
     // the action only: three lanes evaluate one each, at once (a lane's work costs the wavefront's issue slots whether one
     // lane or three are live; two sincos fewer are 180 of an arena's 11 500 vector instructions on c2).
+    // Lanes 3 and 4 ride along with them and take the scan's two configuration-only quotients (step_consts_publish); this
+    // phase's barrier orders their stores before every scan of the step, the re-scans included.
     const int l0 = tid - kPhase0Thread;
-    if (l0 >= 0 && l0 < 3) {
+    if (l0 >= 0 && l0 < (NAVSIM_STEP_CONSTS_LDS ? 5 : 3)) {
         const double th_old = rp_g[2];
         double a0 = 0.0, a1 = 0.0;
         if (!reset_only) {
@@ -1396,6 +1470,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
         const int w0 = kPhase0Thread & 63;                      // lane of l0 = 0 inside its wavefront (0)
         const double s0 = __shfl(sn, w0), c0 = __shfl(cs, w0), s1 = __shfl(sn, w0 + 1), c1 = __shfl(cs, w0 + 1);
         const double sT = __shfl(sn, w0 + 2), cT = __shfl(cs, w0 + 2);
+        if (NAVSIM_STEP_CONSTS_LDS && l0 >= 3) step_consts_publish(c, sh, l0 - 3);
         if (l0 == 0) {
             sh.old_rp[0] = rp_g[0]; sh.old_rp[1] = rp_g[1]; sh.old_rp[2] = th_old;
             sh.nseg = 0; sh.ndisc = 0; sh.rescan = 0; sh.respawn = 0; sh.term = 0;
@@ -1443,7 +1518,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
             sh.step_key = (unsigned long long)st.episode[e] * 0x100000000ULL +
                           (unsigned long long)(reset_only ? 0 : st.steps[e]) * 2ULL;
             sh.rescan_key = sh.step_key + 1;
-            sh.next_chunk = 0; sh.park_count = 0; sh.park_next = 0; sh.pair_done = 0;
+            sh.next_chunk = 0; sh.park_count = 0; sh.park_next = 0; sh.pair_done = 0; sh.vote = 0;
         }
     }
     __syncthreads();
@@ -1538,8 +1613,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
     NAVSIM_STAMP(3);
     bool restart_next = false;                                  // (thread 0) NEXT_STEP: the state restarts behind phase 6
     if (!reset_only) {
-        crash = __syncthreads_or(crash);
-        discomfort = __syncthreads_or(discomfort);
+        vote_flags<BLOCK, PEDS>(sh, crash, discomfort);
         double rmin = 1.0e300;
         if (discomfort && !crash) {                             // env.py:563-569
             for (int k = tid; k < B; k += BLOCK)

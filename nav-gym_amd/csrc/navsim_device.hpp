@@ -37,25 +37,48 @@ __device__ __forceinline__ void beam_dir(float heading, float& dx, float& dy) {
 }
 
 // Same direction from the beam table: cos/sin(lin_k + th + delta) by one angle addition, accepted only when the
-// float32 rounding is PROVABLY the one beam_dir() produces.  Error budget of the candidate against the true cos/sin
-// of the float32 heading (all values at most 1 in magnitude, 1 ulp = 1.1e-16): the table entries and cos/sin(th) are
-// within 1 ulp; C = fma(ct, cT, -(st sT)) inherits 2.2e-16 per product and adds one rounding each: <= 6.6e-16; the
-// second-order series in delta (|delta| <= 5e-7) is exact to 2e-20 and adds two fma roundings: <= 8.8e-16 in all;
-// beam_dir() itself is within 1.1e-16.  So both round alike whenever the candidate sits more than 3e-15 inside its
-// float32 rounding interval; otherwise the caller falls back to beam_dir() -- a few beams in 1e7.
+// float32 rounding is PROVABLY the one beam_dir() produces: the candidate must sit more than a MARGIN inside its float32
+// rounding interval, and the margin bounds the candidate's distance from beam_dir()'s float64 value.  Otherwise the caller
+// falls back to beam_dir().  Any form of the candidate is therefore bit-identical by construction, as long as its margin
+// bounds its error: precision (float64 instructions, the slowest class of the chip, once per 64-beam chunk of every scan)
+// can be traded for margin (a few more beams in 1e6 that take the fallback).
+//
+// Error budget against the true cos/sin of the float32 heading (all values at most 1 in magnitude, 1 ulp = 1.1e-16):
+//   [T] the table entries and cos/sin(th) are within 1 ulp; C = fma(ct, cT, -(st sT)) inherits 2.2e-16 per product and
+//       adds one rounding each: <= 6.6e-16.  beam_dir() itself is within 1.1e-16.
+//   [S] the series in delta, c = C - S delta - C delta^2 / 2.  |delta| <= half a float32 ulp of the heading, 2^-19 for
+//       |heading| <= 64: the remainder is below |delta|^3 / 6 = 1.2e-18, two fma roundings on top.  With [T] 8.8e-16 +
+//       1.1e-16, for which the margin has been 3e-15 since round 2 (kDirBudget).
+//   [D] delta.  heading = fl32(ang) with ang = fl64(lin + lth), and delta = heading - ang is exact (Sterbenz).  The table
+//       product's true angle is lin + lth = ang - eps with |eps| <= ulp64(ang) / 2, the rounding error of the float64 sum.
+//       kDirTwoSum recovers eps (TwoSum: 5 float64 additions per beam) and adds it to delta.  Without it (the default) eps
+//       stays out and enters c and s multiplied by at most 1 (the derivative of cos / sin): <= 2^-48 = 3.6e-15 for
+//       |ang| < 64.  beam_dir_fast() declines |ang| >= 64, where this bound no longer holds (the step's headings are lth in
+//       [0, 2 pi), |lin| <= 2 pi).
+// Margins: with TwoSum 3e-15; without 3e-15 + 3.6e-15 = 6.6e-15.
+// (Not kept, profiles/r20_scan_fixed/: first order, c = C - S delta, for wavefronts whose angles are all below 8 -- remainder
+// delta^2 / 2 <= 2^-45, margin 3.2e-14, 1.6e-5 of the beams fall back -- behind a scalar branch.  It ADDED 40 vector
+// instructions per arena-step on c2 and gained no time.)
 //
 // The interval: f = fl32(v) and r = v - f (exact).  The float32 neighbours of v are spaced 2^(e-23) apart with e the
 // binary exponent of v ITSELF (if f rounded up to the power of two above, the spacing on v's side is still that
 // of v's binade), so v is half_ulp - |r| away from the nearest rounding boundary, half_ulp = 2^(e-24), built from
-// v's exponent field.  A component below 2^-23 has half_ulp < 3e-15 and never passes; a zero exponent field (v = 0)
+// v's exponent field.  A component whose half_ulp is below the margin never passes; a zero exponent field (v = 0)
 // makes half_ulp a negative number and does not pass either: those beams go to beam_dir().
+#ifndef NAVSIM_DIR_TWOSUM               // leave-one-out builds (profiles/r20_scan_fixed/): 1 = recover the sum's rounding error
+#define NAVSIM_DIR_TWOSUM 0
+#endif
+constexpr bool kDirTwoSum = NAVSIM_DIR_TWOSUM != 0;
+constexpr double kDirBudget = 3.0e-15;                                     // [T] + [S]
+constexpr double kDirMargin = kDirTwoSum ? kDirBudget : 6.6e-15;           // ... + [D], |ang| < 64
+constexpr unsigned kDirHi64 = 0x40500000u;                                 // high word of 64.0
 __device__ __forceinline__ bool round_if_safe(double v, float& out) {
     const float f = (float)v;
     const double r = v - (double)f;
     const int hi = __double2hiint(v);
     const double half_ulp = __hiloint2double((hi & 0x7FF00000) - (24 << 20), 0);
     out = f;
-    return half_ulp - __builtin_fabs(r) >= 3.0e-15;
+    return half_ulp - __builtin_fabs(r) >= kDirMargin;
 }
 __device__ __forceinline__ bool beam_dir_from_table(double ct, double st, double cT, double sT, double delta,
                                                     float& dx, float& dy) {
