@@ -5,7 +5,6 @@ import numpy as np
 
 import dwa_spec
 import ref
-from nav_gym_amd import abi
 
 SIN, COS = 0, 1
 # sim.local_map_defaults(cfg) in a world with pedestrians

@@ -5,7 +5,6 @@ import numpy as np
 
 import orca_f64 as f64
 import orca_scenes as scenes
-import ped_orca_spec as spec
 import ped_orca_walls_spec as wspec
 
 SIZE, RES = 120, 0.05                                              # 120 x 120 cells of 0.05 m: 6 m

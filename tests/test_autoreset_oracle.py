@@ -9,27 +9,8 @@ import numpy as np
 import pytest
 
 import ref
-from helpers import load_trace, trace_setup, outdoor_map
-from nav_gym_amd import abi, robots
-
-
-def trace_world(tr, default_config, build_dt, mode):
-    """trace_setup + a one-entry spawn table (the trace's own start) so that the arena can restart."""
-    cfg, arrays, occ = trace_setup(tr, default_config, build_dt)
-    cfg.auto_reset = mode
-    cfg.n_spawn = 1
-    arrays["spawn_pose"] = tr["init_robot_pose"][None, None].copy()
-    arrays["spawn_goal"] = tr["robot_goal"][None, None].copy()
-    return cfg, arrays, occ
-
-
-def check_terminal_row(tr, row, goals, t):
-    S, B = int(tr["S"]), int(tr["B"])
-    assert np.array_equal(row[: S * B], tr["obs_scan"][t]), "terminal scan stack"
-    np.testing.assert_allclose(row[S * B:], tr["obs_tail"][t], rtol=0, atol=2e-6)
-    if goals is not None:                                   # achieved_goal = the pose slots, desired_goal = the goal (env.py:455-461)
-        np.testing.assert_allclose(goals[:2], tr["obs_tail"][t][2:4], rtol=0, atol=2e-6)
-        np.testing.assert_allclose(goals[2:], tr["robot_goal"], rtol=0, atol=2e-6)
+from helpers import check_terminal_row, keti_thresholds, load_trace, trace_world
+from nav_gym_amd import abi
 
 
 @pytest.mark.parametrize("name", ["crash_S3", "success_S2"])
@@ -81,8 +62,7 @@ def _static_world(E, size, seed, mode, S=2, beams=90):
     arrays = world.make_world(cfg, occ, n_peds=0, device="cpu", field=torch.from_numpy(ref.build_dt(occ)), min_goal_dist=1.0,
                               max_goal_dist=2.5, robot_clearance=0.8)
     host = {k: v.numpy() for k, v in arrays.items()}
-    host["scan_threshold"] = ref.scan_threshold(cfg, robots.footprint_array("keti", "threshold_footprint"))
-    host["scan_discomfort"] = ref.scan_threshold(cfg, robots.footprint_array("keti", "discomfort_threshold_footprint"))
+    host["scan_threshold"], host["scan_discomfort"] = keti_thresholds(cfg)
     return cfg, host
 
 

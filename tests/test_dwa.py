@@ -10,6 +10,7 @@ import pytest
 
 import dwa_spec as spec
 import ref
+from helpers import struct_fields
 from nav_gym_amd import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -130,16 +131,6 @@ def test_population_of_the_random_worlds():
 
 
 # ---- C ABI ----------------------------------------------------------------------------------------------------------------------
-def _struct_fields(header, name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        if decl.strip():                                   # "double a, b", "double x[NAVSIM_DWA_MAX_DISCS]", "float* p"
-            names += [re.match(r"\s*(\w+)", part).group(1) for part in decl.strip().split(None, 1)[1].split(",")]
-    return names
-
-
 def test_symbol_and_structures_in_header_library_and_exports():
     from nav_gym_amd import lib
     L = lib.load()
@@ -148,12 +139,12 @@ def test_symbol_and_structures_in_header_library_and_exports():
     assert C.sizeof(abi.NavsimConfig) == 624 == L.navsim_sizeof_config()         # no structure changed its size
     assert C.sizeof(abi.NavsimState) == L.navsim_sizeof_state() and C.sizeof(abi.NavsimStepIO) == L.navsim_sizeof_step_io()
     assert re.search(r"\bint navsim_dwa\(", header) and "navsim_dwa" in abi.EXPORTS and hasattr(L, "navsim_dwa")
-    fields = _struct_fields(header, "navsim_dwa_params")
+    fields = struct_fields(header, "navsim_dwa_params")
     assert fields == ["acc_lin", "acc_rot", "body_radius", "body_offset", "ped_radius", "margin", "clearance_cap", "w_progress",
                       "w_heading", "w_clearance", "w_speed", "n_discs", "n_v", "n_w", "horizon", "use_peds"]
     assert [n for n, _ in abi.NavsimDwaParams._fields_] == fields
     assert C.sizeof(abi.NavsimDwaParams) == 14 * 8 + 5 * 4 + 4 and abi.NavsimDwaParams.n_discs.offset == 112
-    assert _struct_fields(header, "navsim_dwa_out") == [n for n, _ in abi.NavsimDwaOut._fields_] == list(abi.DWA_OUT) == list(spec.KEYS)
+    assert struct_fields(header, "navsim_dwa_out") == [n for n, _ in abi.NavsimDwaOut._fields_] == list(abi.DWA_OUT) == list(spec.KEYS)
     for name, value in (("DWA_MAX_DISCS", 4), ("DWA_OK", 1), ("DWA_BLOCKED", 2)):
         assert re.search(r"#define NAVSIM_%s\s+%d\b" % (name, value), header) and getattr(abi, name) == value
     assert (spec.OK, spec.BLOCKED) == (abi.DWA_OK, abi.DWA_BLOCKED)

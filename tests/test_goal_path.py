@@ -13,6 +13,7 @@ import pytest
 
 import goal_path_spec as spec
 import ref
+from helpers import struct_fields
 from nav_gym_amd import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -181,12 +182,6 @@ def test_spiral_needs_the_whole_corridor():
 
 
 # ---- C ABI ------------------------------------------------------------------------------------------------------------------
-def _struct_fields(header, name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    return re.findall(r"(\w+)\s*;", body)
-
-
 def test_symbol_and_structures_in_header_library_and_exports():
     from nav_gym_amd import lib
     L = lib.load()
@@ -198,12 +193,12 @@ def test_symbol_and_structures_in_header_library_and_exports():
     assert re.search(r"\bint navsim_goal_path\(", header) and re.search(r"\bsize_t navsim_goal_field_bytes\(", header)
     for name in ("navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps"):
         assert name in abi.EXPORTS and hasattr(L, name), name
-    fields = _struct_fields(header, "navsim_goal_path_params")
+    fields = struct_fields(header, "navsim_goal_path_params")
     assert fields == ["hard_clearance", "clearance", "lookahead", "band_cost"]
     assert [n for n, _ in abi.NavsimGoalPathParams._fields_] == fields
     assert C.sizeof(abi.NavsimGoalPathParams) == 32
-    assert _struct_fields(header, "navsim_goal_field") == [n for n, _ in abi.NavsimGoalField._fields_] == ["dist", "key", "rebuilds"]
-    assert _struct_fields(header, "navsim_goal_path_out") == [n for n, _ in abi.NavsimGoalPathOut._fields_] == list(abi.GOAL_PATH_OUT)
+    assert struct_fields(header, "navsim_goal_field") == [n for n, _ in abi.NavsimGoalField._fields_] == ["dist", "key", "rebuilds"]
+    assert struct_fields(header, "navsim_goal_path_out") == [n for n, _ in abi.NavsimGoalPathOut._fields_] == list(abi.GOAL_PATH_OUT)
     for name, value in (("OK", 1), ("REACHED_GOAL_CELL", 2), ("OFF_FIELD", 4)):
         assert re.search(r"#define NAVSIM_GOAL_PATH_%s\s+%d\b" % (name, value), header) and getattr(abi, "GOAL_PATH_" + name) == value
     assert (spec.OK, spec.REACHED, spec.OFF_FIELD) == (1, 2, 4)

@@ -5,37 +5,11 @@ import numpy as np
 import pytest
 
 import ref
-from helpers import load_trace
+from gpu_support import gpu, eq, random_actions, sim_and_oracle, state_equal, to_device, to_numpy  # noqa: F401  (gpu: the module's fixture)
+from helpers import check_terminal_row, load_trace, trace_world
 from nav_gym_amd import abi
-from test_autoreset_oracle import trace_world, check_terminal_row
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from nav_gym_amd import lib, sim, world
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    lib.load()
-    return type("G", (), dict(torch=torch, lib=lib, sim=sim, world=world, dev=torch.device("cuda:0")))
-
-
-def _t(gpu, a, dtype=None):
-    t = gpu.torch.from_numpy(np.ascontiguousarray(a)).to(gpu.dev)
-    return t if dtype is None else t.to(dtype)
-
-
-def _eq(a, b, what):
-    a = np.asarray(a); b = np.asarray(b)
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        diff = np.max(np.abs(a.astype(np.float64) - b.astype(np.float64)))
-        raise AssertionError("%s: %d mismatches, max |diff| %.3e, first at %s" % (what, len(bad), diff, bad[0]))
-
-
-def _np(d):
-    return {k: v.cpu().numpy() for k, v in d.items()}
 
 
 @pytest.mark.parametrize("name", ["crash_S3", "success_S2"])
@@ -47,7 +21,7 @@ def test_terminal_observation_of_the_reference_traces_on_the_device(gpu, name, m
     io.final_obs (same-step restart) resp. as the observation itself (next-step restart), alone and inside a batch whose
     other arenas drive differently (arena 2 of 5 replays the trace)."""
     tr = load_trace(name)
-    cfg, arrays, occ = trace_world(tr, gpu.lib.default_config, lambda o: gpu.sim.build_dt(_t(gpu, o)).cpu().numpy(), mode)
+    cfg, arrays, occ = trace_world(tr, gpu.lib.default_config, lambda o: gpu.sim.build_dt(to_device(gpu, o)).cpu().numpy(), mode)
     me = 2 if E > 1 else 0
     cfg.n_envs = E
     arrays = {k: (np.repeat(v, E, axis=0) if (isinstance(v, np.ndarray) and v.ndim >= 1 and v.shape[0] == 1 and k not in ("scan_threshold", "scan_discomfort")) else v)
@@ -57,7 +31,7 @@ def test_terminal_observation_of_the_reference_traces_on_the_device(gpu, name, m
     host = dict(arrays); host["field"] = ref.build_dt(np.repeat(occ[None], E, axis=0))
     r = ref.RefSim(cfg, host)
     first = g.reset_obs().cpu().numpy()
-    _eq(first, r.reset_obs(), "first observations")
+    eq(first, r.reset_obs(), "first observations")
     T = int(np.argmax(tr["done"] != 0)) + 1
     S, B = int(tr["S"]), int(tr["B"])
     rng = np.random.default_rng(3)
@@ -69,21 +43,21 @@ def test_terminal_observation_of_the_reference_traces_on_the_device(gpu, name, m
         g.set_ped_cmd(cmd); r.set_ped_cmd(cmd)
         obs, out = g.step(act)
         ro, rout = r.step(act)
-        obs = obs.cpu().numpy(); out = _np(out)
+        obs = obs.cpu().numpy(); out = to_numpy(out)
         for k in rout:
-            _eq(out[k], rout[k], "%s at step %d" % (k, t))
-        _eq(obs, ro, "observations at step %d" % t)
+            eq(out[k], rout[k], "%s at step %d" % (k, t))
+        eq(obs, ro, "observations at step %d" % t)
         done = rout["done"] != 0
         if mode == abi.AUTORESET_SAME_STEP and done.any():
-            fin = _np(g.final)
-            _eq(fin["final_obs"][done], r.final["final_obs"][done], "terminal rows at step %d" % t)
-            _eq(fin["final_goals"][done], r.final["final_goals"][done], "terminal goals at step %d" % t)
+            fin = to_numpy(g.final)
+            eq(fin["final_obs"][done], r.final["final_obs"][done], "terminal rows at step %d" % t)
+            eq(fin["final_goals"][done], r.final["final_goals"][done], "terminal goals at step %d" % t)
         if t < T:
             assert out["done"][me] == tr["done"][t] and out["is_crash"][me] == tr["is_crash"][t] and out["is_success"][me] == tr["is_success"][t], t
             assert abs(out["reward"][me] - tr["reward"][t]) < 1e-9, t
         if t == T - 1:
             if mode == abi.AUTORESET_SAME_STEP:
-                fin = _np(g.final)
+                fin = to_numpy(g.final)
                 check_terminal_row(tr, fin["final_obs"][me], fin["final_goals"][me], t)
                 assert np.array_equal(obs[me, S * B:], first[me, S * B:])          # the row: the next episode's first observation
             else:
@@ -91,34 +65,6 @@ def test_terminal_observation_of_the_reference_traces_on_the_device(gpu, name, m
         if t == T and mode == abi.AUTORESET_NEXT_STEP:
             assert g.reset_flags[me].item() == 1 and out["done"][me] == 0 and out["reward"][me] == 0.0
             assert np.array_equal(obs[me, S * B:], first[me, S * B:])
-
-
-def _pair(gpu, cfg, occ, n_peds, final_obs=False, **world_kw):
-    from nav_gym_amd import robots
-    arrays = gpu.world.make_world(cfg, occ, n_peds=n_peds, device=gpu.dev, **world_kw)
-    arrays["scan_threshold"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "threshold_footprint")))
-    arrays["scan_discomfort"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "discomfort_threshold_footprint")))
-    host = {k: v.cpu().numpy() for k, v in arrays.items() if k not in ("field", "field_overflow", "rect_table", "rect_index")}
-    host["field"] = ref.build_dt(occ)
-    g = gpu.sim.NavSim(cfg, arrays, final_obs=final_obs)
-    r = ref.RefSim(cfg, host)
-    _eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
-    return g, r
-
-
-def _actions(rng, cfg, t):
-    E = cfg.n_envs
-    act = np.stack([rng.uniform(0.0, 0.5, E), rng.uniform(-0.64, 0.64, E)], axis=1)
-    if t % 7 == 3:
-        act[:, 0] = 0.5; act[:, 1] = 0.0          # bursts of straight driving provoke crashes
-    return act
-
-
-def _state_eq(g, r, what, skip=()):
-    gs = g.numpy_state()
-    for k, v in r.a.items():
-        if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index", "counters") + tuple(skip):
-            _eq(gs[k], v, "state %s %s" % (k, what))
 
 
 @pytest.mark.parametrize("fmt", [abi.FIELD_F32, abi.FIELD_U16T, "u16t-rects-from-global-memory"])
@@ -141,25 +87,25 @@ def test_autoreset_modes_vs_oracle(gpu, mode, ped_model, S, block, fmt):
     else:
         gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 4343)
-    g, r = _pair(gpu, cfg, occ, 6, final_obs=(mode == abi.AUTORESET_SAME_STEP), min_goal_dist=1.5, max_goal_dist=4.0)
+    g, r, _ = sim_and_oracle(gpu, cfg, occ, 6, final_obs=(mode == abi.AUTORESET_SAME_STEP), min_goal_dist=1.5, max_goal_dist=4.0)
     rng = np.random.default_rng(5)
     crashes = ends = crash_ends = resets = 0
     for t in range(70):
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, E, t)
         if ped_model == abi.PED_EXTERNAL:
             cmd = np.stack([rng.uniform(0, 0.6, (E, N)), rng.uniform(-0.6, 0.6, (E, N))], axis=2)
             g.set_ped_cmd(cmd); r.set_ped_cmd(cmd)
         go, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         ro, rout = r.step(act)
-        gout = _np(gout)
+        gout = to_numpy(gout)
         for k in rout:
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
-        _eq(go.cpu().numpy(), ro, "obs at step %d" % t)
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
+        eq(go.cpu().numpy(), ro, "obs at step %d" % t)
         done = rout["done"] != 0
         if mode == abi.AUTORESET_SAME_STEP and done.any():
-            fin = _np(g.final)
-            _eq(fin["final_obs"][done], r.final["final_obs"][done], "terminal rows at step %d" % t)
-            _eq(fin["final_goals"][done], r.final["final_goals"][done], "terminal goals at step %d" % t)
+            fin = to_numpy(g.final)
+            eq(fin["final_obs"][done], r.final["final_obs"][done], "terminal rows at step %d" % t)
+            eq(fin["final_goals"][done], r.final["final_goals"][done], "terminal goals at step %d" % t)
             # a terminal row that ends in success is what compute_terminals judges `done` (after a crash the reference returns
             # the re-scan at the reverted pose, whose flags are clear: SURVEY.md 9.2 item 8)
             won = done & (rout["is_crash"] == 0)
@@ -167,11 +113,11 @@ def test_autoreset_modes_vs_oracle(gpu, mode, ped_model, S, block, fmt):
                 rd = ref.reward_done(r.cfg, r.final["final_obs"][won], r.final["final_goals"][won][:, 2:], r.a["scan_threshold"], r.a["scan_discomfort"])
                 assert (rd["done"] != 0).all() and (rd["is_success"] != 0).all()
         if mode == abi.AUTORESET_NEXT_STEP:
-            _eq(g.reset_flags.cpu().numpy(), r.reset_flags, "reset flags at step %d" % t)
+            eq(g.reset_flags.cpu().numpy(), r.reset_flags, "reset flags at step %d" % t)
             resets += int(r.reset_flags.sum())
         crashes += int(rout["is_crash"].sum()); ends += int(done.sum()); crash_ends += int((done & (rout["is_crash"] != 0)).sum())
         if t % 10 == 9:
-            _state_eq(g, r, "at step %d" % t)
+            state_equal(g, r, "at step %d" % t, skip=("counters",))
     assert ends > 10 and crash_ends > 2, (ends, crash_ends)
     if mode == abi.AUTORESET_NEXT_STEP:
         assert resets >= ends - E
@@ -192,32 +138,32 @@ def test_next_step_autoreset_with_navsim_regen(gpu, fmt, ped_model, plan, defer)
                                  defer_reset_scan=defer)
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 19)
-    g, r = _pair(gpu, cfg, occ, 5, plan_paths=bool(plan) and ped_model != abi.PED_NONE)
+    g, r, _ = sim_and_oracle(gpu, cfg, occ, 5, plan_paths=bool(plan) and ped_model != abi.PED_NONE)
     rng = np.random.default_rng(6)
     B = cfg.n_beams * cfg.n_scan_stack
     regenerated = capped = 0
     for t in range(50):
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, E, t)
         go, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         ro, rout = r.step(act)
-        go = go.cpu().numpy(); gout = _np(gout)
+        go = go.cpu().numpy(); gout = to_numpy(gout)
         for k in ("reward", "done", "is_success", "is_crash", "distance"):
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
         flags = r.reset_flags != 0
-        _eq(g.reset_flags.cpu().numpy() != 0, flags, "reset flags at step %d" % t)
+        eq(g.reset_flags.cpu().numpy() != 0, flags, "reset flags at step %d" % t)
         keep = ~flags if defer else np.ones(E, bool)          # (deferred: the rows of the arenas being reset come from regen)
-        _eq(go[keep], ro[keep], "obs at step %d" % t)
+        eq(go[keep], ro[keep], "obs at step %d" % t)
         go2 = g.regen().cpu().numpy()
         ro2 = r.regen()
-        _eq(go2, ro2, "obs after regen at step %d" % t)
+        eq(go2, ro2, "obs after regen at step %d" % t)
         for k in ("achieved_goal", "desired_goal"):
-            _eq(g.out[k].cpu().numpy(), r.out[k], "%s after regen at step %d" % (k, t))
+            eq(g.out[k].cpu().numpy(), r.out[k], "%s after regen at step %d" % (k, t))
         n = int(flags.sum())
         regenerated += min(n, cap); capped += n > cap
         if n:
-            _state_eq(g, r, "after regen at step %d" % t)
+            state_equal(g, r, "after regen at step %d" % t, skip=("counters",))
             if fmt == abi.FIELD_F32:
-                _eq(g.numpy_state("field")["field"], r.a["field"], "field after regen at step %d" % t)
+                eq(g.numpy_state("field")["field"], r.a["field"], "field after regen at step %d" % t)
     assert regenerated > 5 and (capped > 0 or not defer), (regenerated, capped)
 
 
@@ -241,7 +187,7 @@ def test_next_step_autoreset_with_the_pipelined_reset_path(gpu, monkeypatch, per
     else:
         gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 31)
-    g, r = _pair(gpu, cfg, occ, 5)
+    g, r, _ = sim_and_oracle(gpu, cfg, occ, 5)
     g.enable_pregen(pipeline=period, install=True, late_beside=beside)
     assert (g.late2 is not None) == beside
     if slow:
@@ -260,23 +206,23 @@ def test_next_step_autoreset_with_the_pipelined_reset_path(gpu, monkeypatch, per
     n_reset = 0
     for t in range(110):
         hold["on"] = slow and (28 <= t <= 36 or 58 <= t <= 66)
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, E, t)
         go, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         ro, rout = r.step(act)
-        go = go.cpu().numpy(); gout = _np(gout)
+        go = go.cpu().numpy(); gout = to_numpy(gout)
         for k in ("reward", "done", "is_success", "is_crash", "distance"):
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
         flags = r.reset_flags != 0
-        _eq(go[~flags], ro[~flags], "obs at step %d" % t)      # (an installed arena's row is already its new world's)
+        eq(go[~flags], ro[~flags], "obs at step %d" % t)      # (an installed arena's row is already its new world's)
         n_reset += int(flags.sum())
         go2 = g.regen().cpu().numpy()
         ro2 = r.regen()
-        _eq(go2, ro2, "obs after regen at step %d" % t)
+        eq(go2, ro2, "obs after regen at step %d" % t)
         for k in ("achieved_goal", "desired_goal"):
-            _eq(g.out[k].cpu().numpy(), r.out[k], "%s after regen at step %d" % (k, t))
+            eq(g.out[k].cpu().numpy(), r.out[k], "%s after regen at step %d" % (k, t))
         if flags.any():
             gpu.torch.cuda.synchronize()
-            _state_eq(g, r, "after regen at step %d" % t, skip=("ped_waypoints",))
+            state_equal(g, r, "after regen at step %d" % t, skip=("counters", "ped_waypoints"))
         if min_steps == 0 and E >= 8 and t in (30, 32, 60, 62):
             # two episode ends two calls apart (the robot put on its goal right after its reset): the second finds nothing staged
             idx = gpu.torch.arange(2, 8, device=gpu.dev)
@@ -302,19 +248,19 @@ def test_reset_of_some_arenas_on_the_device(gpu):
                                  auto_reset=abi.AUTORESET_NONE, seed=77)
     gpu.world.lidar_full_circle(cfg, 180)
     occ = gpu.world.make_maps(E, size, 77)
-    g, r = _pair(gpu, cfg, occ, 3)
+    g, r, _ = sim_and_oracle(gpu, cfg, occ, 3)
     rng = np.random.default_rng(8)
     for t in range(30):
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, E, t)
         go, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         ro, rout = r.step(act)
-        _eq(go.cpu().numpy(), ro, "obs at step %d" % t)
+        eq(go.cpu().numpy(), ro, "obs at step %d" % t)
         if t % 6 == 5:
             mask = (rout["done"] != 0) | (rng.uniform(size=E) < 0.2)      # the finished arenas and a few others
             rows = g.reset_arenas(gpu.torch.from_numpy(mask).to(gpu.dev)).cpu().numpy()
-            _eq(rows, r.restart(mask), "rows after the reset of some arenas at step %d" % t)
-            _eq(g.out["done"].cpu().numpy(), r.out["done"], "done flags after the reset")
-            _state_eq(g, r, "after the reset of some arenas at step %d" % t)
+            eq(rows, r.restart(mask), "rows after the reset of some arenas at step %d" % t)
+            eq(g.out["done"].cpu().numpy(), r.out["done"], "done flags after the reset")
+            state_equal(g, r, "after the reset of some arenas at step %d" % t, skip=("counters",))
 
 
 def test_env_autoreset_modes_and_reset_mask(gpu):

@@ -3,8 +3,8 @@ declared in __init__ at the "not enabled" values, the reset calls run on it as i
 arguments say."""
 import pytest
 
+from gpu_support import gpu, device_sim, regen_layout, seeded_action  # noqa: F401  (gpu: the module's fixture)
 from nav_gym_amd import abi
-from test_gpu_workspaces import _act, _regen_world, _sim, gpu  # noqa: F401  (the module's fixture and world helpers)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,16 +19,16 @@ OFF = dict(pregen=False, pg_install=False, pg_period=0, pg_k=0, pg_passes=0, sta
 
 def test_a_simulator_without_any_enable_call(gpu):
     torch = gpu.torch
-    cfg, occ, _, wkw = _regen_world(gpu, "float32-smallest")       # its map and spawn rules; smaller, packed, with pedestrians
+    cfg, occ, _, wkw = regen_layout(gpu, "float32-smallest")       # its map and spawn rules; smaller, packed, with pedestrians
     E = 6                                                           # no multiple of 4: the last word of `mark` is padding
     cfg.n_envs, cfg.regen_cap, cfg.max_peds, cfg.ped_model, cfg.field_format = E, E, 2, abi.PED_SFM, abi.FIELD_U16T
     gpu.world.lidar_full_circle(cfg, 64)
-    g = _sim(gpu, cfg, occ[:E], 2, **wkw)
+    g = device_sim(gpu, cfg, occ[:E], 2, **wkw)
     for k, v in OFF.items():
         assert getattr(g, k) == v and type(getattr(g, k)) is type(v), k
     g.close(); g.close()
     # the reset calls of an object that has not been through enable_pregen / enable_graphs
-    g.step(_act(gpu, E, 1))
+    g.step(seeded_action(gpu, E, 1))
     g.out["done"].fill_(1)
     goals = g.t["spawn_goal"].clone()
     g.regen()
@@ -48,7 +48,7 @@ def test_a_simulator_without_any_enable_call(gpu):
     assert g.late is not None and g.late.shape == (E,)              # regen_min_steps = 0 < 4 P: the fallback
     assert g.late2 is None and g.lone is False and g.late_poll is False    # same-step restarts, outdoor maps, no planning
     for k in (2, 3, 4):
-        obs, out = g.step(_act(gpu, E, k))
+        obs, out = g.step(seeded_action(gpu, E, k))
         g.regen()
     torch.cuda.synchronize()
     assert torch.isfinite(obs).all() and g.pg_k == 3 and g.pg_passes == 3

@@ -3,84 +3,16 @@ tests/dwa_spec.py, bit for bit -- twist, action, clearance and scores as raw bit
 states at the shapes where the kernel's mapping changes (45 candidates, 512, one), both field formats, every way an arena finds
 its map, pedestrians on and off, a skip mask, a sub-goal, wheel actions, a closed loop through NavGymEnv under every reset path,
 and the refusals.  Every output is pre-filled with a sentinel: the call writes every element."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import dwa_spec as spec
 import ref
+from dwa_call import KEYS, c_params, call, device_state, same, untouched
+from gpu_support import gpu, eq  # noqa: F401  (gpu: the module's fixture)
 from nav_gym_amd import abi
-from test_gpu_autoreset import gpu, _t, _eq  # noqa: F401  (gpu: the module's fixture)
 
 pytestmark = pytest.mark.gpu
-
-KEYS = spec.KEYS
-BITS = dict(twist=np.uint64, action=np.uint64, scores=np.uint64, clearance=np.uint32)
-
-
-def _params(gpu, cfg, params):
-    return gpu.sim.dwa_params(cfg, params)
-
-
-def _call(gpu, cfg, st, params, subgoal=None, skip=None, want_rc=0, n_out=None, with_scores=True, n_cand=None):
-    """navsim_dwa into sentinel-filled outputs (n_out rows; None: cfg.n_envs) -> NumPy arrays."""
-    p = _params(gpu, cfg, params) if isinstance(params, dict) else params
-    torch, E = gpu.torch, cfg.n_envs if n_out is None else n_out
-    Cn = p.n_v * p.n_w if n_cand is None else n_cand
-    out = dict(twist=torch.full((E, 2), 777.0, dtype=torch.float64, device=gpu.dev),
-               action=torch.full((E, 2), 777.0, dtype=torch.float64, device=gpu.dev),
-               clearance=torch.full((E,), 777.0, dtype=torch.float32, device=gpu.dev),
-               best=torch.full((E,), 7777, dtype=torch.int32, device=gpu.dev),
-               status=torch.full((E,), 77, dtype=torch.uint8, device=gpu.dev),
-               scores=torch.full((E, Cn), 777.0, dtype=torch.float64, device=gpu.dev),
-               first_hit=torch.full((E, Cn), 7777, dtype=torch.int32, device=gpu.dev))
-    o = abi.NavsimDwaOut(**{k: (v.data_ptr() if with_scores or k not in ("scores", "first_hit") else None) for k, v in out.items()})
-    t_sub = None if subgoal is None else _t(gpu, np.asarray(subgoal, np.float32))
-    t_skip = None if skip is None else _t(gpu, np.asarray(skip, np.uint8))
-    rc = gpu.lib.load().navsim_dwa(C.byref(cfg), C.byref(st), C.byref(p), None if subgoal is None else t_sub.data_ptr(),
-                                   None if skip is None else t_skip.data_ptr(), C.byref(o), None)
-    assert rc == want_rc, rc
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def _untouched(dev, keys=KEYS):
-    for k in keys:
-        assert (dev[k] == (7777 if k in ("best", "first_hit") else (77 if k == "status" else 777.0))).all(), k
-
-
-def _same(dev, want, what, keys=KEYS):
-    for k in keys:
-        a, b = dev[k], want[k]
-        assert a.dtype == b.dtype and a.shape == b.shape, (what, k, a.dtype, a.shape, b.dtype, b.shape)
-        if k in BITS:
-            a, b = a.view(BITS[k]), b.view(BITS[k])
-        _eq(a, b, "%s: %s" % (what, k))
-
-
-def _device_state(gpu, cfg, occ, w, overflow=False, map_slot=None, peds=True):
-    """navsim_state over device copies of the world `w` and the field of `occ` [M,H,W] in cfg.field_format (overflow: whether the
-    packed field must saturate somewhere; None: as it comes).  -> (st, keepalive)"""
-    occ_t = _t(gpu, occ)
-    keep = {k: _t(gpu, np.asarray(w[k], np.float64)) for k in ("robot_pose", "robot_goal", "prev_action")}
-    if peds:
-        keep.update(n_peds=_t(gpu, np.asarray(w["n_peds"], np.int32)), ped_pose=_t(gpu, np.asarray(w["ped_pose"], np.float64)),
-                    ped_vel=_t(gpu, np.asarray(w["ped_vel"], np.float64)))
-    if cfg.field_format == abi.FIELD_F32:
-        keep["field"] = gpu.sim.build_dt(occ_t)
-    else:
-        keep["field"], plane, nsat = gpu.sim.build_field(occ_t, abi.FIELD_U16T)
-        assert overflow is None or (nsat > 0) == overflow, nsat
-        if nsat > 0:
-            keep["field_overflow"] = plane
-    if map_slot is not None:
-        keep["map_slot"] = _t(gpu, np.asarray(map_slot, np.int32))
-    st = abi.NavsimState()
-    for k, v in keep.items():
-        setattr(st, k, v.data_ptr())
-    return st, keep
-
 
 _WORLDS = {}
 
@@ -103,27 +35,27 @@ def test_base_world_equals_the_spec(gpu, fmt):
     occ, w, fields, params, want = _world("BASE")
     E, N, size, _ = spec.BASE
     cfg = spec.config(E, size, N, field_format=fmt)
-    st, keep = _device_state(gpu, cfg, occ, w)
-    _same(_call(gpu, cfg, st, params), want, "base")
-    dev = _call(gpu, cfg, st, params, with_scores=False)
-    _same(dev, want, "without scores", keys=KEYS[:5])
-    _untouched(dev, ("scores", "first_hit"))
+    st, keep = device_state(gpu, cfg, occ, w)
+    same(call(gpu, cfg, st, params), want, "base")
+    dev = call(gpu, cfg, st, params, with_scores=False)
+    same(dev, want, "without scores", keys=KEYS[:5])
+    untouched(dev, ("scores", "first_hit"))
     skip = np.array([0, 1, 0, 0, 1], np.uint8)
-    _same(_call(gpu, cfg, st, params, skip=skip), spec.plan(cfg, fields, w, params, skip=skip), "skip")
+    same(call(gpu, cfg, st, params, skip=skip), spec.plan(cfg, fields, w, params, skip=skip), "skip")
     rng = np.random.default_rng(3)
     sub = rng.uniform(-2.0, 2.0, (E, 2)).astype(np.float32)
     with_sub = spec.plan(cfg, fields, w, params, subgoal=sub)
     assert (with_sub["scores"] != want["scores"]).any()
-    _same(_call(gpu, cfg, st, params, subgoal=sub), with_sub, "sub-goal")
+    same(call(gpu, cfg, st, params, subgoal=sub), with_sub, "sub-goal")
     off = dict(params, use_peds=0)
     want_off = spec.plan(cfg, fields, w, off)
     assert (want_off["first_hit"] != want["first_hit"]).any()
-    _same(_call(gpu, cfg, st, off), want_off, "use_peds = 0")
+    same(call(gpu, cfg, st, off), want_off, "use_peds = 0")
     for what, p in (("default body", dict(n_v=5, n_w=9, horizon=6)),
                     ("four discs, other weights", dict(params, body_offset=(0.2, 0.0, -0.2, -0.4), body_radius=0.15, margin=0.0,
                                                        w_progress=-1.0, w_heading=2.0, w_clearance=0.0, w_speed=-0.5, clearance_cap=0.4)),
                     ("all weights zero", dict(params, w_progress=0.0, w_heading=0.0, w_clearance=0.0, w_speed=0.0))):
-        _same(_call(gpu, cfg, st, p), spec.plan(cfg, fields, w, p), what)
+        same(call(gpu, cfg, st, p), spec.plan(cfg, fields, w, p), what)
 
 
 def test_the_maxima(gpu):
@@ -131,11 +63,11 @@ def test_the_maxima(gpu):
     occ, w, fields, params, want = _world("MAXIMA")
     E, N, size, _ = spec.MAXIMA
     cfg = spec.config(E, size, N, field_format=abi.FIELD_U16T)
-    st, keep = _device_state(gpu, cfg, occ, w)
-    _same(_call(gpu, cfg, st, params), want, "maxima")
+    st, keep = device_state(gpu, cfg, occ, w)
+    same(call(gpu, cfg, st, params), want, "maxima")
     ragged = dict(w, n_peds=np.array([64, 0, 33], np.int32))
-    st, keep = _device_state(gpu, cfg, occ, ragged)
-    _same(_call(gpu, cfg, st, params), spec.plan(cfg, fields, ragged, params), "ragged counts")
+    st, keep = device_state(gpu, cfg, occ, ragged)
+    same(call(gpu, cfg, st, params), spec.plan(cfg, fields, ragged, params), "ragged counts")
 
 
 def test_one_candidate_and_no_pedestrians(gpu):
@@ -143,18 +75,18 @@ def test_one_candidate_and_no_pedestrians(gpu):
     occ, w, fields, params, _ = _world("BASE")
     E, N, size, _ = spec.BASE
     cfg = spec.config(E, size, N, field_format=abi.FIELD_U16T)
-    st, keep = _device_state(gpu, cfg, occ, w)
+    st, keep = device_state(gpu, cfg, occ, w)
     for nv, nw in ((1, 1), (1, 9), (5, 1), (16, 4), (3, 32)):
         p = dict(params, n_v=nv, n_w=nw)
-        _same(_call(gpu, cfg, st, p), spec.plan(cfg, fields, w, p), "%d x %d" % (nv, nw))
+        same(call(gpu, cfg, st, p), spec.plan(cfg, fields, w, p), "%d x %d" % (nv, nw))
     zero = dict(w, n_peds=np.zeros(E, np.int32))
-    st, keep = _device_state(gpu, cfg, occ, zero)
+    st, keep = device_state(gpu, cfg, occ, zero)
     want = spec.plan(cfg, fields, zero, params)
-    _same(_call(gpu, cfg, st, params), want, "N = 0")
+    same(call(gpu, cfg, st, params), want, "N = 0")
     none = spec.config(E, size, 0, field_format=abi.FIELD_U16T)
     assert none.ped_model == abi.PED_NONE
-    st, keep = _device_state(gpu, none, occ, w, peds=False)
-    _same(_call(gpu, none, st, params), want, "NAVSIM_PED_NONE")
+    st, keep = device_state(gpu, none, occ, w, peds=False)
+    same(call(gpu, none, st, params), want, "NAVSIM_PED_NONE")
 
 
 @pytest.mark.parametrize("fmt", [abi.FIELD_F32, abi.FIELD_U16T])
@@ -162,17 +94,17 @@ def test_shared_field_and_permuted_map_slots(gpu, fmt):
     E, N, size, seed = spec.BASE
     occ, w = spec.random_world(E, N, size, seed + 50, shared=True)
     cfg = spec.config(E, size, N, field_format=fmt, shared_field=1)
-    st, keep = _device_state(gpu, cfg, occ[:1], w)
+    st, keep = device_state(gpu, cfg, occ[:1], w)
     want = spec.plan(cfg, ref.build_dt(occ[:1]), w, spec.BASE_PARAMS)
     assert (want["first_hit"] != 0).any() and (want["first_hit"] == 0).any()
-    _same(_call(gpu, cfg, st, spec.BASE_PARAMS), want, "shared field")
+    same(call(gpu, cfg, st, spec.BASE_PARAMS), want, "shared field")
     occ, w, fields, params, want = _world("BASE")
     perm = np.array([3, 0, 4, 1, 2])
     stored = np.empty_like(occ); stored[perm] = occ                            # arena e's map lies in slot perm[e]
     cfg = spec.config(E, size, N, field_format=fmt)
-    st, keep = _device_state(gpu, cfg, stored, w, map_slot=perm)
-    _same(spec.plan(cfg, ref.build_dt(stored), w, params, map_slot=perm), want, "the specification's own slot table")
-    _same(_call(gpu, cfg, st, params), want, "permuted slots")
+    st, keep = device_state(gpu, cfg, stored, w, map_slot=perm)
+    same(spec.plan(cfg, ref.build_dt(stored), w, params, map_slot=perm), want, "the specification's own slot table")
+    same(call(gpu, cfg, st, params), want, "permuted slots")
 
 
 def test_saturated_packed_field_with_its_overflow_plane(gpu):
@@ -188,10 +120,10 @@ def test_saturated_packed_field_with_its_overflow_plane(gpu):
     p = dict(spec.BASE_PARAMS, clearance_cap=20.0, w_clearance=1.0)
     for fmt in (abi.FIELD_U16T, abi.FIELD_F32):
         cfg = spec.config(3, size, 0, field_format=fmt, shared_field=1)
-        st, keep = _device_state(gpu, cfg, occ, w, overflow=(fmt == abi.FIELD_U16T), peds=False)
+        st, keep = device_state(gpu, cfg, occ, w, overflow=(fmt == abi.FIELD_U16T), peds=False)
         want = spec.plan(cfg, fields, w, p)
         assert want["clearance"][0] > 255 * 0.05 and want["clearance"][1] < 4.0 and (want["status"] == spec.OK).all()
-        _same(_call(gpu, cfg, st, p), want, "format %d" % fmt)
+        same(call(gpu, cfg, st, p), want, "format %d" % fmt)
 
 
 @pytest.mark.parametrize("fmt", [abi.FIELD_F32, abi.FIELD_U16T])
@@ -204,31 +136,31 @@ def test_map_that_is_not_square(gpu, rows, size, fmt):
     occ, w = spec.random_world(E, N, size, 7120, n_obstacles=16, rows=rows)
     assert occ.shape == (E, rows, size)
     cfg = spec.config(E, size, N, map_h=rows, map_w=size, field_format=fmt)
-    st, keep = _device_state(gpu, cfg, occ, w, overflow=None)
+    st, keep = device_state(gpu, cfg, occ, w, overflow=None)
     want = spec.plan(cfg, ref.build_dt(occ), w, spec.BASE_PARAMS)
     assert (w["robot_pose"][:, 0] > rows * 0.05).any() and (want["first_hit"] != 0).any() and (want["first_hit"] == 0).any()
-    _same(_call(gpu, cfg, st, spec.BASE_PARAMS), want, "%d x %d cells" % (rows, size))
+    same(call(gpu, cfg, st, spec.BASE_PARAMS), want, "%d x %d cells" % (rows, size))
     tall = np.ascontiguousarray(occ.transpose(0, 2, 1))                         # 330 rows x 85 columns
     wt = dict(w, robot_pose=w["robot_pose"][:, [1, 0, 2]].copy(), robot_goal=w["robot_goal"][:, ::-1].copy())
     wt["ped_pose"] = w["ped_pose"][:, :, [1, 0, 2]].copy()
     cfg = spec.config(E, size, N, map_h=size, map_w=rows, field_format=fmt)
-    st, keep = _device_state(gpu, cfg, tall, wt, overflow=None)
-    _same(_call(gpu, cfg, st, spec.BASE_PARAMS), spec.plan(cfg, ref.build_dt(tall), wt, spec.BASE_PARAMS), "%d x %d cells" % (size, rows))
+    st, keep = device_state(gpu, cfg, tall, wt, overflow=None)
+    same(call(gpu, cfg, st, spec.BASE_PARAMS), spec.plan(cfg, ref.build_dt(tall), wt, spec.BASE_PARAMS), "%d x %d cells" % (size, rows))
 
 
 def test_wheel_actions(gpu):
     occ, w, fields, params, twist = _world("BASE")
     E, N, size, _ = spec.BASE
     cfg = spec.config(E, size, N, field_format=abi.FIELD_U16T, action_kind=abi.ACTION_WHEELS)
-    st, keep = _device_state(gpu, cfg, occ, w)
+    st, keep = device_state(gpu, cfg, occ, w)
     want = spec.plan(cfg, fields, w, params)
-    _eq(want["twist"], twist["twist"], "prev_action is a twist whatever the action's form")
+    eq(want["twist"], twist["twist"], "prev_action is a twist whatever the action's form")
     assert (want["action"] != want["twist"]).any()
     v, om = want["twist"][:, 0], want["twist"][:, 1]
     r, track = cfg.wheel_radius, cfg.wheel_track
     assert np.allclose(r * (want["action"][:, 0] + want["action"][:, 1]) * 0.5, v, atol=1e-12)
     assert np.allclose(r * (want["action"][:, 1] - want["action"][:, 0]) / track, om, atol=1e-12)
-    _same(_call(gpu, cfg, st, params), want, "wheels")
+    same(call(gpu, cfg, st, params), want, "wheels")
 
 
 # ---- b. refusals -----------------------------------------------------------------------------------------------------------------
@@ -236,10 +168,10 @@ def test_refusals_leave_the_device_alone(gpu):
     occ, w, fields, params, want = _world("BASE")
     E, N, size, _ = spec.BASE
     cfg = spec.config(E, size, N, field_format=abi.FIELD_U16T)
-    st, keep = _device_state(gpu, cfg, occ, w)
+    st, keep = device_state(gpu, cfg, occ, w)
 
     def refused(rc, c=cfg, s=st, **p):
-        _untouched(_call(gpu, c, s, dict(params, **p), want_rc=rc, n_out=E))
+        untouched(call(gpu, c, s, dict(params, **p), want_rc=rc, n_out=E))
 
     nan, inf = float("nan"), float("inf")
     for p in (dict(acc_lin=nan), dict(acc_rot=-1.0), dict(body_radius=inf), dict(ped_radius=-0.1), dict(margin=nan),
@@ -247,11 +179,11 @@ def test_refusals_leave_the_device_alone(gpu):
               dict(body_offset=(0.0, nan))):
         refused(abi.E_ARG, **p)
     for k, bad in (("n_w", 33), ("n_w", 0), ("horizon", 0), ("horizon", 33)):
-        p2 = _params(gpu, cfg, params); setattr(p2, k, bad)
-        _untouched(_call(gpu, cfg, st, p2, want_rc=abi.E_ARG, n_cand=45))
+        p2 = c_params(gpu, cfg, params); setattr(p2, k, bad)
+        untouched(call(gpu, cfg, st, p2, want_rc=abi.E_ARG, n_cand=45))
     for k, bad in (("n_v", 0), ("n_v", 17), ("n_discs", 0), ("n_discs", 5), ("horizon", -1)):
-        p2 = _params(gpu, cfg, params); setattr(p2, k, bad)
-        _untouched(_call(gpu, cfg, st, p2, want_rc=abi.E_ARG, n_cand=45))        # (the buffers are sized by a valid count)
+        p2 = c_params(gpu, cfg, params); setattr(p2, k, bad)
+        untouched(call(gpu, cfg, st, p2, want_rc=abi.E_ARG, n_cand=45))        # (the buffers are sized by a valid count)
     for k, bad in (("n_envs", -1), ("map_h", 0), ("map_w", 0), ("max_peds", 65), ("action_kind", 5)):
         c2 = cfg.copy(); setattr(c2, k, bad)
         refused(abi.E_ARG, c=c2)
@@ -261,11 +193,11 @@ def test_refusals_leave_the_device_alone(gpu):
             setattr(s2, name, None if name == k else v.data_ptr())
         refused(abi.E_ARG, s=s2)
     shared = cfg.copy(); shared.shared_field = 1
-    s2, keep2 = _device_state(gpu, cfg, occ, w, map_slot=np.arange(E))
+    s2, keep2 = device_state(gpu, cfg, occ, w, map_slot=np.arange(E))
     refused(abi.E_ARG, c=shared, s=s2)
     fmt = cfg.copy(); fmt.field_format = 9
     refused(abi.E_UNSUPPORTED, c=fmt)
-    _same(_call(gpu, cfg, st, params), want, "and then the call goes through")
+    same(call(gpu, cfg, st, params), want, "and then the call goes through")
 
 
 # ---- c. closed loop through NavGymEnv ----------------------------------------------------------------------------------------------
@@ -297,7 +229,7 @@ def _from_device_state(env, skip=None):
 def _check(env, h, what, skip=None):
     dev = {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in h.items()}
     want = _from_device_state(env, skip=skip)
-    _same(dev, want, what, keys=KEYS[:5])
+    same(dev, want, what, keys=KEYS[:5])
     return want
 
 
@@ -327,7 +259,7 @@ def test_closed_loop_through_the_env(gpu, path):
         resets += int(done.sum())
         if prev is not None:                                                     # the pair lifetime: last step's rows are intact
             for k in prev[1]:
-                _eq(prev[0][k].cpu().numpy(), prev[1][k], "step %d's %s after step %d" % (t - 1, k, t))
+                eq(prev[0][k].cpu().numpy(), prev[1][k], "step %d's %s after step %d" % (t - 1, k, t))
         prev = (plan, {k: plan[k].cpu().numpy().copy() for k in plan})
         if path == "reset_mask" and done.any():
             env.reset(mask=done.astype(bool))

@@ -9,25 +9,13 @@ import numpy as np
 import pytest
 
 import episode_stats_spec as spec
+from gpu_support import gpu, same_bits, to_device  # noqa: F401  (gpu: the module's fixture)
 from nav_gym_amd import abi
-from test_gpu_autoreset import gpu, _t  # noqa: F401  (gpu: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
 KEYS = (("r", "ep_return"), ("l", "ep_length"), ("path_length", "ep_path_length"), ("min_clearance", "ep_min_clearance"),
         ("discomfort_steps", "ep_discomfort_steps"), ("outcome", "ep_outcome"))
-
-
-def _bits(a):
-    """An array as raw bytes per element: equal means bit for bit (inf and signed zeros included)."""
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint8).reshape(a.shape + (a.dtype.itemsize,))
-
-
-def _same_bits(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
-    assert np.array_equal(_bits(a), _bits(b)), "%s: device %s, spec %s" % (what, a, b)
 
 
 # ---- a. the kernel on synthetic buffers ---------------------------------------------------------------------------------------
@@ -88,14 +76,14 @@ def test_kernel_equals_the_spec_on_synthetic_buffers(gpu, mode, with_truncated):
     for k, v in dev.items():
         setattr(stats, k, v.data_ptr())
     st = abi.NavsimState()
-    t_thr, t_dthr = _t(gpu, thr), _t(gpu, dthr)
+    t_thr, t_dthr = to_device(gpu, thr), to_device(gpu, dthr)
     st.scan_threshold, st.scan_discomfort = t_thr.data_ptr(), t_dthr.data_ptr()
     assert L.navsim_episode_stats_clear(C.byref(cfg), C.byref(stats), None, None) == 0       # 77 -> (0, 0, 0, +inf, 0)
 
     def compare(what):
         torch.cuda.synchronize()
         for k, _ in spec.ACCUMULATORS + spec.PUBLISHED:
-            _same_bits(dev[k].cpu().numpy(), getattr(ref, k), "%s: %s" % (what, k))
+            same_bits(dev[k].cpu().numpy(), getattr(ref, k), "%s: %s" % (what, k))
         assert dev["totals"].cpu().numpy().tolist() == ref.totals.tolist(), what
 
     compare("after clear")
@@ -105,7 +93,7 @@ def test_kernel_equals_the_spec_on_synthetic_buffers(gpu, mode, with_truncated):
             args["final_obs"] = None
         if mode != abi.AUTORESET_NEXT_STEP:
             args["reset_mask"] = None
-        keep = {k: _t(gpu, v) for k, v in args.items() if v is not None}
+        keep = {k: to_device(gpu, v) for k, v in args.items() if v is not None}
         io = abi.NavsimStepIO()
         for k, v in keep.items():
             setattr(io, k, v.data_ptr())
@@ -120,7 +108,7 @@ def test_kernel_equals_the_spec_on_synthetic_buffers(gpu, mode, with_truncated):
     else:
         assert ref.length.tolist() == [3, 1, 1, 0, 2]
     mask = np.array([1, 0, 1, 0, 0], np.uint8)
-    t_mask = _t(gpu, mask)
+    t_mask = to_device(gpu, mask)
     assert L.navsim_episode_stats_clear(C.byref(cfg), C.byref(stats), t_mask.data_ptr(), None) == 0
     ref.clear(mask)
     compare("after clear(mask)")
@@ -177,7 +165,7 @@ def _rollout(env, K, reset_done=False, check_spec=True, first_reset=True):
             row = {name: ep[name][e] for name, _ in KEYS}
             if check_spec:
                 for name, k in KEYS:
-                    _same_bits(row[name], getattr(ref, k)[e], "step %d arena %d %s" % (t, e, name))
+                    same_bits(row[name], getattr(ref, k)[e], "step %d arena %d %s" % (t, e, name))
             episodes.append((t, e, row))
         if reset_done and d.any():
             env.reset(mask=done)
@@ -185,7 +173,7 @@ def _rollout(env, K, reset_done=False, check_spec=True, first_reset=True):
     torch.cuda.synchronize()
     if check_spec:
         for k, _ in spec.ACCUMULATORS:
-            _same_bits(_np(env.sim.ep_acc[k]), getattr(ref, k), "accumulator %s" % k)
+            same_bits(_np(env.sim.ep_acc[k]), getattr(ref, k), "accumulator %s" % k)
     return episodes, ref
 
 
@@ -225,7 +213,7 @@ def test_one_world_on_three_step_paths(gpu):
         for (t0, e0, r0), (t1, e1, r1) in zip(runs[0], other):
             assert (t0, e0) == (t1, e1)
             for name, _ in KEYS:
-                _same_bits(r0[name], r1[name], "step %d arena %d %s" % (t0, e0, name))
+                same_bits(r0[name], r1[name], "step %d arena %d %s" % (t0, e0, name))
     totals = [e.episode_totals() for e in envs]
     assert totals[0] == totals[1] == totals[2] and totals[0]["episodes"] == len(runs[0])
     for e in envs:
@@ -262,13 +250,13 @@ def test_state_dict_round_trip(gpu):
     totals_first = env.episode_totals(reset=False)
     env.load_state_dict(sd)
     for k, _ in spec.ACCUMULATORS:
-        _same_bits(_np(env.sim.ep_acc[k]), sd["episode." + k].numpy(), k)
+        same_bits(_np(env.sim.ep_acc[k]), sd["episode." + k].numpy(), k)
     second, _ = _rollout(env, 10, check_spec=False, first_reset=False)
     assert len(first) == len(second) > 0
     for (t0, e0, r0), (t1, e1, r1) in zip(first, second):
         assert (t0, e0) == (t1, e1)
         for name, _ in KEYS:
-            _same_bits(r0[name], r1[name], "step %d arena %d %s" % (t0, e0, name))
+            same_bits(r0[name], r1[name], "step %d arena %d %s" % (t0, e0, name))
     assert env.episode_totals(reset=False) == totals_first
     bare = {k: v for k, v in sd.items() if not k.startswith("episode.")}
     env.load_state_dict(bare)

@@ -12,31 +12,11 @@ import numpy as np
 import pytest
 
 import ref
-from nav_gym_amd import abi, robots
+from gpu_support import gpu, device_world, eq, random_actions, sim_and_oracle, state_equal  # noqa: F401  (gpu: the module's fixture)
+from nav_gym_amd import abi
 
 pytestmark = pytest.mark.gpu
 
-NOT_STATE = ("field", "field_overflow", "rect_table", "rect_index")
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from nav_gym_amd import lib, sim, world
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    lib.load()
-    return type("G", (), dict(torch=torch, lib=lib, sim=sim, world=world, dev=torch.device("cuda:0")))
-
-
-def _t(gpu, a):
-    return gpu.torch.from_numpy(np.ascontiguousarray(a)).to(gpu.dev)
-
-
-def _eq(a, b, what):
-    a = np.asarray(a); b = np.asarray(b)
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        raise AssertionError("%s: %d mismatches, first at %s: %r != %r" % (what, len(bad), bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
 
 
 def _lidar(gpu, cfg, B):
@@ -46,33 +26,12 @@ def _lidar(gpu, cfg, B):
         gpu.world.lidar_full_circle(cfg, B)
 
 
-def _pair(gpu, cfg, occ, n_peds, thr=None, dthr=None, **world_kw):
-    """The same world in the HIP step and in the oracle (the rollout pattern of test_gpu_parity.py).  thr / dthr: float32 [B]
-    arrays in place of the robot's footprint thresholds."""
-    arrays = gpu.world.make_world(cfg, occ, n_peds=n_peds, device=gpu.dev, **world_kw)
-    for key, name, given in (("scan_threshold", "threshold_footprint", thr), ("scan_discomfort", "discomfort_threshold_footprint", dthr)):
-        arrays[key] = _t(gpu, given) if given is not None else gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", name)))
-    host = {k: v.cpu().numpy() for k, v in arrays.items() if k not in NOT_STATE}
-    host["field"] = ref.build_dt(occ)                 # the oracle always reads its own float32 field
-    g = gpu.sim.NavSim(cfg, arrays)
-    r = ref.RefSim(cfg, host)
-    _eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
-    return g, r, host
-
-
-def _actions(rng, E, t):
-    act = np.stack([rng.uniform(0.0, 0.5, E), rng.uniform(-0.64, 0.64, E)], axis=1)
-    if t % 7 == 3:
-        act[:, 0] = 0.5; act[:, 1] = 0.0              # bursts of straight driving provoke crashes
-    return act
-
-
 def _step_both(gpu, g, r, act, what):
     go, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
     ro, rout = r.step(act)
     for k in rout:
-        _eq(gout[k].cpu().numpy(), rout[k], "%s %s" % (k, what))
-    _eq(go.cpu().numpy(), ro, "obs %s" % what)
+        eq(gout[k].cpu().numpy(), rout[k], "%s %s" % (k, what))
+    eq(go.cpu().numpy(), ro, "obs %s" % what)
     return ro, rout
 
 
@@ -103,7 +62,7 @@ def test_one_beam_decides_the_flag(gpu, directed_maps, B, kstar, which, step_blo
     flagged = np.zeros(B, np.float32); flagged[kstar] = 100.0
     zero = np.zeros(B, np.float32)
     thr, dthr = (flagged, zero) if which == "crash" else (zero, flagged)
-    g, r, host = _pair(gpu, cfg, directed_maps, 0, thr=thr, dthr=dthr)
+    g, r, host = sim_and_oracle(gpu, cfg, directed_maps, 0, thr=thr, dthr=dthr)
     act = np.tile(np.array([[0.2, 0.1]]), (E, 1))
     ro, rout = _step_both(gpu, g, r, act, "with beam %d of %d flagged" % (kstar, B))
     # the oracle itself must have seen the flag: against its own run with both arrays zero
@@ -132,21 +91,18 @@ def _rollout(gpu, occ, S, B, step_block, ped_model, n_peds, steps=30):
     cfg = gpu.lib.default_config(n_envs=E, map_h=120, map_w=120, max_peds=4 if n_peds else 1, n_scan_stack=S, ped_model=ped_model,
                                  auto_reset=1, n_spawn=8, seed=ROLLOUT_SEED, step_block=step_block)
     _lidar(gpu, cfg, B)
-    g, r, _ = _pair(gpu, cfg, occ, n_peds, robot_clearance=ROLLOUT_CLEARANCE)
+    g, r, _ = sim_and_oracle(gpu, cfg, occ, n_peds, robot_clearance=ROLLOUT_CLEARANCE)
     dthr = r.a["scan_discomfort"]
     rng = np.random.default_rng(5)
     n = dict(crash=0, discomfort=0, restart=0, neither=0)
     for t in range(steps):
-        ro, rout = _step_both(gpu, g, r, _actions(rng, E, t), "at step %d" % t)
+        ro, rout = _step_both(gpu, g, r, random_actions(rng, E, t), "at step %d" % t)
         done = rout["done"] != 0
         # an arena that did not finish keeps its scan as the newest row: below the discomfort threshold somewhere, and no crash
         close = (ro[:, (S - 1) * B:S * B] < dthr[None, :]).any(axis=1) & ~done
         n["crash"] += int((rout["is_crash"] != 0).sum()); n["restart"] += int(done.sum())
         n["discomfort"] += int(close.sum()); n["neither"] += int((~close & ~done).sum())
-    gs = g.numpy_state()
-    for k, v in r.a.items():
-        if k in gs and k not in NOT_STATE:
-            _eq(gs[k], v, "state %s at the end" % k)
+    state_equal(g, r, "at the end")
     assert min(n.values()) > 0, "the oracle's run lacks one of crash / discomfort alone / restart / neither: %s" % n
 
 
@@ -172,18 +128,14 @@ def test_noise_does_not_depend_on_the_launch_shape(gpu, rollout_maps):
         cfg = gpu.lib.default_config(n_envs=E, map_h=120, map_w=120, max_peds=1, n_scan_stack=S, ped_model=abi.PED_NONE,
                                      auto_reset=1, n_spawn=8, seed=ROLLOUT_SEED, step_block=step_block, add_scan_noise=noise)
         _lidar(gpu, cfg, B)
-        arrays = gpu.world.make_world(cfg, rollout_maps, n_peds=0, device=gpu.dev, robot_clearance=ROLLOUT_CLEARANCE,
-                                      noise_std_range=(0.02, 0.02))
-        for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
-            arrays[key] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", name)))
-        g = gpu.sim.NavSim(cfg, arrays)
+        g = gpu.sim.NavSim(cfg, device_world(gpu, cfg, rollout_maps, 0, robot_clearance=ROLLOUT_CLEARANCE, noise_std_range=(0.02, 0.02)))
         out = [g.reset_obs().cpu().numpy().copy()]
         rng = np.random.default_rng(5)
         for t in range(steps):
-            go, gout = g.step(gpu.torch.from_numpy(_actions(rng, E, t)).to(gpu.dev))
+            go, gout = g.step(gpu.torch.from_numpy(random_actions(rng, E, t)).to(gpu.dev))
             out.append(go.cpu().numpy().copy())
             out.append(np.concatenate([gout[k].cpu().numpy().astype(np.float64).reshape(E, -1) for k in sorted(gout)], axis=1))
         runs.append(out)
     assert (runs[0][0] != runs[2][0]).any(), "the noise is not on"
     for i, (a, b) in enumerate(zip(runs[0], runs[1])):
-        _eq(a, b, "array %d of the run (64 vs 256 threads per arena)" % i)
+        eq(a, b, "array %d of the run (64 vs 256 threads per arena)" % i)

@@ -3,102 +3,16 @@ tests/goal_path_spec.py, bit for bit -- dist, distance and subgoal as raw bits, 
 sizes where the rebuild's thread-to-cell mapping changes, both field formats, hand-made scenes with known answers, the rebuild /
 skip / key rules, a closed loop through NavGymEnv under every reset path, and the refusals.  Every output is pre-filled with a
 sentinel: the call writes every element."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import goal_path_spec as spec
 import ref
+from goal_path_call import H3, INF, KEYS, GoalField, answer, call, device_state, same
+from gpu_support import gpu, eq, to_device  # noqa: F401  (gpu: the module's fixture)
 from nav_gym_amd import abi
-from test_gpu_autoreset import gpu, _t, _eq  # noqa: F401  (gpu: the module's fixture)
 
 pytestmark = pytest.mark.gpu
-
-KEYS = tuple(abi.GOAL_PATH_OUT)
-INF = spec.INF
-H3 = 3 * 0.05                        # the least hard_clearance: three map cells (0.15000000000000002, as the entry computes it)
-
-
-def _params(**kw):
-    p = dict(spec.DEFAULT, **kw)
-    return abi.NavsimGoalPathParams(hard_clearance=p["hard_clearance"], clearance=p["clearance"], lookahead=p["lookahead"],
-                                    band_cost=p["band_cost"])
-
-
-class _Field:
-    """A navsim_goal_field of its own: dist filled with a sentinel, the keys -1, the counter 0."""
-
-    def __init__(self, gpu, cfg):
-        torch = gpu.torch
-        Hc, Wc = spec.grid_shape(cfg)
-        self.dist = torch.full((cfg.n_envs, Hc, Wc), 0x7777, dtype=torch.int16, device=gpu.dev)
-        self.key = torch.full((cfg.n_envs, 3), -1, dtype=torch.int64, device=gpu.dev)
-        self.rebuilds = torch.zeros(1, dtype=torch.int64, device=gpu.dev)
-        self.c = abi.NavsimGoalField(dist=self.dist.data_ptr(), key=self.key.data_ptr(), rebuilds=self.rebuilds.data_ptr())
-
-    def host(self):
-        return self.dist.cpu().numpy().view(np.uint16)
-
-    def count(self):
-        return int(self.rebuilds.item())
-
-
-def _call(gpu, cfg, st, params, field=None, rebuild=None, skip=None, want_rc=0, n_out=None):
-    """navsim_goal_path into sentinel-filled outputs (n_out rows; None: cfg.n_envs) -> NumPy arrays (+ 'dist', and the field
-    object as 'field')."""
-    p = _params(**params) if isinstance(params, dict) else params
-    torch, E = gpu.torch, cfg.n_envs if n_out is None else n_out
-    field = field or _Field(gpu, cfg)
-    out = dict(distance=torch.full((E,), 777.0, dtype=torch.float32, device=gpu.dev),
-               subgoal=torch.full((E, 2), 777.0, dtype=torch.float32, device=gpu.dev),
-               status=torch.full((E,), 77, dtype=torch.uint8, device=gpu.dev))
-    o = abi.NavsimGoalPathOut(**{k: v.data_ptr() for k, v in out.items()})
-    t_rebuild = None if rebuild is None else _t(gpu, np.asarray(rebuild, np.uint8))
-    t_skip = None if skip is None else _t(gpu, np.asarray(skip, np.uint8))
-    rc = gpu.lib.load().navsim_goal_path(C.byref(cfg), C.byref(st), C.byref(p), None if rebuild is None else t_rebuild.data_ptr(),
-                                         None if skip is None else t_skip.data_ptr(), C.byref(field.c), C.byref(o), None)
-    assert rc == want_rc, rc
-    torch.cuda.synchronize()
-    res = {k: v.cpu().numpy() for k, v in out.items()}
-    res.update(dist=field.host(), field=field)
-    return res
-
-
-def _same(dev, want, what, arenas=None):
-    """status, dist, distance and subgoal (raw bits) of `arenas` (None: all)."""
-    sel = slice(None) if arenas is None else np.asarray(arenas)
-    for k in ("status", "dist", "distance", "subgoal"):
-        a, b = dev[k], want[k]
-        assert a.dtype == b.dtype and a.shape == b.shape, (what, k, a.dtype, a.shape, b.dtype, b.shape)
-        if k in ("distance", "subgoal"):
-            a, b = a.view(np.uint32), b.view(np.uint32)
-        _eq(a[sel], b[sel], "%s: %s" % (what, k))
-
-
-def _device_state(gpu, cfg, occ, w, overflow=False, map_slot=None):
-    """navsim_state over device copies of the world `w` and the field of `occ` [M,H,W] in cfg.field_format (overflow: whether the
-    packed field must saturate somewhere; None: as it comes).  -> (st, keepalive)"""
-    occ_t = _t(gpu, occ)
-    keep = dict(robot_pose=_t(gpu, np.asarray(w["robot_pose"], np.float64)), robot_goal=_t(gpu, np.asarray(w["robot_goal"], np.float64)),
-                episode=_t(gpu, np.asarray(w["episode"], np.int64)))
-    if cfg.field_format == abi.FIELD_F32:
-        keep["field"] = gpu.sim.build_dt(occ_t)
-    else:
-        keep["field"], plane, nsat = gpu.sim.build_field(occ_t, abi.FIELD_U16T)
-        assert overflow is None or (nsat > 0) == overflow, nsat
-        if nsat > 0:
-            keep["field_overflow"] = plane
-    if map_slot is not None:
-        keep["map_slot"] = _t(gpu, np.asarray(map_slot, np.int32))
-    st = abi.NavsimState()
-    for k, v in keep.items():
-        setattr(st, k, v.data_ptr())
-    return st, keep
-
-
-def _spec(cfg, fields, w, params, **kw):
-    return spec.goal_path(cfg, fields, w["robot_pose"], w["robot_goal"], params, **kw)
 
 
 # ---- a. single calls ---------------------------------------------------------------------------------------------------------
@@ -111,23 +25,23 @@ def test_single_call_equals_the_spec(gpu, E, size, seed, fmt):
     occ, w = spec.random_world(E, size, seed)
     cfg = spec.config(E, size, field_format=fmt)
     fields = ref.build_dt(occ)
-    st, keep = _device_state(gpu, cfg, occ, w)
-    want = _spec(cfg, fields, w, {})
-    dev = _call(gpu, cfg, st, {})
-    _same(dev, want, "defaults")
+    st, keep = device_state(gpu, cfg, occ, w)
+    want = answer(cfg, fields, w, {})
+    dev = call(gpu, cfg, st, {})
+    same(dev, want, "defaults")
     assert dev["field"].count() == E
     assert (dev["field"].key.cpu().numpy()[:, 0] == w["episode"]).all()
-    again = _call(gpu, cfg, st, {}, field=dev["field"])
-    _same(again, want, "second call")
+    again = call(gpu, cfg, st, {}, field=dev["field"])
+    same(again, want, "second call")
     assert again["field"].count() == E
     for what, p in (("narrow", dict(hard_clearance=H3, clearance=H3, band_cost=1, lookahead=0.5)),
                     ("wide band", dict(hard_clearance=0.2, clearance=1.5, band_cost=16, lookahead=6.0))):
-        _same(_call(gpu, cfg, st, p), _spec(cfg, fields, w, p), what)
+        same(call(gpu, cfg, st, p), answer(cfg, fields, w, p), what)
     skip = (np.arange(E) % 2 == 0).astype(np.uint8)
-    dev = _call(gpu, cfg, st, {}, skip=skip)
-    want = _spec(cfg, fields, w, {}, skip=skip)
+    dev = call(gpu, cfg, st, {}, skip=skip)
+    want = answer(cfg, fields, w, {}, skip=skip)
     want["dist"][skip != 0] = 0x7777                                             # neither rebuilt ...
-    _same(dev, want, "skip")
+    same(dev, want, "skip")
     assert dev["field"].count() == int((skip == 0).sum()) and (dev["field"].key.cpu().numpy()[skip != 0] == -1).all()
 
 
@@ -144,12 +58,12 @@ def test_maps_that_are_not_square(gpu, rows, size, fmt):
     w["robot_goal"] = np.minimum(w["robot_goal"], [size * 0.05 - 0.3, rows * 0.05 - 0.3])
     cfg = spec.config(E, size, map_h=rows, map_w=size, field_format=fmt)
     assert spec.grid_shape(cfg) == (rows // 5, size // 5)
-    st, keep = _device_state(gpu, cfg, occ, w)
-    want = _spec(cfg, ref.build_dt(occ), w, {})
+    st, keep = device_state(gpu, cfg, occ, w)
+    want = answer(cfg, ref.build_dt(occ), w, {})
     assert (want["status"] & spec.OK).sum() >= 2 and ((want["dist"] != INF) & (want["dist"] > 0)).sum() > 500
-    _same(_call(gpu, cfg, st, {}), want, "%d x %d cells" % (rows, size))
+    same(call(gpu, cfg, st, {}), want, "%d x %d cells" % (rows, size))
     p = dict(hard_clearance=H3, clearance=0.5, band_cost=2, lookahead=4.0)
-    _same(_call(gpu, cfg, st, p), _spec(cfg, ref.build_dt(occ), w, p), "%d x %d cells, other parameters" % (rows, size))
+    same(call(gpu, cfg, st, p), answer(cfg, ref.build_dt(occ), w, p), "%d x %d cells, other parameters" % (rows, size))
 
 
 def test_the_lds_limit(gpu):
@@ -157,10 +71,10 @@ def test_the_lds_limit(gpu):
     E, size = 2, 1000
     occ, w = spec.random_world(E, size, 5304, n_obstacles=60)
     cfg = spec.config(E, size, field_format=abi.FIELD_U16T)
-    st, keep = _device_state(gpu, cfg, occ, w, overflow=None)
-    want = _spec(cfg, ref.build_dt(occ), w, {})
+    st, keep = device_state(gpu, cfg, occ, w, overflow=None)
+    want = answer(cfg, ref.build_dt(occ), w, {})
     assert (want["status"] != 0).all() and ((want["dist"] != INF) & (want["dist"] > 700)).any()
-    _same(_call(gpu, cfg, st, {}), want, "200 x 200 nav cells")
+    same(call(gpu, cfg, st, {}), want, "200 x 200 nav cells")
 
 
 def test_saturated_packed_field_with_its_overflow_plane(gpu):
@@ -176,11 +90,11 @@ def test_saturated_packed_field_with_its_overflow_plane(gpu):
     p = dict(clearance=13.0, lookahead=3.0)
     for fmt in (abi.FIELD_U16T, abi.FIELD_F32):
         cfg = spec.config(2, size, field_format=fmt, shared_field=1)
-        st, keep = _device_state(gpu, cfg, occ, w, overflow=(fmt == abi.FIELD_U16T))
-        want = _spec(cfg, fields, w, p, detail=True)
+        st, keep = device_state(gpu, cfg, occ, w, overflow=(fmt == abi.FIELD_U16T))
+        want = answer(cfg, fields, w, p, detail=True)
         m = want["classes"][0]
         assert (m == 1).sum() > 20 and (m == 3).sum() > 5000                      # the few clear cells in the middle
-        _same(_call(gpu, cfg, st, p), want, "format %d" % fmt)
+        same(call(gpu, cfg, st, p), want, "format %d" % fmt)
 
 
 def test_permuted_map_slots(gpu):
@@ -189,10 +103,10 @@ def test_permuted_map_slots(gpu):
     perm = np.array([3, 0, 4, 1, 2])
     stored = np.empty_like(occ); stored[perm] = occ                            # arena e's map lies in slot perm[e]
     cfg = spec.config(E, size, field_format=abi.FIELD_U16T)
-    st, keep = _device_state(gpu, cfg, stored, w, map_slot=perm)
-    want = _spec(cfg, ref.build_dt(stored), w, {}, map_slot=perm)
-    _same(want, _spec(cfg, ref.build_dt(occ), w, {}), "the specification's own slot table")
-    _same(_call(gpu, cfg, st, {}), want, "permuted slots")
+    st, keep = device_state(gpu, cfg, stored, w, map_slot=perm)
+    want = answer(cfg, ref.build_dt(stored), w, {}, map_slot=perm)
+    same(want, answer(cfg, ref.build_dt(occ), w, {}), "the specification's own slot table")
+    same(call(gpu, cfg, st, {}), want, "permuted slots")
 
 
 # ---- b. hand-made scenes with known answers ------------------------------------------------------------------------------------
@@ -200,10 +114,10 @@ def _scene(gpu, nav, pose, goal, fmt=abi.FIELD_U16T, **params):
     occ = spec.scale5(nav)[None]
     cfg = spec.config(1, occ.shape[1], field_format=fmt)
     w = dict(robot_pose=np.array([pose], np.float64), robot_goal=np.array([goal], np.float64), episode=np.zeros(1, np.int64))
-    st, keep = _device_state(gpu, cfg, occ, w)
-    want = _spec(cfg, ref.build_dt(occ), w, params, detail=True)
-    dev = _call(gpu, cfg, st, params)
-    _same(dev, want, "scene")
+    st, keep = device_state(gpu, cfg, occ, w)
+    want = answer(cfg, ref.build_dt(occ), w, params, detail=True)
+    dev = call(gpu, cfg, st, params)
+    same(dev, want, "scene")
     return dev, want, cfg
 
 
@@ -252,12 +166,12 @@ def test_rebuild_skip_and_the_key(gpu):
     occ, w = spec.random_world(E, size, seed)
     cfg = spec.config(E, size, field_format=abi.FIELD_U16T)
     fields = ref.build_dt(occ)
-    st, keep = _device_state(gpu, cfg, occ, w)
-    want = _spec(cfg, fields, w, {})
+    st, keep = device_state(gpu, cfg, occ, w)
+    want = answer(cfg, fields, w, {})
     assert want["status"].tolist() == [1, 3, 4, 3, 1, 1]                         # (this seed: arena 0 walks and does not arrive)
-    dev = _call(gpu, cfg, st, {})
+    dev = call(gpu, cfg, st, {})
     F = dev["field"]
-    _same(dev, want, "first call")
+    same(dev, want, "first call")
     assert F.count() == E
     # nothing changed: nothing is rebuilt -- not even the arena whose stored field the test scribbles on, which proves that
     # the look-up reads the STORED field
@@ -265,38 +179,38 @@ def test_rebuild_skip_and_the_key(gpu):
     scribbled = want["dist"].copy()
     finite = scribbled[e] != INF
     scribbled[e][finite] = (scribbled[e][finite].astype(np.int64) * 2 + 9).clip(0, INF - 1).astype(np.uint16)
-    F.dist.copy_(_t(gpu, scribbled.view(np.int16)))
-    dev = _call(gpu, cfg, st, {}, field=F)
-    want2 = _spec(cfg, fields, w, {}, dist=scribbled)
-    _same(dev, want2, "scribbled")
+    F.dist.copy_(to_device(gpu, scribbled.view(np.int16)))
+    dev = call(gpu, cfg, st, {}, field=F)
+    want2 = answer(cfg, fields, w, {}, dist=scribbled)
+    same(dev, want2, "scribbled")
     assert F.count() == E and dev["distance"][e] != want["distance"][e]
     # a new goal for arena 1, a new episode number for arena 4: those two alone are rebuilt (the scribble stays)
     w["robot_goal"][1] = w["robot_pose"][3, :2]
     w["episode"][4] += 1
-    keep["robot_goal"].copy_(_t(gpu, w["robot_goal"]))
-    keep["episode"].copy_(_t(gpu, w["episode"]))
+    keep["robot_goal"].copy_(to_device(gpu, w["robot_goal"]))
+    keep["episode"].copy_(to_device(gpu, w["episode"]))
     others = [x for x in range(E) if x not in (1, 4, e)]
-    fresh = _spec(cfg, fields, w, {})
-    dev = _call(gpu, cfg, st, {}, field=F)
-    _same(dev, fresh, "goal / episode: rebuilt", arenas=[x for x in (1, 4) if x != e] + others)
+    fresh = answer(cfg, fields, w, {})
+    dev = call(gpu, cfg, st, {}, field=F)
+    same(dev, fresh, "goal / episode: rebuilt", arenas=[x for x in (1, 4) if x != e] + others)
     assert F.count() == E + 2
     if e not in (1, 4):
-        _eq(dev["dist"][e], scribbled[e], "the scribble stays")
+        eq(dev["dist"][e], scribbled[e], "the scribble stays")
     # rebuild[e] forces it
     force = np.zeros(E, np.uint8); force[e] = 1
-    dev = _call(gpu, cfg, st, {}, field=F, rebuild=force)
-    _same(dev, fresh, "forced")
+    dev = call(gpu, cfg, st, {}, field=F, rebuild=force)
+    same(dev, fresh, "forced")
     assert F.count() == E + 3
     # a skipped arena is neither rebuilt (although forced, although its key is stale) nor read
     w["episode"][2] += 5
-    keep["episode"].copy_(_t(gpu, w["episode"]))
+    keep["episode"].copy_(to_device(gpu, w["episode"]))
     skip = np.zeros(E, np.uint8); skip[2] = 1
-    dev = _call(gpu, cfg, st, {}, field=F, rebuild=np.ones(E, np.uint8), skip=skip)
+    dev = call(gpu, cfg, st, {}, field=F, rebuild=np.ones(E, np.uint8), skip=skip)
     assert F.count() == E + 3 + (E - 1) and dev["status"][2] == 0 and dev["distance"][2] == 0 and not dev["subgoal"][2].any()
     assert F.key.cpu().numpy()[2, 0] == w["episode"][2] - 5
-    _same(dev, fresh, "skip", arenas=[x for x in range(E) if x != 2])
-    dev = _call(gpu, cfg, st, {}, field=F)                                       # ... and is rebuilt by the next call that reads it
-    _same(dev, fresh, "after the skip")
+    same(dev, fresh, "skip", arenas=[x for x in range(E) if x != 2])
+    dev = call(gpu, cfg, st, {}, field=F)                                       # ... and is rebuilt by the next call that reads it
+    same(dev, fresh, "after the skip")
     assert F.count() == E + 3 + (E - 1) + 1
 
 
@@ -348,7 +262,7 @@ def _host(env, h):
 def _check(env, h, what, skip=None):
     dev, want = _host(env, h), _from_device_state(env, skip=skip)
     live = None if skip is None else np.flatnonzero(np.asarray(skip) == 0)      # (a skipped arena's field is not touched)
-    _same(dev, want, what, arenas=live)
+    same(dev, want, what, arenas=live)
     if skip is not None:
         sk = np.asarray(skip) != 0
         assert not dev["status"][sk].any() and not dev["distance"][sk].any() and not dev["subgoal"][sk].any(), what
@@ -392,7 +306,7 @@ def test_closed_loop_through_the_env(gpu, path):
             now = _check(env, h, "step %d" % t)
         if prev is not None:                                                     # the pair lifetime: last step's rows are intact
             for k in KEYS:
-                _eq(prev[0][k].cpu().numpy(), prev[1][k], "step %d's %s after step %d" % (t - 1, k, t))
+                eq(prev[0][k].cpu().numpy(), prev[1][k], "step %d's %s after step %d" % (t - 1, k, t))
         prev = (h, {k: h[k].cpu().numpy().copy() for k in KEYS})
         if path == "reset_mask" and done.any():
             env.reset(mask=done.astype(bool))
@@ -427,7 +341,7 @@ def test_single_environment_returns_numpy(gpu):
         assert isinstance(h["subgoal"], np.ndarray) and h["subgoal"].shape == (2,) and h["subgoal"].dtype == np.float32
         want = _from_device_state(env)
         assert h["distance"].view(np.uint32) == want["distance"][0].view(np.uint32) and h["status"] == want["status"][0]
-        _eq(h["subgoal"].view(np.uint32), want["subgoal"][0].view(np.uint32), "subgoal")
+        eq(h["subgoal"].view(np.uint32), want["subgoal"][0].view(np.uint32), "subgoal")
     env.close()
 
 
@@ -448,11 +362,11 @@ def test_refusals_leave_the_device_alone(gpu):
     E, size = 3, 100
     occ, w = spec.random_world(E, size, 5307)
     cfg = spec.config(E, size, field_format=abi.FIELD_U16T)
-    st, keep = _device_state(gpu, cfg, occ, w)
-    F = _Field(gpu, cfg)
+    st, keep = device_state(gpu, cfg, occ, w)
+    F = GoalField(gpu, cfg)
 
     def refused(rc, c=cfg, s=st, **p):
-        dev = _call(gpu, c, s, p, field=F, want_rc=rc, n_out=E)
+        dev = call(gpu, c, s, p, field=F, want_rc=rc, n_out=E)
         assert (dev["distance"] == 777.0).all() and (dev["subgoal"] == 777.0).all() and (dev["status"] == 77).all()
         assert (dev["dist"] == 0x7777).all() and F.count() == 0 and (F.key.cpu().numpy() == -1).all()
 
@@ -469,10 +383,10 @@ def test_refusals_leave_the_device_alone(gpu):
             setattr(s2, name, None if name == k else v.data_ptr())
         refused(abi.E_ARG, s=s2)
     shared = cfg.copy(); shared.shared_field = 1
-    s2, keep2 = _device_state(gpu, cfg, occ, w, map_slot=np.arange(E))
+    s2, keep2 = device_state(gpu, cfg, occ, w, map_slot=np.arange(E))
     refused(abi.E_ARG, c=shared, s=s2)
     fmt = cfg.copy(); fmt.field_format = 9
     refused(abi.E_UNSUPPORTED, c=fmt)
     big = cfg.copy(); big.map_h = big.map_w = 1200
     refused(abi.E_UNSUPPORTED, c=big)
-    _same(_call(gpu, cfg, st, {}, field=F), _spec(cfg, ref.build_dt(occ), w, {}), "and then the call goes through")
+    same(call(gpu, cfg, st, {}, field=F), answer(cfg, ref.build_dt(occ), w, {}), "and then the call goes through")

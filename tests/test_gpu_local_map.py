@@ -11,11 +11,12 @@ import pytest
 
 import dwa_spec
 import local_map_spec as spec
+import map_geometry_runs as runs
 import map_geometry_scenes as mg
 import ref
+from dwa_call import device_state
+from gpu_support import gpu, eq, same_bits, to_device  # noqa: F401  (gpu: the module's fixture)
 from nav_gym_amd import abi
-from test_gpu_autoreset import gpu, _t, _eq  # noqa: F401  (gpu: the module's fixture)
-from test_gpu_dwa import _device_state
 
 pytestmark = pytest.mark.gpu
 
@@ -37,8 +38,8 @@ def _call(gpu, cfg, st, params, G, visible=None, skip=None, want_rc=0, n_out=Non
     n = E * Cn * G * G
     flat = torch.full((n + 8,), SENTINEL, dtype=torch.float32, device=gpu.dev)
     out = flat[shift:shift + n]
-    t_vis = None if visible is None else _t(gpu, np.asarray(visible, np.uint8))
-    t_skip = None if skip is None else _t(gpu, np.asarray(skip, np.uint8))
+    t_vis = None if visible is None else to_device(gpu, np.asarray(visible, np.uint8))
+    t_skip = None if skip is None else to_device(gpu, np.asarray(skip, np.uint8))
     rc = gpu.lib.load().navsim_local_map(C.byref(cfg), C.byref(st), C.byref(p), None if visible is None else t_vis.data_ptr(),
                                          None if skip is None else t_skip.data_ptr(), out.data_ptr(), None)
     assert rc == want_rc, rc
@@ -51,7 +52,7 @@ def _call(gpu, cfg, st, params, G, visible=None, skip=None, want_rc=0, n_out=Non
 def _same(dev, want, what):
     assert dev.dtype == want.dtype == np.float32 and dev.shape == want.shape, (what, dev.dtype, dev.shape, want.dtype, want.shape)
     for ch in range(want.shape[1]):
-        _eq(dev[:, ch].view(np.uint32), want[:, ch].view(np.uint32), "%s: channel %d" % (what, ch))
+        same_bits(dev[:, ch], want[:, ch], "%s: channel %d" % (what, ch))
 
 
 _BASE = {}
@@ -80,7 +81,7 @@ def test_base_world_equals_the_spec(gpu, fmt):
     b = _base()
     E, N, size, _ = spec.BASE
     cfg = spec.config(E, size, N, field_format=fmt)
-    st, keep = _device_state(gpu, cfg, b["occ"], b["w"], overflow=False)
+    st, keep = device_state(gpu, cfg, b["occ"], b["w"], overflow=False)
     for G, cell, ahead, ch in spec.CALLS:
         p = spec.call_params(cell, ahead, ch)
         want = _want(cfg, (G, cell, ahead, ch), p, G)
@@ -113,7 +114,7 @@ def test_saturated_packed_field_with_its_overflow_plane(gpu):
     p = dict(cell=0.33, ahead=0.5, cap=20.0, ped_radius=0.3, channels=1)
     for fmt in (U16T, F32):
         cfg = spec.config(3, size, 0, field_format=fmt, shared_field=1)
-        st, keep = _device_state(gpu, cfg, occ, w, overflow=(fmt == U16T), peds=False)
+        st, keep = device_state(gpu, cfg, occ, w, overflow=(fmt == U16T), peds=False)
         for G in (64, 7):
             want = spec.local_map(cfg, fields, w, p, G)
             assert want[0].max() > 255 * 0.05 and (G == 7 or (want[1] == 0).any())
@@ -127,7 +128,7 @@ def test_shared_field_and_permuted_map_slots(gpu, fmt):
     E, N, size, _ = spec.BASE
     p, G = spec.call_params(0.1, 0.0, 4), 64
     cfg = spec.config(E, size, N, field_format=fmt, shared_field=1)
-    st, keep = _device_state(gpu, cfg, b["occ"][2:3], b["w"], overflow=False)
+    st, keep = device_state(gpu, cfg, b["occ"][2:3], b["w"], overflow=False)
     want = spec.local_map(cfg, b["fields"][2:3], b["w"], p, G)
     own = _want(spec.config(E, size, N), (G, 0.1, 0.0, 4), p, G)
     assert (want[2] == own[2]).all() and (want[0, 0] != own[0, 0]).any()
@@ -135,7 +136,7 @@ def test_shared_field_and_permuted_map_slots(gpu, fmt):
     perm = np.array([3, 0, 4, 1, 2])
     stored = np.empty_like(b["occ"]); stored[perm] = b["occ"]                    # arena e's map lies in slot perm[e]
     cfg = spec.config(E, size, N, field_format=fmt)
-    st, keep = _device_state(gpu, cfg, stored, b["w"], overflow=False, map_slot=perm)
+    st, keep = device_state(gpu, cfg, stored, b["w"], overflow=False, map_slot=perm)
     _same(spec.local_map(cfg, ref.build_dt(stored), b["w"], p, G, map_slot=perm), own, "the specification's own slot table")
     _same(_call(gpu, cfg, st, p, G), own, "permuted slots")
 
@@ -148,10 +149,9 @@ def test_maps_that_are_not_square_off_the_origin(gpu, H, W, origin, k, fmt):
     """The worlds of tests/map_geometry_scenes.py with walking pedestrians, robots beyond the leading min(H, W) square in every
     second arena, on grids of 0.1, 0.025 and 0.05 m whose origins are no multiples of them: a cell beyond the leading square
     shows the map that is stored there (the rule bounds column i by map_w and row j by map_h; xy_to_ij's clip does not)."""
-    import test_map_geometry as cpu
-    cfg, occ, w = cpu.scene(H, W, abi.PED_EXTERNAL, inside=False, seed=9, N=8, E=5, field_format=fmt)
+    cfg, occ, w = runs.scene(H, W, abi.PED_EXTERNAL, inside=False, seed=9, N=8, E=5, field_format=fmt)
     cfg, w = mg.geometry_twin(cfg, w, origin, k)
-    st, keep = _device_state(gpu, cfg, occ, w, overflow=None)
+    st, keep = device_state(gpu, cfg, occ, w, overflow=None)
     M = min(H, W)
     beyond = 0
     for G, p in ((64, dict(cell=0.1 * k, ahead=0.0, cap=0.8 * k, ped_radius=0.3 * k, channels=4)),
@@ -186,7 +186,7 @@ def test_maps_smaller_than_the_window(gpu, H, W, fmt):
     cfg = spec.config(E, max(H, W), N, map_h=H, map_w=W, field_format=fmt, origin_x=-1.3, origin_y=0.7)
     for k in ("robot_pose", "ped_pose"):
         w[k][..., 0] += cfg.origin_x; w[k][..., 1] += cfg.origin_y
-    st, keep = _device_state(gpu, cfg, occ, w, overflow=False)
+    st, keep = device_state(gpu, cfg, occ, w, overflow=False)
     fields = ref.build_dt(occ)
     for G, p in ((16, spec.call_params(0.1, 0.0, 4)), (64, spec.call_params(0.05, 0.0, 4)), (7, spec.call_params(0.33, 0.5, 2))):
         want, info = spec.local_map(cfg, fields, w, p, G, detail=True)
@@ -206,7 +206,7 @@ def test_skip_mask(gpu, G):
     skip = np.array([0, 1, 0, 0, 1], np.uint8)
     want = _want(cfg, ("skip", G), p, G, skip=skip)
     assert not want[1].any() and not want[4].any() and want[0].any()
-    st, keep = _device_state(gpu, cfg, b["occ"], b["w"], overflow=False)
+    st, keep = device_state(gpu, cfg, b["occ"], b["w"], overflow=False)
     _same(_call(gpu, cfg, st, p, G, skip=skip), want, "skip")
     bad = {k: np.array(v, copy=True) for k, v in b["w"].items()}
     bad["robot_pose"][1] = np.nan
@@ -214,7 +214,7 @@ def test_skip_mask(gpu, G):
     bad["n_peds"][[1, 4]] = (1 << 30, -5)
     bad["ped_pose"][1] = np.inf
     bad["ped_vel"][4] = np.nan
-    st, keep = _device_state(gpu, cfg, b["occ"], bad, overflow=False)
+    st, keep = device_state(gpu, cfg, b["occ"], bad, overflow=False)
     _same(_call(gpu, cfg, st, p, G, skip=skip), want, "invalid data behind the skip")
     _same(_call(gpu, cfg, st, p, G, skip=np.ones(E, np.uint8)), np.zeros_like(want), "every arena skipped")
 
@@ -223,7 +223,7 @@ def test_visible_mask(gpu):
     b = _base()
     E, N, size, _ = spec.BASE
     cfg = spec.config(E, size, N, field_format=U16T)
-    st, keep = _device_state(gpu, cfg, b["occ"], b["w"], overflow=False)
+    st, keep = device_state(gpu, cfg, b["occ"], b["w"], overflow=False)
     rng = np.random.default_rng(5)
     vis = (rng.random((E, N)) < 0.5).astype(np.uint8)
     vis[spec.TIE_ARENA, :2] = (0, 1)                                            # the tie's loser alone: its velocity shows
@@ -242,7 +242,7 @@ def test_visible_mask(gpu):
     none = _call(gpu, cfg, st, p, 16, visible=np.zeros((E, N), np.uint8))
     _same(none, spec.local_map(cfg, b["fields"], b["w"], p, 16, visible=np.zeros((E, N), np.uint8)), "nobody visible")
     assert (none[:, 1] == np.float32(spec.CAP)).all() and not none[:, 2:].any()
-    _eq(none[:, 0], _want(cfg, (16, 0.1, 0.0, 4), p, 16)[:, 0], "the wall channel does not depend on the mask")
+    eq(none[:, 0], _want(cfg, (16, 0.1, 0.0, 4), p, 16)[:, 0], "the wall channel does not depend on the mask")
 
 
 def test_sixty_four_pedestrians(gpu):
@@ -250,7 +250,7 @@ def test_sixty_four_pedestrians(gpu):
     E, N, size = 3, 64, 200
     occ, w = dwa_spec.random_world(E, N, size, 8104, n_peds=[0, 1, 64])
     cfg = spec.config(E, size, N, field_format=U16T)
-    st, keep = _device_state(gpu, cfg, occ, w, overflow=False)
+    st, keep = device_state(gpu, cfg, occ, w, overflow=False)
     fields = ref.build_dt(occ)
     vis = (np.arange(E * N).reshape(E, N) % 3 != 0).astype(np.uint8)
     for G, p in ((64, spec.call_params(0.15, 0.0, 4, cap=1.0)), (7, spec.call_params(0.33, 0.5, 2)), (128, spec.call_params(0.08, 0.0, 4))):
@@ -266,7 +266,7 @@ def test_one_arena_and_none(gpu):
     _, N, size, _ = spec.BASE
     one = {k: v[3:4] for k, v in b["w"].items()}
     cfg = spec.config(1, size, N, field_format=U16T)
-    st, keep = _device_state(gpu, cfg, b["occ"][3:4], one, overflow=False)
+    st, keep = device_state(gpu, cfg, b["occ"][3:4], one, overflow=False)
     for G in (16, 128, 7):
         p = spec.call_params(0.1, 0.0, 4)
         _same(_call(gpu, cfg, st, p, G), spec.local_map(cfg, b["fields"][3:4], one, p, G), "E = 1, G %d" % G)
@@ -279,7 +279,7 @@ def test_refusals_leave_the_device_alone(gpu):
     b = _base()
     E, N, size, _ = spec.BASE
     cfg = spec.config(E, size, N, field_format=U16T)
-    st, keep = _device_state(gpu, cfg, b["occ"], b["w"], overflow=False)
+    st, keep = device_state(gpu, cfg, b["occ"], b["w"], overflow=False)
     good = spec.call_params(0.1, 0.0, 4)
 
     def refused(rc, c=cfg, s=st, **kw):
@@ -303,7 +303,7 @@ def test_refusals_leave_the_device_alone(gpu):
             setattr(s2, name, None if name == k else v.data_ptr())
         refused(abi.E_ARG, s=s2)
     shared = cfg.copy(); shared.shared_field = 1
-    s2, keep2 = _device_state(gpu, cfg, b["occ"], b["w"], overflow=False, map_slot=np.arange(E))
+    s2, keep2 = device_state(gpu, cfg, b["occ"], b["w"], overflow=False, map_slot=np.arange(E))
     refused(abi.E_ARG, c=shared, s=s2)
     fmt = cfg.copy(); fmt.field_format = 9
     refused(abi.E_UNSUPPORTED, c=fmt)
@@ -385,7 +385,7 @@ def test_through_the_env(gpu, path):
             assert all(now[e].any() for e in np.flatnonzero(waiting & (done == 0)))
             waiting = done != 0
         if prev is not None:                                                     # the pair lifetime
-            _eq(prev[0].cpu().numpy().view(np.uint32), prev[1].view(np.uint32), "step %d's map after step %d" % (t - 1, t))
+            same_bits(prev[0].cpu().numpy(), prev[1], "step %d's map after step %d" % (t - 1, t))
         prev = (m, now.copy())
         ends += int(done.sum())
         if path == "reset_mask" and done.any():
@@ -412,7 +412,7 @@ def test_lifetime_of_a_returned_map(gpu):
         maps.append(info["local_map"])
         copies.append(info["local_map"].cpu().numpy().copy())
         if t >= 1:
-            _eq(maps[t - 1].cpu().numpy().view(np.uint32), copies[t - 1].view(np.uint32), "step %d's map after step %d" % (t - 1, t))
+            same_bits(maps[t - 1].cpu().numpy(), copies[t - 1], "step %d's map after step %d" % (t - 1, t))
         if t >= 2:
             assert maps[t - 2].data_ptr() == maps[t].data_ptr() and maps[t - 1].data_ptr() != maps[t].data_ptr()
             assert (maps[t - 2].cpu().numpy() != copies[t - 2]).any(), "the robots moved: two steps later the buffer holds a new map"

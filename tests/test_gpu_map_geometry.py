@@ -7,11 +7,20 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import dwa_call
+import dwa_spec
+import goal_path_call
+import goal_path_spec
+import map_geometry_runs as cpu
 import map_geometry_scenes as mg
+import ped_observe_call
+import ped_orca_spec
+import ped_orca_walls_spec as wspec
 import ref
-import test_map_geometry as cpu
+from gpu_support import (gpu, decode_rect_index, decode_rect_table, device_map_arrays, device_world, eq, host_arrays,  # noqa: F401
+                         rollout_pair, state_equal, to_device)
+from helpers import keti_thresholds
 from nav_gym_amd import abi
-from test_gpu_parity import gpu, _t, _eq, _decode_rect_table, _decode_rect_index  # noqa: F401  (gpu: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,18 +41,18 @@ def test_build_field_both_formats(gpu, H, W):
     occ = np.concatenate([_maps(H, W), _maps(H, W, "open", 2)])
     occ[-1] = 0; occ[-1, H // 3, W // 4] = 1                      # one obstacle cell: distances up to the far corner
     want = ref.build_dt(occ)
-    f32, none, nsat = gpu.sim.build_field(_t(gpu, occ), abi.FIELD_F32)
-    _eq(f32.cpu().numpy(), want, "float32 field %d x %d" % (H, W))
+    f32, none, nsat = gpu.sim.build_field(to_device(gpu, occ), abi.FIELD_F32)
+    eq(f32.cpu().numpy(), want, "float32 field %d x %d" % (H, W))
     assert none is None and nsat == 0
-    packed, plane, nsat = gpu.sim.build_field(_t(gpu, occ), abi.FIELD_U16T)
-    _eq(plane.cpu().numpy(), want, "float32 plane beside the packed field")
+    packed, plane, nsat = gpu.sim.build_field(to_device(gpu, occ), abi.FIELD_U16T)
+    eq(plane.cpu().numpy(), want, "float32 plane beside the packed field")
     n, th, tw = occ.shape[0], (H + 7) // 8, (W + 7) // 8
     assert packed.numel() * 2 == gpu.lib.load().navsim_field_bytes(n, H, W, abi.FIELD_U16T) == n * th * tw * 128
     raw = packed.cpu().numpy().view(np.uint16).reshape(n, th, tw, 8, 8)          # rows of tiles, tw tiles a row
     full = raw.transpose(0, 1, 3, 2, 4).reshape(n, th * 8, tw * 8)[:, :H, :W]
     sat = np.rint(want.astype(np.float64) ** 2) >= 65535                        # stored as 0xFFFF: read from the float32 plane
     assert nsat == int(sat.sum()) and np.array_equal(full == 0xFFFF, sat)
-    _eq(np.sqrt(full.astype(np.float32))[~sat], want[~sat], "decoded tiles %d x %d" % (H, W))
+    eq(np.sqrt(full.astype(np.float32))[~sat], want[~sat], "decoded tiles %d x %d" % (H, W))
 
 
 @pytest.mark.parametrize("H,W", BUILDER_SHAPES)
@@ -52,13 +61,13 @@ def test_build_rects_and_index(gpu, H, W):
     the index rows name the records; navsim_maps_closed sees a single free cell of the ring on each of the four sides."""
     occ = np.concatenate([_maps(H, W), _maps(H, W, "open", 1)])
     n = occ.shape[0]
-    occ_t = _t(gpu, occ)
+    occ_t = to_device(gpu, occ)
     field, f32, _ = gpu.sim.build_field(occ_t, abi.FIELD_U16T)
     table_t = gpu.sim.build_rects(occ_t, field, abi.FIELD_U16T, f32)
     table = table_t.cpu().numpy()
     T = ((H + 7) // 8) * ((W + 7) // 8)
     assert table.shape == (n, T, 4) and T * 16 == gpu.lib.load().navsim_rect_table_bytes(1, H, W)
-    d2, valid = _decode_rect_table(table, H, W)
+    d2, valid = decode_rect_table(table, H, W)
     exact = np.rint(ref.build_dt(occ).astype(np.float64) ** 2).astype(np.int64)
     assert np.array_equal(d2[valid], exact[valid]), "a valid record disagrees with the exact field"
     print("%d x %d: %.3f of the cells lie in tiles with a valid record" % (H, W, valid.mean()))
@@ -72,17 +81,17 @@ def test_build_rects_and_index(gpu, H, W):
                 assert occ[m, y0:y1 + 1, x0:x1 + 1].all(), (m, t, x0, y0, x1, y1)
     rows, n_rects = gpu.sim.build_rect_index(table_t, H, W)
     assert rows.shape[1] == abi.rect_index_row_bytes(H, W) == gpu.lib.load().navsim_rect_index_bytes(1, H, W)
-    named, has = _decode_rect_index(rows.cpu().numpy(), H, W)
+    named, has = decode_rect_index(rows.cpu().numpy(), H, W)
     tile_valid = (rec[..., 0] & 0xFFFF) != 0x7FFF
     assert (n_rects.cpu().numpy() <= 255).all() and np.array_equal(has, tile_valid), "every valid record has an index"
-    _eq(named[has], rec[has], "records named by the index rows")
+    eq(named[has], rec[has], "records named by the index rows")
     # closed / open: the generated maps, then one free cell in the ring's inner layer on each side in turn, and a corner
     assert gpu.sim.maps_closed(occ_t).cpu().numpy().tolist() == [1] * (n - 1) + [0]
     holes = [(2, W // 2), (H - 3, W // 2), (H // 2, 2), (H // 2, W - 3), (H - 1, W - 1), (0, W - 1), (H - 1, 0)]
     one = np.repeat(occ[:1], len(holes) + 1, axis=0)
     for k, (y, x) in enumerate(holes):
         one[k, y, x] = 0
-    assert gpu.sim.maps_closed(_t(gpu, one)).cpu().numpy().tolist() == [0] * len(holes) + [1]
+    assert gpu.sim.maps_closed(to_device(gpu, one)).cpu().numpy().tolist() == [0] * len(holes) + [1]
 
 
 @pytest.mark.parametrize("H,W", [(85, 330), (203, 96)])
@@ -95,7 +104,7 @@ def test_world_closed_sees_one_free_cell_on_each_side(gpu, H, W, fmt):
         occ[k, y, x] = 0
     E = occ.shape[0]
     cfg = gpu.lib.default_config(n_envs=E, map_h=H, map_w=W, field_format=fmt)
-    field, plane, _ = gpu.sim.build_field(_t(gpu, occ), fmt)
+    field, plane, _ = gpu.sim.build_field(to_device(gpu, occ), fmt)
     st = abi.NavsimState()
     st.field = field.data_ptr()
     n_open = gpu.torch.zeros(1, dtype=gpu.torch.int32, device=gpu.dev)
@@ -108,9 +117,9 @@ def test_world_closed_sees_one_free_cell_on_each_side(gpu, H, W, fmt):
 def test_costmap(gpu, H, W):
     occ = np.concatenate([_maps(H, W), _maps(H, W, "open", 2)])
     occ[-1] = 0; occ[-1, 0, 0] = 1                     # one sampled obstacle cell in a corner: the inflation leaves free cells at any size
-    got = gpu.sim.costmap(_t(gpu, occ)).cpu().numpy()
+    got = gpu.sim.costmap(to_device(gpu, occ)).cpu().numpy()
     assert got.shape == (occ.shape[0], H // 5, W // 5)
-    _eq(got, ref.costmap(occ), "costmap %d x %d" % (H, W))
+    eq(got, ref.costmap(occ), "costmap %d x %d" % (H, W))
     assert 0 < got[-1].mean() < 1
 
 
@@ -129,13 +138,13 @@ def test_xy_to_ij(gpu, H, W, origin, res):
     xy = np.concatenate([xy, b, b + 0.5 * res, np.nextafter(b32, np.float32(np.inf)).astype(np.float64),
                          np.nextafter(b32, np.float32(-np.inf)).astype(np.float64)]) + np.asarray(origin)
     cfg = gpu.lib.default_config(map_h=H, map_w=W, origin_x=origin[0], origin_y=origin[1], resolution=res)
-    got = gpu.sim.debug_xy_to_ij(cfg, _t(gpu, xy), False).cpu().numpy()
-    _eq(got, mg.xy_to_ij_f64(xy, origin, res, H, W), "float64 form")
-    _eq(got, ref.xy_to_ij(xy, origin, res, H, W).astype(np.int32), "float64 form against the oracle")
+    got = gpu.sim.debug_xy_to_ij(cfg, to_device(gpu, xy), False).cpu().numpy()
+    eq(got, mg.xy_to_ij_f64(xy, origin, res, H, W), "float64 form")
+    eq(got, ref.xy_to_ij(xy, origin, res, H, W).astype(np.int32), "float64 form against the oracle")
     xy32 = xy.astype(np.float32)
-    got = gpu.sim.debug_xy_to_ij(cfg, _t(gpu, xy32.astype(np.float64)), True).cpu().numpy()
-    _eq(got, mg.xy_to_ij_f32(xy32, origin, res, H, W), "float32 form")
-    _eq(got, ref.xy_to_ij_f32(xy32, origin, res, H, W).astype(np.int32), "float32 form against the oracle")
+    got = gpu.sim.debug_xy_to_ij(cfg, to_device(gpu, xy32.astype(np.float64)), True).cpu().numpy()
+    eq(got, mg.xy_to_ij_f32(xy32, origin, res, H, W), "float32 form")
+    eq(got, ref.xy_to_ij_f32(xy32, origin, res, H, W).astype(np.int32), "float32 form against the oracle")
     if H != W:                                  # the clip quirk is live: indices the map's own side would not allow
         assert (got[:, 0] >= W).any() if H > W else (got[:, 1] >= H).any()
     assert got.min() == 0 and got[:, 0].max() == H - 1 and got[:, 1].max() == W - 1
@@ -164,32 +173,16 @@ def test_cast_static(gpu, H, W, rule):
             q[e, 2 * k, 2] = np.arctan2(H / 2 - p[1], W / 2 - p[0]); q[e, 2 * k + 1, 2] = q[e, 2 * k, 2] + np.pi
     max_range = float(H * W)
     want = ref.cast_static(field, q, max_range, rule)
-    got = gpu.sim.cast_static(_t(gpu, field), _t(gpu, q), max_range, rule).cpu().numpy()
-    _eq(got, want, "cast_static %d x %d rule %d" % (H, W, rule))
+    got = gpu.sim.cast_static(to_device(gpu, field), to_device(gpu, q), max_range, rule).cpu().numpy()
+    eq(got, want, "cast_static %d x %d rule %d" % (H, W, rule))
     assert (want[2:] == max_range).mean() > 0.01, "no ray left the open maps"
     assert (want[:2, 2 * len(out):] < max_range).all(), "a ray left a closed map"
 
 
 # ---- the fused step and navsim_reset_obs ---------------------------------------------------------------------------------------
-def _device_arrays(gpu, cfg, occ, world, form):
-    """The world's arrays with the field, record table and index rows the device builds from occ, in world.make_world's order
-    (field, records, index rows, closed_maps).  Sets cfg.closed_maps."""
-    occ_t = _t(gpu, occ)
-    a = {k: v for k, v in world.items() if k != "field"}
-    packed, f32, nsat = gpu.sim.build_field(occ_t, cfg.field_format)
-    a["field"] = packed
-    if cfg.field_format != abi.FIELD_F32:
-        assert nsat == 0
-        if form != NO_RECTS:
-            a["rect_table"] = gpu.sim.build_rects(occ_t, packed, cfg.field_format, f32)
-            a["rect_index"], _ = gpu.sim.build_rect_index(a["rect_table"], occ.shape[1], occ.shape[2])
-            cfg.closed_maps = int(bool((gpu.sim.maps_closed(occ_t) == 1).all().item()))
-    return a
-
-
 def _device_run(gpu, cfg, occ, world, form=NO_RECTS, steps=STEPS, seed=5, v_scale=1.0):
     cfg = cfg.copy()
-    arrays = _device_arrays(gpu, cfg, occ, world, form)
+    arrays = device_map_arrays(gpu, cfg, occ, world, form != NO_RECTS)
     if form == RECTS_LDS:
         assert cfg.closed_maps == 1, "the LDS form marches without a bounds test: closed maps only"
     g = gpu.sim.NavSim(cfg, arrays)
@@ -211,13 +204,13 @@ def _device_run(gpu, cfg, occ, world, form=NO_RECTS, steps=STEPS, seed=5, v_scal
 def _equal_runs(dev, want, label):
     assert len(dev) == len(want)
     for t, (a, b) in enumerate(zip(dev, want)):
-        _eq(a["obs"], b["obs"], "%s: observation %d" % (label, t))
+        eq(a["obs"], b["obs"], "%s: observation %d" % (label, t))
         if b["out"] is not None:
             for k in b["out"]:
-                _eq(a["out"][k], b["out"][k], "%s: %s at step %d" % (label, k, t))
+                eq(a["out"][k], b["out"][k], "%s: %s at step %d" % (label, k, t))
         for k in mg.STATE:
             if k in b:
-                _eq(a[k], b[k], "%s: state %s at observation %d" % (label, k, t))
+                eq(a[k], b[k], "%s: state %s at observation %d" % (label, k, t))
 
 
 def _both(gpu, cfg, occ, world, form, label, **kw):
@@ -258,7 +251,7 @@ def test_step_on_closed_maps(gpu, H, W, fmt, form, block, ped_model, n_beams):
     crashes, successes, restarts = mg.census(dev)
     assert crashes > 0 and restarts > 0
     if ped_model != abi.PED_NONE:
-        _eq(g.ped_scans().cpu().numpy(), r.ped_scans(), "pedestrian scans")
+        eq(g.ped_scans().cpu().numpy(), r.ped_scans(), "pedestrian scans")
 
 
 @pytest.mark.parametrize("H,W,fmt,form,block,ped_model", [
@@ -275,7 +268,7 @@ def test_step_on_open_maps(gpu, H, W, fmt, form, block, ped_model):
     B = cfg.n_scan_stack * cfg.n_beams
     assert sum(int((d["obs"][:, :B] == np.float32(cfg.range_max)).sum()) for d in dev) > 0, "no ray left the map"
     if ped_model != abi.PED_NONE:
-        _eq(g.ped_scans().cpu().numpy(), r.ped_scans(), "pedestrian scans")
+        eq(g.ped_scans().cpu().numpy(), r.ped_scans(), "pedestrian scans")
 
 
 @pytest.mark.parametrize("H,W", [(85, 330), (330, 85)])
@@ -291,7 +284,7 @@ def test_first_observation_of_robots_outside_the_map(gpu, H, W, fmt, form):
     cfg = cpu.config(H, W, E=E, n_beams=127, field_format=fmt, step_block=64, rect_lds=1 if form == RECTS_GLOBAL else 0,
                      auto_reset=0, n_spawn=1)
     occ = mg.make_maps(E, H, W, 4, "open")
-    world = mg.make_world(cfg, occ, ref.build_dt(occ), cpu.thresholds(cfg), 4, inside=False)
+    world = mg.make_world(cfg, occ, ref.build_dt(occ), keti_thresholds(cfg), 4, inside=False)
     for e, cell in enumerate(places):
         world["robot_pose"][e, :2] = mg.cell_xy(cfg, np.array(cell))
     dev, g = _device_run(gpu, cfg, occ, world, form, steps=0)
@@ -379,14 +372,13 @@ def ped_world(H, W, origin, k, N=8, seed=9, **kw):
 @pytest.mark.parametrize("H,W", [(85, 330), (330, 85), (120, 120)])
 @pytest.mark.parametrize("fmt", [F32, U16T])
 def test_ped_observe(gpu, H, W, origin, k, fmt):
-    import ped_observe_spec as spec
-    import test_gpu_ped_observe as dev
+    dev = ped_observe_call
     cfg, occ, w = ped_world(H, W, origin, k, field_format=fmt)
-    st, keep = dev._device_state(gpu, cfg, occ, w)
+    st, keep = dev.device_state(gpu, cfg, occ, w)
     seen = hidden = 0
     for p in (dict(sensor_range=6.0 * k, ped_radius=0.3 * k, max_obs=4, rays=3), dict(sensor_range=3.0 * k, ped_radius=0.3 * k, max_obs=8, rays=1, fov=0)):
-        want = dev._spec(cfg, w["field"], w, p)
-        dev._same(dev._call(gpu, cfg, st, p), want, "%d x %d origin %s resolution %g %s" % (H, W, origin, cfg.resolution, p))
+        want = dev.answer(cfg, w["field"], w, p)
+        dev.same(dev.call(gpu, cfg, st, p), want, "%d x %d origin %s resolution %g %s" % (H, W, origin, cfg.resolution, p))
         seen += int(want["count"].sum()); hidden += int((want["visible"] == 0).sum())
     assert seen > 0 and hidden > 0
 
@@ -400,7 +392,7 @@ def test_ped_scans(gpu, H, W, origin, k):
     want, r = cpu.run(cfg, w, steps=2)
     _equal_runs(dev, want, "two steps")
     scans = r.ped_scans()
-    _eq(g.ped_scans().cpu().numpy(), scans, "pedestrian scans %d x %d origin %s resolution %g" % (H, W, origin, cfg.resolution))
+    eq(g.ped_scans().cpu().numpy(), scans, "pedestrian scans %d x %d origin %s resolution %g" % (H, W, origin, cfg.resolution))
     assert (scans < np.float32(cfg.ped_range_max)).any() and (scans > 0).any()
 
 
@@ -408,10 +400,9 @@ def test_ped_scans(gpu, H, W, origin, k):
 @pytest.mark.parametrize("H,W", [(85, 330), (330, 85), (120, 120)])
 def test_ped_orca_walls(gpu, H, W, origin, k):
     """max_obst_rects = 8, time_horizon_obst = 2 on the rectangles the device listed for the map."""
-    import ped_orca_spec as spec
-    import ped_orca_walls_spec as wspec
+    spec = ped_orca_spec
     cfg, occ, w = ped_world(H, W, origin, k, field_format=U16T, rect_lds=1)
-    arrays = _device_arrays(gpu, cfg, occ, {n: v for n, v in w.items() if n != "ped_wp_head"}, RECTS_GLOBAL)
+    arrays = device_map_arrays(gpu, cfg, occ, {n: v for n, v in w.items() if n != "ped_wp_head"}, True)
     g = gpu.sim.NavSim(cfg, arrays)
     g.reset_obs()
     rects = wspec.decode_rows(g.t["rect_index"].cpu().numpy())
@@ -428,9 +419,9 @@ def test_ped_orca_walls(gpu, H, W, origin, k):
     got = g.ped_orca_walls({n: p[n] for n in spec.KEYS}, 8, dropped).cpu().numpy()
     want_cmd, want_head, want_dropped, census = wspec.ped_orca_walls(cfg, a, p, rects, 8)
     what = "%d x %d origin %s resolution %g" % (H, W, origin, cfg.resolution)
-    _eq(got, want_cmd, "ped_cmd " + what)
-    _eq(g.t["ped_wp_head"].cpu().numpy(), want_head, "ped_wp_head " + what)
-    _eq(dropped.cpu().numpy(), want_dropped, "dropped " + what)
+    eq(got, want_cmd, "ped_cmd " + what)
+    eq(g.t["ped_wp_head"].cpu().numpy(), want_head, "ped_wp_head " + what)
+    eq(dropped.cpu().numpy(), want_dropped, "dropped " + what)
     print(what, dict(census))
     assert census["0 edges in range"] < cfg.n_envs * cfg.max_peds, "no pedestrian has a wall in range"
 
@@ -438,60 +429,52 @@ def test_ped_orca_walls(gpu, H, W, origin, k):
 @pytest.mark.parametrize("origin,k", GEOMETRIES)
 @pytest.mark.parametrize("fmt", [F32, U16T])
 def test_goal_path(gpu, origin, k, fmt):
-    import goal_path_spec as spec
-    import test_gpu_goal_path as dev
+    spec, dev = goal_path_spec, goal_path_call
     E, size, seed = 12, 100, 5301
     occ, w = spec.random_world(E, size, seed)
     cfg, w = mg.geometry_twin(spec.config(E, size, field_format=fmt), w, origin, k)
-    st, keep = dev._device_state(gpu, cfg, occ, w)
+    st, keep = dev.device_state(gpu, cfg, occ, w)
     fields = ref.build_dt(occ)
     for p in ({}, dict(hard_clearance=0.2, clearance=1.5, band_cost=16, lookahead=6.0)):
         p = _scaled(dict(spec.DEFAULT, **p), k, ("hard_clearance", "clearance", "lookahead"))
-        want = dev._spec(cfg, fields, w, p)
+        want = dev.answer(cfg, fields, w, p)
         assert (want["status"] & spec.OK).sum() >= 2 and ((want["dist"] != spec.INF) & (want["dist"] > 0)).sum() > 200
-        dev._same(dev._call(gpu, cfg, st, p), want, "origin %s resolution %g %s" % (origin, cfg.resolution, p))
+        dev.same(dev.call(gpu, cfg, st, p), want, "origin %s resolution %g %s" % (origin, cfg.resolution, p))
 
 
 @pytest.mark.parametrize("origin,k", GEOMETRIES)
 @pytest.mark.parametrize("fmt", [F32, U16T])
 def test_dwa(gpu, origin, k, fmt):
-    import dwa_spec as spec
-    import test_gpu_dwa as dev
+    spec, dev = dwa_spec, dwa_call
     E, N, size, seed = spec.BASE
     occ, w = spec.random_world(E, N, size, seed)
     cfg = spec.config(E, size, N, field_format=fmt)
     cfg.linvel_lo, cfg.linvel_hi = cfg.linvel_lo * k, cfg.linvel_hi * k
     cfg, w = mg.geometry_twin(cfg, w, origin, k)
     p = _scaled(dict(spec.DEFAULT, **spec.BASE_PARAMS), k, ("acc_lin", "body_radius", "body_offset", "ped_radius", "margin", "clearance_cap"))
-    st, keep = dev._device_state(gpu, cfg, occ, w)
+    st, keep = dev.device_state(gpu, cfg, occ, w)
     want = spec.plan(cfg, ref.build_dt(occ), w, p)
     assert (want["first_hit"] != 0).any() and (want["first_hit"] == 0).any()
-    dev._same(dev._call(gpu, cfg, st, p), want, "origin %s resolution %g" % (origin, cfg.resolution))
+    dev.same(dev.call(gpu, cfg, st, p), want, "origin %s resolution %g" % (origin, cfg.resolution))
 
 
 @pytest.mark.parametrize("H,W", [(330, 85), (85, 330)])
 def test_replan_inside_the_step_on_a_costmap_that_is_not_square(gpu, H, W):
     """navsim_step_replan (one launch: the arenas with a waiting pedestrian re-plan first) on 66 x 17 and 17 x 66 costmaps at a
     shifted origin: the oracle's serial step, replan, step, ... bit for bit, and navsim_replan on its own behind it."""
-    from test_gpu_parity import _state_equal
-    from nav_gym_amd import robots
     E, N, cap = 6, 4, 64
     cfg = gpu.lib.default_config(n_envs=E, map_h=H, map_w=W, max_peds=N, ped_model=abi.PED_SFM, n_spawn=4, auto_reset=0, seed=29,
                                  field_format=U16T, ped_min_goal_dist=1.5, origin_x=-7.3, origin_y=12.9)
     gpu.world.lidar_full_circle(cfg, 127)
     occ = mg.make_maps(E, H, W, 29, n_boxes=1)
-    arrays = gpu.world.make_world(cfg, occ, n_peds=N, device=gpu.dev, plan_paths=True, v_pref_range=(0.5, 0.6),
-                                  min_goal_dist=1.0, max_goal_dist=3.0, robot_clearance=0.6)
+    arrays = device_world(gpu, cfg, occ, N, plan_paths=True, v_pref_range=(0.5, 0.6), min_goal_dist=1.0, max_goal_dist=3.0,
+                          robot_clearance=0.6)
     assert tuple(arrays["costmap"].shape) == (E, H // 5, W // 5)
-    _eq(arrays["costmap"].cpu().numpy(), ref.costmap(occ), "costmap")
-    arrays["scan_threshold"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "threshold_footprint")))
-    arrays["scan_discomfort"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "discomfort_threshold_footprint")))
-    host = {k: v.cpu().numpy() for k, v in arrays.items() if k not in ("field", "field_overflow", "rect_table", "rect_index")}
-    host["field"] = ref.build_dt(occ)
+    eq(arrays["costmap"].cpu().numpy(), ref.costmap(occ), "costmap")
     g = gpu.sim.NavSim(cfg, arrays)
     g.replan_in_step = True
-    r = ref.RefSim(cfg, host)
-    _eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
+    r = ref.RefSim(cfg, host_arrays(arrays, occ))
+    eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
     assert (r.a["ped_n_waypoints"] > 1).any(), "no pedestrian started with a planned path"
     rng = np.random.default_rng(3)
     for t in range(60):
@@ -500,18 +483,17 @@ def test_replan_inside_the_step_on_a_costmap_that_is_not_square(gpu, H, W):
             r.replan(cap)
         ro, rout = r.step(act)
         go, gout = g.step_overlapped(gpu.torch.from_numpy(act).to(gpu.dev), cap)
-        _eq(go.cpu().numpy(), ro, "obs at step %d" % t)
+        eq(go.cpu().numpy(), ro, "obs at step %d" % t)
         for k in rout:
-            _eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
+            eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
     g.replan(cap); r.replan(cap)
-    _state_equal(g, r, cfg, "at the end")
+    state_equal(g, r, "at the end", live_waypoints_only=True)
     assert g.counters() == r.counters() and r.counters()["replan_served"] >= 1, r.counters()
 
 
 def test_regen_at_a_shifted_origin_and_resolution(gpu):
     """navsim_regen on square maps of 0.1 m cells whose origin is (-7.3, 12.9): new maps, tables, pedestrians and first
     observations equal the oracle's."""
-    from test_gpu_parity import _rollout_pair
     E, size = 8, 120
     cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, max_peds=3, ped_model=abi.PED_SFM, n_spawn=4, auto_reset=1, seed=29,
                                  field_format=U16T, regen_cap=4, min_goal_dist=2.0, max_goal_dist=6.0, spawn_clearance=0.8,
@@ -519,15 +501,12 @@ def test_regen_at_a_shifted_origin_and_resolution(gpu):
     gpu.world.lidar_full_circle(cfg, 90)
     occ = gpu.world.make_maps(E, size, 29)
     regenerated = 0
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=3, steps=30, seed=3, min_goal_dist=2.0, max_goal_dist=6.0,
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=3, steps=30, seed=3, min_goal_dist=2.0, max_goal_dist=6.0,
                                                      robot_clearance=0.8):
-        _eq(go, ro, "obs at step %d" % t)
+        eq(go, ro, "obs at step %d" % t)
         regenerated += min(int(rout["done"].sum()), 4)
-        _eq(g.regen().cpu().numpy(), r.regen(), "obs after regen at step %d" % t)
-    gs = g.numpy_state()
-    for k, v in r.a.items():
-        if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index"):
-            _eq(gs[k], v, "state %s" % k)
+        eq(g.regen().cpu().numpy(), r.regen(), "obs after regen at step %d" % t)
+    state_equal(g, r, "at the end")
     assert regenerated >= 2
     lo, hi = np.array([-7.3, 12.9]), np.array([-7.3, 12.9]) + size * 0.1
     assert ((r.a["spawn_pose"][..., :2] > lo) & (r.a["spawn_pose"][..., :2] < hi)).all(), "a spawn outside the shifted map"

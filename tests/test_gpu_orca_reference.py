@@ -10,8 +10,7 @@ import orca_f64 as f64
 import orca_scenes as sc
 import ped_orca_spec as spec
 import ref
-from test_gpu_autoreset import gpu, _t, _eq  # noqa: F401  (gpu: the module's fixture)
-from test_gpu_ped_orca import _small_cfg, _pair, SENTINEL
+from gpu_support import gpu, eq, orca_pair, small_orca_config, to_device, ORCA_SENTINEL as SENTINEL  # noqa: F401  (gpu: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,10 +18,10 @@ pytestmark = pytest.mark.gpu
 # ---- crowd_orca_kernel ------------------------------------------------------------------------------------------------------
 def _crowd(gpu, p, ag, pv, na=None, verts=None, what="ORCA velocity"):
     """navsim_crowd_orca on the device, equal to the oracle bit for bit -> velocities"""
-    gv, _ = gpu.sim.crowd_orca(p, _t(gpu, ag), _t(gpu, pv), None if verts is None else _t(gpu, verts),
-                               None if na is None else _t(gpu, na))
+    gv, _ = gpu.sim.crowd_orca(p, to_device(gpu, ag), to_device(gpu, pv), None if verts is None else to_device(gpu, verts),
+                               None if na is None else to_device(gpu, na))
     gv = gv.cpu().numpy()
-    _eq(gv, ref.crowd_orca(p, ag, pv, verts, na)[0], what)
+    eq(gv, ref.crowd_orca(p, ag, pv, verts, na)[0], what)
     return gv
 
 
@@ -67,23 +66,23 @@ class _Arenas:
     """One simulator and one oracle of E arenas x N pedestrians whose state every call overwrites with a scene."""
 
     def __init__(self, gpu, E, N):
-        self.gpu, self.cfg = gpu, _small_cfg(gpu, E, N)
-        self.g, self.r = _pair(gpu, self.cfg, N, moving=False)
+        self.gpu, self.cfg = gpu, small_orca_config(gpu, E, N)
+        self.g, self.r = orca_pair(gpu, self.cfg, N, moving=False)
 
     def answer(self, s, kw):
         gpu, g, r = self.gpu, self.g, self.r
         a = sc.ped_state(s, self.cfg.max_waypoints)
         for k in KEYS:
             r.a[k][...] = a[k]
-            g.t[k].copy_(_t(gpu, r.a[k]))
+            g.t[k].copy_(to_device(gpu, r.a[k]))
         g.t["ped_cmd"].fill_(SENTINEL)
         r.a["ped_cmd"][...] = SENTINEL
         p = spec.params(self.cfg, **kw)
         want, head, _ = spec.ped_orca(self.cfg, r.a, p)
         got = g.ped_orca({k: p[k] for k in spec.KEYS}).cpu().numpy()
         what = "E %d N %d %s" % (self.cfg.n_envs, self.cfg.max_peds, kw)
-        _eq(got, want, "ped_cmd (%s)" % what)                          # live rows, and dead rows still holding the sentinel
-        _eq(g.numpy_state("ped_wp_head")["ped_wp_head"], head, "ped_wp_head (%s)" % what)
+        eq(got, want, "ped_cmd (%s)" % what)                          # live rows, and dead rows still holding the sentinel
+        eq(g.numpy_state("ped_wp_head")["ped_wp_head"], head, "ped_wp_head (%s)" % what)
         live = np.arange(self.cfg.max_peds)[None, :] < r.a["n_peds"][:, None]
         assert (got[~live] == SENTINEL).all() and np.isfinite(got[live]).all()
         return got, self.cfg.time_step, p

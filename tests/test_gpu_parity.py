@@ -11,47 +11,23 @@ import numpy as np
 import pytest
 
 import ref
-from helpers import load_trace, trace_setup
-from nav_gym_amd import abi
+from gpu_support import (NOT_STATE, gpu, decode_rect_index, decode_rect_table, device_world, eq, host_arrays, random_actions,  # noqa: F401
+                         rollout_pair, state_equal, to_device)
+from helpers import crowd_golden, finished_world, keti_thresholds, load_trace, trace_setup
+from nav_gym_amd import abi, robots
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-5   # north_star tolerance on ranges / pose (we assert equality, which is stricter)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from nav_gym_amd import lib, sim, world
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    lib.load()
-    return type("G", (), dict(torch=torch, lib=lib, sim=sim, world=world, dev=torch.device("cuda:0")))
-
-
-def _t(gpu, a, dtype=None):
-    t = gpu.torch.from_numpy(np.ascontiguousarray(a)).to(gpu.dev)
-    return t if dtype is None else t.to(dtype)
-
-
-def _eq(a, b, what):
-    a = np.asarray(a); b = np.asarray(b)
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        diff = np.max(np.abs(a.astype(np.float64) - b.astype(np.float64)))
-        raise AssertionError("%s: %d mismatches, max |diff| %.3e (north_star tol %g), first at %s"
-                             % (what, len(bad), diff, TOL, bad[0]))
-
 
 def test_device_math_bit_exact(gpu):
     rng = np.random.default_rng(0)
     x = np.concatenate([rng.uniform(-40, 40, 200000), [0.0, np.pi, -np.pi, 2 * np.pi, 1e-12, -3.141592]])
     for fn in (0, 1, 4, 5):
-        _eq(gpu.sim.debug_math(fn, _t(gpu, x)).cpu().numpy(), ref.math_fn(fn, x), "math fn %d" % fn)
+        eq(gpu.sim.debug_math(fn, to_device(gpu, x)).cpu().numpy(), ref.math_fn(fn, x), "math fn %d" % fn)
     y, xx = rng.normal(size=200000), rng.normal(size=200000)
     y[:4] = [0, 1, -1, 0]; xx[:4] = [1, 0, 0, -1]
-    _eq(gpu.sim.debug_math(2, _t(gpu, y), _t(gpu, xx)).cpu().numpy(), ref.math_fn(2, y, xx), "atan2")
+    eq(gpu.sim.debug_math(2, to_device(gpu, y), to_device(gpu, xx)).cpu().numpy(), ref.math_fn(2, y, xx), "atan2")
     e = -rng.uniform(0, 720, 200000)
-    _eq(gpu.sim.debug_math(3, _t(gpu, e)).cpu().numpy(), ref.math_fn(3, e), "exp")
+    eq(gpu.sim.debug_math(3, to_device(gpu, e)).cpu().numpy(), ref.math_fn(3, e), "exp")
 
 
 def test_social_force_pair_term_is_antisymmetric(gpu):
@@ -71,13 +47,13 @@ def test_packed_field_sqrt_is_correctly_rounded(gpu):
     x = gpu.torch.arange(n, dtype=gpu.torch.float64, device=gpu.dev)
     got = gpu.sim.debug_math(6, x).cpu().numpy()
     exp = np.sqrt(np.arange(n, dtype=np.float32)).astype(np.float64)
-    _eq(got, exp, "exact integer sqrt")
+    eq(got, exp, "exact integer sqrt")
     # the march step fl32(fl64(d) * 0.999) and its float32-only evaluation (kernels_field.hpp march_step) agree on
     # every d = sqrtf(n), n < 2^22, and both equal NumPy's float64 computation
     a, b = gpu.sim.debug_math(11, x).cpu().numpy(), gpu.sim.debug_math(12, x).cpu().numpy()
     ref_step = np.maximum((exp * 0.999).astype(np.float32), np.float32(1.0)).astype(np.float64)
-    _eq(a, ref_step, "march step, float64 form")
-    _eq(b, ref_step, "march step, float32-only form")
+    eq(a, ref_step, "march step, float64 form")
+    eq(b, ref_step, "march step, float32-only form")
 
 
 def test_beam_table_direction_is_the_full_evaluation(gpu):
@@ -107,7 +83,7 @@ def test_beam_table_direction_is_the_full_evaluation(gpu):
         sl = slice(j, None, 9)
         for _ in range(abs(j - 4)):
             lth32[sl] = np.nextafter(lth32[sl], np.float32(np.inf if j > 4 else -np.inf))
-    code = gpu.sim.debug_math(13, _t(gpu, lth32.astype(np.float64)), _t(gpu, lin)).cpu().numpy()
+    code = gpu.sim.debug_math(13, to_device(gpu, lth32.astype(np.float64)), to_device(gpu, lin)).cpu().numpy()
     assert (code != 2).all(), "special directions: %d wrong" % int((code == 2).sum())
     assert (code == 0).mean() > 0.5           # the fast path is not simply declining everything here
 
@@ -115,8 +91,8 @@ def test_beam_table_direction_is_the_full_evaluation(gpu):
 @pytest.mark.parametrize("size,n", [(100, 3), (400, 2), (500, 2), (1000, 1)])
 def test_build_dt(gpu, size, n):
     occ = gpu.world.make_maps(n, size, 77 + size, indoor_ratio=0.5 if size == 1000 else 0.0)
-    got = gpu.sim.build_dt(_t(gpu, occ)).cpu().numpy()
-    _eq(got, ref.build_dt(occ), "distance field %d" % size)
+    got = gpu.sim.build_dt(to_device(gpu, occ)).cpu().numpy()
+    eq(got, ref.build_dt(occ), "distance field %d" % size)
 
 
 def test_build_dt_ragged_and_empty(gpu):
@@ -125,8 +101,8 @@ def test_build_dt_ragged_and_empty(gpu):
     occ[1] = 0; occ[1, 0, 0] = 1
     occ[2] = 0                                      # no obstacle at all
     occ[3] = 1                                      # everything occupied
-    got = gpu.sim.build_dt(_t(gpu, occ)).cpu().numpy()
-    _eq(got, ref.build_dt(occ), "ragged distance field")
+    got = gpu.sim.build_dt(to_device(gpu, occ)).cpu().numpy()
+    eq(got, ref.build_dt(occ), "ragged distance field")
 
 
 def _queries(rng, occ, n):
@@ -147,11 +123,11 @@ def test_device_xy_to_ij_reference_goldens(gpu, golden_dir, size):
     float64 inputs and the float32 inputs of the lidar origin (env.py:386, 419): exact integers."""
     units = np.load(os.path.join(golden_dir, "golden_units.npz"))
     cfg = gpu.lib.default_config(map_h=size, map_w=size)
-    got = gpu.sim.debug_xy_to_ij(cfg, _t(gpu, units["xy_%d" % size]), False).cpu().numpy()
-    _eq(got, units["ij_%d" % size].astype(np.int32), "xy_to_ij float64 %d" % size)
-    got = gpu.sim.debug_xy_to_ij(cfg, _t(gpu, units["xyf32_%d" % size].astype(np.float64)), True).cpu().numpy()
-    _eq(got, units["ijf32_%d" % size].astype(np.int32), "xy_to_ij float32 %d" % size)
-    _eq(got, ref.xy_to_ij_f32(units["xyf32_%d" % size], (0.0, 0.0), 0.05, size, size).astype(np.int32), "oracle")
+    got = gpu.sim.debug_xy_to_ij(cfg, to_device(gpu, units["xy_%d" % size]), False).cpu().numpy()
+    eq(got, units["ij_%d" % size].astype(np.int32), "xy_to_ij float64 %d" % size)
+    got = gpu.sim.debug_xy_to_ij(cfg, to_device(gpu, units["xyf32_%d" % size].astype(np.float64)), True).cpu().numpy()
+    eq(got, units["ijf32_%d" % size].astype(np.int32), "xy_to_ij float32 %d" % size)
+    eq(got, ref.xy_to_ij_f32(units["xyf32_%d" % size], (0.0, 0.0), 0.05, size, size).astype(np.int32), "oracle")
 
 
 @pytest.mark.parametrize("rule", abi.MARCH_RULES)
@@ -162,9 +138,9 @@ def test_cast_static(gpu, size, rule):
     field = ref.build_dt(occ)
     q = _queries(rng, occ, 4096)
     q[0, :8, 0:2] = [[-3, 5], [size + 2, 5], [5, -1], [5, size], [0, 0], [size - 1, size - 1], [2.5, 2.5], [7, 7]]
-    got = gpu.sim.cast_static(_t(gpu, field), _t(gpu, q), float(size * size), rule).cpu().numpy()
-    _eq(got, ref.cast_static(field, q, float(size * size), rule), "cast_static %d rule %d" % (size, rule))
-    assert gpu.sim.cast_static(_t(gpu, field), _t(gpu, q[:, :0]), 1.0).shape == (3, 0)
+    got = gpu.sim.cast_static(to_device(gpu, field), to_device(gpu, q), float(size * size), rule).cpu().numpy()
+    eq(got, ref.cast_static(field, q, float(size * size), rule), "cast_static %d rule %d" % (size, rule))
+    assert gpu.sim.cast_static(to_device(gpu, field), to_device(gpu, q[:, :0]), 1.0).shape == (3, 0)
 
 
 def test_march_rule_switch_full_step(gpu):
@@ -180,12 +156,12 @@ def test_march_rule_switch_full_step(gpu):
         gpu.world.lidar_1081(cfg)
         occ = gpu.world.make_maps(E, size, 99)
         rows = []
-        for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=5, steps=25, seed=3):
-            _eq(go, ro, "obs at step %d (rule %d)" % (t, rule))
+        for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=5, steps=25, seed=3):
+            eq(go, ro, "obs at step %d (rule %d)" % (t, rule))
             for k in rout:
-                _eq(gout[k], rout[k], "%s at step %d (rule %d)" % (k, t, rule))
+                eq(gout[k], rout[k], "%s at step %d (rule %d)" % (k, t, rule))
             rows.append(go.copy())
-        _eq(g.ped_scans().cpu().numpy(), r.ped_scans(), "pedestrian scans (rule %d)" % rule)
+        eq(g.ped_scans().cpu().numpy(), r.ped_scans(), "pedestrian scans (rule %d)" % rule)
         obs[rule] = rows
     # liveness of the switch on the device: rays on which the two rules are KNOWN to differ (about 3 in 10^6 do;
     # tests/test_oracle_crosscheck.py wrote the fixture from 10^7) give the recorded answer under each rule
@@ -193,11 +169,11 @@ def test_march_rule_switch_full_step(gpu):
     for m in range(int(d["n_maps"])):
         H, W = [int(x) for x in d["shape_%d" % m]]
         occ = np.unpackbits(d["occ_%d" % m])[: H * W].reshape(1, H, W)
-        f = gpu.sim.build_dt(_t(gpu, occ))
-        q = _t(gpu, d["q_%d" % m][None])
-        _eq(gpu.sim.cast_static(f, q, float(H * W), abi.MARCH_F64).cpu().numpy()[0], d["r64_%d" % m], "rule F64 map %d" % m)
-        _eq(gpu.sim.cast_static(f, q, float(H * W), abi.MARCH_F32).cpu().numpy()[0], d["r32_%d" % m], "rule F32 map %d" % m)
-        _eq(gpu.sim.cast_static(f, q, float(H * W), abi.MARCH_F32_FMA).cpu().numpy()[0], d["r32fma_%d" % m], "rule F32_FMA map %d" % m)
+        f = gpu.sim.build_dt(to_device(gpu, occ))
+        q = to_device(gpu, d["q_%d" % m][None])
+        eq(gpu.sim.cast_static(f, q, float(H * W), abi.MARCH_F64).cpu().numpy()[0], d["r64_%d" % m], "rule F64 map %d" % m)
+        eq(gpu.sim.cast_static(f, q, float(H * W), abi.MARCH_F32).cpu().numpy()[0], d["r32_%d" % m], "rule F32 map %d" % m)
+        eq(gpu.sim.cast_static(f, q, float(H * W), abi.MARCH_F32_FMA).cpu().numpy()[0], d["r32fma_%d" % m], "rule F32_FMA map %d" % m)
         assert not np.array_equal(d["r64_%d" % m], d["r32_%d" % m])
         assert not np.array_equal(d["r32_%d" % m], d["r32fma_%d" % m])
 
@@ -220,18 +196,18 @@ def test_render_polys_and_legs(gpu):
             verts[e, 4 * c:4 * c + 4, 1:] = fp @ R.T + [cx, cy]
     verts[3, :5, 0] = 0                              # a closed 5-vertex contour (env.py:411)
     verts[3, 4, 1:] = verts[3, 0, 1:]
-    got = gpu.sim.render_polys(_t(gpu, ranges), _t(gpu, angles), _t(gpu, verts), _t(gpu, n_verts), _t(gpu, origin))
+    got = gpu.sim.render_polys(to_device(gpu, ranges), to_device(gpu, angles), to_device(gpu, verts), to_device(gpu, n_verts), to_device(gpu, origin))
     exp = ref.render_polys(ranges, angles, verts, n_verts, origin)
-    _eq(got.cpu().numpy(), exp, "render_polys")
+    eq(got.cpu().numpy(), exp, "render_polys")
     assert (exp < ranges).any()
     agents = np.zeros((E, A, 8), np.float32)
     agents[:, :, 0:2] = origin[:, None, :] + rng.uniform(-3, 3, (E, A, 2))
     agents[:, :, 2] = rng.uniform(0, 6.28, (E, A))
     agents[:, :, 3:6] = rng.uniform(-2, 2, (E, A, 3))
     n_agents = np.array([6, 0, 3, 1, 6], np.int32)
-    got = gpu.sim.render_legs(_t(gpu, ranges), _t(gpu, angles), _t(gpu, agents), _t(gpu, n_agents), _t(gpu, origin))
+    got = gpu.sim.render_legs(to_device(gpu, ranges), to_device(gpu, angles), to_device(gpu, agents), to_device(gpu, n_agents), to_device(gpu, origin))
     exp = ref.render_legs(ranges, angles, agents, n_agents, origin)
-    _eq(got.cpu().numpy(), exp, "render_legs")
+    eq(got.cpu().numpy(), exp, "render_legs")
     assert (exp < ranges).any()
 
 
@@ -241,18 +217,18 @@ def test_integrate_and_thresholds(gpu, golden_dir):
     inp = u["set_vel_in"]
     m = inp[:, 5] == 0.2
     for off, key in ((0.0, "human_set_vel_out"), (0.14474, "keti_set_vel_out")):
-        pose = _t(gpu, inp[m, 0:3].copy()); vel = gpu.torch.zeros((int(m.sum()), 2), dtype=gpu.torch.float64, device=gpu.dev)
-        gpu.sim.integrate(pose, _t(gpu, inp[m, 3:5].copy()), 0.2, off, vel)
+        pose = to_device(gpu, inp[m, 0:3].copy()); vel = gpu.torch.zeros((int(m.sum()), 2), dtype=gpu.torch.float64, device=gpu.dev)
+        gpu.sim.integrate(pose, to_device(gpu, inp[m, 3:5].copy()), 0.2, off, vel)
         exp_pose, exp_vel = ref.integrate(inp[m, 0:3], inp[m, 3:5], 0.2, off)
-        _eq(pose.cpu().numpy(), exp_pose, "set_vel pose"); _eq(vel.cpu().numpy(), exp_vel, "set_vel vel")
+        eq(pose.cpu().numpy(), exp_pose, "set_vel pose"); eq(vel.cpu().numpy(), exp_vel, "set_vel vel")
         np.testing.assert_allclose(pose.cpu().numpy(), u[key][m][:, 0:3], rtol=0, atol=1e-12)   # vs the reference
     for B in (512, 1081, 64):
         cfg = gpu.lib.default_config()
         if B == 1081: gpu.world.lidar_1081(cfg)
         if B == 64: gpu.world.lidar_full_circle(cfg, 64)
         for key in ("keti_threshold_footprint", "keti_discomfort_footprint"):
-            got = gpu.sim.scan_threshold(cfg, _t(gpu, u[key].astype(np.float32))).cpu().numpy()
-            _eq(got, ref.scan_threshold(cfg, u[key]), "scan_threshold B=%d" % B)
+            got = gpu.sim.scan_threshold(cfg, to_device(gpu, u[key].astype(np.float32))).cpu().numpy()
+            eq(got, ref.scan_threshold(cfg, u[key]), "scan_threshold B=%d" % B)
 
 
 @pytest.mark.parametrize("S,B", [(1, 128), (3, 64)])
@@ -266,10 +242,10 @@ def test_reward_done(gpu, golden_dir, S, B, f64):
     if not f64:
         obs = obs.astype(np.float32); goals = goals.astype(np.float32)
     cfg = gpu.lib.default_config(n_beams=B, n_scan_stack=S)
-    got = gpu.sim.reward_done(cfg, _t(gpu, obs), _t(gpu, goals), _t(gpu, u[tag + "thr"]), _t(gpu, u[tag + "dthr"]))
+    got = gpu.sim.reward_done(cfg, to_device(gpu, obs), to_device(gpu, goals), to_device(gpu, u[tag + "thr"]), to_device(gpu, u[tag + "dthr"]))
     exp = ref.reward_done(cfg, obs, goals, u[tag + "thr"], u[tag + "dthr"])
     for k in exp:
-        _eq(got[k].cpu().numpy(), exp[k], "reward_done " + k)
+        eq(got[k].cpu().numpy(), exp[k], "reward_done " + k)
     if f64:                                          # and against the reference's own outputs
         np.testing.assert_allclose(got["reward"].cpu().numpy(), u[tag + "reward"], rtol=0, atol=1e-9)
         assert np.array_equal(got["done"].cpu().numpy().astype(bool), u[tag + "done"].astype(bool))
@@ -282,12 +258,12 @@ def test_step_golden_traces(gpu, name):
     """The fused HIP step reproduces the reference's own reset()/step() traces (corridor_S1: on the reference's own
     1000 x 1000 corridor map, recorded in round 4)."""
     tr = load_trace(name)
-    cfg, arrays, occ = trace_setup(tr, gpu.lib.default_config, lambda o: gpu.sim.build_dt(_t(gpu, o)).cpu().numpy())
-    _eq(arrays["field"], ref.build_dt(occ[None]), "field")
+    cfg, arrays, occ = trace_setup(tr, gpu.lib.default_config, lambda o: gpu.sim.build_dt(to_device(gpu, o)).cpu().numpy())
+    eq(arrays["field"], ref.build_dt(occ[None]), "field")
     sim = gpu.sim.NavSim(cfg, arrays)
     S, B = int(tr["S"]), int(tr["B"])
     first = sim.reset_obs().cpu().numpy()
-    _eq(first[0, : S * B], tr["first_obs"][: S * B].astype(np.float32), "first scan")
+    eq(first[0, : S * B], tr["first_obs"][: S * B].astype(np.float32), "first scan")
     np.testing.assert_allclose(first[0, S * B:], tr["first_obs"][S * B:], rtol=0, atol=2e-6)
     for t in range(tr["actions"].shape[0]):
         sim.set_ped_cmd(tr["ped_cmd"][t][None])
@@ -296,49 +272,15 @@ def test_step_golden_traces(gpu, name):
         assert o["done"][0] == tr["done"][t] and o["is_crash"][0] == tr["is_crash"][t] \
             and o["is_success"][0] == tr["is_success"][t], t
         assert abs(o["reward"][0] - tr["reward"][t]) < 1e-9, t
-        _eq(obs[0, : S * B], tr["obs_scan"][t], "scan stack at step %d" % t)
+        eq(obs[0, : S * B], tr["obs_scan"][t], "scan stack at step %d" % t)
         np.testing.assert_allclose(obs[0, S * B:], tr["obs_tail"][t], rtol=0, atol=2e-6)
         if "ped_scan_steps" in tr and t in tr["ped_scan_steps"]:          # env.py:685-693 on the GPU
             idx = int(np.where(tr["ped_scan_steps"] == t)[0][0])
-            _eq(sim.ped_scans().cpu().numpy()[0, : tr["ped_scan"].shape[1]], tr["ped_scan"][idx], "pedestrian scans")
+            eq(sim.ped_scans().cpu().numpy()[0, : tr["ped_scan"].shape[1]], tr["ped_scan"][idx], "pedestrian scans")
         stt = sim.numpy_state("robot_pose", "ped_pose", "ped_dist")
         np.testing.assert_allclose(stt["robot_pose"][0], tr["traj_robot_pose"][t], rtol=0, atol=1e-12)
         np.testing.assert_allclose(stt["ped_pose"][0], tr["traj_ped_pose"][t], rtol=0, atol=1e-12)
         np.testing.assert_allclose(stt["ped_dist"][0], tr["traj_ped_dist"][t], rtol=0, atol=1e-10)
-
-
-def _rollout_pair(gpu, cfg, occ, n_peds, steps, seed, noise=False, policy=None, **world_kw):
-    """Runs the same world through the HIP step and the oracle; yields per-step comparisons.
-    policy: HumanPolicy weights -> pedestrians are driven by navsim_ped_policy on both sides."""
-    torch = gpu.torch
-    world_kw_policy = policy
-    arrays = gpu.world.make_world(cfg, occ, n_peds=n_peds, device=gpu.dev, **world_kw)
-    key = "keti"
-    from nav_gym_amd import robots
-    arrays["scan_threshold"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array(key, "threshold_footprint")))
-    arrays["scan_discomfort"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array(key, "discomfort_threshold_footprint")))
-    host = {k: v.cpu().numpy() for k, v in arrays.items() if k not in ("field", "field_overflow", "rect_table", "rect_index")}
-    host["field"] = ref.build_dt(occ)                 # the oracle always reads its own float32 field
-    g = gpu.sim.NavSim(cfg, arrays)
-    r = ref.RefSim(cfg, host)
-    _eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
-    policy = world_kw_policy
-    rng = np.random.default_rng(seed)
-    E = cfg.n_envs
-    for t in range(steps):
-        act = np.stack([rng.uniform(0.0, 0.5, E), rng.uniform(-0.64, 0.64, E)], axis=1)
-        if t % 7 == 3:
-            act[:, 0] = 0.5; act[:, 1] = 0.0          # bursts of straight driving provoke crashes
-        if policy is not None:
-            if t == 0:
-                g.set_policy(policy)
-            g.ped_policy(); r.ped_policy(policy)
-        elif cfg.ped_model == abi.PED_EXTERNAL:
-            cmd = np.stack([rng.uniform(0, 0.6, (E, cfg.max_peds)), rng.uniform(-0.6, 0.6, (E, cfg.max_peds))], axis=2)
-            g.set_ped_cmd(cmd); r.set_ped_cmd(cmd)
-        go, gout = g.step(torch.from_numpy(act).to(gpu.dev))
-        ro, rout = r.step(act)
-        yield t, go.cpu().numpy(), {k: v.cpu().numpy() for k, v in gout.items()}, ro, rout, g, r
 
 
 @pytest.mark.parametrize("fmt", [abi.FIELD_F32, abi.FIELD_U16T, "u16t-no-rects", "u16t-rects-from-global-memory"])
@@ -360,17 +302,14 @@ def test_step_rollout_vs_oracle(gpu, ped_model, S, auto_reset, fmt):
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 4242)
     crashes = resets = 0
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=6, steps=60, seed=1, **world_kw):
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=6, steps=60, seed=1, **world_kw):
         assert ("rect_table" in g.t) == (fmt == abi.FIELD_U16T and not world_kw)
         for k in rout:
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
-        _eq(go, ro, "obs at step %d" % t)
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
+        eq(go, ro, "obs at step %d" % t)
         crashes += int(rout["is_crash"].sum()); resets += int(rout["done"].sum())
         if t % 10 == 9:
-            gs = g.numpy_state()
-            for k, v in r.a.items():
-                if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index"):
-                    _eq(gs[k], v, "state %s at step %d" % (k, t))
+            state_equal(g, r, "at step %d" % t)
     assert crashes > 0, "rollout never exercised the crash-revert branch"
     assert resets > 0
 
@@ -391,15 +330,12 @@ def test_step_rollout_256_threads_parked_rays(gpu, fmt, S):
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 77)
     crashes = resets = 0
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=0, steps=80, seed=3, **world_kw):
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=0, steps=80, seed=3, **world_kw):
         for k in rout:
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
-        _eq(go, ro, "obs at step %d" % t)
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
+        eq(go, ro, "obs at step %d" % t)
         crashes += int(rout["is_crash"].sum()); resets += int(rout["done"].sum())
-    gs = g.numpy_state()
-    for k, v in r.a.items():
-        if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index"):
-            _eq(gs[k], v, "state %s at the end" % k)
+    state_equal(g, r, "at the end")
     assert crashes > 0 and resets > 0
 
 
@@ -414,14 +350,11 @@ def test_step_rollout_with_split_pedestrian_kernel(gpu, ped_model, N, n_peds):
                                  auto_reset=1, n_spawn=8, seed=13, field_format=abi.FIELD_U16T, ped_split=2)
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 13)
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=n_peds, steps=40 if N == 8 else 12, seed=5):
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=n_peds, steps=40 if N == 8 else 12, seed=5):
         for k in rout:
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
-        _eq(go, ro, "obs at step %d" % t)
-    gs = g.numpy_state()
-    for k, v in r.a.items():
-        if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index"):
-            _eq(gs[k], v, "state %s" % k)
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
+        eq(go, ro, "obs at step %d" % t)
+    state_equal(g, r, "at the end")
 
 
 # NAVSIM_FUZZ_SEEDS=n widens the sweep for a one-off run (profiles/r03_soak/fuzz_4000.txt: 4000 seeds at the final kernels)
@@ -450,7 +383,6 @@ def test_step_fuzzed_configurations(gpu, seed):
         cfg.n_beams = nb
         cfg.angle_min = float(rng.uniform(-3.1, -0.5)); cfg.angle_last = float(rng.uniform(0.5, 3.1))
     if rng.random() < 0.5:
-        from nav_gym_amd import robots
         cfg.axle_offset = robots.ROBOTS["husky"]["axle_offset"]
     n_peds = 0 if ped_model == abi.PED_NONE else int(rng.integers(0, N + 1))
     width = int(rng.choice([97, 128, 200, 253, 320]))
@@ -459,15 +391,12 @@ def test_step_fuzzed_configurations(gpu, seed):
     occ = np.ascontiguousarray(gpu.world.make_maps(E, max(size, width), seed)[:, :size, :width])
     occ[:, size - 5:, :] = 1; occ[:, :, width - 5:] = 1          # the border wall along the cut
     goal = (1.0, 3.0) if min(size, width) < 200 else (2.0, 5.0)
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=n_peds, steps=8, seed=seed,
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=n_peds, steps=8, seed=seed,
                                                      min_goal_dist=goal[0], max_goal_dist=goal[1], robot_clearance=0.5):
         for k in rout:
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
-        _eq(go, ro, "obs at step %d" % t)
-    gs = g.numpy_state()
-    for k, v in r.a.items():
-        if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index"):
-            _eq(gs[k], v, "state %s" % k)
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
+        eq(go, ro, "obs at step %d" % t)
+    state_equal(g, r, "at the end")
 
 
 @pytest.mark.parametrize("step_block", [64, 256, 1024])
@@ -480,33 +409,33 @@ def test_step_rollout_with_the_maximum_pedestrian_count(gpu, step_block):
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 77)
     steps = 0
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=N, steps=6, seed=77,
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=N, steps=6, seed=77,
                                                      min_goal_dist=4.0, max_goal_dist=9.0, robot_clearance=0.6):
         if t == 0:                                   # a ragged count in two arenas (n_peds is read every step)
             for sim_arrays in (g.t["n_peds"],):
                 sim_arrays[1] = 37; sim_arrays[4] = 1
             r.a["n_peds"][1] = 37; r.a["n_peds"][4] = 1
         for k in rout:
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
-        _eq(go, ro, "obs at step %d" % t)
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
+        eq(go, ro, "obs at step %d" % t)
         steps += 1
     assert steps == 6
     gs = g.numpy_state()
     for k in ("ped_pose", "ped_vel", "ped_dist", "ped_prev_yaw", "robot_pose"):
-        _eq(gs[k], r.a[k], "state %s" % k)
+        eq(gs[k], r.a[k], "state %s" % k)
 
 
 def test_packed_field_decodes_to_float_field(gpu):
     """uint16 tiles: sqrtf(d2) must be the float32 field bit for bit; odd sizes exercise edge tiles."""
     for size, n in ((100, 2), (253, 2), (500, 1)):
         occ = gpu.world.make_maps(n, size, 31 + size)
-        packed, f32, nsat = gpu.sim.build_field(_t(gpu, occ), abi.FIELD_U16T)
-        _eq(f32.cpu().numpy(), ref.build_dt(occ), "overflow plane %d" % size)
+        packed, f32, nsat = gpu.sim.build_field(to_device(gpu, occ), abi.FIELD_U16T)
+        eq(f32.cpu().numpy(), ref.build_dt(occ), "overflow plane %d" % size)
         assert nsat == 0
         tpr = (size + 7) // 8
         raw = packed.cpu().numpy().view(np.uint16).reshape(n, tpr, tpr, 8, 8)
         full = raw.transpose(0, 1, 3, 2, 4).reshape(n, tpr * 8, tpr * 8)[:, :size, :size]
-        _eq(np.sqrt(full.astype(np.float32)), ref.build_dt(occ), "decoded tiles %d" % size)
+        eq(np.sqrt(full.astype(np.float32)), ref.build_dt(occ), "decoded tiles %d" % size)
 
 
 def test_packed_field_overflow_path(gpu):
@@ -519,14 +448,14 @@ def test_packed_field_overflow_path(gpu):
     cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, n_spawn=4, auto_reset=1, seed=5,
                                  field_format=abi.FIELD_U16T)
     gpu.world.lidar_1081(cfg)
-    packed, f32, nsat = gpu.sim.build_field(_t(gpu, occ), abi.FIELD_U16T)
+    packed, f32, nsat = gpu.sim.build_field(to_device(gpu, occ), abi.FIELD_U16T)
     assert nsat > 0
     seen = 0
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=0, steps=25, seed=3):
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=0, steps=25, seed=3):
         assert "field_overflow" in g.t
-        _eq(go, ro, "obs at step %d" % t)
+        eq(go, ro, "obs at step %d" % t)
         for k in rout:
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
         seen += 1
     assert seen == 25
 
@@ -539,10 +468,10 @@ def test_ped_scans_vs_oracle(gpu, fmt):
                                  auto_reset=1, seed=31, field_format=fmt)
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 31)
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=17, steps=6, seed=8):
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=17, steps=6, seed=8):
         got = g.ped_scans().cpu().numpy()
         exp = r.ped_scans()
-        _eq(got[:, :17], exp[:, :17], "pedestrian scans at step %d" % t)
+        eq(got[:, :17], exp[:, :17], "pedestrian scans at step %d" % t)
         assert (exp[:, :17] < 6.0).any()
 
 
@@ -558,10 +487,10 @@ def test_ped_scans_few_beams_many_pedestrians(gpu, beams):
                                      auto_reset=1, seed=seed, field_format=abi.FIELD_U16T, ped_n_beams=beams)
         gpu.world.lidar_1081(cfg)
         occ = gpu.world.make_maps(E, size, seed)
-        for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=n_peds, steps=3, seed=8):
+        for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=n_peds, steps=3, seed=8):
             exp = r.ped_scans()
             for rep in range(3):
-                _eq(g.ped_scans().cpu().numpy()[:, :n_peds], exp[:, :n_peds],
+                eq(g.ped_scans().cpu().numpy()[:, :n_peds], exp[:, :n_peds],
                     "pedestrian scans, %d beams, %d pedestrians, step %d" % (beams, n_peds, t))
             assert (exp[:, :n_peds] < 6.0).any()
 
@@ -588,31 +517,28 @@ def test_regen_vs_oracle(gpu, fmt, ped_model, plan, defer):
     occ = gpu.world.make_maps(E, size, 17)
     regenerated = capped = 0
     B = cfg.n_beams * cfg.n_scan_stack
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=5, steps=45, seed=6,
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=5, steps=45, seed=6,
                                                      plan_paths=bool(plan) and ped_model != abi.PED_NONE):
         if defer:
             live = rout["done"] == 0
-            _eq(go[live], ro[live], "obs of the unfinished arenas at step %d" % t)
-            _eq(go[:, B:], ro[:, B:], "tails at step %d" % t)
+            eq(go[live], ro[live], "obs of the unfinished arenas at step %d" % t)
+            eq(go[:, B:], ro[:, B:], "tails at step %d" % t)
             for k in rout:
-                _eq(gout[k], rout[k], "%s at step %d" % (k, t))
+                eq(gout[k], rout[k], "%s at step %d" % (k, t))
         else:
-            _eq(go, ro, "obs at step %d" % t)
+            eq(go, ro, "obs at step %d" % t)
         n_done = int(rout["done"].sum())
         go2 = g.regen().cpu().numpy()
         ro2 = r.regen()
-        _eq(go2, ro2, "obs after regen at step %d" % t)
+        eq(go2, ro2, "obs after regen at step %d" % t)
         regenerated += min(n_done, cap); capped += n_done > cap
         if n_done:
-            gs = g.numpy_state()
-            for k, v in r.a.items():
-                if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index"):
-                    _eq(gs[k], v, "state %s after regen at step %d" % (k, t))
+            gs = state_equal(g, r, "after regen at step %d" % t)
             if fmt == abi.FIELD_F32:
-                _eq(gs["field"], r.a["field"], "field after regen at step %d" % t)
+                eq(gs["field"], r.a["field"], "field after regen at step %d" % t)
     assert regenerated > 5 and (capped > 0 or not defer)
     if fmt == abi.FIELD_U16T:           # navsim_regen keeps the two-rectangle tile records of the new maps current
-        d2, valid = _decode_rect_table(g.t["rect_table"].cpu().numpy(), size, size)
+        d2, valid = decode_rect_table(g.t["rect_table"].cpu().numpy(), size, size)
         exact = np.rint(r.a["field"].astype(np.float64) ** 2).astype(np.int64)
         assert np.array_equal(d2[valid], exact[valid]) and valid.mean() > 0.9
     if plan and ped_model != abi.PED_NONE:
@@ -641,29 +567,22 @@ def test_pregenerated_worlds_equal_navsim_regen(gpu, fmt, ped_model, plan):
     occ = gpu.world.make_maps(E, size, 23)
     regenerated = 0
     twice = np.zeros(E, int)
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=5, steps=70, seed=9,
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=5, steps=70, seed=9,
                                                      plan_paths=bool(plan) and ped_model != abi.PED_NONE):
         if t == 0:
             g.enable_pregen()
-        _eq(go, ro, "obs at step %d" % t)
+        eq(go, ro, "obs at step %d" % t)
         n_done = int(rout["done"].sum())
         twice += rout["done"].astype(int)
         go2 = g.regen().cpu().numpy()
         ro2 = r.regen()
-        _eq(go2, ro2, "obs after the swap at step %d" % t)
+        eq(go2, ro2, "obs after the swap at step %d" % t)
         regenerated += n_done
         if n_done:
             gpu.torch.cuda.synchronize()
-            gs = g.numpy_state()
-            for k, v in r.a.items():
-                if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index"):
-                    if k == "ped_waypoints":      # slots beyond n_waypoints keep whatever the buffer held before
-                        live = np.arange(cfg.max_waypoints)[None, None, :] < r.a["ped_n_waypoints"][..., None]
-                        _eq(gs[k][live], v[live], "state %s after the swap at step %d" % (k, t))
-                    else:
-                        _eq(gs[k], v, "state %s after the swap at step %d" % (k, t))
+            gs = state_equal(g, r, "after the swap at step %d" % t, live_waypoints_only=True)
             if fmt == abi.FIELD_F32:
-                _eq(gs["field"], r.a["field"], "field after the swap at step %d" % t)
+                eq(gs["field"], r.a["field"], "field after the swap at step %d" % t)
     assert regenerated > 8 and (twice >= 2).any(), (regenerated, twice.max())
 
 
@@ -697,7 +616,7 @@ def test_pipelined_pregeneration_equals_navsim_regen(gpu, monkeypatch, period, m
         install = "slots"
     occ = gpu.world.make_maps(E, size, 29)
     n_long = n_short = 0
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=5, steps=110, seed=13):
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=5, steps=110, seed=13):
         if t == 0:
             with pytest.raises(ValueError, match="regen_min_steps"):
                 g.enable_pregen(pipeline=min_steps // 4 + 1)
@@ -713,21 +632,18 @@ def test_pipelined_pregeneration_equals_navsim_regen(gpu, monkeypatch, period, m
                 monkeypatch.setattr(g.lib, "navsim_regen_stage", delayed)
         done = rout["done"].astype(bool)
         for k in ("reward", "done", "is_success", "is_crash"):
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
         keep = ~done if install else np.ones(E, bool)       # (navsim_step_install: the finished arenas' rows are already the new worlds')
-        _eq(go[keep], ro[keep], "obs at step %d" % t)
+        eq(go[keep], ro[keep], "obs at step %d" % t)
         lng = r.a["done_steps"] >= cfg.regen_min_steps
         n_long += int((done & lng).sum()); n_short += int((done & ~lng).sum())
-        _eq(g.t["done_steps"].cpu().numpy()[done], r.a["done_steps"][done], "episode lengths at step %d" % t)
+        eq(g.t["done_steps"].cpu().numpy()[done], r.a["done_steps"][done], "episode lengths at step %d" % t)
         go2 = g.regen().cpu().numpy()
         ro2 = r.regen()
-        _eq(go2, ro2, "obs after the swap at step %d" % t)
+        eq(go2, ro2, "obs after the swap at step %d" % t)
         if done.any():
             gpu.torch.cuda.synchronize()
-            gs = g.numpy_state()
-            for k, v in r.a.items():
-                if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index", "ped_waypoints", "counters"):
-                    _eq(gs[k], v, "state %s after the swap at step %d" % (k, t))
+            state_equal(g, r, "after the swap at step %d" % t, skip=("ped_waypoints", "counters"))
         if min_steps < 4 * period and E >= 8 and t in (30, 31, 60, 61):
             # two episode ends one step apart (the robot put on its goal twice): the second finds nothing staged
             idx = gpu.torch.arange(2, 8, device=gpu.dev)
@@ -758,10 +674,7 @@ def test_more_late_arenas_than_the_fallback_cap_are_counted(gpu):
                                  regen_plan=0, regen_indoor_ratio=0.0, regen_min_steps=0)
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 29)
-    arrays = gpu.world.make_world(cfg, occ, n_peds=5, device=gpu.dev)
-    from nav_gym_amd import robots
-    arrays["scan_threshold"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "threshold_footprint")))
-    arrays["scan_discomfort"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "discomfort_threshold_footprint")))
+    arrays = device_world(gpu, cfg, occ, 5)
     g = gpu.sim.NavSim(cfg, arrays)
     g.reset_obs()
     g.enable_pregen(pipeline=2, install=True, fallback_cap=4)
@@ -894,25 +807,25 @@ def test_env_reset_at_the_reference_map_size(gpu):
     for e in (0, 5, 11):
         c1 = cfg.copy(); c1.n_envs = 1; c1.env_index_base = int(e); c1.regen_cap = 1
         host = {k: v.cpu().numpy() for k, v in gpu.world.empty_world(c1, device="cpu", plan_paths=True).items()
-                if k not in ("field", "field_overflow", "rect_table", "rect_index")}
+                if k not in NOT_STATE}
         host["field"] = np.zeros((1, size, size), np.float32)
         host["scan_threshold"] = env.scan_threshold.cpu().numpy(); host["scan_discomfort"] = env.scan_discomfort_threshold.cpu().numpy()
         r = ref.RefSim(c1, host)
         r.out["done"][:] = 1
-        _eq(o[e:e + 1], r.regen(), "first observation of arena %d" % e)
-        _eq(ovf[e], r.a["field"][0], "float plane of arena %d" % e)
+        eq(o[e:e + 1], r.regen(), "first observation of arena %d" % e)
+        eq(ovf[e], r.a["field"][0], "float plane of arena %d" % e)
         refs.append((e, r))
-    d2, valid = _decode_rect_table(env.sim.t["rect_table"].cpu().numpy()[:2], size, size)
+    d2, valid = decode_rect_table(env.sim.t["rect_table"].cpu().numpy()[:2], size, size)
     assert np.array_equal(d2[valid], np.rint(ovf[:2].astype(np.float64) ** 2).astype(np.int64)[valid]) and valid.mean() > 0.9
     rng = np.random.default_rng(3)
     for t in range(6):
-        act = np.stack([rng.uniform(0, 0.5, E), rng.uniform(-0.64, 0.64, E)], axis=1)
+        act = random_actions(rng, E)
         obs, _, _, _ = env.step(act)
         og = obs["observation"].cpu().numpy()
         for e, r in refs:
             ro, _ = r.step(act[e:e + 1])
             r.replan(1024)
-            _eq(og[e:e + 1], ro, "arena %d obs at step %d" % (e, t))
+            eq(og[e:e + 1], ro, "arena %d obs at step %d" % (e, t))
 
 
 @pytest.mark.parametrize("pipeline", [0, 2, "graphs", "norule"])
@@ -959,13 +872,13 @@ def test_reference_default_configuration_sampled_oracle(gpu, pipeline):
     for e in sample:
         c1 = cfg.copy(); c1.n_envs = 1; c1.env_index_base = int(e); c1.regen_cap = 1
         host = {k: v.cpu().numpy() for k, v in gpu.world.empty_world(c1, device="cpu", plan_paths=True).items()
-                if k not in ("field", "field_overflow", "rect_table", "rect_index")}
+                if k not in NOT_STATE}
         host["field"] = np.zeros((1, 1000, 1000), np.float32)
         host["scan_threshold"] = env.scan_threshold.cpu().numpy(); host["scan_discomfort"] = env.scan_discomfort_threshold.cpu().numpy()
         r = ref.RefSim(c1, host)
         r.out["done"][:] = 1
         r.a["done_steps"][:] = 1 << 20                       # reset(): whatever cfg.regen_min_steps says about short episodes
-        _eq(o0[e:e + 1], r.regen(), "first observation of arena %d" % e)
+        eq(o0[e:e + 1], r.regen(), "first observation of arena %d" % e)
         if e in (1, 100):
             r.a["robot_goal"][0] = r.a["robot_pose"][0, :2]
             r.a["steps"][0] = 30
@@ -975,7 +888,7 @@ def test_reference_default_configuration_sampled_oracle(gpu, pipeline):
     rng = np.random.default_rng(3)
     regenerated = 0
     for t in range(10):
-        act = np.stack([rng.uniform(0, 0.5, E), rng.uniform(-0.64, 0.64, E)], axis=1)
+        act = random_actions(rng, E)
         obs, rew, done, info = env.step(torch.from_numpy(act).to(gpu.dev))
         og = obs["observation"].cpu().numpy()
         dn = done.cpu().numpy()
@@ -985,10 +898,10 @@ def test_reference_default_configuration_sampled_oracle(gpu, pipeline):
             if t > 0:
                 r.replan(1024)                              # the device plans the previous step's arrivals beside this step
             ro, rout = r.step(act[e:e + 1])
-            _eq(dn[e:e + 1].astype(np.uint8), rout["done"], "arena %d done at step %d" % (e, t))
-            _eq(rew[e:e + 1].cpu().numpy(), rout["reward"], "arena %d reward at step %d" % (e, t))
+            eq(dn[e:e + 1].astype(np.uint8), rout["done"], "arena %d done at step %d" % (e, t))
+            eq(rew[e:e + 1].cpu().numpy(), rout["reward"], "arena %d reward at step %d" % (e, t))
             regenerated += int(rout["done"][0])
-            _eq(og[e:e + 1], r.regen(), "arena %d obs at step %d" % (e, t))
+            eq(og[e:e + 1], r.regen(), "arena %d obs at step %d" % (e, t))
     assert regenerated >= 2, "no sampled arena went through navsim_regen"
     c = env.counters()
     assert c["regen_served"] >= regenerated and c["regen_unserved"] == 0 and (c["regen_late"] == 0 or norule)
@@ -1021,28 +934,21 @@ def test_reset_path_fuzzed(gpu, seed):
     with_costmap = bool(plan) and ped_model != abi.PED_NONE
     cfg.defer_reset_scan = int(seed % 3 == 0)          # (drawn from the seed, not from rng: the worlds of the old seeds stay)
     regenerated = 0
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=N - 1, steps=22, seed=seed,
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=N - 1, steps=22, seed=seed,
                                                      min_goal_dist=2.0, max_goal_dist=5.0, robot_clearance=0.6,
                                                      plan_paths=with_costmap):
         if cfg.defer_reset_scan:                       # the scan rows of finished arenas are navsim_regen's to write
             live = rout["done"] == 0
-            _eq(go[live], ro[live], "obs of the unfinished arenas at step %d" % t)
+            eq(go[live], ro[live], "obs of the unfinished arenas at step %d" % t)
         else:
-            _eq(go, ro, "obs at step %d" % t)
+            eq(go, ro, "obs at step %d" % t)
         regenerated += int(rout["done"].sum())
-        _eq(g.regen().cpu().numpy(), r.regen(), "obs after regen at step %d" % t)
+        eq(g.regen().cpu().numpy(), r.regen(), "obs after regen at step %d" % t)
         if with_costmap:
             g.replan(4); r.replan(4)
-    gs = g.numpy_state()
-    for k, v in r.a.items():
-        if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index"):
-            if k == "ped_waypoints":
-                live = np.arange(cfg.max_waypoints)[None, None, :] < r.a["ped_n_waypoints"][..., None]
-                _eq(gs[k][live], v[live], "state %s" % k)
-            else:
-                _eq(gs[k], v, "state %s" % k)
+    gs = state_equal(g, r, "at the end", live_waypoints_only=True)
     if fmt == abi.FIELD_F32:
-        _eq(gs["field"], r.a["field"], "field")
+        eq(gs["field"], r.a["field"], "field")
     assert regenerated > 0 or seed > 212           # (the suite's twelve worlds all finish episodes; a wider sweep may draw one that does not)
 
 
@@ -1058,15 +964,12 @@ def test_regen_odd_map_size(gpu, fmt):
     gpu.world.lidar_full_circle(cfg, 90)
     occ = gpu.world.make_maps(E, size, 29)
     regenerated = 0
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=3, steps=30, seed=3):
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=3, steps=30, seed=3):
         regenerated += min(int(rout["done"].sum()), 4)
-        _eq(g.regen().cpu().numpy(), r.regen(), "obs after regen at step %d" % t)
-    gs = g.numpy_state()
-    for k, v in r.a.items():
-        if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index"):
-            _eq(gs[k], v, "state %s" % k)
+        eq(g.regen().cpu().numpy(), r.regen(), "obs after regen at step %d" % t)
+    gs = state_equal(g, r, "at the end")
     if fmt == abi.FIELD_F32:
-        _eq(gs["field"], r.a["field"], "field")
+        eq(gs["field"], r.a["field"], "field")
     assert regenerated >= 2
 
 
@@ -1082,25 +985,25 @@ def test_replan_vs_oracle(gpu, fmt):
     occ = gpu.world.make_maps(E, size, 23, n_obstacles=6)
     replans = 0
     prev_n = None
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=5, steps=120, seed=4, plan_paths=True,
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=5, steps=120, seed=4, plan_paths=True,
                                                      v_pref_range=(0.5, 0.6)):
-        _eq(go, ro, "obs at step %d" % t)
+        eq(go, ro, "obs at step %d" % t)
         if prev_n is None:
             assert (r.a["ped_n_waypoints"] > 1).any(), "no pedestrian started with a planned path"
         cap = 2 if t % 2 else 64
-        _eq(g.numpy_state("ped_due")["ped_due"], r.a["ped_due"], "who waits for a re-plan after step %d" % t)
+        eq(g.numpy_state("ped_due")["ped_due"], r.a["ped_due"], "who waits for a re-plan after step %d" % t)
         # the candidates: the step's own flags (ABI 5) / the call's pass over the state, alternating -- the same set
         g.replan(cap, flags=(t % 4 < 2)); r.replan(cap)
         gs = g.numpy_state("ped_waypoints", "ped_n_waypoints", "ped_wp_head", "costmap")
         n_now, head_now = r.a["ped_n_waypoints"].copy(), r.a["ped_wp_head"].copy()
-        _eq(gs["ped_n_waypoints"], n_now, "waypoint counts at step %d" % t)
-        _eq(gs["ped_wp_head"], head_now, "current waypoints at step %d" % t)
+        eq(gs["ped_n_waypoints"], n_now, "waypoint counts at step %d" % t)
+        eq(gs["ped_wp_head"], head_now, "current waypoints at step %d" % t)
         live = np.arange(cfg.max_waypoints)[None, None, :] < n_now[..., None]
-        _eq(gs["ped_waypoints"][live], r.a["ped_waypoints"][live], "waypoints at step %d" % t)
+        eq(gs["ped_waypoints"][live], r.a["ped_waypoints"][live], "waypoints at step %d" % t)
         if prev_n is not None:                  # a new route starts at its first waypoint
             replans += int(((head_now < prev_n[1]) | (n_now != prev_n[0])).sum())
         prev_n = (n_now, head_now)
-    _eq(gs["costmap"], r.a["costmap"], "costmap")
+    eq(gs["costmap"], r.a["costmap"], "costmap")
     assert replans >= 5, replans
 
 
@@ -1120,16 +1023,12 @@ def test_replan_beside_the_step_equals_the_serial_sequence(gpu, mode, graphs, E)
     gpu.world.lidar_full_circle(cfg, 180)
     occ = gpu.world.make_maps(E, size, 29, n_obstacles=6)
     torch = gpu.torch
-    from nav_gym_amd import robots
-    arrays = gpu.world.make_world(cfg, occ, n_peds=5, device=gpu.dev, plan_paths=True, v_pref_range=(0.5, 0.6))
-    arrays["scan_threshold"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "threshold_footprint")))
-    arrays["scan_discomfort"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "discomfort_threshold_footprint")))
-    host = {k: v.cpu().numpy() for k, v in arrays.items() if k not in ("field", "field_overflow", "rect_table", "rect_index")}
-    host["field"] = ref.build_dt(occ)
+    arrays = device_world(gpu, cfg, occ, 5, plan_paths=True, v_pref_range=(0.5, 0.6))
+    host = host_arrays(arrays, occ)
     g = gpu.sim.NavSim(cfg, arrays)
     g.replan_in_step = mode == "in_step"
     r = ref.RefSim(cfg, host)
-    _eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
+    eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
     if graphs:
         g.enable_graphs(regen=False, replan_cap=cap, overlap=True)
     rng = np.random.default_rng(3)
@@ -1145,13 +1044,13 @@ def test_replan_beside_the_step_equals_the_serial_sequence(gpu, mode, graphs, E)
             go, gout = g.step_graphed(torch.from_numpy(act).to(gpu.dev))
         else:
             go, gout = g.step_overlapped(torch.from_numpy(act).to(gpu.dev), cap)
-        _eq(go.cpu().numpy(), ro, "obs at step %d" % t)
+        eq(go.cpu().numpy(), ro, "obs at step %d" % t)
         for k in rout:
-            _eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
+            eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
         assert int(g.t["steps"].min()) == t + 1 == int(g.t["steps"].max()), "an arena was stepped twice or not at all"
         if t % 10 == 9:
-            _state_equal(g, r, cfg, "at step %d" % t)
-    _state_equal(g, r, cfg, "at the end")
+            state_equal(g, r, "at step %d" % t, live_waypoints_only=True)
+    state_equal(g, r, "at the end", live_waypoints_only=True)
     assert waited >= 5 and split >= 5, (waited, split)
     assert g.counters() == r.counters() and r.counters()["replan_served"] >= 5
     if E >= 100:
@@ -1174,15 +1073,11 @@ def test_pipelined_reset_with_the_replan_inside_the_step(gpu, monkeypatch, E, sl
     gpu.world.lidar_full_circle(cfg, 180)
     occ = gpu.world.make_maps(E, size, 31, n_obstacles=6)
     torch = gpu.torch
-    from nav_gym_amd import robots
-    arrays = gpu.world.make_world(cfg, occ, n_peds=5, device=gpu.dev, plan_paths=True, v_pref_range=(0.5, 0.6))
-    arrays["scan_threshold"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "threshold_footprint")))
-    arrays["scan_discomfort"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "discomfort_threshold_footprint")))
-    host = {k: v.cpu().numpy() for k, v in arrays.items() if k not in ("field", "field_overflow", "rect_table", "rect_index")}
-    host["field"] = ref.build_dt(occ)
+    arrays = device_world(gpu, cfg, occ, 5, plan_paths=True, v_pref_range=(0.5, 0.6))
+    host = host_arrays(arrays, occ)
     g = gpu.sim.NavSim(cfg, arrays)
     r = ref.RefSim(cfg, host)
-    _eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
+    eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
     g.enable_pregen(pipeline=2, install=True)
     assert g.late is not None
     g.pg_replan_cap = cap
@@ -1196,9 +1091,7 @@ def test_pipelined_reset_with_the_replan_inside_the_step(gpu, monkeypatch, E, sl
     rng = np.random.default_rng(5)
     ended = waited = 0
     for t in range(90 if E < 100 else 40):
-        act = np.stack([rng.uniform(0.0, 0.5, E), rng.uniform(-0.64, 0.64, E)], axis=1)
-        if t % 7 == 3:
-            act[:, 0] = 0.5; act[:, 1] = 0.0            # bursts of straight driving: crashes, episode ends
+        act = random_actions(rng, E, t)                   # bursts of straight driving: crashes, episode ends
         waited += int((r.a["ped_due"] != 0).sum())
         if t > 0:
             r.replan(cap)
@@ -1206,9 +1099,9 @@ def test_pipelined_reset_with_the_replan_inside_the_step(gpu, monkeypatch, E, sl
         ro2 = r.regen()
         go, gout = g.step(torch.from_numpy(act).to(gpu.dev))
         go2 = g.regen().cpu().numpy()
-        _eq(go2, ro2, "obs after step + regen at step %d" % t)
+        eq(go2, ro2, "obs after step + regen at step %d" % t)
         for k in rout:                                   # (the goal arrays are the new worlds' on both sides by now)
-            _eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
+            eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
         ended += int(rout["done"].sum())
         if slow and t in (30, 31, 50, 51):              # two episode ends one step apart: the second finds nothing staged
             idx = torch.arange(2, 8, device=gpu.dev)
@@ -1216,10 +1109,7 @@ def test_pipelined_reset_with_the_replan_inside_the_step(gpu, monkeypatch, E, sl
             r.a["robot_goal"][2:8] = r.a["robot_pose"][2:8, :2]
         if t % 10 == 9:
             gpu.torch.cuda.synchronize()
-            gs = g.numpy_state()
-            for k, v in r.a.items():
-                if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index", "ped_waypoints", "counters"):
-                    _eq(gs[k], v, "state %s at step %d" % (k, t))
+            state_equal(g, r, "at step %d" % t, skip=("ped_waypoints", "counters"))
     assert g.pg_replan_in_step, "the search did not fit the arena's workgroup: the launch fell back"
     assert ended > 8 and waited >= 5, (ended, waited)
     cg, cr = g.counters(), r.counters()
@@ -1241,32 +1131,20 @@ def test_long_routes_on_the_device(gpu, golden_dir):
     mi = np.zeros(n, np.int32)
     full = None
     for cap in (gpu.lib.default_config().max_waypoints, 8):
-        gw, gn, gc, gl = gpu.sim.plan(_t(gpu, cost), _t(gpu, d["route_start"]), _t(gpu, d["route_goal"]), 2.0, max_wp=cap,
-                                      res_c=res_c, map_index=_t(gpu, mi))
+        gw, gn, gc, gl = gpu.sim.plan(to_device(gpu, cost), to_device(gpu, d["route_start"]), to_device(gpu, d["route_goal"]), 2.0, max_wp=cap,
+                                      res_c=res_c, map_index=to_device(gpu, mi))
         rw, rn, rcells, rl = ref.plan(cost, d["route_start"], d["route_goal"], 2.0, max_wp=cap, res_c=res_c, map_index=mi)
-        _eq(gn.cpu().numpy(), rn, "waypoint counts (capacity %d)" % cap)
-        _eq(gc.cpu().numpy(), rcells, "path cells"); _eq(gc.cpu().numpy(), d["route_cells"].astype(np.int32), "path cells vs the reference's")
-        _eq(gl.cpu().numpy(), rl, "path_distance")
+        eq(gn.cpu().numpy(), rn, "waypoint counts (capacity %d)" % cap)
+        eq(gc.cpu().numpy(), rcells, "path cells"); eq(gc.cpu().numpy(), d["route_cells"].astype(np.int32), "path cells vs the reference's")
+        eq(gl.cpu().numpy(), rl, "path_distance")
         live = np.arange(cap)[None, :] < rn[:, None]
-        _eq(gw.cpu().numpy()[live], rw[live], "waypoints (capacity %d)" % cap)
+        eq(gw.cpu().numpy()[live], rw[live], "waypoints (capacity %d)" % cap)
         if full is None:
             full = (rw, rn, rl)
             assert rn.max() > 16 and rn.max() < cap
         else:
             assert (rn == np.minimum(full[1], cap)).all() and np.array_equal(rl, full[2])
             assert np.array_equal(rw[live], full[0][:, :cap][live])
-
-
-def _state_equal(g, r, cfg, what, skip=()):
-    gs = g.numpy_state()
-    for k, v in r.a.items():
-        if k not in gs or k in ("field", "field_overflow", "rect_table", "rect_index") or k in skip:
-            continue
-        if k == "ped_waypoints":                  # slots beyond n_waypoints keep whatever the buffer held before
-            live = np.arange(cfg.max_waypoints)[None, None, :] < r.a["ped_n_waypoints"][..., None]
-            _eq(gs[k][live], v[live], "state %s %s" % (k, what))
-        else:
-            _eq(gs[k], v, "state %s %s" % (k, what))
 
 
 def test_cut_routes_resume_to_their_goal(gpu):
@@ -1282,9 +1160,9 @@ def test_cut_routes_resume_to_their_goal(gpu):
     occ = gpu.world.make_maps(E, size, 37, n_obstacles=6)
     goal0 = None
     kept = 0
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=5, steps=110, seed=4, plan_paths=True,
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=5, steps=110, seed=4, plan_paths=True,
                                                      v_pref_range=(0.55, 0.6)):
-        _eq(go, ro, "obs at step %d" % t)
+        eq(go, ro, "obs at step %d" % t)
         if goal0 is None:
             goal0 = r.a["ped_goal"].copy()
             last = r.a["ped_waypoints"][np.arange(E)[:, None], np.arange(N)[None, :], r.a["ped_n_waypoints"] - 1]
@@ -1295,8 +1173,8 @@ def test_cut_routes_resume_to_their_goal(gpu):
         if r.counters()["routes_resumed"] > before:          # a resumed route keeps its goal
             kept += 1
         if t % 10 == 9:
-            _state_equal(g, r, cfg, "at step %d" % t)
-    _state_equal(g, r, cfg, "at the end")
+            state_equal(g, r, "at step %d" % t, live_waypoints_only=True)
+    state_equal(g, r, "at the end", live_waypoints_only=True)
     c = r.counters()
     assert g.counters() == c
     # (the first routes of this world were cut by the host-side navsim_plan calls of make_world, which count nothing:
@@ -1312,8 +1190,6 @@ def test_restart_noise_does_not_depend_on_who_scans(gpu):
     (noise key of the old episode's step) or, with cfg.defer_reset_scan, by navsim_regen's masked launch (the new
     episode's reset key) -- the same arena saw different noise depending on the batch size that picks the mode.  Both
     paths draw from the reset key now: with scan noise ON, the observations after step + regen are identical."""
-    from helpers import finished_world
-    from nav_gym_amd import robots
     E, size, N = 24, 200, 4
     cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, max_peds=N, ped_model=abi.PED_SFM, n_spawn=4,
                                  auto_reset=1, seed=5, field_format=abi.FIELD_F32, regen_cap=5, min_goal_dist=3.0,
@@ -1321,9 +1197,7 @@ def test_restart_noise_does_not_depend_on_who_scans(gpu):
                                  add_scan_noise=1)
     gpu.world.lidar_full_circle(cfg, 90)
     occ = gpu.world.make_maps(E, size, 5)
-    thr = ref.scan_threshold(cfg, robots.footprint_array("keti", "threshold_footprint"))
-    dthr = ref.scan_threshold(cfg, robots.footprint_array("keti", "discomfort_threshold_footprint"))
-    host = finished_world(cfg, occ, ref.build_dt(occ), 3, (thr, dthr))       # every robot already stands on its goal
+    host = finished_world(cfg, occ, ref.build_dt(occ), 3, keti_thresholds(cfg))      # every robot already stands on its goal
     host["scan_noise_std"][:] = 0.03
     # spread the in-place restarts over free cells (finished_world's table holds the finish pose only)
     for e in range(E):
@@ -1335,11 +1209,11 @@ def test_restart_noise_does_not_depend_on_who_scans(gpu):
         c = cfg.copy(); c.defer_reset_scan = defer
         g = gpu.sim.NavSim(c, {k: v.copy() for k, v in host.items()})
         g.reset_obs()
-        _, out = g.step(_t(gpu, np.zeros((E, 2))))
+        _, out = g.step(to_device(gpu, np.zeros((E, 2))))
         assert bool(out["done"].all())
         obs.append(g.regen().cpu().numpy().copy())
         assert g.counters()["regen_unserved"] == E - 5
-    _eq(obs[0], obs[1], "observations after step + regen, scan noise on, step-scanned vs regen-scanned restarts")
+    eq(obs[0], obs[1], "observations after step + regen, scan noise on, step-scanned vs regen-scanned restarts")
     assert len(np.unique(obs[0][5:, :90])) > 100             # the rows of the in-place restarts carry noise
 
 
@@ -1347,26 +1221,22 @@ def test_caps_are_counted(gpu):
     """Round-3 verdict: arenas beyond cfg.regen_cap "play on in place" and pedestrians beyond navsim_replan's
     max_queries wait -- silently.  navsim_state.counters makes both observable: device == oracle, and the numbers are
     the ones the done flags / the waiting pedestrians imply."""
-    from helpers import finished_world
-    from nav_gym_amd import robots
     E, size, N = 24, 200, 4
     cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, max_peds=N, ped_model=abi.PED_SFM, n_spawn=4,
                                  auto_reset=1, seed=5, field_format=abi.FIELD_F32, regen_cap=5, min_goal_dist=3.0,
                                  max_goal_dist=8.0, spawn_clearance=0.8, ped_min_robot_dist=1.5, ped_min_goal_dist=3.0)
     gpu.world.lidar_full_circle(cfg, 90)
     occ = gpu.world.make_maps(E, size, 5)
-    thr = ref.scan_threshold(cfg, robots.footprint_array("keti", "threshold_footprint"))
-    dthr = ref.scan_threshold(cfg, robots.footprint_array("keti", "discomfort_threshold_footprint"))
-    host = finished_world(cfg, occ, ref.build_dt(occ), 3, (thr, dthr))       # every robot already stands on its goal
+    host = finished_world(cfg, occ, ref.build_dt(occ), 3, keti_thresholds(cfg))      # every robot already stands on its goal
     host["costmap"] = ref.costmap(occ)
     host["ped_goal"] = np.zeros((E, N, 2))
     r = ref.RefSim(cfg, host)
     g = gpu.sim.NavSim(cfg, {k: v for k, v in host.items()})
-    _eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
+    eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
     act = np.zeros((E, 2))
-    go, gout = g.step(_t(gpu, act)); ro, rout = r.step(act)
+    go, gout = g.step(to_device(gpu, act)); ro, rout = r.step(act)
     assert rout["done"].all()
-    _eq(g.regen().cpu().numpy(), r.regen(), "obs after regen")
+    eq(g.regen().cpu().numpy(), r.regen(), "obs after regen")
     c = r.counters()
     assert g.counters() == c
     assert c["regen_served"] == 5 and c["regen_unserved"] == E - 5, c
@@ -1386,7 +1256,7 @@ def test_caps_are_counted(gpu):
     c2 = r.counters()
     assert g.counters() == c2
     assert c2["replan_served"] == 2 and c2["replan_unserved"] == due + (due - 2), c2
-    _state_equal(g, r, cfg, "after the capped calls")
+    state_equal(g, r, "after the capped calls", live_waypoints_only=True)
 
 
 @pytest.mark.parametrize("clamp", [0, 1])
@@ -1395,7 +1265,6 @@ def test_wheel_speed_actions(gpu, clamp):
     skid-steer base's left / right wheel pairs, converted on the device with the Husky's wheel radius and track
     (husky.urdf.xacro:61-67), optionally clamped to linvel_range x rotvel_range.  Device == oracle bit for bit, and
     the rollout equals the one driven by the converted (and clipped) twists."""
-    from nav_gym_amd import robots
     E, size = 24, 200
     kw = dict(n_envs=E, map_h=size, map_w=size, max_peds=4, ped_model=abi.PED_SFM, n_spawn=6, auto_reset=1, seed=19,
               field_format=abi.FIELD_U16T, axle_offset=0.0, clamp_action=clamp, linvel_lo=0.0, linvel_hi=1.0,
@@ -1406,13 +1275,10 @@ def test_wheel_speed_actions(gpu, clamp):
     for cfg in (cfg_w, cfg_t):
         gpu.world.lidar_full_circle(cfg, 128)
     occ = gpu.world.make_maps(E, size, 19)
-    arrays = gpu.world.make_world(cfg_w, occ, n_peds=3, device=gpu.dev)
-    arrays["scan_threshold"] = gpu.sim.scan_threshold(cfg_w, _t(gpu, robots.footprint_array("husky", "threshold_footprint")))
-    arrays["scan_discomfort"] = gpu.sim.scan_threshold(cfg_w, _t(gpu, robots.footprint_array("husky", "discomfort_threshold_footprint")))
-    host = {k: v.cpu().numpy() for k, v in arrays.items() if k not in ("field", "field_overflow", "rect_table", "rect_index")}
-    host["field"] = ref.build_dt(occ)
+    arrays = device_world(gpu, cfg_w, occ, 3, robot="husky")
+    host = host_arrays(arrays, occ)
     gw, gt, r = gpu.sim.NavSim(cfg_w, arrays), gpu.sim.NavSim(cfg_t, arrays), ref.RefSim(cfg_w, host)
-    _eq(gw.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs"); gt.reset_obs()
+    eq(gw.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs"); gt.reset_obs()
     rng = np.random.default_rng(2)
     clipped = 0
     for t in range(25):
@@ -1421,15 +1287,15 @@ def test_wheel_speed_actions(gpu, clamp):
         if clamp:
             clipped += int((twist[:, 0] > 1.0).sum() + (twist[:, 0] < 0.0).sum() + (np.abs(twist[:, 1]) > 2.0).sum())
             twist = np.stack([np.clip(twist[:, 0], 0.0, 1.0), np.clip(twist[:, 1], -2.0, 2.0)], axis=1)
-        go, gout = gw.step(_t(gpu, wheels)); ro, rout = r.step(wheels)
+        go, gout = gw.step(to_device(gpu, wheels)); ro, rout = r.step(wheels)
         go = go.cpu().numpy().copy()
-        _eq(go, ro, "obs at step %d" % t)
+        eq(go, ro, "obs at step %d" % t)
         for k in rout:
-            _eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
-        go2, gout2 = gt.step(_t(gpu, twist))
-        _eq(go2.cpu().numpy(), go, "twist-driven obs at step %d" % t)
-    _state_equal(gw, r, cfg_w, "wheel-driven")
-    _eq(gw.numpy_state("prev_action")["prev_action"], gt.numpy_state("prev_action")["prev_action"], "prev_action holds the twist")
+            eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
+        go2, gout2 = gt.step(to_device(gpu, twist))
+        eq(go2.cpu().numpy(), go, "twist-driven obs at step %d" % t)
+    state_equal(gw, r, "wheel-driven", live_waypoints_only=True)
+    eq(gw.numpy_state("prev_action")["prev_action"], gt.numpy_state("prev_action")["prev_action"], "prev_action holds the twist")
     assert not clamp or clipped > 20
 
 
@@ -1457,16 +1323,13 @@ def test_policy_closed_loop_vs_oracle(gpu, fmt):
     occ = gpu.world.make_maps(E, size, 41)
     w = _policy_weights_random(7)
     first = True
-    rollout = _rollout_pair(gpu, cfg, occ, n_peds=17, steps=8, seed=9, policy=w)
+    rollout = rollout_pair(gpu, cfg, occ, n_peds=17, steps=8, seed=9, policy=w)
     for t, go, gout, ro, rout, g, r in rollout:
-        _eq(go, ro, "obs at step %d" % t)
-        _eq(g.t["policy_prev_actions"].cpu().numpy(), r.prev_actions, "network output at step %d" % t)
-        _eq(g.t["ped_cmd"].cpu().numpy(), r.a["ped_cmd"], "pedestrian commands at step %d" % t)
+        eq(go, ro, "obs at step %d" % t)
+        eq(g.t["policy_prev_actions"].cpu().numpy(), r.prev_actions, "network output at step %d" % t)
+        eq(g.t["ped_cmd"].cpu().numpy(), r.a["ped_cmd"], "pedestrian commands at step %d" % t)
         if t % 4 == 3:
-            gs = g.numpy_state()
-            for k, v in r.a.items():
-                if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index"):
-                    _eq(gs[k], v, "state %s at step %d" % (k, t))
+            state_equal(g, r, "at step %d" % t)
     m = r.prev_actions[:, :17]
     assert (m[..., 0] > 0).all() and (m[..., 0] < 1).all() and np.abs(m[..., 1]).max() < 1 and m.std() > 1e-3
 
@@ -1481,10 +1344,7 @@ def test_policy_large_batch_is_chunk_invariant(gpu):
                                   auto_reset=1, seed=3, field_format=abi.FIELD_F32)
     gpu.world.lidar_full_circle(cfg0, 64)
     occ = gpu.world.make_maps(E0, size, 3)
-    base = gpu.world.make_world(cfg0, occ, n_peds=18, device=gpu.dev, min_goal_dist=2.0, max_goal_dist=4.0, robot_clearance=0.6)
-    from nav_gym_amd import robots
-    for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
-        base[key] = gpu.sim.scan_threshold(cfg0, _t(gpu, robots.footprint_array("keti", name)))
+    base = device_world(gpu, cfg0, occ, 18, min_goal_dist=2.0, max_goal_dist=4.0, robot_clearance=0.6)
     rng = np.random.default_rng(1)
     scans0 = rng.uniform(0.0, 7.0, (E0, N, 512)).astype(np.float32)
     w = _policy_weights_random(11)
@@ -1496,10 +1356,10 @@ def test_policy_large_batch_is_chunk_invariant(gpu):
     big = {k: (v if k in shared else v.repeat((rep,) + (1,) * (v.dim() - 1))) for k, v in base.items()}
     g = gpu.sim.NavSim(cfg, big)
     g.set_policy(w)
-    cmd, mean = g.ped_policy(_t(gpu, scans0).repeat(rep, 1, 1))
+    cmd, mean = g.ped_policy(to_device(gpu, scans0).repeat(rep, 1, 1))
     cmd = cmd.cpu().numpy().reshape(rep, E0, N, 2); mean = mean.cpu().numpy().reshape(rep, E0, N, 2)
-    _eq(cmd[0], rc, "commands of the first copy vs oracle")
-    _eq(mean[0], rm, "network output of the first copy vs oracle")
+    eq(cmd[0], rc, "commands of the first copy vs oracle")
+    eq(mean[0], rm, "network output of the first copy vs oracle")
     assert (cmd == cmd[:1]).all() and (mean == mean[:1]).all()
     assert np.abs(mean[0, :, :18]).max() > 0
 
@@ -1516,10 +1376,7 @@ def test_fused_scan_policy_equals_the_two_calls(gpu, fmt, rects):
                                  auto_reset=1, seed=23, field_format=fmt)
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 23)
-    arrays = gpu.world.make_world(cfg, occ, n_peds=17, device=gpu.dev, rect_table=rects)
-    from nav_gym_amd import robots
-    for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
-        arrays[key] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", name)))
+    arrays = device_world(gpu, cfg, occ, 17, rect_table=rects)
     arrays["n_peds"][::3] = 9
     arrays["n_peds"][1] = 0
     g = gpu.sim.NavSim(cfg, arrays)
@@ -1547,7 +1404,7 @@ def test_policy_vs_reference_trace(gpu, name):
     recorded with, the device reproduces the (v, omega) the reference handed to Human.set_vel (1e-5)."""
     from helpers import policy_weights
     tr = load_trace(name)
-    cfg, arrays, occ = trace_setup(tr, gpu.lib.default_config, lambda o: gpu.sim.build_dt(_t(gpu, o)).cpu().numpy())
+    cfg, arrays, occ = trace_setup(tr, gpu.lib.default_config, lambda o: gpu.sim.build_dt(to_device(gpu, o)).cpu().numpy())
     N = tr["init_ped_pose"].shape[0]
     wp = np.zeros((1, N, cfg.max_waypoints, 2)); wp[0, :, :tr["init_ped_waypoints"].shape[1]] = tr["init_ped_waypoints"]
     arrays["ped_waypoints"] = wp
@@ -1558,14 +1415,14 @@ def test_policy_vs_reference_trace(gpu, name):
     worst, checked = 0.0, 0
     for t in range(10):                                   # no crash and no re-plan in the first steps of these traces
         if t > 0:
-            g.t["policy_prev_actions"][0] = _t(gpu, tr["ped_mean"][t - 1])
+            g.t["policy_prev_actions"][0] = to_device(gpu, tr["ped_mean"][t - 1])
         cmd, mean = g.ped_policy()
         ok = np.ones(N, bool) if name == "random_S1" or t == 0 else np.arange(N) > 0   # peds_S1: pedestrian 0 re-plans
         worst = max(worst, np.abs(cmd[0].cpu().numpy()[ok] - tr["ped_cmd"][t][ok]).max(),
                     np.abs(mean[0].cpu().numpy()[ok] - tr["ped_mean"][t][ok]).max())
         checked += int(ok.sum())
-        g.set_ped_cmd(_t(gpu, tr["ped_cmd"][t][None]))
-        g.step(_t(gpu, tr["actions"][t][None]))
+        g.set_ped_cmd(to_device(gpu, tr["ped_cmd"][t][None]))
+        g.step(to_device(gpu, tr["actions"][t][None]))
     assert checked > 50 and worst < 1e-5, (checked, worst)
 
 
@@ -1593,16 +1450,13 @@ def test_launch_order_is_result_neutral(gpu):
                                  auto_reset=1, seed=5, field_format=abi.FIELD_U16T)
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 5)
-    arrays = gpu.world.make_world(cfg, occ, n_peds=5, device=gpu.dev)
-    from nav_gym_amd import robots
-    for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
-        arrays[key] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", name)))
+    arrays = device_world(gpu, cfg, occ, 5)
     plain = gpu.sim.NavSim(cfg, arrays, launch_order=False)
     lpt = gpu.sim.NavSim(cfg, arrays, launch_order=True)   # a 64-arena launch is one generation: off by default
     lpt.lpt_period = 3
     lpt.t["launch_order"].copy_(torch.arange(E - 1, -1, -1, dtype=torch.int32, device=gpu.dev))
     assert "launch_order" not in plain.t
-    _eq(plain.reset_obs().cpu().numpy(), lpt.reset_obs().cpu().numpy(), "reset obs")
+    eq(plain.reset_obs().cpu().numpy(), lpt.reset_obs().cpu().numpy(), "reset obs")
     g = torch.Generator(device=gpu.dev); g.manual_seed(2)
     for t in range(10):
         act = torch.rand((E, 2), generator=g, device=gpu.dev, dtype=torch.float64)
@@ -1614,7 +1468,7 @@ def test_launch_order_is_result_neutral(gpu):
             assert torch.equal(out1[k], out2[k]), (k, t)
     s1, s2 = plain.numpy_state(), lpt.numpy_state()
     for k in s1:
-        _eq(s1[k], s2[k], "state %s" % k)
+        eq(s1[k], s2[k], "state %s" % k)
     assert (lpt.t["arena_cost"] > 0).all()
     assert not np.array_equal(lpt.t["launch_order"].cpu().numpy(), np.arange(E - 1, -1, -1))      # re-sorted by now
 
@@ -1623,15 +1477,14 @@ def test_crowd_check_vs_reference_and_oracle(gpu):
     """CrowdSim-v0's collision / goal / reward block (crowd_sim.py:808-949) on the device:
     equal to the oracle bit for bit, and to the reference's own CrowdSim.step on the 600 golden situations;
     plus a larger random batch with ragged agent counts against the oracle."""
-    from test_oracle_golden import _crowd_golden
-    d, maps, params = _crowd_golden()
-    got = gpu.sim.crowd_check(params, _t(gpu, maps), _t(gpu, d["robot"]), _t(gpu, d["agents"]), _t(gpu, d["global_time"]))
+    d, maps, params = crowd_golden()
+    got = gpu.sim.crowd_check(params, to_device(gpu, maps), to_device(gpu, d["robot"]), to_device(gpu, d["agents"]), to_device(gpu, d["global_time"]))
     reward, done, info, md = [x.cpu().numpy() for x in got]
     assert np.array_equal(info, d["info"]) and np.array_equal(done, d["done"])
     assert np.abs(reward - d["reward"]).max() < 1e-12
     exp = ref.crowd_check(params, maps, d["robot"], d["agents"], d["global_time"])
     for a, b, what in zip((reward, done, info, md), exp, ("reward", "done", "info", "min_dist")):
-        _eq(a, b, what)
+        eq(a, b, what)
     rng = np.random.default_rng(8)
     E, A, G = 3000, 70, 128
     params2 = dict(params, map_size_m=12.8, map_resolution=0.1)
@@ -1643,10 +1496,10 @@ def test_crowd_check_vs_reference_and_oracle(gpu):
     agents[..., 2:4] = rng.uniform(-1, 1, (E, A, 2)); agents[..., 4] = rng.uniform(0.2, 0.4, (E, A))
     na = rng.integers(0, A + 1, E).astype(np.int32)
     gt = rng.uniform(0, 26, E)
-    got = gpu.sim.crowd_check(params2, _t(gpu, fm), _t(gpu, robot), _t(gpu, agents), _t(gpu, gt), _t(gpu, na))
+    got = gpu.sim.crowd_check(params2, to_device(gpu, fm), to_device(gpu, robot), to_device(gpu, agents), to_device(gpu, gt), to_device(gpu, na))
     exp = ref.crowd_check(params2, fm, robot, agents, gt, na)
     for a, b, what in zip(got, exp, ("reward", "done", "info", "min_dist")):
-        _eq(a.cpu().numpy(), b, what + " (random batch)")
+        eq(a.cpu().numpy(), b, what + " (random batch)")
     assert len(np.unique(exp[2])) >= 4
 
 
@@ -1659,13 +1512,13 @@ def test_crowd_local_maps_vs_reference_and_oracle(gpu, golden_dir):
     P = {str(k): float(v) for k, v in zip(d["param_names"], d["params"])}
     maps = np.unpackbits(d["maps"])[: int(np.prod(d["map_shape"]))].reshape(d["map_shape"])
     lmap = np.unpackbits(d["lmap"])[: int(np.prod(d["lmap_shape"]))].reshape(d["lmap_shape"])
-    got = gpu.sim.crowd_angular_map(P, _t(gpu, d["robot"]), _t(gpu, d["verts"]), _t(gpu, d["n_obst"])).cpu().numpy()
-    _eq(got, ref.crowd_angular_map(P, d["robot"], d["verts"], d["n_obst"]), "angular map vs oracle")
+    got = gpu.sim.crowd_angular_map(P, to_device(gpu, d["robot"]), to_device(gpu, d["verts"]), to_device(gpu, d["n_obst"])).cpu().numpy()
+    eq(got, ref.crowd_angular_map(P, d["robot"], d["verts"], d["n_obst"]), "angular map vs oracle")
     np.testing.assert_allclose(got, d["amap"], rtol=0, atol=1e-12)
-    w = gpu.sim.crowd_local_map(P, _t(gpu, maps), _t(gpu, d["robot2"]), rotate=False).cpu().numpy()
-    _eq(w, lmap, "local-map window vs the reference")
-    r = gpu.sim.crowd_local_map(P, _t(gpu, maps), _t(gpu, d["robot2"]), rotate=True).cpu().numpy()
-    _eq(r, ref.crowd_local_map(P, maps, d["robot2"], rotate=True), "rotated local map vs oracle")
+    w = gpu.sim.crowd_local_map(P, to_device(gpu, maps), to_device(gpu, d["robot2"]), rotate=False).cpu().numpy()
+    eq(w, lmap, "local-map window vs the reference")
+    r = gpu.sim.crowd_local_map(P, to_device(gpu, maps), to_device(gpu, d["robot2"]), rotate=True).cpu().numpy()
+    eq(r, ref.crowd_local_map(P, maps, d["robot2"], rotate=True), "rotated local map vs oracle")
     assert not np.array_equal(r, w)
     # a larger random batch, other parameters: 5000 envs, 36 sectors over the front half plane, 8-vertex outlines
     rng = np.random.default_rng(9)
@@ -1677,11 +1530,11 @@ def test_crowd_local_maps_vs_reference_and_oracle(gpu, golden_dir):
     ctr = rng.uniform(-4, 4, (E, O, 1, 2)); rad = rng.uniform(0.2, 1.5, (E, O, V, 1))
     verts = ctr + rad * np.stack([np.cos(ang), np.sin(ang)], axis=3)
     n_obst = rng.integers(0, O + 1, E).astype(np.int32)
-    _eq(gpu.sim.crowd_angular_map(P2, _t(gpu, robot), _t(gpu, verts), _t(gpu, n_obst)).cpu().numpy(),
+    eq(gpu.sim.crowd_angular_map(P2, to_device(gpu, robot), to_device(gpu, verts), to_device(gpu, n_obst)).cpu().numpy(),
         ref.crowd_angular_map(P2, robot, verts, n_obst), "angular map, random batch")
     G = 100
     fm = (rng.random((600, G, G)) > 0.08).astype(np.uint8)
-    _eq(gpu.sim.crowd_local_map(P2, _t(gpu, fm), _t(gpu, robot[:600]), rotate=True).cpu().numpy(),
+    eq(gpu.sim.crowd_local_map(P2, to_device(gpu, fm), to_device(gpu, robot[:600]), rotate=True).cpu().numpy(),
         ref.crowd_local_map(P2, fm, robot[:600], rotate=True), "rotated local map, random batch")
 
 
@@ -1706,17 +1559,17 @@ def test_crowd_orca_and_agent_step_vs_oracle(gpu, golden_dir):
     n_obst = rng.integers(0, O + 1, S).astype(np.int32)
     obst_set = rng.integers(0, S, Q).astype(np.int32)
     theta = rng.uniform(0, 2 * np.pi, Q)
-    gv, ga = gpu.sim.crowd_orca(P, _t(gpu, ag), _t(gpu, pv), _t(gpu, verts), _t(gpu, n_agents), _t(gpu, n_obst),
-                                _t(gpu, obst_set), _t(gpu, theta))
+    gv, ga = gpu.sim.crowd_orca(P, to_device(gpu, ag), to_device(gpu, pv), to_device(gpu, verts), to_device(gpu, n_agents), to_device(gpu, n_obst),
+                                to_device(gpu, obst_set), to_device(gpu, theta))
     rv, ra = ref.crowd_orca(P, ag, pv, verts, n_agents, n_obst, obst_set, theta)
-    _eq(gv.cpu().numpy(), rv, "ORCA velocity")
-    _eq(ga.cpu().numpy(), ra, "ORCA action")
+    eq(gv.cpu().numpy(), rv, "ORCA velocity")
+    eq(ga.cpu().numpy(), ra, "ORCA action")
     assert (np.linalg.norm(rv, axis=1) <= ag[:, 0, 5] * (1 + 5e-3)).all()               # the speed disc (float32 LP: a few 1e-4 over)
     assert (np.abs(rv - pv) > 1e-3).any(axis=1).mean() > 0.3                             # the constraints do bind
     d = np.load(os.path.join(golden_dir, "golden_crowd_agent.npz"))
-    gp, gvel = gpu.sim.crowd_agent_step(_t(gpu, d["pose"]), _t(gpu, d["action"]), float(d["time_step"]))
+    gp, gvel = gpu.sim.crowd_agent_step(to_device(gpu, d["pose"]), to_device(gpu, d["action"]), float(d["time_step"]))
     rp, rvel = ref.crowd_agent_step(d["pose"], d["action"], float(d["time_step"]))
-    _eq(gp.cpu().numpy(), rp, "Agent.step pose"); _eq(gvel.cpu().numpy(), rvel, "Agent.step velocity")
+    eq(gp.cpu().numpy(), rp, "Agent.step pose"); eq(gvel.cpu().numpy(), rvel, "Agent.step velocity")
     np.testing.assert_allclose(rp, d["pose_out"], rtol=0, atol=1e-12)
 
 
@@ -1748,14 +1601,14 @@ def test_crowd_sim_step_pipeline_vs_oracle(gpu):
                              rng.uniform(0, 2 * np.pi, (E, H, 1))], axis=-1)
     robot = np.concatenate([rng.uniform(-1, 1, (E, 2)), np.zeros((E, 2)), np.full((E, 1), 0.3), np.ones((E, 1)),
                             rng.uniform(-4, 4, (E, 2)), rng.uniform(0, 2 * np.pi, (E, 1))], axis=1)
-    stp = CrowdSimStepper(_t(gpu, humans), _t(gpu, robot), _t(gpu, verts), _t(gpu, n_obst), _t(gpu, free), params,
+    stp = CrowdSimStepper(to_device(gpu, humans), to_device(gpu, robot), to_device(gpu, verts), to_device(gpu, n_obst), to_device(gpu, free), params,
                           map_params=mp)
     h, r, gt = humans.copy(), robot.copy(), np.zeros(E)
     orca_p = dict(time_step=0.25, neighbor_dist=10, time_horizon=5, time_horizon_obst=5, max_neighbors=10)
     deviated = 0
     for t in range(25):
         act = np.stack([rng.uniform(0, 1.0, E), rng.uniform(-0.5, 0.5, E)], axis=1)
-        out = stp.step(_t(gpu, act))
+        out = stp.step(to_device(gpu, act))
         # ---- the same composition with the oracle
         ag = np.zeros((E, H, H + 1, 6)); pv = np.zeros((E, H, 2))
         for k in range(H):
@@ -1774,12 +1627,12 @@ def test_crowd_sim_step_pipeline_vs_oracle(gpu):
         h[..., 0:2] = hpn[:, :2].reshape(E, H, 2); h[..., 2:4] = hvn.reshape(E, H, 2); h[..., 8] = hpn[:, 2].reshape(E, H)
         gt = gt + 0.25
         amap = ref.crowd_angular_map(mp, np.stack([r[:, 0], r[:, 1], r[:, 8], r[:, 4]], 1), verts, n_obst)
-        _eq(out["reward"].cpu().numpy(), rew, "reward at step %d" % t)
-        _eq(out["info"].cpu().numpy(), info, "info at step %d" % t)
-        _eq(out["done"].cpu().numpy(), done, "done at step %d" % t)
-        _eq(stp.h.cpu().numpy(), h, "pedestrian states at step %d" % t)
-        _eq(stp.r.cpu().numpy(), r, "robot states at step %d" % t)
-        _eq(out["local_map"].cpu().numpy(), amap, "angular map at step %d" % t)
+        eq(out["reward"].cpu().numpy(), rew, "reward at step %d" % t)
+        eq(out["info"].cpu().numpy(), info, "info at step %d" % t)
+        eq(out["done"].cpu().numpy(), done, "done at step %d" % t)
+        eq(stp.h.cpu().numpy(), h, "pedestrian states at step %d" % t)
+        eq(stp.r.cpu().numpy(), r, "robot states at step %d" % t)
+        eq(out["local_map"].cpu().numpy(), amap, "angular map at step %d" % t)
         deviated += int((np.abs(hvn.reshape(E, H, 2) - pv * 1.0).max(axis=-1) > 0.05).sum())
     assert deviated > 100
 
@@ -1792,7 +1645,6 @@ def test_crowd_sim_env_reset_and_steps(gpu, golden_dir):
     ITS humans only (ragged lists, the robot appended for the humans that see it): reward, info, done, every agent state
     and the local map bit for bit."""
     import crowd_sim
-    from nav_gym_amd import crowd
     d = np.load(os.path.join(golden_dir, "golden_crowd_reset.npz"))
     E = 10
     env = crowd_sim.make("CrowdSim-v0", num_envs=E, device=gpu.dev)
@@ -1803,9 +1655,9 @@ def test_crowd_sim_env_reset_and_steps(gpu, golden_dir):
         assert str(d["phase"][e]) == "test" and int(d["case"][e]) == e
         hg = d["humans_%d" % e]
         assert nh[e] == len(hg)
-        _eq(ob["humans"][e, :nh[e]].cpu().numpy(), np.stack([hg[:, 0], hg[:, 1], hg[:, 4], hg[:, 5], hg[:, 7]], 1), "humans of case %d" % e)
+        eq(ob["humans"][e, :nh[e]].cpu().numpy(), np.stack([hg[:, 0], hg[:, 1], hg[:, 4], hg[:, 5], hg[:, 7]], 1), "humans of case %d" % e)
         ks = int(ob["n_static"][e])
-        _eq(ob["static"][e, :ks].cpu().numpy(), d["static_%d" % e], "static obstacles of case %d" % e)
+        eq(ob["static"][e, :ks].cpu().numpy(), d["static_%d" % e], "static obstacles of case %d" % e)
         np.testing.assert_allclose(lm[e], d["local_map_%d" % e], rtol=0, atol=1e-12)
     assert len(set(nh.tolist())) >= 3 and env.case_counter["test"] == E
     # ---- closed loop against the oracle, env by env
@@ -1823,7 +1675,7 @@ def test_crowd_sim_env_reset_and_steps(gpu, golden_dir):
     moved = 0
     for t in range(20):
         act = np.stack([rng.uniform(0.2, 1.0, E), rng.uniform(-0.3, 0.3, E)], axis=1)
-        ob, local_map, reward, done, info = env.step(_t(gpu, act))
+        ob, local_map, reward, done, info = env.step(to_device(gpu, act))
         for e in range(E):
             n = nh[e]
             hact = np.zeros((n, 2))
@@ -1852,9 +1704,9 @@ def test_crowd_sim_env_reset_and_steps(gpu, golden_dir):
                                          verts[e][None] if len(verts[e]) else np.zeros((1, 0, 4, 2)),
                                          np.array([len(verts[e])], np.int32))
             assert float(reward[e]) == float(rew[0]) and int(info[e]) == int(inf[0]) and bool(done[e]) == bool(dn[0]), (t, e)
-            _eq(st.h[e, :n].cpu().numpy(), h[e], "pedestrians of env %d at step %d" % (e, t))
-            _eq(st.r[e].cpu().numpy(), r[e], "robot of env %d at step %d" % (e, t))
-            _eq(local_map[e].cpu().numpy(), amap[0], "angular map of env %d at step %d" % (e, t))
+            eq(st.h[e, :n].cpu().numpy(), h[e], "pedestrians of env %d at step %d" % (e, t))
+            eq(st.r[e].cpu().numpy(), r[e], "robot of env %d at step %d" % (e, t))
+            eq(local_map[e].cpu().numpy(), amap[0], "angular map of env %d at step %d" % (e, t))
             if n < st.h.shape[1]:                     # padding rows never move
                 assert float(st.h[e, n:, 0].min()) >= 1e6
     assert moved > 200
@@ -1887,12 +1739,12 @@ def test_plan_random_costmaps_of_many_shapes(gpu, shape):
     joined = 0
     for interval, P in ((2.0, 64), (0.6, 16)):
         exp = ref.plan(cost, start, goal, interval, max_wp=P, res_c=res, map_index=mi)
-        got = gpu.sim.plan(_t(gpu, cost), _t(gpu, start), _t(gpu, goal), interval, max_wp=P, res_c=res, map_index=_t(gpu, mi))
+        got = gpu.sim.plan(to_device(gpu, cost), to_device(gpu, start), to_device(gpu, goal), interval, max_wp=P, res_c=res, map_index=to_device(gpu, mi))
         live = np.arange(P)[None, :] < exp[1][:, None]
-        _eq(got[1].cpu().numpy(), exp[1], "waypoint counts")
-        _eq(got[2].cpu().numpy(), exp[2], "path cells")
-        _eq(got[3].cpu().numpy(), exp[3], "path length")
-        _eq(got[0].cpu().numpy()[live], exp[0][live], "waypoints")
+        eq(got[1].cpu().numpy(), exp[1], "waypoint counts")
+        eq(got[2].cpu().numpy(), exp[2], "path cells")
+        eq(got[3].cpu().numpy(), exp[3], "path length")
+        eq(got[0].cpu().numpy()[live], exp[0][live], "waypoints")
         joined += int((exp[1] > 0).sum())
     assert joined > 20
 
@@ -1902,10 +1754,10 @@ def test_config1_single_env_64_beams(gpu):
     cfg = gpu.lib.default_config(n_envs=1, map_h=100, map_w=100, n_spawn=4, auto_reset=0, seed=7)
     gpu.world.lidar_full_circle(cfg, 64)
     occ = gpu.world.make_maps(1, 100, 7)
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=0, steps=80, seed=2):
-        _eq(go, ro, "obs at step %d" % t)
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=0, steps=80, seed=2):
+        eq(go, ro, "obs at step %d" % t)
         for k in rout:
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
 
 
 def test_scan_noise_statistics(gpu):
@@ -1915,10 +1767,7 @@ def test_scan_noise_statistics(gpu):
     cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, n_spawn=4, add_scan_noise=1, seed=99)
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 99)
-    from nav_gym_amd import robots
-    arrays = gpu.world.make_world(cfg, occ, device=gpu.dev, noise_std_range=(0.03, 0.03))
-    arrays["scan_threshold"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "threshold_footprint")))
-    arrays["scan_discomfort"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "discomfort_threshold_footprint")))
+    arrays = device_world(gpu, cfg, occ, 0, noise_std_range=(0.03, 0.03))
     noisy = gpu.sim.NavSim(cfg, arrays).reset_obs().cpu().numpy()[:, :1081]
     cfg.add_scan_noise = 0
     clean = gpu.sim.NavSim(cfg, arrays).reset_obs().cpu().numpy()[:, :1081]
@@ -2017,7 +1866,7 @@ def test_env_graph_replay_equals_eager_steps(gpu):
     assert envs[0]._graphed is False and envs[1]._graphed is False
     o = [e.reset() for e in envs]
     assert envs[0]._graphed and not envs[1]._graphed
-    _eq(o[0]["observation"].cpu().numpy(), o[1]["observation"].cpu().numpy(), "reset observation")
+    eq(o[0]["observation"].cpu().numpy(), o[1]["observation"].cpu().numpy(), "reset observation")
     g = torch.Generator(device=gpu.dev); g.manual_seed(2)
     finished = 0
     for t in range(70):
@@ -2026,12 +1875,12 @@ def test_env_graph_replay_equals_eager_steps(gpu):
         act[:, 1] = act[:, 1] * 1.28 - 0.64
         res = [e.step(act) for e in envs]
         for k in ("observation", "achieved_goal", "desired_goal"):
-            _eq(res[0][0][k].cpu().numpy(), res[1][0][k].cpu().numpy(), "%s at step %d" % (k, t))
-        _eq(res[0][1].cpu().numpy(), res[1][1].cpu().numpy(), "reward at step %d" % t)
-        _eq(res[0][2].cpu().numpy(), res[1][2].cpu().numpy(), "done at step %d" % t)
+            eq(res[0][0][k].cpu().numpy(), res[1][0][k].cpu().numpy(), "%s at step %d" % (k, t))
+        eq(res[0][1].cpu().numpy(), res[1][1].cpu().numpy(), "reward at step %d" % t)
+        eq(res[0][2].cpu().numpy(), res[1][2].cpu().numpy(), "done at step %d" % t)
         finished += int(res[1][2].sum())
     for k in ("robot_pose", "ped_pose", "ped_waypoints", "episode", "n_peds"):
-        _eq(envs[0].sim.t[k].cpu().numpy(), envs[1].sim.t[k].cpu().numpy(), "state " + k)
+        eq(envs[0].sim.t[k].cpu().numpy(), envs[1].sim.t[k].cpu().numpy(), "state " + k)
     c0, c1 = envs[0].counters(), envs[1].counters()
     assert finished > 3 and c0 == c1 and c1["regen_served"] >= finished and c1["regen_unserved"] == 0, (finished, c0, c1)
     assert envs[1].counters() == {k: 0 for k in abi.COUNTERS}            # counters() reads and clears
@@ -2080,10 +1929,10 @@ def test_env_reset_runs_on_the_device_and_matches_the_oracle(gpu, monkeypatch):
         r = ref.RefSim(c1, host)
         r.out["done"][:] = 1
         ro = r.regen()
-        _eq(o_clean[e:e + 1], ro, "first observation of arena %d" % e)
+        eq(o_clean[e:e + 1], ro, "first observation of arena %d" % e)
         for k, v in st.items():
-            _eq(v[e:e + 1], r.a[k], "arena %d state %s" % (e, k))
-        _eq(env.sim.occupancy(e), (r.a["field"][0] == 0).astype(np.uint8), "arena %d map" % e)
+            eq(v[e:e + 1], r.a[k], "arena %d state %s" % (e, k))
+        eq(env.sim.occupancy(e), (r.a["field"][0] == 0).astype(np.uint8), "arena %d map" % e)
     first_maps = [env.sim.occupancy(e) for e in range(4)]
     env.reset()
     assert all(not np.array_equal(env.sim.occupancy(e), first_maps[e]) for e in range(4))
@@ -2157,23 +2006,23 @@ def test_full_size_c2_properties_and_sampled_oracle(gpu, full_c2):
         a_host = act.cpu().numpy()
         for e, r in zip(sample, refs):
             ro, rout = r.step(a_host[e:e + 1])
-            _eq(o[e:e + 1], ro, "arena %d obs at step %d" % (e, t))
+            eq(o[e:e + 1], ro, "arena %d obs at step %d" % (e, t))
             for k in rout:
-                _eq(out[k][e:e + 1].cpu().numpy(), rout[k], "arena %d %s at step %d" % (e, k, t))
+                eq(out[k][e:e + 1].cpu().numpy(), rout[k], "arena %d %s at step %d" % (e, k, t))
         if regen:
             # navsim_regen serves the finished arenas lowest index first, at most regen_cap of them: below the cap
             # an arena's fate does not depend on the others and the single-arena oracles stay comparable
             assert int(done.sum()) <= cfg.regen_cap, "more arenas finished than regen_cap: raise the cap of this test"
             o2 = sim.regen().cpu().numpy()
             for e, r in zip(sample, refs):
-                _eq(o2[e:e + 1], r.regen(), "arena %d obs after regen at step %d" % (e, t))
+                eq(o2[e:e + 1], r.regen(), "arena %d obs after regen at step %d" % (e, t))
                 regenerated_samples += int(done[e])
             if t in (0, 11):
                 gs = sim.numpy_state("robot_pose", "robot_goal", "spawn_pose", "spawn_goal", "ped_pose", "ped_v_pref",
                                      "ped_has_legs", "ped_waypoints", "ped_n_waypoints", "episode", "steps")
                 for e, r in zip(sample, refs):
                     for k, v in gs.items():
-                        _eq(v[e:e + 1], r.a[k], "arena %d state %s after regen at step %d" % (e, k, t))
+                        eq(v[e:e + 1], r.a[k], "arena %d state %s after regen at step %d" % (e, k, t))
     assert total_done > 0
     if regen:
         assert regenerated_samples >= 4, "no sampled arena went through navsim_regen"
@@ -2239,41 +2088,19 @@ def test_regen_writes_the_rect_records_of_outdoor_maps_from_the_generator(gpu, s
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 23)
     regenerated = 0
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=3, steps=40, seed=9):
-        _eq(go, ro, "obs at step %d" % t)
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=3, steps=40, seed=9):
+        eq(go, ro, "obs at step %d" % t)
         assert "rect_table" in g.t
         n_done = int(rout["done"].sum())
-        _eq(g.regen().cpu().numpy(), r.regen(), "obs after regen at step %d" % t)
+        eq(g.regen().cpu().numpy(), r.regen(), "obs after regen at step %d" % t)
         regenerated += min(n_done, 8)
         if n_done:
-            gs = g.numpy_state()
-            for k, v in r.a.items():
-                if k in gs and k not in ("field", "field_overflow", "rect_table", "rect_index"):
-                    _eq(gs[k], v, "state %s after regen at step %d" % (k, t))
-            d2, valid = _decode_rect_table(g.t["rect_table"].cpu().numpy(), size, size)
+            state_equal(g, r, "after regen at step %d" % t)
+            d2, valid = decode_rect_table(g.t["rect_table"].cpu().numpy(), size, size)
             exact = np.rint(r.a["field"].astype(np.float64) ** 2).astype(np.int64)
             assert np.array_equal(d2[valid], exact[valid]), "a record differs from the exact field at step %d" % t
             assert valid.mean() > 0.93          # 200 x 200 cells with 10 boxes: 0.97; the bench's 500 x 500: 0.995
     assert regenerated >= 6
-
-
-def _decode_rect_table(table, H, W):
-    """Host evaluation of navsim_build_rects records: -> (d2 int64 [E,H,W], valid bool [E,H,W])."""
-    E = table.shape[0]
-    tpr = (W + 7) // 8
-    rec = table.view(np.uint32).reshape(E, -1, 4)
-    yy, xx = np.mgrid[0:H, 0:W]
-    tile = (yy // 8) * tpr + (xx // 8)
-    r = rec[:, tile]                                            # [E,H,W,4]
-    def sx(w): return (w & 0xFFFF).astype(np.int16).astype(np.int64)
-    def sy(w): return (w >> 16).astype(np.int16).astype(np.int64)
-    def dist2(lo, hi):
-        ddx = np.maximum(0, np.maximum(sx(lo) - xx, xx - sx(hi)))
-        ddy = np.maximum(0, np.maximum(sy(lo) - yy, yy - sy(hi)))
-        return ddx * ddx + ddy * ddy
-    d2 = np.minimum(dist2(r[..., 0], r[..., 1]), dist2(r[..., 2], r[..., 3]))
-    valid = (r[..., 0] & 0xFFFF) != 0x7FFF
-    return d2, valid
 
 
 @pytest.mark.parametrize("size,indoor,fmt", [(100, 0.0, abi.FIELD_U16T), (253, 0.5, abi.FIELD_U16T), (500, 0.0, abi.FIELD_U16T),
@@ -2286,9 +2113,9 @@ def test_rect_table_reproduces_field(gpu, size, indoor, fmt):
     the float32 plane supplies their exact distance."""
     n = 3 if size <= 500 else 1
     occ = gpu.world.make_maps(n, size, 31, indoor_ratio=indoor)
-    field, f32, nsat = gpu.sim.build_field(_t(gpu, occ), fmt)
-    table = gpu.sim.build_rects(_t(gpu, occ), field, fmt, f32 if fmt == abi.FIELD_U16T else None).cpu().numpy()
-    d2, valid = _decode_rect_table(table, size, size)
+    field, f32, nsat = gpu.sim.build_field(to_device(gpu, occ), fmt)
+    table = gpu.sim.build_rects(to_device(gpu, occ), field, fmt, f32 if fmt == abi.FIELD_U16T else None).cpu().numpy()
+    d2, valid = decode_rect_table(table, size, size)
     exact = np.rint(ref.build_dt(occ).astype(np.float64) ** 2).astype(np.int64)
     assert np.array_equal(d2[valid], exact[valid]), "a valid record disagrees with the exact field"
     frac = valid.mean()                     # small maps: a larger share of the tiles sits between several obstacles
@@ -2306,8 +2133,8 @@ def test_rect_table_reproduces_field(gpu, size, indoor, fmt):
     if size == 1000 and fmt == abi.FIELD_U16T:
         assert nsat > 0
         # without the float plane the tiles holding a saturated cell must come out invalid, never wrong
-        t2 = gpu.sim.build_rects(_t(gpu, occ), field, fmt, None).cpu().numpy()
-        d2b, validb = _decode_rect_table(t2, size, size)
+        t2 = gpu.sim.build_rects(to_device(gpu, occ), field, fmt, None).cpu().numpy()
+        d2b, validb = decode_rect_table(t2, size, size)
         assert np.array_equal(d2b[validb], exact[validb]) and validb.sum() < valid.sum()
 
 
@@ -2327,36 +2154,21 @@ def test_rect_table_on_arbitrary_maps(gpu):
     occ[5][60:100, 50:120] = 1
     for e in range(E):                                   # keep a free patch for the robots
         occ[e, 20:45, 20:45] = 0
-    field, f32, _ = gpu.sim.build_field(_t(gpu, occ), abi.FIELD_U16T)
-    table = gpu.sim.build_rects(_t(gpu, occ), field, abi.FIELD_U16T, f32).cpu().numpy()
-    d2, valid = _decode_rect_table(table, size, size)
+    field, f32, _ = gpu.sim.build_field(to_device(gpu, occ), abi.FIELD_U16T)
+    table = gpu.sim.build_rects(to_device(gpu, occ), field, abi.FIELD_U16T, f32).cpu().numpy()
+    d2, valid = decode_rect_table(table, size, size)
     exact = np.rint(ref.build_dt(occ).astype(np.float64) ** 2).astype(np.int64)
     assert np.array_equal(d2[valid], exact[valid])
     assert valid[5].mean() > 0.95 and valid[0].mean() < 0.9          # a box: valid; speckle: mostly not
     cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, n_spawn=4, auto_reset=1, seed=8,
                                  field_format=abi.FIELD_U16T)
     gpu.world.lidar_1081(cfg)
-    for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=0, steps=25, seed=2, min_goal_dist=1.0,
+    for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=0, steps=25, seed=2, min_goal_dist=1.0,
                                                      max_goal_dist=3.0, robot_clearance=0.4):
         assert "rect_table" in g.t
-        _eq(go, ro, "obs at step %d" % t)
+        eq(go, ro, "obs at step %d" % t)
         for k in rout:
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
-
-
-def _decode_rect_index(rows, H, W):
-    """Host evaluation of the index form (navsim_build_rect_index): rows uint8 [E, R] -> the 16-byte records it stands for
-    (uint32 [E, T, 4]) and which tiles carry an index."""
-    E = rows.shape[0]
-    T_ = ((H + 7) // 8) * ((W + 7) // 8)
-    lst = rows[:, :2048].copy().view(np.uint32).reshape(E, 256, 2)
-    pair = rows[:, 2048:2048 + 2 * T_].copy().view(np.uint16).reshape(E, T_)
-    has = pair != 0xFFFF
-    ia, ib = (pair & 0xFF).astype(np.int64), (pair >> 8).astype(np.int64)
-    rec = np.zeros((E, T_, 4), np.uint32)
-    ar = np.arange(E)[:, None]
-    rec[..., 0:2] = lst[ar, ia]; rec[..., 2:4] = lst[ar, ib]
-    return rec, has
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
 
 
 @pytest.mark.parametrize("size,indoor", [(500, 0.0), (500, 1.0), (253, 0.5), (1000, 1.0)])
@@ -2367,16 +2179,16 @@ def test_rect_index_is_the_record_table(gpu, size, indoor):
     14 rectangles for an outdoor map, a few dozen to ~200 for a corridor map); closed maps are recognised."""
     n = 3 if size <= 500 else 1
     occ = gpu.world.make_maps(n, size, 9 + size, indoor_ratio=indoor)
-    field, f32, _ = gpu.sim.build_field(_t(gpu, occ), abi.FIELD_U16T)
-    table = gpu.sim.build_rects(_t(gpu, occ), field, abi.FIELD_U16T, f32)
+    field, f32, _ = gpu.sim.build_field(to_device(gpu, occ), abi.FIELD_U16T)
+    table = gpu.sim.build_rects(to_device(gpu, occ), field, abi.FIELD_U16T, f32)
     rows, n_rects = gpu.sim.build_rect_index(table, size, size)
-    closed = gpu.sim.maps_closed(_t(gpu, occ))
+    closed = gpu.sim.maps_closed(to_device(gpu, occ))
     assert rows.shape[1] == abi.rect_index_row_bytes(size, size) == gpu.lib.load().navsim_rect_index_bytes(1, size, size)
-    rec, has = _decode_rect_index(rows.cpu().numpy(), size, size)
+    rec, has = decode_rect_index(rows.cpu().numpy(), size, size)
     tab = table.cpu().numpy().view(np.uint32).reshape(n, -1, 4)
     valid = (tab[..., 0] & 0xFFFF) != 0x7FFF
     assert not (has & ~valid).any()                                  # an index only where there is a valid record
-    _eq(rec[has], tab[has], "records named by the index rows")
+    eq(rec[has], tab[has], "records named by the index rows")
     nr = n_rects.cpu().numpy()
     assert (nr >= 5).all()
     if (nr <= 255).all():
@@ -2385,7 +2197,7 @@ def test_rect_index_is_the_record_table(gpu, size, indoor):
     # a gap in the border wall: not closed
     occ2 = occ.copy(); occ2[0, :8, 40:60] = 0
     occ2[-1, 100, size - 3] = 0                                      # one cell of the ring's inner layer
-    c2 = gpu.sim.maps_closed(_t(gpu, occ2)).cpu().numpy()
+    c2 = gpu.sim.maps_closed(to_device(gpu, occ2)).cpu().numpy()
     assert c2[0] == 0 and c2[-1] == 0 and (c2[1:-1] == 1).all()
 
 
@@ -2401,11 +2213,11 @@ def test_open_maps_keep_the_bounds_test(gpu):
         cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, n_spawn=6, auto_reset=1, seed=61, field_format=abi.FIELD_U16T)
         gpu.world.lidar_1081(cfg)
         left_the_map = 0
-        for t, go, gout, ro, rout, g, r in _rollout_pair(gpu, cfg, occ, n_peds=0, steps=30, seed=6, min_goal_dist=2.0,
+        for t, go, gout, ro, rout, g, r in rollout_pair(gpu, cfg, occ, n_peds=0, steps=30, seed=6, min_goal_dist=2.0,
                                                          max_goal_dist=6.0, robot_clearance=0.6):
-            _eq(go, ro, "obs at step %d (gap %s)" % (t, gap))
+            eq(go, ro, "obs at step %d (gap %s)" % (t, gap))
             for k in rout:
-                _eq(gout[k], rout[k], "%s at step %d" % (k, t))
+                eq(gout[k], rout[k], "%s at step %d" % (k, t))
             left_the_map += int((go[:, :1081] == 25.0).sum())
         assert "rect_index" in g.t and g.cfg.closed_maps == (0 if gap else 1)
         assert (left_the_map > 0) == gap
@@ -2415,10 +2227,7 @@ def test_open_maps_keep_the_bounds_test(gpu):
     occ[3, 60:140, :8] = 0
     cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, n_spawn=6, auto_reset=1, seed=61, field_format=abi.FIELD_U16T)
     gpu.world.lidar_1081(cfg)
-    arrays = gpu.world.make_world(cfg, occ, n_peds=0, device=gpu.dev, min_goal_dist=2.0, max_goal_dist=6.0, robot_clearance=0.6)
-    from nav_gym_amd import robots
-    for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
-        arrays[key] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", name)))
+    arrays = device_world(gpu, cfg, occ, 0, min_goal_dist=2.0, max_goal_dist=6.0, robot_clearance=0.6)
     assert cfg.closed_maps == 0
     cfg.closed_maps = 1                                              # "every map of this world is closed": not true of arena 3
     with pytest.raises(ValueError, match="1 arenas have a map without a closed ring"):
@@ -2432,9 +2241,9 @@ def test_costmap_and_planner_vs_oracle(gpu, size, indoor):
     torch = gpu.torch
     n_maps, per = 3, 12
     occ = gpu.world.make_maps(n_maps, size, 3 + size, indoor_ratio=indoor)
-    cost = gpu.sim.costmap(_t(gpu, occ))
+    cost = gpu.sim.costmap(to_device(gpu, occ))
     rc = ref.costmap(occ)
-    _eq(cost.cpu().numpy(), rc, "costmap")
+    eq(cost.cpu().numpy(), rc, "costmap")
     rng = np.random.default_rng(size)
     start, goal, mi = [], [], []
     for m in range(n_maps):
@@ -2446,12 +2255,12 @@ def test_costmap_and_planner_vs_oracle(gpu, size, indoor):
     start, goal, mi = np.concatenate(start), np.concatenate(goal), np.concatenate(mi).astype(np.int32)
     start[0] = [0.1, 0.1]                                # inside the border wall: no path
     for interval in (2.0, 5.0):
-        gw, gn, gc, gl = gpu.sim.plan(cost, _t(gpu, start), _t(gpu, goal), interval, max_wp=8, map_index=_t(gpu, mi))
+        gw, gn, gc, gl = gpu.sim.plan(cost, to_device(gpu, start), to_device(gpu, goal), interval, max_wp=8, map_index=to_device(gpu, mi))
         rw, rn, rcells, rl = ref.plan(rc, start, goal, interval, max_wp=8, map_index=mi)
-        _eq(gn.cpu().numpy(), rn, "n_wp"); _eq(gc.cpu().numpy(), rcells, "path cells")
-        _eq(gl.cpu().numpy(), rl, "path length")
+        eq(gn.cpu().numpy(), rn, "n_wp"); eq(gc.cpu().numpy(), rcells, "path cells")
+        eq(gl.cpu().numpy(), rl, "path length")
         for q in range(len(rn)):
-            _eq(gw.cpu().numpy()[q, : rn[q]], rw[q, : rn[q]], "waypoints of query %d" % q)
+            eq(gw.cpu().numpy()[q, : rn[q]], rw[q, : rn[q]], "waypoints of query %d" % q)
         assert rn[0] == 0
         if True:
             assert (rn[1:] > 0).sum() > len(rn) // 3, rn
@@ -2670,25 +2479,20 @@ def test_edge_shapes(gpu):
     gpu.world.lidar_full_circle(cfg, 77)
     occ = gpu.world.make_maps(E, size, 91)
     n_peds = torch.tensor([0, 1, 64, 17, 64], dtype=torch.int32)
-    arrays = gpu.world.make_world(cfg, occ, n_peds=n_peds, device=gpu.dev, min_goal_dist=2, max_goal_dist=6,
-                                  robot_clearance=0.8)
-    from nav_gym_amd import robots
-    arrays["scan_threshold"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "threshold_footprint")))
-    arrays["scan_discomfort"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "discomfort_threshold_footprint")))
-    host = {k: v.cpu().numpy() for k, v in arrays.items() if k not in ("field", "field_overflow", "rect_table", "rect_index")}
-    host["field"] = ref.build_dt(occ)
+    arrays = device_world(gpu, cfg, occ, n_peds, min_goal_dist=2, max_goal_dist=6, robot_clearance=0.8)
+    host = host_arrays(arrays, occ)
     g = gpu.sim.NavSim(cfg, arrays); r = ref.RefSim(cfg, host)
-    _eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
+    eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
     rng = np.random.default_rng(4)
     for t in range(30):
         act = np.stack([rng.uniform(-0.3, 0.9, E), rng.uniform(-1.5, 1.5, E)], axis=1)    # out of range: not clipped
         cmd = np.stack([rng.uniform(0, 0.6, (E, N)), rng.uniform(-0.6, 0.6, (E, N))], axis=2)
         g.set_ped_cmd(cmd); r.set_ped_cmd(cmd)
         go, gout = g.step(torch.from_numpy(act).to(gpu.dev)); ro, rout = r.step(act)
-        _eq(go.cpu().numpy(), ro, "obs at step %d" % t)
+        eq(go.cpu().numpy(), ro, "obs at step %d" % t)
         for k in rout:
-            _eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
-    _eq(g.ped_scans().cpu().numpy()[2], r.ped_scans()[2], "64-pedestrian scans")
+            eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
+    eq(g.ped_scans().cpu().numpy()[2], r.ped_scans()[2], "64-pedestrian scans")
     # empty batches
     L = gpu.lib.load()
     cfg0 = cfg.copy(); cfg0.n_envs = 0
@@ -2716,10 +2520,7 @@ def test_pipelined_ped_policy_equals_the_two_calls(gpu):
                                  auto_reset=1, seed=31, field_format=abi.FIELD_U16T)
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 31)
-    arrays = gpu.world.make_world(cfg, occ, n_peds=9, device=gpu.dev, min_goal_dist=2.0, max_goal_dist=6.0, robot_clearance=0.6)
-    from nav_gym_amd import robots
-    for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
-        arrays[key] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", name)))
+    arrays = device_world(gpu, cfg, occ, 9, min_goal_dist=2.0, max_goal_dist=6.0, robot_clearance=0.6)
     arrays["n_peds"][::5] = 12
     arrays["n_peds"][3] = 0
     g = gpu.sim.NavSim(cfg, arrays)

@@ -15,11 +15,10 @@ import numpy as np
 import pytest
 
 import map_geometry_scenes as mg
+import ped_edge_runs as cpu
 import ped_edge_scenes as ps
-import ref
-import test_ped_edge_scenes as cpu
+from gpu_support import gpu, device_map_arrays, eq, to_device  # noqa: F401  (gpu: the module's fixture)
 from nav_gym_amd import abi
-from test_gpu_autoreset import gpu, _t, _eq  # noqa: F401  (gpu: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,18 +31,11 @@ STATE = mg.STATE + ("ped_goal", "n_peds", "ped_due")
 def _device_arrays(gpu, cfg, occ, world, field):
     """The world's arrays with the field (and the rect records) the device builds from occ; sets the configuration's
     field_format, rect_lds and closed_maps."""
-    occ_t = _t(gpu, occ)
     cfg.field_format = abi.FIELD_F32 if field == "f32" else abi.FIELD_U16T
     cfg.rect_lds = {"f32": 0, "u16t": 0, "rects": 1, "rects_lds": 2}[field]
-    a = {k: v for k, v in world.items() if k != "field"}
-    packed, f32, nsat = gpu.sim.build_field(occ_t, cfg.field_format)
-    assert nsat == 0
-    a["field"] = packed
-    if field in ("rects", "rects_lds"):
-        a["rect_table"] = gpu.sim.build_rects(occ_t, packed, cfg.field_format, f32)
-        a["rect_index"], _ = gpu.sim.build_rect_index(a["rect_table"], occ.shape[1], occ.shape[2])
-        cfg.closed_maps = int(bool((gpu.sim.maps_closed(occ_t) == 1).all().item()))
-        assert cfg.closed_maps == 1
+    rects = field in ("rects", "rects_lds")
+    a = device_map_arrays(gpu, cfg, occ, world, rects)
+    assert not rects or cfg.closed_maps == 1
     return a
 
 
@@ -56,7 +48,7 @@ def _device_run(gpu, cfg, occ, world, action, steps, block, field, split, march_
     assert ("rect_table" in g.t) == (field in ("rects", "rects_lds"))
     names = [k for k in STATE if k in g.t or k == "ped_due"]
     rec = [dict(obs=g.reset_obs().cpu().numpy(), out=None, state=g.numpy_state(*names))]
-    act = _t(gpu, np.tile(np.asarray(action, np.float64), (cfg.n_envs, 1)))
+    act = to_device(gpu, np.tile(np.asarray(action, np.float64), (cfg.n_envs, 1)))
     for _ in range(steps):
         obs, out = g.step(act)
         rec.append(dict(obs=obs.cpu().numpy(), out={k: v.cpu().numpy() for k, v in out.items()}, state=g.numpy_state(*names)))
@@ -68,15 +60,15 @@ def _equal(dev, want, names, label):
     assert len(dev) == len(want)
     for t, (a, b) in enumerate(zip(dev, want)):
         for e in np.flatnonzero((a["obs"] != b["obs"]).any(axis=1))[:1]:           # name the scene of the first row that differs
-            _eq(a["obs"][e], b["obs"][e], "%s: observation %d of scene '%s'" % (label, t, names[e]))
+            eq(a["obs"][e], b["obs"][e], "%s: observation %d of scene '%s'" % (label, t, names[e]))
         if b["out"] is not None:
             assert set(a["out"]) == set(b["out"])
             for k in b["out"]:
-                _eq(a["out"][k], b["out"][k], "%s: %s at step %d" % (label, k, t))
+                eq(a["out"][k], b["out"][k], "%s: %s at step %d" % (label, k, t))
         compared = 0
         for k in STATE:
             if k in b["state"] and k in a["state"]:
-                _eq(a["state"][k], b["state"][k], "%s: state %s at observation %d" % (label, k, t))
+                eq(a["state"][k], b["state"][k], "%s: state %s at observation %d" % (label, k, t))
                 compared += 1
         assert compared >= 12, compared
 
@@ -102,7 +94,7 @@ def _lidar_case(gpu, name, block, field, split, march_rule=None):
     label = "%s, %d threads, %s, ped_split %d" % (name, block, field, split)
     _equal(dev, want, names, label)
     for e in np.flatnonzero((scans != want_scans).any(axis=(1, 2)))[:1]:
-        _eq(scans[e], want_scans[e], "%s: pedestrian scans of scene '%s'" % (label, names[e]))
+        eq(scans[e], want_scans[e], "%s: pedestrian scans of scene '%s'" % (label, names[e]))
     B = cfg.n_beams
     assert sum(int(x["out"]["is_crash"].sum()) for x in want[1:]) > 0, "the near scenes crash"
     assert (want[0]["obs"][:, -7 - B:-7] < np.float32(cfg.range_max)).any() and (want_scans < np.float32(cfg.ped_range_max)).any()
@@ -134,7 +126,7 @@ def _sfm_case(gpu, max_peds, block, field, split, march_rule=None):
     dev, scans = _device_run(gpu, cfg, occ, world, ps.SFM_ACTION, cpu.STEPS, block, field, split, march_rule)
     label = "social force, max_peds %d, %d threads, %s, ped_split %d" % (max_peds, block, field, split)
     _equal(dev, want, names, label)
-    _eq(scans, want_scans, label + ": pedestrian scans")
+    eq(scans, want_scans, label + ": pedestrian scans")
     moved = np.abs(want[-1]["state"]["ped_pose"] - world["ped_pose"]).max(axis=(1, 2)) > 0
     assert moved.sum() >= len(scenes) - 1                   # (every arena but the one with n_peds = 0)
 
@@ -160,7 +152,7 @@ def test_a_lidar_above_one_turn_without_pedestrians(gpu, name, block, field):
     scenes = ps.lidar_scenes(lidar, crowd=False)
     cfg = cpu.config(lidar, len(scenes), abi.PED_NONE, range_max=25.0)
     world = ps.lidar_world(cfg, scenes)
-    occ = cpu._with_map(cfg, world)
+    occ = cpu.with_map(cfg, world)
     assert cfg.angle_last - cfg.angle_min > 2 * np.pi
     want, _ = cpu.run(cfg, world, (0.3, 0.2))
     dev, _ = _device_run(gpu, cfg, occ, world, (0.3, 0.2), cpu.STEPS, block, field, 0)

@@ -2,76 +2,16 @@
 of tests/ped_observe_spec.py, bit for bit: single calls at the shapes where the lane packing changes, each of the nine
 instantiations, the hand-made cases with their known answers, a closed loop beside the oracle under the three reset protocols,
 and the gym surface.  Every output is pre-filled with a sentinel: the call writes every element."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import ped_observe_spec as spec
 import ref
+from gpu_support import gpu, eq, random_actions, sim_and_oracle, to_device  # noqa: F401  (gpu: the module's fixture)
 from nav_gym_amd import abi
-from test_gpu_autoreset import gpu, _t, _eq, _pair, _actions  # noqa: F401  (gpu: the module's fixture)
+from ped_observe_call import KEYS, STATE, answer, call, device_state, same
 
 pytestmark = pytest.mark.gpu
-
-KEYS = tuple(abi.PED_OBSERVATION)
-STATE_KEYS = ("robot_pose", "n_peds", "ped_pose", "ped_vel")
-
-
-def _params(**kw):
-    p = dict(spec.DEFAULT, **kw)
-    return abi.NavsimPedObserveParams(ped_radius=p["ped_radius"], sensor_range=p["sensor_range"], max_obs=p["max_obs"],
-                                      rays=p["rays"], occlusion=p["occlusion"], fov=p["fov"])
-
-
-def _call(gpu, cfg, st, params, skip=None, visible=True):
-    """navsim_ped_observe into sentinel-filled outputs -> NumPy arrays."""
-    p = _params(**params) if isinstance(params, dict) else params
-    torch, E, N, K = gpu.torch, cfg.n_envs, cfg.max_peds, p.max_obs
-    out = dict(state=torch.full((E, K, 5), 777.0, dtype=torch.float32, device=gpu.dev),
-               index=torch.full((E, K), 777, dtype=torch.int32, device=gpu.dev),
-               count=torch.full((E,), 777, dtype=torch.int32, device=gpu.dev),
-               visible=torch.full((E, N), 77, dtype=torch.uint8, device=gpu.dev))
-    o = abi.NavsimPedObservation()
-    for k, v in out.items():
-        setattr(o, k, v.data_ptr() if (visible or k != "visible") else None)
-    t_skip = None if skip is None else _t(gpu, np.asarray(skip, np.uint8))
-    rc = gpu.lib.load().navsim_ped_observe(C.byref(cfg), C.byref(st), C.byref(p), None if skip is None else t_skip.data_ptr(),
-                                           C.byref(o), None)
-    assert rc == 0, rc
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def _same(dev, want, what):
-    for k in ("count", "visible", "index", "state"):               # (the small arrays first: their mismatch says more)
-        assert dev[k].dtype == want[k].dtype and dev[k].shape == want[k].shape, (what, k, dev[k].dtype, dev[k].shape)
-        _eq(dev[k].view(np.uint32) if k == "state" else dev[k], want[k].view(np.uint32) if k == "state" else want[k],
-            "%s: %s" % (what, k))
-
-
-def _device_state(gpu, cfg, occ, w, overflow=False, map_slot=None):
-    """navsim_state over device copies of the world `w` and the field of `occ` [M,H,W] in cfg.field_format.  -> (st, keepalive)"""
-    occ_t = _t(gpu, occ)
-    keep = {k: _t(gpu, np.ascontiguousarray(w[k], dtype=np.int32 if k == "n_peds" else np.float64)) for k in STATE_KEYS}
-    if cfg.field_format == abi.FIELD_F32:
-        keep["field"] = gpu.sim.build_dt(occ_t)
-    else:
-        keep["field"], plane, nsat = gpu.sim.build_field(occ_t, abi.FIELD_U16T)
-        assert (nsat > 0) == overflow, nsat
-        if overflow:
-            keep["field_overflow"] = plane
-    if map_slot is not None:
-        keep["map_slot"] = _t(gpu, np.asarray(map_slot, np.int32))
-    st = abi.NavsimState()
-    for k, v in keep.items():
-        setattr(st, k, v.data_ptr())
-    return st, keep
-
-
-def _spec(cfg, fields, w, params, **kw):
-    return spec.observe(cfg, fields, w["robot_pose"], w["n_peds"], w["ped_pose"], w["ped_vel"], params, **kw)
-
 
 # ---- a. single calls at the shapes where the lane packing changes ------------------------------------------------------------
 @pytest.mark.parametrize("E,N,seed,n_peds", spec.RANDOM_WORLDS, ids=lambda v: str(v) if isinstance(v, int) else "n")
@@ -82,25 +22,25 @@ def test_single_call_equals_the_spec(gpu, E, N, seed, n_peds):
     cfg = spec.random_config(E, N, spec.RANDOM_SIZE, field_format=abi.FIELD_U16T)
     gpu.world.lidar_1081(cfg)
     fields = ref.build_dt(occ)
-    st, keep = _device_state(gpu, cfg, occ, w)
+    st, keep = device_state(gpu, cfg, occ, w)
     seen = 0
     for K in sorted({1, min(4, N), N}):
         for rays in (1, 3):
             p = dict(sensor_range=3.0, max_obs=K, rays=rays)
-            want = _spec(cfg, fields, w, p)
-            _same(_call(gpu, cfg, st, p), want, "K %d rays %d" % (K, rays))
+            want = answer(cfg, fields, w, p)
+            same(call(gpu, cfg, st, p), want, "K %d rays %d" % (K, rays))
             seen += int(want["count"].sum())
     K = min(4, N)
     for what, p, kw in (("fov off", dict(fov=0), {}), ("occlusion off", dict(occlusion=0), {}),
                         ("long range", dict(sensor_range=9.0), {}), ("point pedestrians", dict(ped_radius=0.0), {}),
                         ("skip", {}, dict(skip=(np.arange(E) % 2 == 0).astype(np.uint8)))):
         p = dict(dict(sensor_range=3.0, max_obs=K), **p)
-        _same(_call(gpu, cfg, st, p, **kw), _spec(cfg, fields, w, p, **kw), what)
-    dev = _call(gpu, cfg, st, dict(sensor_range=3.0, max_obs=K), visible=False)
+        same(call(gpu, cfg, st, p, **kw), answer(cfg, fields, w, p, **kw), what)
+    dev = call(gpu, cfg, st, dict(sensor_range=3.0, max_obs=K), visible=False)
     assert (dev["visible"] == 77).all()                                          # NULL: not written
-    want = _spec(cfg, fields, w, dict(sensor_range=3.0, max_obs=K))
+    want = answer(cfg, fields, w, dict(sensor_range=3.0, max_obs=K))
     for k in ("state", "index", "count"):
-        _eq(dev[k], want[k], "without visible: %s" % k)
+        eq(dev[k], want[k], "without visible: %s" % k)
     assert N == 1 or seen > 0
 
 
@@ -114,11 +54,11 @@ def test_field_formats_and_march_rules(gpu, fmt, rule):
     E, N, seed, n_peds = spec.RANDOM_WORLDS[4]
     occ, w = spec.random_world(E, N, spec.RANDOM_SIZE, seed, n_peds)
     cfg = spec.random_config(E, N, spec.RANDOM_SIZE, field_format=fmt, march_rule=rule)
-    st, keep = _device_state(gpu, cfg, occ, w)
+    st, keep = device_state(gpu, cfg, occ, w)
     p = dict(sensor_range=3.0, max_obs=8)
-    want = _spec(cfg, ref.build_dt(occ), w, p)
+    want = answer(cfg, ref.build_dt(occ), w, p)
     assert want["count"].sum() > 40 and (want["visible"] == 0).sum() > 40
-    _same(_call(gpu, cfg, st, p), want, "format %d rule %d" % (fmt, rule))
+    same(call(gpu, cfg, st, p), want, "format %d rule %d" % (fmt, rule))
 
 
 @pytest.mark.parametrize("rule", RULES)
@@ -129,11 +69,11 @@ def test_packed_field_with_an_overflow_plane(gpu, rule):
     cfg = spec.random_config(2, 8, occ.shape[1], field_format=abi.FIELD_U16T, march_rule=rule, shared_field=1)
     fields = ref.build_dt(occ)
     assert fields.max() >= 256.0
-    st, keep = _device_state(gpu, cfg, occ, w, overflow=True)
+    st, keep = device_state(gpu, cfg, occ, w, overflow=True)
     p = dict(sensor_range=30.0, ped_radius=0.1, max_obs=8, fov=0)
-    want = _spec(cfg, fields, w, p)
+    want = answer(cfg, fields, w, p)
     assert want["count"].tolist() == [4, 4] and want["visible"][:, 4:].sum() == 0          # the four in the open; none in the wall
-    _same(_call(gpu, cfg, st, p), want, "overflow plane, rule %d" % rule)
+    same(call(gpu, cfg, st, p), want, "overflow plane, rule %d" % rule)
 
 
 def test_shared_field_and_permuted_map_slots(gpu):
@@ -141,26 +81,26 @@ def test_shared_field_and_permuted_map_slots(gpu):
     p = dict(sensor_range=3.0, max_obs=6)
     occ, w = spec.random_world(E, N, spec.RANDOM_SIZE, seed, shared=True)
     cfg = spec.random_config(E, N, spec.RANDOM_SIZE, field_format=abi.FIELD_U16T, shared_field=1)
-    st, keep = _device_state(gpu, cfg, occ[:1], w)
-    want = _spec(cfg, ref.build_dt(occ[:1]), w, p)
+    st, keep = device_state(gpu, cfg, occ[:1], w)
+    want = answer(cfg, ref.build_dt(occ[:1]), w, p)
     assert want["count"].sum() > 10
-    _same(_call(gpu, cfg, st, p), want, "shared field")
+    same(call(gpu, cfg, st, p), want, "shared field")
     # arena e's map lies in slot perm[e] of the field array
     occ, w = spec.random_world(E, N, spec.RANDOM_SIZE, seed)
     perm = np.array([3, 0, 4, 1, 2])
     stored = np.empty_like(occ); stored[perm] = occ
     cfg = spec.random_config(E, N, spec.RANDOM_SIZE, field_format=abi.FIELD_U16T)
-    st, keep = _device_state(gpu, cfg, stored, w, map_slot=perm)
-    want = _spec(cfg, ref.build_dt(stored), w, p, map_slot=perm)
-    _same(want, _spec(cfg, ref.build_dt(occ), w, p), "the specification's own slot table")
-    _same(_call(gpu, cfg, st, p), want, "permuted slots")
+    st, keep = device_state(gpu, cfg, stored, w, map_slot=perm)
+    want = answer(cfg, ref.build_dt(stored), w, p, map_slot=perm)
+    same(want, answer(cfg, ref.build_dt(occ), w, p), "the specification's own slot table")
+    same(call(gpu, cfg, st, p), want, "permuted slots")
 
 
 # ---- c. the hand-made cases, with their known answers -------------------------------------------------------------------------
 def _wall(gpu, peds, fmt, robot_cell_occupied=False, lidar_270=False, skip=None, **params):
     cfg = spec.wall_config(len(peds), lidar_270=lidar_270, field_format=fmt)
-    st, keep = _device_state(gpu, cfg, spec.wall_map(robot_cell_occupied)[None], spec.wall_case(peds))
-    return _call(gpu, cfg, st, dict(spec.DEFAULT, **params), skip=skip)
+    st, keep = device_state(gpu, cfg, spec.wall_map(robot_cell_occupied)[None], spec.wall_case(peds))
+    return call(gpu, cfg, st, dict(spec.DEFAULT, **params), skip=skip)
 
 
 @pytest.mark.parametrize("fmt", [abi.FIELD_F32, abi.FIELD_U16T])
@@ -200,16 +140,16 @@ def test_closed_loop_beside_the_oracle(gpu, protocol):
                                  auto_reset=mode, n_spawn=8, seed=4343, field_format=abi.FIELD_U16T)
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 4343)
-    g, r = _pair(gpu, cfg, occ, 5, final_obs=(mode == abi.AUTORESET_SAME_STEP), min_goal_dist=1.5, max_goal_dist=4.0)
+    g, r, _ = sim_and_oracle(gpu, cfg, occ, 5, final_obs=(mode == abi.AUTORESET_SAME_STEP), min_goal_dist=1.5, max_goal_dist=4.0)
     fields = ref.build_dt(occ)
     p = dict(spec.DEFAULT, sensor_range=4.0, max_obs=K)            # (every key: NavSim's own defaults are the footprints')
     g.enable_ped_observe(p)
 
     def check(what, skip=None):
-        t_skip = None if skip is None else _t(gpu, skip)
+        t_skip = None if skip is None else to_device(gpu, skip)
         dev = {k: v.cpu().numpy() for k, v in g.ped_observe(skip=t_skip).items()}
         want = spec.observe(r.cfg, fields, r.a["robot_pose"], r.a["n_peds"], r.a["ped_pose"], r.a["ped_vel"], p, skip=skip)
-        _same(dev, want, what)
+        same(dev, want, what)
         return want
 
     check("after the reset")
@@ -217,10 +157,10 @@ def test_closed_loop_beside_the_oracle(gpu, protocol):
     ends = seen = hidden = skipped = 0
     sets = set()
     for t in range(30):
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, E, t)
         go, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         ro, rout = r.step(act)
-        _eq(go.cpu().numpy(), ro, "obs at step %d" % t)
+        eq(go.cpu().numpy(), ro, "obs at step %d" % t)
         done = rout["done"].copy()
         ends += int(done.sum())
         want = check("step %d" % t, skip=done if protocol == "next_step" else None)
@@ -252,13 +192,13 @@ def _env(**kw):
 def _direct(gpu, env, skip=None):
     """A direct navsim_ped_observe on the environment's current state, into buffers of its own."""
     sim = env.sim
-    return _call(gpu, sim.cfg, sim.st, sim.obs_params, skip=skip)
+    return call(gpu, sim.cfg, sim.st, sim.obs_params, skip=skip)
 
 
 def _from_device_state(env, skip=None):
     """The specification on the environment's state, read back from the device (the maps through their occupancy)."""
     sim = env.sim
-    s = sim.numpy_state(*STATE_KEYS)
+    s = sim.numpy_state(*STATE)
     fields = ref.build_dt(np.stack([sim.occupancy(e) for e in range(env.num_envs)]))
     p = sim.obs_params
     return spec.observe(sim.cfg, fields, s["robot_pose"], s["n_peds"], s["ped_pose"], s["ped_vel"],
@@ -290,8 +230,8 @@ def test_info_humans(gpu, model, mode):
     assert set(h) == set(KEYS)
     assert (h["state"].dtype, h["index"].dtype, h["count"].dtype, h["visible"].dtype) == (torch.float32, torch.int32, torch.int32, torch.bool)
     assert (tuple(h["state"].shape), tuple(h["index"].shape), tuple(h["count"].shape), tuple(h["visible"].shape)) == ((E, K, 5), (E, K), (E,), (E, N))
-    _same(_host(h), _direct(gpu, env), "after reset()")
-    _same(_host(h), _from_device_state(env), "after reset(): specification")
+    same(_host(h), _direct(gpu, env), "after reset()")
+    same(_host(h), _from_device_state(env), "after reset(): specification")
     prev, ptrs, ends, empty = None, set(), 0, 0
     for t in range(14):
         kw = dict(human_actions=np.full((E, N, 2), 0.2)) if model == "external" else {}
@@ -301,13 +241,13 @@ def test_info_humans(gpu, model, mode):
         ptrs.add(h["state"].data_ptr())
         skip = done.cpu().numpy().astype(np.uint8) if mode == "next_step" else None
         now = _host(h)
-        _same(now, _direct(gpu, env, skip=skip), "step %d" % t)
-        _same(now, _from_device_state(env, skip=skip), "step %d: specification" % t)
+        same(now, _direct(gpu, env, skip=skip), "step %d" % t)
+        same(now, _from_device_state(env, skip=skip), "step %d: specification" % t)
         if mode == "next_step" and skip.any():
             assert (now["count"][skip != 0] == 0).all() and (now["index"][skip != 0] == -1).all()
             empty += int(skip.sum())
         if prev is not None:                                                     # the pair lifetime
-            _same(_host(prev[0]), prev[1], "step %d's rows after step %d" % (t - 1, t))
+            same(_host(prev[0]), prev[1], "step %d's rows after step %d" % (t - 1, t))
         prev = (h, now)
         ends += int(done.sum())
         assert "humans" not in info.get("final_observation", {})
@@ -317,7 +257,7 @@ def test_info_humans(gpu, model, mode):
     env.reset(mask=mask)
     after = _host(env.observed_humans())
     assert (env.sim.numpy_state("robot_pose")["robot_pose"][mask] != before[mask]).any(axis=1).all()      # they did restart
-    _same(after, _from_device_state(env, skip=env.sim.out["done"].cpu().numpy() if mode == "next_step" else None), "after reset(mask)")
+    same(after, _from_device_state(env, skip=env.sim.out["done"].cpu().numpy() if mode == "next_step" else None), "after reset(mask)")
     env.close()
 
 
@@ -330,7 +270,7 @@ def test_worlds_that_draw_a_map_per_episode(gpu, pipeline):
     ends = 0
     for t in range(12):
         _, _, done, info = env.step(_drive(8))
-        _same(_host(info["humans"]), _from_device_state(env), "step %d" % t)
+        same(_host(info["humans"]), _from_device_state(env), "step %d" % t)
         ends += int(done.sum())
     assert env._step_path == ("pipelined" if pipeline is None else "plain") and ends >= 8
     env.close()
@@ -347,7 +287,7 @@ def test_single_environment_returns_numpy(gpu):
         assert h["index"].shape == (3,) and h["index"].dtype == np.int32 and isinstance(h["count"], int)
         assert h["visible"].shape == (env.cfg.max_peds,) and h["visible"].dtype == bool
         want = _from_device_state(env)
-        _eq(h["state"], want["state"][0], "state"); _eq(h["index"], want["index"][0], "index")
+        eq(h["state"], want["state"][0], "state"); eq(h["index"], want["index"][0], "index")
         assert h["count"] == want["count"][0] and h["visible"].tolist() == (want["visible"][0] != 0).tolist()
     env.close()
 

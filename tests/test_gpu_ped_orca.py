@@ -6,38 +6,10 @@ import pytest
 
 import ped_orca_spec as spec
 from nav_gym_amd import abi
-from test_gpu_autoreset import gpu, _t, _eq, _np, _actions, _state_eq  # noqa: F401  (gpu: the module's fixture)
-from test_gpu_time_limit import _cfg, _world, _sim, _ref, _env, _acts, _rollout
+from gpu_support import (gpu, action_rows, env_rollout, eq, fresh_oracle, fresh_sim, limit_config, limit_world, nav_env,  # noqa: F401
+                         orca_pair, random_actions, small_orca_config, state_equal, to_numpy, ORCA_SENTINEL as SENTINEL)
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = -7.25
-
-
-def _small_cfg(gpu, E, N, size=240, mode=abi.AUTORESET_SAME_STEP):
-    cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, max_peds=N, n_scan_stack=1, ped_model=abi.PED_EXTERNAL,
-                                 auto_reset=mode, n_spawn=8, seed=4343, field_format=abi.FIELD_U16T)
-    gpu.world.lidar_full_circle(cfg, 64)
-    return cfg
-
-
-def _pair(gpu, cfg, n_peds, moving=True, hand_made=None, **world_kw):
-    """The same world on the device and in the oracle; moving: pedestrians and robots already have velocities."""
-    occ = gpu.world.make_maps(cfg.n_envs, cfg.map_h, 4343)
-    arrays, host = _world(gpu, cfg, occ, n_peds=n_peds, v_pref_range=(0.3, 0.6), **world_kw)
-    if hand_made is not None:
-        hand_made(host)
-        for k in ("ped_waypoints", "ped_n_waypoints"):
-            arrays[k] = _t(gpu, host[k])
-    g, r = _sim(gpu, cfg, arrays), _ref(cfg, host)
-    if moving:                                                       # (after the first observation, which clears prev_action)
-        rng = np.random.default_rng(11)
-        vel = rng.uniform(-0.5, 0.5, host["ped_vel"].shape)
-        prev = np.stack([rng.uniform(0.0, 0.5, cfg.n_envs), rng.uniform(-0.64, 0.64, cfg.n_envs)], axis=1)
-        g.t["ped_vel"].copy_(_t(gpu, vel)); r.a["ped_vel"][...] = vel
-        g.t["prev_action"].copy_(_t(gpu, prev)); r.a["prev_action"][...] = prev
-    return g, r
-
 
 def _check_call(gpu, g, r, p, what):
     g.t["ped_cmd"].fill_(SENTINEL)
@@ -47,8 +19,8 @@ def _check_call(gpu, g, r, p, what):
     live = np.arange(r.cfg.max_peds)[None, :] < r.a["n_peds"][:, None]
     assert live.any() or r.cfg.n_envs == 0
     assert (want_cmd[~live] == SENTINEL).all() and not (want_cmd[live] == SENTINEL).any()
-    _eq(got, want_cmd, "ped_cmd (%s)" % what)                        # live rows, and dead rows still holding the sentinel
-    _eq(g.numpy_state("ped_wp_head")["ped_wp_head"], want_head, "ped_wp_head (%s)" % what)
+    eq(got, want_cmd, "ped_cmd (%s)" % what)                        # live rows, and dead rows still holding the sentinel
+    eq(g.numpy_state("ped_wp_head")["ped_wp_head"], want_head, "ped_wp_head (%s)" % what)
     return want_cmd, want_head
 
 
@@ -70,13 +42,13 @@ def _two_pops(host):
     (5, 1, dict(robot_visible=0)),             # lists of no entries
 ])
 def test_single_call_vs_specification(gpu, E, N, kw):
-    cfg = _small_cfg(gpu, E, N)
+    cfg = small_orca_config(gpu, E, N)
     n_peds = N
     if N == 8:
         n_peds = np.array([(3 * e + 2) % 9 for e in range(E)], np.int32)         # 2, 5, 8, 2, ...; arena 2 -> 8
         n_peds[1] = 6; n_peds[4] = 0; n_peds[7] = 1; n_peds[44] = 0
         assert set(n_peds) >= {0, 1, 8}
-    g, r = _pair(gpu, cfg, n_peds, hand_made=_two_pops if N == 8 else None)
+    g, r = orca_pair(gpu, cfg, n_peds, hand_made=_two_pops if N == 8 else None)
     p = spec.params(cfg, **kw)
     _, head = _check_call(gpu, g, r, p, "E %d N %d %s" % (E, N, kw))
     if N == 8:
@@ -86,8 +58,8 @@ def test_single_call_vs_specification(gpu, E, N, kw):
 def test_crowded_world_closed_loop(gpu):
     """12 pedestrians per 6 m arena: they do come closer than the combined radius, so the overlapping-agents branch and the
     infeasible linear program (lp3) run.  80 steps, every call against the specification."""
-    cfg = _small_cfg(gpu, 8, 12, size=120)
-    g, r = _pair(gpu, cfg, 12, moving=False, min_goal_dist=1.0, max_goal_dist=3.0, robot_clearance=0.6)
+    cfg = small_orca_config(gpu, 8, 12, size=120)
+    g, r = orca_pair(gpu, cfg, 12, moving=False, min_goal_dist=1.0, max_goal_dist=3.0, robot_clearance=0.6)
     p = spec.params(cfg)
     comb = 2 * (p["ped_radius"] + 0.01)
     iu = np.triu_indices(12, 1)
@@ -100,9 +72,9 @@ def test_crowded_world_closed_loop(gpu):
         cmd, head = _check_call(gpu, g, r, p, "step %d" % t)
         r.a["ped_wp_head"][...] = head
         r.set_ped_cmd(cmd)
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, cfg.n_envs, t)
         g.step(gpu.torch.from_numpy(act).to(gpu.dev)); r.step(act)
-    _state_eq(g, r, "after 80 steps")
+    state_equal(g, r, "after 80 steps", skip=("counters",))
     print("crowded world: %d of %d pair-steps closer than the combined radius" % (overlaps, 8 * 66 * 80))
     assert overlaps > 0
 
@@ -111,9 +83,9 @@ def test_crowded_world_closed_loop(gpu):
 def test_closed_loop_vs_oracle(gpu, mode):
     """ped_orca(); step(act) for 40 steps of 48 arenas with 1081 beams: observations, every output and every state array equal
     specification + oracle step bit for bit, through episode ends and restarts."""
-    cfg = _cfg(gpu, mode, abi.PED_EXTERNAL)
-    arrays, host = _world(gpu, cfg, v_pref_range=(0.3, 0.6))
-    g, r = _sim(gpu, cfg, arrays), _ref(cfg, host)
+    cfg = limit_config(gpu, mode, abi.PED_EXTERNAL)
+    arrays, host = limit_world(gpu, cfg, v_pref_range=(0.3, 0.6))
+    g, r = fresh_sim(gpu, cfg, arrays), fresh_oracle(cfg, host)
     p = spec.params(cfg)
     rng = np.random.default_rng(5)
     ends = 0
@@ -122,14 +94,14 @@ def test_closed_loop_vs_oracle(gpu, mode):
         r.a["ped_wp_head"][...] = head
         r.set_ped_cmd(cmd)
         g.ped_orca()
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, cfg.n_envs, t)
         obs, out = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         ro, rout = r.step(act)
-        _eq(obs.cpu().numpy(), ro, "observations at step %d" % t)
-        out = _np(out)
+        eq(obs.cpu().numpy(), ro, "observations at step %d" % t)
+        out = to_numpy(out)
         for k in rout:
-            _eq(out[k], rout[k], "%s at step %d" % (k, t))
-        _state_eq(g, r, "at step %d" % t)
+            eq(out[k], rout[k], "%s at step %d" % (k, t))
+        state_equal(g, r, "at step %d" % t, skip=("counters",))
         ends += int(rout["done"].sum())
     assert ends >= 5, ends
 
@@ -142,12 +114,12 @@ def _spec_state(env):
 
 def test_gym_surface_equals_external_fed_by_the_specification(gpu):
     kw = dict(num_humans=5, seed=23)
-    a = _env(pedestrian_model="orca", **kw)
-    b = _env(pedestrian_model="external", **kw)
+    a = nav_env(pedestrian_model="orca", **kw)
+    b = nav_env(pedestrian_model="external", **kw)
     oa, ob = a.reset()["observation"], b.reset()["observation"]
     assert gpu.torch.equal(oa, ob)
     p = spec.params(a.sim.cfg)
-    for t, act in enumerate(_acts(25, 48)):
+    for t, act in enumerate(action_rows(25, 48)):
         cmd, _, _ = spec.ped_orca(b.sim.cfg, _spec_state(b), p)
         xa, xb = a.step(act), b.step(act, human_actions=cmd)
         assert gpu.torch.equal(xa[0]["observation"], xb[0]["observation"]), t
@@ -160,9 +132,9 @@ def test_gym_surface_equals_external_fed_by_the_specification(gpu):
 
 
 def test_gym_surface_with_new_maps_per_episode(gpu):
-    env = _env(pedestrian_model="orca", num_humans=5, randomize_maps=True, pregen_pipeline=0)
+    env = nav_env(pedestrian_model="orca", num_humans=5, randomize_maps=True, pregen_pipeline=0)
     assert env.pregen_pipeline == 0
-    rec = _rollout(env, _acts(30, 48))
+    rec = env_rollout(env, action_rows(30, 48))
     assert not env._graphed and sum(int(x["done"].sum()) for x in rec[1:]) > 0
     assert env.counters()["regen_unserved"] == 0
     env.close()
@@ -170,11 +142,11 @@ def test_gym_surface_with_new_maps_per_episode(gpu):
 
 def test_two_shards_equal_one_world(gpu):
     kw = dict(pedestrian_model="orca", num_humans=5)
-    full = _env(**kw)
-    shards = [_env(num_envs=24, env_index_base=24 * i, **kw) for i in (0, 1)]
-    acts = _acts(12, 48)
-    rf = _rollout(full, acts)
-    rs = [_rollout(s, [x[24 * i:24 * i + 24] for x in acts]) for i, s in enumerate(shards)]
+    full = nav_env(**kw)
+    shards = [nav_env(num_envs=24, env_index_base=24 * i, **kw) for i in (0, 1)]
+    acts = action_rows(12, 48)
+    rf = env_rollout(full, acts)
+    rs = [env_rollout(s, [x[24 * i:24 * i + 24] for x in acts]) for i, s in enumerate(shards)]
     torch = gpu.torch
     assert torch.equal(rf[0], torch.cat([r[0] for r in rs]))
     for t in range(1, len(rf)):

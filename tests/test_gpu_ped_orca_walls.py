@@ -8,13 +8,11 @@ import functools
 import numpy as np
 import pytest
 
-import orca_scenes as scenes
 import ped_orca_spec as spec
 import ped_orca_walls_scenes as ws
 import ped_orca_walls_spec as wspec
 from nav_gym_amd import abi
-from test_gpu_autoreset import gpu, _t, _eq  # noqa: F401  (gpu: the module's fixture)
-from test_gpu_time_limit import _world, _sim, _acts
+from gpu_support import gpu, action_rows, eq, fresh_sim, limit_world, to_device  # noqa: F401  (gpu: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,15 +26,15 @@ def _device_world(gpu, E, N, occ):
     cfg = gpu.lib.default_config(n_envs=E, map_h=ws.SIZE, map_w=ws.SIZE, max_peds=N, n_scan_stack=1, ped_model=abi.PED_EXTERNAL,
                                  auto_reset=abi.AUTORESET_NONE, n_spawn=8, seed=4343, field_format=abi.FIELD_U16T, time_step=0.2)
     gpu.world.lidar_full_circle(cfg, 64)
-    arrays, _ = _world(gpu, cfg, occ, n_peds=N, v_pref_range=(0.3, 0.6), robot_clearance=0.6)
+    arrays, _ = limit_world(gpu, cfg, occ, n_peds=N, v_pref_range=(0.3, 0.6), robot_clearance=0.6)
     assert "rect_index" in arrays and (cfg.resolution, cfg.origin_x, cfg.origin_y) == (ws.RES, 0.0, 0.0)
-    g = _sim(gpu, cfg, arrays)
+    g = fresh_sim(gpu, cfg, arrays)
     return cfg, g, wspec.decode_rows(g.t["rect_index"].cpu().numpy())
 
 
 def _load(gpu, g, a):
     for k in STATE:
-        g.t[k].copy_(_t(gpu, np.ascontiguousarray(a[k])).to(g.t[k].dtype).reshape(g.t[k].shape))
+        g.t[k].copy_(to_device(gpu, np.ascontiguousarray(a[k])).to(g.t[k].dtype).reshape(g.t[k].shape))
     g.t["ped_cmd"].fill_(SENTINEL)
 
 
@@ -49,9 +47,9 @@ def _call(gpu, g, cfg, a, p, rects, K, what):
     want_cmd, want_head, want_dropped, census = wspec.ped_orca_walls(cfg, a, p, rects, K)
     live = np.arange(cfg.max_peds)[None, :] < np.clip(a["n_peds"], 0, cfg.max_peds)[:, None]
     assert (want_cmd[~live] == SENTINEL).all() and not (want_cmd[live] == SENTINEL).any()
-    _eq(got, want_cmd, "ped_cmd (%s)" % what)                         # live rows, and dead rows still holding the sentinel
-    _eq(g.t["ped_wp_head"].cpu().numpy(), want_head, "ped_wp_head (%s)" % what)
-    _eq(dropped.cpu().numpy(), np.where(live, want_dropped, -1), "dropped (%s)" % what)
+    eq(got, want_cmd, "ped_cmd (%s)" % what)                         # live rows, and dead rows still holding the sentinel
+    eq(g.t["ped_wp_head"].cpu().numpy(), want_head, "ped_wp_head (%s)" % what)
+    eq(dropped.cpu().numpy(), np.where(live, want_dropped, -1), "dropped (%s)" % what)
     return got, census
 
 
@@ -104,7 +102,7 @@ def test_no_rectangles_is_navsim_ped_orca(gpu):
     got = g.ped_orca_walls({k: p[k] for k in spec.KEYS}, 0, dropped)
     assert gpu.torch.equal(got, want) and gpu.torch.equal(g.t["ped_wp_head"], want_head)
     live = np.arange(N)[None, :] < a["n_peds"][:, None]
-    _eq(dropped.cpu().numpy(), np.where(live, 0, -1), "dropped at max_rects 0")
+    eq(dropped.cpu().numpy(), np.where(live, 0, -1), "dropped at max_rects 0")
     assert (want.cpu().numpy()[live] != SENTINEL).all()
 
 
@@ -118,7 +116,7 @@ def test_permuted_map_slot(gpu):
     a, p = ws.state(s, cfg), spec.params(cfg, time_horizon_obst=2.0)
     straight, _ = _call(gpu, g, cfg, a, p, rects, 8, "own slots")
     perm = np.array([3, 0, 5, 1, 2, 4], np.int32)
-    slots = _t(gpu, perm)
+    slots = to_device(gpu, perm)
     g.st.map_slot = slots.data_ptr()
     try:
         permuted, _ = _call(gpu, g, cfg, a, p, rects[perm], 8, "permuted slots")
@@ -143,7 +141,7 @@ def test_regenerated_world(gpu):
     assert "map_slot" not in sim.t
     rects = wspec.decode_rows(sim.t["rect_index"].cpu().numpy())
     assert all(int(r.any(1).sum()) >= 4 for r in rects), [int(r.any(1).sum()) for r in rects]      # the ring at least
-    for act in _acts(3, 6):                                          # pedestrians and robots in motion
+    for act in action_rows(3, 6):                                          # pedestrians and robots in motion
         env.step(act)
     rects = wspec.decode_rows(sim.t["rect_index"].cpu().numpy())
     a = _spec_state(sim)
@@ -152,11 +150,11 @@ def test_regenerated_world(gpu):
         p = spec.params(sim.cfg, time_horizon_obst=tho)
         want_cmd, want_head, want_dropped, census = wspec.ped_orca_walls(sim.cfg, a, p, rects, K)
         dropped = gpu.torch.zeros((6, sim.cfg.max_peds), dtype=gpu.torch.int32, device=gpu.dev)
-        sim.t["ped_wp_head"].copy_(_t(gpu, a["ped_wp_head"]))
+        sim.t["ped_wp_head"].copy_(to_device(gpu, a["ped_wp_head"]))
         got = sim.ped_orca_walls({k: p[k] for k in spec.KEYS}, K, dropped).cpu().numpy()
-        _eq(got, want_cmd, "ped_cmd on the regenerated world, max_rects %d" % K)
-        _eq(sim.t["ped_wp_head"].cpu().numpy(), want_head, "ped_wp_head on the regenerated world")
-        _eq(dropped.cpu().numpy(), want_dropped, "dropped on the regenerated world")
+        eq(got, want_cmd, "ped_cmd on the regenerated world, max_rects %d" % K)
+        eq(sim.t["ped_wp_head"].cpu().numpy(), want_head, "ped_wp_head on the regenerated world")
+        eq(dropped.cpu().numpy(), want_dropped, "dropped on the regenerated world")
         binds += census["walls bind"]
     assert binds > 0
     env.close()
@@ -173,7 +171,7 @@ def test_through_the_env(gpu):
     occ = [a.sim.occupancy(e) for e in range(4)]
     cfg = a.sim.cfg
     assert int(a.sim.t["n_peds"].sum()) > 0
-    for t, act in enumerate(_acts(50, 4)):
+    for t, act in enumerate(action_rows(50, 4)):
         cmd = b.sim.ped_orca_walls(dict(time_horizon_obst=2.0), 8).clone()
         xa, xb = a.step(act), b.step(act, human_actions=cmd)
         assert gpu.torch.equal(xa[0]["observation"], xb[0]["observation"]), t

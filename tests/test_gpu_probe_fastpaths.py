@@ -10,29 +10,13 @@ import pytest
 
 import probe_fastpaths_spec as spec
 import ref
-from nav_gym_amd import abi, robots
+from gpu_support import gpu, device_world, eq, host_arrays, state_equal, to_device  # noqa: F401  (gpu: the module's fixture)
+from nav_gym_amd import abi
 
 pytestmark = pytest.mark.gpu
 
-NOT_STATE = ("field", "field_overflow", "rect_table", "rect_index")
 STEPS = 12
 RULES = {"f32": abi.MARCH_F32, "f32_fma": abi.MARCH_F32_FMA, "f64": abi.MARCH_F64}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from nav_gym_amd import lib, sim, world
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    lib.load()
-    return type("G", (), dict(torch=torch, lib=lib, sim=sim, world=world, dev=torch.device("cuda:0")))
-
-
-def _eq(a, b, what):
-    a = np.asarray(a); b = np.asarray(b)
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        raise AssertionError("%s: %d mismatches, first at %s: %r != %r" % (what, len(bad), bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
 
 
 def _actions(E, t):
@@ -52,18 +36,14 @@ def _world(gpu, kind, B, step_block, rule):
                                  auto_reset=1, n_spawn=2, seed=14, step_block=step_block, rect_lds=2, march_rule=rule,
                                  field_format=abi.FIELD_U16T)
     spec.lidar(cfg, B)
-    arrays = gpu.world.make_world(cfg, occ, n_peds=0, device=gpu.dev, robot_clearance=0.3)
+    arrays = device_world(gpu, cfg, occ, 0, robot_clearance=0.3)
     assert cfg.closed_maps == 1 and "rect_index" in arrays, "the scene does not take the LDS form of the march (RECT = 2)"
     xy = spec.poses_xy(cfg, poses)
     spawn = np.stack([xy, np.roll(xy, 1, axis=0)], axis=1)                  # [E, 2, 3]: the arena's own pose and its neighbour's
     goal = np.repeat(spec.goals_xy(cfg, poses, size)[:, None], 2, axis=1).copy()   # (out of reach)
-    t = lambda a: gpu.torch.from_numpy(np.ascontiguousarray(a)).to(gpu.dev)
-    arrays["spawn_pose"] = t(spawn); arrays["spawn_goal"] = t(goal)
-    arrays["robot_pose"] = t(spawn[:, 0]); arrays["robot_goal"] = t(goal[:, 0])
-    for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
-        arrays[key] = gpu.sim.scan_threshold(cfg, t(robots.footprint_array("keti", name)))
-    host = {k: v.cpu().numpy() for k, v in arrays.items() if k not in NOT_STATE}
-    host["field"] = ref.build_dt(occ)
+    arrays["spawn_pose"] = to_device(gpu, spawn); arrays["spawn_goal"] = to_device(gpu, goal)
+    arrays["robot_pose"] = to_device(gpu, spawn[:, 0]); arrays["robot_goal"] = to_device(gpu, goal[:, 0])
+    host = host_arrays(arrays, occ)
     tiles = (size + 7) // 8
     pairs = arrays["rect_index"].cpu().numpy().reshape(E, -1)[:, 2048:2048 + tiles * tiles * 2].copy().view(np.uint16).reshape(E, tiles, tiles)
     return cfg, gpu.sim.NavSim(cfg, arrays), ref.RefSim(cfg, host), host["field"], pairs
@@ -72,7 +52,7 @@ def _world(gpu, kind, B, step_block, rule):
 def _rollout(gpu, kind, B, step_block, rule):
     cfg, g, r, field, pairs = _world(gpu, kind, B, step_block, RULES[rule])
     E = cfg.n_envs
-    _eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
+    eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
     scans = [(e,) + tuple(r.a["robot_pose"][e]) for e in range(E)]
     crashes = 0
     for t in range(STEPS):
@@ -80,14 +60,11 @@ def _rollout(gpu, kind, B, step_block, rule):
         go, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         ro, rout = r.step(act)
         for k in rout:
-            _eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
-        _eq(go.cpu().numpy(), ro, "obs at step %d" % t)
+            eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
+        eq(go.cpu().numpy(), ro, "obs at step %d" % t)
         crashes += int((rout["is_crash"] != 0).sum())
         scans += [(e,) + tuple(r.a["robot_pose"][e]) for e in range(E)]
-    gs = g.numpy_state()
-    for k, v in r.a.items():
-        if k in gs and k not in NOT_STATE:
-            _eq(gs[k], v, "state %s at the end" % k)
+    state_equal(g, r, "at the end")
     assert crashes > 0, "no arena of the oracle's run crashed and restarted"
     park = 16 if step_block == 256 else 0                                   # (kernels_step.hpp step_parks)
     return spec.round_forms(cfg, field, pairs, scans, park, ref.beam_dirs)

@@ -9,8 +9,7 @@ import pytest
 
 import ref
 from nav_gym_amd import abi
-from test_gpu_autoreset import _actions, _eq, _pair, _state_eq
-from test_gpu_workspaces import _rect_pairs, _sim, gpu  # noqa: F401  (the module's fixture and world helpers)
+from gpu_support import gpu, device_sim, eq, random_actions, rect_pairs, sim_and_oracle, state_equal  # noqa: F401  (gpu: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,8 +26,8 @@ def _world(gpu, E, size, mode, seed, n_peds=3, max_peds=4, min_steps=0, **kw):
 
 def _trio(gpu, cfg, occ, n_peds, **wkw):
     """(simulator that will stage worlds, simulator that will not, the oracle): the same world three times"""
-    u, r = _pair(gpu, cfg, occ, n_peds, **wkw)
-    p = _sim(gpu, cfg, occ, n_peds, **wkw)
+    u, r, _ = sim_and_oracle(gpu, cfg, occ, n_peds, **wkw)
+    p = device_sim(gpu, cfg, occ, n_peds, **wkw)
     return p, u, r
 
 
@@ -40,7 +39,7 @@ def _state(g):
         if k in ("arena_cost", "launch_order", "counters", "map_slot") or "_ws" in k:
             continue
         if k == "rect_index":
-            v = _rect_pairs(g.by_arena(k), g.cfg.map_h, g.cfg.map_w)
+            v = rect_pairs(g.by_arena(k), g.cfg.map_h, g.cfg.map_w)
         if k == "ped_waypoints":        # slots beyond a route's length keep whatever the buffer held
             live = np.arange(g.cfg.max_waypoints)[None, None, :] < s["ped_n_waypoints"][..., None]
             v = np.where(live[..., None], v, 0.0)
@@ -52,13 +51,13 @@ def _state(g):
 def _twin_eq(gpu, p, u, what):
     """rows, every output, every state array and the count of served arenas of the two simulators"""
     gpu.torch.cuda.synchronize()
-    _eq(p.obs.cpu().numpy(), u.obs.cpu().numpy(), "rows %s" % what)
+    eq(p.obs.cpu().numpy(), u.obs.cpu().numpy(), "rows %s" % what)
     for k in u.out:
-        _eq(p.out[k].cpu().numpy(), u.out[k].cpu().numpy(), "%s %s" % (k, what))
+        eq(p.out[k].cpu().numpy(), u.out[k].cpu().numpy(), "%s %s" % (k, what))
     sp, su = _state(p), _state(u)
     assert set(sp) == set(su), set(sp) ^ set(su)
     for k in su:
-        _eq(sp[k], su[k], "state %s %s" % (k, what))
+        eq(sp[k], su[k], "state %s %s" % (k, what))
     assert p.counters()["regen_served"] == u.counters()["regen_served"], what
 
 
@@ -86,39 +85,39 @@ def _reset_both(gpu, p, u, mask, what, r=None):
     m = gpu.torch.from_numpy(np.asarray(mask, dtype=np.uint8)).to(gpu.dev)
     rows_p = p.reset_arenas(m, new_world=True).cpu().numpy()
     rows_u = u.reset_arenas(m, new_world=True).cpu().numpy()
-    _eq(rows_p, rows_u, "returned rows %s" % what)
+    eq(rows_p, rows_u, "returned rows %s" % what)
     _twin_eq(gpu, p, u, what)
     keep = np.asarray(mask) == 0
     after = _state(p)
-    _eq(rows_p[keep], rows_before[keep], "rows of the unmasked arenas %s" % what)
+    eq(rows_p[keep], rows_before[keep], "rows of the unmasked arenas %s" % what)
     for k in before:
         if before[k].shape[0] != len(keep):
-            _eq(after[k], before[k], "state %s %s" % (k, what))
+            eq(after[k], before[k], "state %s %s" % (k, what))
             continue
-        _eq(after[k][keep], before[k][keep], "state %s of the unmasked arenas %s" % (k, what))
+        eq(after[k][keep], before[k][keep], "state %s of the unmasked arenas %s" % (k, what))
     assert (p.t["episode"].cpu().numpy()[~keep] > 0).all()
     if r is not None:
-        _eq(rows_u, _oracle_reset(r, mask), "rows against the oracle %s" % what)
-        _eq(u.out["done"].cpu().numpy(), r.out["done"], "done flags against the oracle %s" % what)
-        _state_eq(u, r, "against the oracle %s" % what, skip=("ped_waypoints",))
+        eq(rows_u, _oracle_reset(r, mask), "rows against the oracle %s" % what)
+        eq(u.out["done"].cpu().numpy(), r.out["done"], "done flags against the oracle %s" % what)
+        state_equal(u, r, "against the oracle %s" % what, skip=("counters", "ped_waypoints"))
         assert u.counters()["regen_served"] == r.counters()["regen_served"], what
 
 
 def _step_both(gpu, rng, cfg, t, p, u, r=None):
-    act = _actions(rng, cfg, t)
+    act = random_actions(rng, cfg.n_envs, t)
     a = gpu.torch.from_numpy(act).to(gpu.dev)
     op, outp = p.step(a)
     ou, outu = u.step(a)
     for k in ("reward", "done", "is_success", "is_crash", "distance"):
-        _eq(outp[k].cpu().numpy(), outu[k].cpu().numpy(), "%s at step %d" % (k, t))
+        eq(outp[k].cpu().numpy(), outu[k].cpu().numpy(), "%s at step %d" % (k, t))
     done = outu["done"].cpu().numpy() != 0
     p.regen(); u.regen()                   # (an arena that installed inside the step has its new world's rows and goals already)
-    _eq(p.obs.cpu().numpy(), u.obs.cpu().numpy(), "rows after regen at step %d" % t)
+    eq(p.obs.cpu().numpy(), u.obs.cpu().numpy(), "rows after regen at step %d" % t)
     for k in u.out:
-        _eq(p.out[k].cpu().numpy(), u.out[k].cpu().numpy(), "%s after regen at step %d" % (k, t))
+        eq(p.out[k].cpu().numpy(), u.out[k].cpu().numpy(), "%s after regen at step %d" % (k, t))
     if r is not None:
         r.step(act)
-        _eq(u.obs.cpu().numpy(), r.regen(), "rows against the oracle after regen at step %d" % t)
+        eq(u.obs.cpu().numpy(), r.regen(), "rows against the oracle after regen at step %d" % t)
     return done
 
 
@@ -225,8 +224,8 @@ def test_nothing_staged_means_everybody_is_late_and_still_correct(gpu, monkeypat
 def test_reset_of_some_arenas_in_worlds_of_corridor_maps_with_planned_starts(gpu):
     E = 8
     cfg, occ, n_peds = _world(gpu, E, 200, abi.AUTORESET_SAME_STEP, seed=19, regen_plan=1, regen_indoor_ratio=0.5)
-    u, r = _pair(gpu, cfg, occ, n_peds, plan_paths=True)
-    p = _sim(gpu, cfg, occ, n_peds, plan_paths=True)
+    u, r, _ = sim_and_oracle(gpu, cfg, occ, n_peds, plan_paths=True)
+    p = device_sim(gpu, cfg, occ, n_peds, plan_paths=True)
     p.enable_pregen(pipeline=2, install=True)
     assert len(p.stage_lane) == 2 and "costmap" in p.t
     rng = np.random.default_rng(2)

@@ -16,32 +16,12 @@ import pytest
 
 import probe_fastpaths_spec as spec
 import ref
-from nav_gym_amd import abi, robots
+from gpu_support import gpu, device_world, eq, host_arrays, state_equal, to_device  # noqa: F401  (gpu: the module's fixture)
+from nav_gym_amd import abi
 
 pytestmark = pytest.mark.gpu
 
-NOT_STATE = ("field", "field_overflow", "rect_table", "rect_index")
 STEPS = 12
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from nav_gym_amd import lib, sim, world
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    lib.load()
-    return type("G", (), dict(torch=torch, lib=lib, sim=sim, world=world, dev=torch.device("cuda:0")))
-
-
-def _eq(a, b, what):
-    a = np.asarray(a); b = np.asarray(b)
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        raise AssertionError("%s: %d mismatches, first at %s: %r != %r" % (what, len(bad), bad[0], a[tuple(bad[0])], b[tuple(bad[0])]))
-
-
-def _t(gpu, a):
-    return gpu.torch.from_numpy(np.ascontiguousarray(a)).to(gpu.dev)
 
 
 # ------------------------------------------------------------------------------------------------ directions
@@ -52,7 +32,7 @@ GUARD = 64.0                               # beam_dir_fast declines |lin + lth| 
 def _codes(gpu, lth, lin):
     """debug function 13 on whole wavefronts: 0 = accepted and equal to beam_dir(), 1 = not accepted, 2 = accepted and different"""
     assert len(lth) % 64 == 0 and len(lth) == len(lin)
-    return gpu.sim.debug_math(13, _t(gpu, np.asarray(lth, np.float64)), _t(gpu, np.asarray(lin, np.float64))).cpu().numpy()
+    return gpu.sim.debug_math(13, to_device(gpu, np.asarray(lth, np.float64)), to_device(gpu, np.asarray(lin, np.float64))).cpu().numpy()
 
 
 def _lidar_angles(rng, n):
@@ -149,16 +129,13 @@ def _world(gpu, occ1, poses, B, step_block, final_obs=False, n_peds=0, **cfg_kw)
     cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, n_scan_stack=1, auto_reset=1, n_spawn=2, seed=20,
                                  step_block=step_block, field_format=abi.FIELD_U16T, **ped, **cfg_kw)
     spec.lidar(cfg, B)
-    arrays = gpu.world.make_world(cfg, occ, n_peds=n_peds, device=gpu.dev, robot_clearance=0.3)
+    arrays = device_world(gpu, cfg, occ, n_peds, robot_clearance=0.3)
     xy = spec.poses_xy(cfg, poses)
     spawn = np.stack([xy, xy], axis=1)
     goal = np.repeat(spec.goals_xy(cfg, poses, size)[:, None], 2, axis=1).copy()
-    arrays["spawn_pose"] = _t(gpu, spawn); arrays["spawn_goal"] = _t(gpu, goal)
-    arrays["robot_pose"] = _t(gpu, spawn[:, 0]); arrays["robot_goal"] = _t(gpu, goal[:, 0])
-    for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
-        arrays[key] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", name)))
-    host = {k: v.cpu().numpy() for k, v in arrays.items() if k not in NOT_STATE}
-    host["field"] = ref.build_dt(occ)
+    arrays["spawn_pose"] = to_device(gpu, spawn); arrays["spawn_goal"] = to_device(gpu, goal)
+    arrays["robot_pose"] = to_device(gpu, spawn[:, 0]); arrays["robot_goal"] = to_device(gpu, goal[:, 0])
+    host = host_arrays(arrays, occ)
     return cfg, gpu.sim.NavSim(cfg, arrays, final_obs=final_obs), ref.RefSim(cfg, host), host
 
 
@@ -170,7 +147,7 @@ def _rollout(gpu, cfg, g, r, host, census=True, final_obs=False):
     E, B = cfg.n_envs, cfg.n_beams
     probe = ref.RefSim(cfg, host) if census else None
     thr, dthr = host["scan_threshold"], host["scan_discomfort"]
-    _eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
+    eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
     seen = []
     for t in range(STEPS):
         act = _actions(E, t)
@@ -178,13 +155,13 @@ def _rollout(gpu, cfg, g, r, host, census=True, final_obs=False):
         go, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         ro, rout = r.step(act)
         for k in rout:
-            _eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
-        _eq(go.cpu().numpy(), ro, "obs at step %d" % t)
+            eq(gout[k].cpu().numpy(), rout[k], "%s at step %d" % (k, t))
+        eq(go.cpu().numpy(), ro, "obs at step %d" % t)
         done = rout["done"] != 0
         if final_obs and done.any():
             fin = {k: v.cpu().numpy() for k, v in g.final.items()}
             for k in ("final_obs", "final_goals"):
-                _eq(fin[k][done], r.final[k][done], "%s at step %d" % (k, t))
+                eq(fin[k][done], r.final[k][done], "%s at step %d" % (k, t))
         if not census:
             seen += [(bool(rout["is_crash"][e]), None, None, None) for e in range(E)]
             continue
@@ -196,10 +173,7 @@ def _rollout(gpu, cfg, g, r, host, census=True, final_obs=False):
             crashed = bool(rout["is_crash"][e])
             assert crashed == bool(C), "the census scan disagrees with the oracle's crash flag (arena %d, step %d)" % (e, t)
             seen.append((crashed, C, D, frozenset((np.flatnonzero(ro[e, :B] < dthr) // 64).tolist()) if crashed else None))
-    gs = g.numpy_state()
-    for k, v in r.a.items():
-        if k in gs and k not in NOT_STATE:
-            _eq(gs[k], v, "state %s at the end" % k)
+    state_equal(g, r, "at the end")
     return seen
 
 

@@ -7,7 +7,7 @@ of the documented dtypes.  What each product computes is held to its specificati
 import numpy as np
 import pytest
 
-from test_gpu_autoreset import gpu  # noqa: F401  (the module's fixture)
+from gpu_support import gpu, same_bits  # noqa: F401  (gpu: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +38,7 @@ def _host(v):
 def _same_bits(a, b, what):
     assert set(a) == set(b), what
     for k in a:
-        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), (what, k)
+        same_bits(a[k], b[k], "%s: %s" % (what, k))
 
 
 def _getters(env):

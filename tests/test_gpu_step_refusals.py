@@ -9,8 +9,8 @@ import ctypes as C
 
 import pytest
 
+from gpu_support import gpu  # noqa: F401  (the module's fixture)
 from nav_gym_amd import abi
-from test_gpu_autoreset import gpu  # noqa: F401  (the module's fixture)
 
 pytestmark = pytest.mark.gpu
 

@@ -13,38 +13,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from nav_gym_amd import abi, robots
+from gpu_support import gpu, device_world, eq, to_device  # noqa: F401  (gpu: the module's fixture)
+from nav_gym_amd import abi
 
 pytestmark = pytest.mark.gpu
 
 SIZE = 100                  # cells per side of the sweep's maps
 OUTLIER = 2_000_000_000
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from nav_gym_amd import lib, sim, world
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    lib.load()
-    return type("G", (), dict(torch=torch, lib=lib, sim=sim, world=world, dev=torch.device("cuda:0")))
-
-
-def _t(gpu, a):
-    return gpu.torch.from_numpy(np.ascontiguousarray(a)).to(gpu.dev)
-
-
-def _eq(a, b, what):
-    a = np.asarray(a); b = np.asarray(b)
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
-        raise AssertionError("%s: %d mismatches, first at %s" % (what, len(bad), bad[0]))
-
-
-def _thresholds(gpu, cfg, arrays):
-    for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
-        arrays[key] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", name)))
-    return arrays
 
 
 @pytest.fixture(scope="module")
@@ -61,7 +36,7 @@ def sweep_worlds(gpu, base_maps):
                                      auto_reset=1, n_scan_stack=1, seed=41, field_format=abi.FIELD_U16T)
         gpu.world.lidar_full_circle(cfg, 65)
         occ = np.ascontiguousarray(np.tile(base_maps, ((E + 7) // 8, 1, 1))[:E])
-        arrays = _thresholds(gpu, cfg, gpu.world.make_world(cfg, occ, n_peds=2, device=gpu.dev, min_goal_dist=3.0, max_goal_dist=8.0))
+        arrays = device_world(gpu, cfg, occ, 2, min_goal_dist=3.0, max_goal_dist=8.0)
         assert "rect_index" in arrays and cfg.closed_maps == 1
         worlds[E] = (cfg, arrays)
     return worlds
@@ -125,9 +100,7 @@ def _plain_world(gpu, base_maps, E, rect_table, beams, **cfg_kw):
         gpu.world.lidar_1081(cfg)
     else:
         gpu.world.lidar_full_circle(cfg, beams)
-    arrays = _thresholds(gpu, cfg, gpu.world.make_world(cfg, base_maps[:E], device=gpu.dev, rect_table=rect_table,
-                                                        min_goal_dist=3.0, max_goal_dist=8.0))
-    return cfg, arrays
+    return cfg, device_world(gpu, cfg, base_maps[:E], 0, rect_table=rect_table, min_goal_dist=3.0, max_goal_dist=8.0)
 
 
 def _snapshot(g):
@@ -154,7 +127,7 @@ def test_unsupported_without_room_for_the_sort(gpu, base_maps):
     assert (order.cpu().numpy() == -7).all()
     after = _snapshot(g)
     for k in before:
-        _eq(before[k], after[k], k)
+        eq(before[k], after[k], k)
     # ... and NavSim then sorts with the separate kernel, for good
     g.lpt_period = 1
     g.t["launch_order"].copy_(gpu.torch.arange(7, -1, -1, dtype=gpu.torch.int32, device=gpu.dev))
@@ -181,7 +154,7 @@ def test_refusals_launch_nothing(gpu, base_maps):
         assert (order.cpu().numpy() == -7).all(), what
         after = _snapshot(g)
         for k in before:
-            _eq(before[k], after[k], "%s: %s" % (what, k))
+            eq(before[k], after[k], "%s: %s" % (what, k))
     assert _step_sorted(gpu, g, cost, order) == 0                # the same call with proper buffers is accepted
     assert np.array_equal(np.sort(order.cpu().numpy()), np.arange(8))
 
@@ -198,7 +171,7 @@ def rollout_worlds(gpu):
                               ("B", dict(max_peds=1, ped_model=abi.PED_NONE, step_block=256), 0)):
         cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, n_spawn=8, auto_reset=1, seed=5, field_format=abi.FIELD_U16T, **kw)
         gpu.world.lidar_1081(cfg)
-        arrays = _thresholds(gpu, cfg, gpu.world.make_world(cfg, occ, n_peds=n_peds, device=gpu.dev))
+        arrays = device_world(gpu, cfg, occ, n_peds)
         gen = torch.Generator(device=gpu.dev); gen.manual_seed(2)
         acts = torch.rand((10, E, 2), generator=gen, device=gpu.dev, dtype=torch.float64)
         acts[..., 0] *= 0.5; acts[..., 1] = acts[..., 1] * 1.28 - 0.64
@@ -220,16 +193,16 @@ def _rollout_against(gpu, world, in_launch):
     lpt.lpt_period = 3
     if not in_launch:
         lpt.sort_in_launch = False                               # as if the library had no navsim_step_sorted
-    lpt.t["launch_order"].copy_(_t(gpu, rev.astype(np.int32)))
-    _eq(lpt.reset_obs().cpu().numpy(), trace[0][0], "reset obs")
+    lpt.t["launch_order"].copy_(to_device(gpu, rev.astype(np.int32)))
+    eq(lpt.reset_obs().cpu().numpy(), trace[0][0], "reset obs")
     for t in range(10):
         o, out = lpt.step(acts[t])
-        _eq(o.cpu().numpy(), trace[t + 1][0], "obs of step %d" % t)
+        eq(o.cpu().numpy(), trace[t + 1][0], "obs of step %d" % t)
         for k, v in trace[t + 1][1].items():
-            _eq(out[k].cpu().numpy(), v, "%s of step %d" % (k, t))
+            eq(out[k].cpu().numpy(), v, "%s of step %d" % (k, t))
     s = lpt.numpy_state()
     for k in state:
-        _eq(s[k], state[k], "state %s" % k)
+        eq(s[k], state[k], "state %s" % k)
     order = lpt.t["launch_order"].cpu().numpy()
     assert np.array_equal(np.sort(order), np.arange(E)) and not np.array_equal(order, rev)      # re-sorted by now
     assert (lpt.t["arena_cost"] > 0).all()

@@ -8,48 +8,12 @@ import pytest
 
 import ref
 from nav_gym_amd import abi
-from test_gpu_autoreset import gpu, _t, _eq, _np, _actions, _state_eq  # noqa: F401  (gpu: the module's fixture)
+from gpu_support import (gpu, action_rows, env_rollout, eq, fresh_oracle, fresh_sim, limit_config, limit_world, nav_env,  # noqa: F401
+                         random_actions, state_equal, to_numpy)
 
 pytestmark = pytest.mark.gpu
 
 E, SIZE, N = 48, 240, 8
-
-
-def _cfg(gpu, mode, ped_model=abi.PED_NONE, S=2, fmt=abi.FIELD_U16T, T=0, **kw):
-    cfg = gpu.lib.default_config(n_envs=E, map_h=SIZE, map_w=SIZE, max_peds=N, n_scan_stack=S, ped_model=ped_model,
-                                 auto_reset=mode, n_spawn=8, seed=4343, field_format=fmt, **kw)
-    gpu.world.lidar_1081(cfg)
-    cfg.max_episode_steps = T
-    return cfg
-
-
-def _world(gpu, cfg, occ=None, n_peds=6, **world_kw):
-    from nav_gym_amd import robots
-    if occ is None:
-        occ = gpu.world.make_maps(cfg.n_envs, cfg.map_h, 4343)
-    world_kw = dict(dict(min_goal_dist=1.5, max_goal_dist=4.0), **world_kw)
-    arrays = gpu.world.make_world(cfg, occ, n_peds=n_peds, device=gpu.dev, **world_kw)
-    arrays["scan_threshold"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "threshold_footprint")))
-    arrays["scan_discomfort"] = gpu.sim.scan_threshold(cfg, _t(gpu, robots.footprint_array("keti", "discomfort_threshold_footprint")))
-    host = {k: v.cpu().numpy() for k, v in arrays.items() if k not in ("field", "field_overflow", "rect_table", "rect_index")}
-    host["field"] = ref.build_dt(occ)
-    host["done_steps"] = np.zeros(cfg.n_envs, np.int32)       # (also under NAVSIM_AUTORESET_NONE: restart_state records it)
-    return arrays, host
-
-
-def _sim(gpu, cfg, arrays, final_obs=False):
-    g = gpu.sim.NavSim(cfg, {k: v.clone() for k, v in arrays.items()}, final_obs=final_obs)
-    g.reset_obs()
-    return g
-
-
-def _ref(cfg, host, mode=None):
-    c = cfg.copy()
-    if mode is not None:
-        c.auto_reset = mode
-    r = ref.RefSim(c, {k: v.copy() for k, v in host.items()})
-    r.reset_obs()
-    return r
 
 
 def _restart_state(r, mask):
@@ -74,14 +38,14 @@ def test_nothing_changes_below_the_limit(gpu, mode, ped_model, fmt, final_obs):
     """A limit beyond the rollout: every output, row, terminal row and state array equals T = 0's bit for bit (for PED_NONE
     same-step calls without final_obs T = 0 runs the plain form of the kernel: featured == plain); truncated stays 0."""
     K = 45
-    cfg0 = _cfg(gpu, mode, ped_model, fmt=fmt, T=0)
-    cfgT = _cfg(gpu, mode, ped_model, fmt=fmt, T=10 * K)
-    arrays, _ = _world(gpu, cfg0)
-    a, b = _sim(gpu, cfg0, arrays, final_obs), _sim(gpu, cfgT, arrays, final_obs)
+    cfg0 = limit_config(gpu, mode, ped_model, fmt=fmt, T=0)
+    cfgT = limit_config(gpu, mode, ped_model, fmt=fmt, T=10 * K)
+    arrays, _ = limit_world(gpu, cfg0)
+    a, b = fresh_sim(gpu, cfg0, arrays, final_obs), fresh_sim(gpu, cfgT, arrays, final_obs)
     rng = np.random.default_rng(5)
     ends = 0
     for t in range(K):
-        act = gpu.torch.from_numpy(_actions(rng, cfg0, t)).to(gpu.dev)
+        act = gpu.torch.from_numpy(random_actions(rng, cfg0.n_envs, t)).to(gpu.dev)
         oa, outa = a.step(act)
         ob, outb = b.step(act)
         assert gpu.torch.equal(oa, ob), "obs at step %d" % t
@@ -96,18 +60,18 @@ def test_nothing_changes_below_the_limit(gpu, mode, ped_model, fmt, final_obs):
         ends += int(outa["done"].sum())
     sa, sb = a.numpy_state(), b.numpy_state()
     for k in sa:
-        _eq(sa[k], sb[k], "state %s" % k)
+        eq(sa[k], sb[k], "state %s" % k)
     assert ends > 5
 
 
 def _limited_run(gpu, mode, T, K, seed=5):
-    cfg = _cfg(gpu, mode, T=T)
-    arrays, _ = _world(gpu, cfg)
-    g = _sim(gpu, cfg, arrays)
+    cfg = limit_config(gpu, mode, T=T)
+    arrays, _ = limit_world(gpu, cfg)
+    g = fresh_sim(gpu, cfg, arrays)
     rng = np.random.default_rng(seed)
     rec = []
     for t in range(K):
-        _, out = g.step(gpu.torch.from_numpy(_actions(rng, cfg, t)).to(gpu.dev))
+        _, out = g.step(gpu.torch.from_numpy(random_actions(rng, cfg.n_envs, t)).to(gpu.dev))
         assert ("truncated" in out) == (T > 0)
         rec.append({k: out[k].cpu().numpy().copy() for k in ("done", "truncated", "is_success", "is_crash") if k in out})
     return rec
@@ -133,8 +97,8 @@ def test_truncation_flags(gpu, mode):
         steps += 1
         term = (o["is_success"] != 0) | (o["is_crash"] != 0)
         trunc = (steps >= T) & ~term
-        _eq(o["truncated"], trunc.astype(np.uint8), "truncated at step %d" % t)
-        _eq(o["done"], (term | trunc).astype(np.uint8), "done at step %d" % t)
+        eq(o["truncated"], trunc.astype(np.uint8), "truncated at step %d" % t)
+        eq(o["done"], (term | trunc).astype(np.uint8), "done at step %d" % t)
         if t + 1 == T:
             assert (o["done"][winners] == 1).all() and (o["truncated"][winners] == 0).all()
         cut += int(trunc.sum())
@@ -148,43 +112,43 @@ def test_compositions_hold_for_arenas_that_finish_by_themselves(gpu):
     """The oracle has no limit: the tests below apply the restart it would do at `done`.  Checked first on arenas that finish
     by themselves -- SAME_STEP (PED_NONE): a NONE-mode oracle + terminal rows + RefSim.restart equals a SAME_STEP oracle run;
     NEXT_STEP: a NONE-mode oracle + navsim_restart_cpu leaves the state a NEXT_STEP run leaves after the finishing step."""
-    cfg = _cfg(gpu, abi.AUTORESET_SAME_STEP, abi.PED_NONE, S=3)
-    _, host = _world(gpu, cfg)
-    a, b = _ref(cfg, host, abi.AUTORESET_NONE), _ref(cfg, host)
+    cfg = limit_config(gpu, abi.AUTORESET_SAME_STEP, abi.PED_NONE, S=3)
+    _, host = limit_world(gpu, cfg)
+    a, b = fresh_oracle(cfg, host, abi.AUTORESET_NONE), fresh_oracle(cfg, host)
     rng = np.random.default_rng(5)
     ends = crash_ends = 0
     for t in range(60):
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, cfg.n_envs, t)
         oa, outa = a.step(act)
         ob, outb = b.step(act)
         outa = {k: v.copy() for k, v in outa.items()}
         m = outa["done"] != 0
         if m.any():
-            _eq(oa[m], b.final["final_obs"][m], "terminal rows at step %d" % t)
-            _eq(np.concatenate([outa["achieved_goal"], outa["desired_goal"]], axis=1)[m], b.final["final_goals"][m],
+            eq(oa[m], b.final["final_obs"][m], "terminal rows at step %d" % t)
+            eq(np.concatenate([outa["achieved_goal"], outa["desired_goal"]], axis=1)[m], b.final["final_goals"][m],
                 "terminal goals at step %d" % t)
             oa = a.restart(m)
-        _eq(oa, ob, "obs at step %d" % t)
+        eq(oa, ob, "obs at step %d" % t)
         for k in outb:
-            _eq(a.out[k] if k in ("achieved_goal", "desired_goal") else outa[k], outb[k], "%s at step %d" % (k, t))
+            eq(a.out[k] if k in ("achieved_goal", "desired_goal") else outa[k], outb[k], "%s at step %d" % (k, t))
         for k in set(a.a) & set(b.a):
-            _eq(a.a[k], b.a[k], "state %s at step %d" % (k, t))
+            eq(a.a[k], b.a[k], "state %s at step %d" % (k, t))
         ends += int(m.sum()); crash_ends += int((m & (outa["is_crash"] != 0)).sum())
     assert ends > 10 and crash_ends > 2, (ends, crash_ends)
 
-    a, b = _ref(cfg, host, abi.AUTORESET_NONE), _ref(cfg, host, abi.AUTORESET_NEXT_STEP)
+    a, b = fresh_oracle(cfg, host, abi.AUTORESET_NONE), fresh_oracle(cfg, host, abi.AUTORESET_NEXT_STEP)
     rng = np.random.default_rng(5)
     live = np.ones(E, bool)                 # arenas that have not finished before: the two runs agree on them
     checked = 0
     for t in range(60):
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, cfg.n_envs, t)
         _, outa = a.step(act)
         b.step(act)
         m = (outa["done"] != 0) & live
         if m.any():
             _restart_state(a, m)
             for k in ("robot_pose", "robot_goal", "episode", "steps", "done_steps"):
-                _eq(a.a[k][live], b.a[k][live], "state %s at step %d" % (k, t))
+                eq(a.a[k][live], b.a[k][live], "state %s at step %d" % (k, t))
             checked += int(m.sum())
         live &= outa["done"] == 0
     assert checked > 5
@@ -193,35 +157,35 @@ def test_compositions_hold_for_arenas_that_finish_by_themselves(gpu):
 @pytest.mark.parametrize("T", [1, 9, 23])
 def test_none_mode_against_the_oracle(gpu, T):
     """NAVSIM_AUTORESET_NONE: the unlimited oracle's outputs and rows, done |= truncated; arenas past T stay truncated."""
-    cfg = _cfg(gpu, abi.AUTORESET_NONE, abi.PED_SFM, T=T)
-    arrays, host = _world(gpu, cfg)
-    g, r = _sim(gpu, cfg, arrays), _ref(cfg, host)
+    cfg = limit_config(gpu, abi.AUTORESET_NONE, abi.PED_SFM, T=T)
+    arrays, host = limit_world(gpu, cfg)
+    g, r = fresh_sim(gpu, cfg, arrays), fresh_oracle(cfg, host)
     rng = np.random.default_rng(7)
     for t in range(3 * T + 6):
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, cfg.n_envs, t)
         go, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         ro, rout = r.step(act)
-        gout = _np(gout)
+        gout = to_numpy(gout)
         trunc = (r.a["steps"] >= T) & (rout["done"] == 0)
         for k in ("reward", "is_success", "is_crash", "distance", "achieved_goal", "desired_goal"):
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
-        _eq(gout["done"], rout["done"] | trunc, "done at step %d" % t)
-        _eq(gout["truncated"], trunc.astype(np.uint8), "truncated at step %d" % t)
-        _eq(go.cpu().numpy(), ro, "obs at step %d" % t)
-    _state_eq(g, r, "at the end")
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
+        eq(gout["done"], rout["done"] | trunc, "done at step %d" % t)
+        eq(gout["truncated"], trunc.astype(np.uint8), "truncated at step %d" % t)
+        eq(go.cpu().numpy(), ro, "obs at step %d" % t)
+    state_equal(g, r, "at the end", skip=("counters",))
 
 
 @pytest.mark.parametrize("T,S,fmt", [(1, 2, abi.FIELD_U16T), (9, 3, abi.FIELD_U16T), (23, 2, abi.FIELD_F32)])
 def test_same_step_against_the_oracle(gpu, T, S, fmt):
     """SAME_STEP, PED_NONE: a truncated arena's terminal row / goals are the unlimited oracle's row after the step; its next
     state and row are RefSim.restart's (navsim_restart_cpu + reset_obs); done_steps records T."""
-    cfg = _cfg(gpu, abi.AUTORESET_SAME_STEP, abi.PED_NONE, S=S, fmt=fmt, T=T)
-    arrays, host = _world(gpu, cfg)
-    g, r = _sim(gpu, cfg, arrays, final_obs=True), _ref(cfg, host)
+    cfg = limit_config(gpu, abi.AUTORESET_SAME_STEP, abi.PED_NONE, S=S, fmt=fmt, T=T)
+    arrays, host = limit_world(gpu, cfg)
+    g, r = fresh_sim(gpu, cfg, arrays, final_obs=True), fresh_oracle(cfg, host)
     rng = np.random.default_rng(9)
     cut = 0
     for t in range(max(3 * T, 40)):
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, cfg.n_envs, t)
         go, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         ro, rout = r.step(act)
         rout = {k: v.copy() for k, v in rout.items()}
@@ -233,21 +197,21 @@ def test_same_step_against_the_oracle(gpu, T, S, fmt):
         if trunc.any():
             ro = r.restart(trunc)
             assert (r.a["done_steps"][trunc] == T).all()
-        gout = _np(gout)
+        gout = to_numpy(gout)
         for k in ("reward", "is_success", "is_crash", "distance"):
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
         for k in ("achieved_goal", "desired_goal"):
-            _eq(gout[k], r.out[k], "%s at step %d" % (k, t))
-        _eq(gout["done"], (nat | trunc).astype(np.uint8), "done at step %d" % t)
-        _eq(gout["truncated"], trunc.astype(np.uint8), "truncated at step %d" % t)
-        _eq(go.cpu().numpy(), ro, "obs at step %d" % t)
+            eq(gout[k], r.out[k], "%s at step %d" % (k, t))
+        eq(gout["done"], (nat | trunc).astype(np.uint8), "done at step %d" % t)
+        eq(gout["truncated"], trunc.astype(np.uint8), "truncated at step %d" % t)
+        eq(go.cpu().numpy(), ro, "obs at step %d" % t)
         d = nat | trunc
-        fin = _np(g.final)
-        _eq(fin["final_obs"][d], fin_obs[d], "terminal rows at step %d" % t)
-        _eq(fin["final_goals"][d], fin_goals[d], "terminal goals at step %d" % t)
+        fin = to_numpy(g.final)
+        eq(fin["final_obs"][d], fin_obs[d], "terminal rows at step %d" % t)
+        eq(fin["final_goals"][d], fin_goals[d], "terminal goals at step %d" % t)
         cut += int(trunc.sum())
         if t % 5 == 4:
-            _state_eq(g, r, "at step %d" % t)
+            state_equal(g, r, "at step %d" % t, skip=("counters",))
     assert cut > E
 
 
@@ -255,40 +219,40 @@ def test_same_step_against_the_oracle(gpu, T, S, fmt):
 def test_next_step_against_the_oracle(gpu, T, ped_model):
     """NEXT_STEP: the call that truncates returns the terminal row (the unlimited oracle's) with done = truncated = 1 and restarts
     the state (navsim_restart_cpu); the next call resets the arena through its reset mask, truncated 0 there."""
-    cfg = _cfg(gpu, abi.AUTORESET_NEXT_STEP, ped_model, S=3 if ped_model == abi.PED_SFM else 2, T=T)
-    arrays, host = _world(gpu, cfg)
-    g, r = _sim(gpu, cfg, arrays), _ref(cfg, host)
+    cfg = limit_config(gpu, abi.AUTORESET_NEXT_STEP, ped_model, S=3 if ped_model == abi.PED_SFM else 2, T=T)
+    arrays, host = limit_world(gpu, cfg)
+    g, r = fresh_sim(gpu, cfg, arrays), fresh_oracle(cfg, host)
     rng = np.random.default_rng(11)
     cut = 0
     for t in range(max(3 * T + 3, 40)):
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, cfg.n_envs, t)
         if ped_model == abi.PED_EXTERNAL:
             cmd = np.stack([rng.uniform(0, 0.6, (E, N)), rng.uniform(-0.6, 0.6, (E, N))], axis=2)
             g.set_ped_cmd(cmd); r.set_ped_cmd(cmd)
         go, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         ro, rout = r.step(act)
-        _eq(g.reset_flags.cpu().numpy(), r.reset_flags, "reset flags at step %d" % t)
+        eq(g.reset_flags.cpu().numpy(), r.reset_flags, "reset flags at step %d" % t)
         trunc = (r.a["steps"] >= T) & (rout["done"] == 0)
-        gout = _np(gout)
+        gout = to_numpy(gout)
         for k in ("reward", "is_success", "is_crash", "distance", "achieved_goal", "desired_goal"):
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
-        _eq(gout["done"], rout["done"] | trunc, "done at step %d" % t)
-        _eq(gout["truncated"], trunc.astype(np.uint8), "truncated at step %d" % t)
-        _eq(go.cpu().numpy(), ro, "obs at step %d" % t)
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
+        eq(gout["done"], rout["done"] | trunc, "done at step %d" % t)
+        eq(gout["truncated"], trunc.astype(np.uint8), "truncated at step %d" % t)
+        eq(go.cpu().numpy(), ro, "obs at step %d" % t)
         if trunc.any():
             _restart_state(r, trunc)
             r.out["done"][trunc] = 1
             r.prev_done[trunc] = 1
         cut += int(trunc.sum())
         if t % 5 == 4:
-            _state_eq(g, r, "at step %d" % t)
+            state_equal(g, r, "at step %d" % t, skip=("counters",))
     assert cut > E // 2
 
 
 def test_negative_limit_is_rejected(gpu):
-    cfg = _cfg(gpu, abi.AUTORESET_SAME_STEP)
-    arrays, _ = _world(gpu, cfg)
-    g = _sim(gpu, cfg, arrays)
+    cfg = limit_config(gpu, abi.AUTORESET_SAME_STEP)
+    arrays, _ = limit_world(gpu, cfg)
+    g = fresh_sim(gpu, cfg, arrays)
     g.cfg.max_episode_steps = -1
     assert g.lib.navsim_step(C.byref(g.cfg), C.byref(g.st), C.byref(g.io), None) == abi.E_ARG
     assert g.lib.navsim_reset_obs(C.byref(g.cfg), C.byref(g.st), C.byref(g.io), None, None) == abi.E_ARG
@@ -306,66 +270,36 @@ def test_navsim_regen_path_against_the_oracle(gpu, T, ped_model, fmt):
                                  regen_plan=0, regen_indoor_ratio=0.0, defer_reset_scan=1)
     gpu.world.lidar_1081(cfg)
     cfg.max_episode_steps = T
-    arrays, host = _world(gpu, cfg, occ=gpu.world.make_maps(E_, size, 19), n_peds=5, min_goal_dist=10.0, max_goal_dist=20.0)
+    arrays, host = limit_world(gpu, cfg, occ=gpu.world.make_maps(E_, size, 19), n_peds=5, min_goal_dist=10.0, max_goal_dist=20.0)
     g = gpu.sim.NavSim(cfg, arrays)
     r = ref.RefSim(cfg, host)
-    _eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
+    eq(g.reset_obs().cpu().numpy(), r.reset_obs(), "reset obs")
     rng = np.random.default_rng(6)
     cut = 0
     for t in range(3 * T + 5):
-        act = _actions(rng, cfg, t)
+        act = random_actions(rng, cfg.n_envs, t)
         _, gout = g.step(gpu.torch.from_numpy(act).to(gpu.dev))
         _, rout = r.step(act)
         trunc = (r.a["steps"] >= T) & (rout["done"] == 0)
-        gout = _np(gout)
+        gout = to_numpy(gout)
         for k in ("reward", "is_success", "is_crash", "distance"):
-            _eq(gout[k], rout[k], "%s at step %d" % (k, t))
-        _eq(gout["done"], rout["done"] | trunc, "done at step %d" % t)
-        _eq(gout["truncated"], trunc.astype(np.uint8), "truncated at step %d" % t)
+            eq(gout[k], rout[k], "%s at step %d" % (k, t))
+        eq(gout["done"], rout["done"] | trunc, "done at step %d" % t)
+        eq(gout["truncated"], trunc.astype(np.uint8), "truncated at step %d" % t)
         if trunc.any():
             _restart_state(r, trunc)
             r.out["done"][trunc] = 1
-        _eq(g.regen().cpu().numpy(), r.regen(), "obs after regen at step %d" % t)
+        eq(g.regen().cpu().numpy(), r.regen(), "obs after regen at step %d" % t)
         for k in ("achieved_goal", "desired_goal"):
-            _eq(g.out[k].cpu().numpy(), r.out[k], "%s after regen at step %d" % (k, t))
+            eq(g.out[k].cpu().numpy(), r.out[k], "%s after regen at step %d" % (k, t))
         cut += int(trunc.sum())
         if trunc.any() or t % 5 == 4:
-            _state_eq(g, r, "after regen at step %d" % t)
+            state_equal(g, r, "after regen at step %d" % t, skip=("counters",))
     assert cut > E_ // 2
     assert g.counters()["regen_unserved"] == 0
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-def _env(**kw):
-    from nav_gym_amd import registry
-    base = dict(num_envs=48, map_size=200, n_beams=256, seed=23, plan_paths=False, min_goal_dist=2.0, max_goal_dist=6.0,
-                indoor_ratio=0.0, num_humans=3)
-    base.update(kw)
-    return registry.make("NavGym-v0", **base)
-
-
-def _acts(K, E_, seed=2):
-    rng = np.random.default_rng(seed)
-    return [np.stack([rng.uniform(0.0, 0.5, E_), rng.uniform(-0.64, 0.64, E_)], axis=1) for _ in range(K)]
-
-
-def _rollout(env, acts):
-    import torch
-    obs = env.reset()
-    rec = [obs["observation"].clone()]
-    for act in acts:
-        o, rew, done, info = env.step(act)
-        item = dict(obs=o["observation"].clone(), rew=rew.clone(), done=done.clone())
-        item["trunc"] = info["TimeLimit.truncated"].clone() if "TimeLimit.truncated" in info else torch.zeros_like(done)
-        if "final_observation" in info:
-            item["final"] = info["final_observation"]["observation"].clone()
-        if "reset_mask" in info:
-            item["reset"] = info["reset_mask"].clone()
-        rec.append(item)
-    torch.cuda.synchronize()
-    return rec
-
-
 def _same(ra, rb):
     import torch
     assert torch.equal(ra[0], rb[0])
@@ -382,11 +316,11 @@ def test_staged_worlds_equal_navsim_regen_with_the_limit(gpu, mode):
     """The env's default reset path for randomize_maps (worlds staged ahead, installed inside the step) is bit-identical to
     pregen_pipeline=0 (navsim_regen behind every step) over the whole rollout with the limit on; no cap binds in either."""
     T, K = 9, 30
-    a = _env(randomize_maps=True, autoreset_mode=mode, max_episode_steps=T, use_graphs=False)
-    b = _env(randomize_maps=True, autoreset_mode=mode, max_episode_steps=T, pregen_pipeline=0, use_graphs=False)
+    a = nav_env(randomize_maps=True, autoreset_mode=mode, max_episode_steps=T, use_graphs=False)
+    b = nav_env(randomize_maps=True, autoreset_mode=mode, max_episode_steps=T, pregen_pipeline=0, use_graphs=False)
     assert a.pregen_pipeline > 0 and b.pregen_pipeline == 0
-    acts = _acts(K, 48)
-    ra, rb = _rollout(a, acts), _rollout(b, acts)
+    acts = action_rows(K, 48)
+    ra, rb = env_rollout(a, acts), env_rollout(b, acts)
     _same(ra, rb)
     assert sum(int(x["trunc"].sum()) for x in ra[1:]) > 24
     assert a.counters()["regen_unserved"] == 0 and b.counters()["regen_unserved"] == 0
@@ -395,11 +329,11 @@ def test_staged_worlds_equal_navsim_regen_with_the_limit(gpu, mode):
 
 def test_graphs_equal_plain_launches_with_the_limit(gpu):
     T, K = 7, 24
-    a = _env(randomize_maps=True, max_episode_steps=T, pregen_pipeline=0, use_graphs=True)
-    b = _env(randomize_maps=True, max_episode_steps=T, pregen_pipeline=0, use_graphs=False)
+    a = nav_env(randomize_maps=True, max_episode_steps=T, pregen_pipeline=0, use_graphs=True)
+    b = nav_env(randomize_maps=True, max_episode_steps=T, pregen_pipeline=0, use_graphs=False)
     assert a.use_graphs and not b.use_graphs
-    acts = _acts(K, 48)
-    ra, rb = _rollout(a, acts), _rollout(b, acts)
+    acts = action_rows(K, 48)
+    ra, rb = env_rollout(a, acts), env_rollout(b, acts)
     _same(ra, rb)
     assert sum(int(x["trunc"].sum()) for x in ra[1:]) > 24
     a.close(); b.close()
@@ -409,8 +343,8 @@ def test_graphs_equal_plain_launches_with_the_limit(gpu):
 def test_gym_surface_single_arena(gpu):
     """E = 1: the first T - 1 steps equal an unlimited env's; step T: done True, TimeLimit.truncated True, same reward; reset()."""
     T = 9
-    a = _env(num_envs=1, max_episode_steps=T, pedestrian_model="none", num_humans=0)
-    b = _env(num_envs=1, pedestrian_model="none", num_humans=0)
+    a = nav_env(num_envs=1, max_episode_steps=T, pedestrian_model="none", num_humans=0)
+    b = nav_env(num_envs=1, pedestrian_model="none", num_humans=0)
     oa, ob = a.reset(), b.reset()
     assert np.array_equal(oa["observation"], ob["observation"])
     act = np.array([0.0, 0.3])                                 # turning on the spot: no success, no crash
@@ -431,10 +365,10 @@ def test_gym_surface_same_step(gpu):
     arena's first truncation the two rollouts are one); no episode runs longer than T steps (counted on the host from done)."""
     import torch
     T, K = 9, 30
-    a = _env(max_episode_steps=T, pedestrian_model="none", num_humans=0)
-    b = _env(pedestrian_model="none", num_humans=0)
-    acts = _acts(K, 48)
-    ra, rb = _rollout(a, acts), _rollout(b, acts)
+    a = nav_env(max_episode_steps=T, pedestrian_model="none", num_humans=0)
+    b = nav_env(pedestrian_model="none", num_humans=0)
+    acts = action_rows(K, 48)
+    ra, rb = env_rollout(a, acts), env_rollout(b, acts)
     same = torch.ones(48, dtype=torch.bool, device=ra[0].device)
     length = torch.zeros(48, dtype=torch.int64, device=ra[0].device)
     compared = 0
@@ -460,17 +394,17 @@ def test_gym_surface_next_step_and_state_dict(gpu):
     into a fresh env truncates at the same steps as the uninterrupted run."""
     import torch
     T, K, k0 = 9, 30, 4
-    a = _env(max_episode_steps=T, autoreset_mode="next_step", pedestrian_model="none", num_humans=0)
-    ra = _rollout(a, _acts(K, 48))
+    a = nav_env(max_episode_steps=T, autoreset_mode="next_step", pedestrian_model="none", num_humans=0)
+    ra = env_rollout(a, action_rows(K, 48))
     for t in range(1, K):
         assert torch.equal(ra[t + 1]["reset"], ra[t]["done"]) and bool((ra[t + 1]["reset"] | ~ra[t]["trunc"]).all()), t
         assert not bool((ra[t + 1]["trunc"] & ra[t + 1]["reset"]).any()), t
     assert sum(int(x["trunc"].sum()) for x in ra[1:]) > 24
     a.close()
 
-    a, b = _env(max_episode_steps=T), _env(max_episode_steps=T)
+    a, b = nav_env(max_episode_steps=T), nav_env(max_episode_steps=T)
     a.reset(); b.reset()
-    acts = _acts(3 * T, 48, seed=8)
+    acts = action_rows(3 * T, 48, seed=8)
     for t in range(k0):
         a.step(acts[t])
     b.load_state_dict(a.state_dict())
@@ -489,10 +423,10 @@ def test_two_shards_equal_one_world_with_the_limit(gpu):
     import torch
     T, K = 7, 20
     kw = dict(max_episode_steps=T, randomize_maps=True, pregen_pipeline=0, use_graphs=False)
-    one = _env(**kw)
-    s0, s1 = _env(num_envs=24, env_index_base=0, **kw), _env(num_envs=24, env_index_base=24, **kw)
-    acts = _acts(K, 48)
-    r1 = _rollout(one, acts)
+    one = nav_env(**kw)
+    s0, s1 = nav_env(num_envs=24, env_index_base=0, **kw), nav_env(num_envs=24, env_index_base=24, **kw)
+    acts = action_rows(K, 48)
+    r1 = env_rollout(one, acts)
     o0, o1 = s0.reset(), s1.reset()
     assert torch.equal(torch.cat([o0["observation"], o1["observation"]]), r1[0])
     for t in range(K):

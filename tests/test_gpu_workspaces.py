@@ -10,21 +10,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_support import gpu, device_sim, rect_pairs, regen_layout, seeded_action  # noqa: F401  (gpu: the module's fixture)
 from helpers import policy_weights
-from nav_gym_amd import abi, robots
+from nav_gym_amd import abi
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 1 << 20
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from nav_gym_amd import lib, sim, world
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    lib.load()
-    return type("G", (), dict(torch=torch, lib=lib, sim=sim, world=world, dev=torch.device("cuda:0")))
 
 
 def _guarded(gpu, nbytes):
@@ -44,30 +36,6 @@ def _guards_intact(gpu, buf, nbytes, what):
     assert bool((buf[GUARD + nbytes:] == 0xA5).all()), "%s: wrote beyond the %d bytes its query returns" % (what, nbytes)
 
 
-def _sim(gpu, cfg, occ, n_peds, **world_kw):
-    cfg = cfg.copy()                                    # (make_world notes in it whether the maps are closed)
-    arrays = gpu.world.make_world(cfg, occ, n_peds=n_peds, device=gpu.dev, **world_kw)
-    for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
-        fp = gpu.torch.from_numpy(robots.footprint_array("keti", name)).to(gpu.dev)
-        arrays[key] = gpu.sim.scan_threshold(cfg, fp)
-    g = gpu.sim.NavSim(cfg, arrays)
-    g.reset_obs()
-    return g
-
-
-def _rect_pairs(rows, H, W):
-    """navsim_state.rect_index decoded: the two rectangles every tile names (-1: none).  Which list index a rectangle gets
-    depends on the order its workgroup's threads insert it (kernels_rect.hpp rect_index_kernel); what a tile names does not."""
-    rows = rows.cpu().numpy()
-    T = ((H + 7) // 8) * ((W + 7) // 8)
-    lst = np.ascontiguousarray(rows[:, :256 * 8]).view(np.int64)                     # [E, 256]
-    pair = np.ascontiguousarray(rows[:, 256 * 8:256 * 8 + 2 * T]).view(np.uint16)    # [E, T]: A | B << 8
-    both = np.stack([np.take_along_axis(lst, (pair & 0xFF).astype(np.int64), 1),
-                     np.take_along_axis(lst, (pair >> 8).astype(np.int64), 1)], axis=2)
-    both[pair == 0xFFFF] = -1
-    return both
-
-
 def _same_arrays(gpu, ta, tb, cfg, what):
     """two dicts of state arrays, bit for bit (scheduling hints and the workspaces apart; waypoint slots beyond a route's
     length keep whatever the buffer held; the record index compared by what it says)"""
@@ -78,7 +46,7 @@ def _same_arrays(gpu, ta, tb, cfg, what):
             continue
         x, y = ta[k], tb[k]
         if k == "rect_index":
-            assert np.array_equal(_rect_pairs(x, cfg.map_h, cfg.map_w), _rect_pairs(y, cfg.map_h, cfg.map_w)), "%s: state %s" % (what, k)
+            assert np.array_equal(rect_pairs(x, cfg.map_h, cfg.map_w), rect_pairs(y, cfg.map_h, cfg.map_w)), "%s: state %s" % (what, k)
             continue
         if k == "ped_waypoints":
             live = gpu.torch.arange(cfg.max_waypoints, device=gpu.dev)[None, None, :] < ta["ped_n_waypoints"][..., None].long()
@@ -96,58 +64,27 @@ def _same(gpu, a, b, what):
     _same_arrays(gpu, a.t, b.t, a.cfg, what)
 
 
-def _act(gpu, E, seed):
-    rng = np.random.default_rng(seed)
-    return gpu.torch.from_numpy(np.stack([rng.uniform(0.0, 0.5, E), rng.uniform(-0.64, 0.64, E)], axis=1)).to(gpu.dev)
-
-
-def _regen_world(gpu, layout):
-    """(cfg, occ, pedestrians, make_world keywords) of the three navsim_regen layouts"""
-    kw = dict(auto_reset=1, n_spawn=6, seed=31, min_goal_dist=3.0, max_goal_dist=8.0, spawn_clearance=0.9,
-              ped_min_robot_dist=2.0, ped_min_goal_dist=4.0)
-    if layout == "packed-corridors-planned":            # distance transform, rect builder, the fork, both planner stages
-        E, size = 12, 260
-        cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, max_peds=6, ped_model=abi.PED_SFM, regen_cap=3,
-                                     field_format=abi.FIELD_U16T, regen_plan=1, regen_indoor_ratio=0.5, **kw)
-        occ, n_peds, wkw = gpu.world.make_maps(E, size, 31), 5, dict(plan_paths=True)
-    elif layout == "float32-smallest":
-        E, size = 12, 200
-        cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, max_peds=1, ped_model=abi.PED_NONE, regen_cap=3,
-                                     field_format=abi.FIELD_F32, regen_plan=0, regen_indoor_ratio=0.0, **kw)
-        occ, n_peds, wkw = gpu.world.make_maps(E, size, 31), 0, {}
-    else:                                               # "packed-overflow-plane": its scratch exists above 520 cells per side only
-        E, size = 4, 528
-        cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, max_peds=1, ped_model=abi.PED_NONE, regen_cap=2,
-                                     field_format=abi.FIELD_U16T, regen_plan=0, regen_indoor_ratio=0.0, **kw)
-        occ = np.zeros((E, size, size), np.uint8)       # 259 free cells from the border wall to the centre: the field saturates
-        occ[:, :5] = 1; occ[:, -5:] = 1; occ[:, :, :5] = 1; occ[:, :, -5:] = 1
-        occ[:, 40:60, 40:60] = 1
-        n_peds, wkw = 0, {}
-    gpu.world.lidar_full_circle(cfg, 180)
-    return cfg, occ, n_peds, wkw
-
-
 @pytest.mark.parametrize("layout", ["packed-corridors-planned", "float32-smallest", "packed-overflow-plane"])
 def test_regen_stays_inside_the_queried_workspace(gpu, layout):
     """navsim_regen: one step, every done flag set by hand (more arenas than regen_cap: the cap applies), regen()."""
-    cfg, occ, n_peds, wkw = _regen_world(gpu, layout)
+    cfg, occ, n_peds, wkw = regen_layout(gpu, layout)
     nbytes = gpu.lib.load().navsim_regen_workspace_bytes(C.byref(cfg))
     buf, view = _guarded(gpu, nbytes)
     sims = []
     for ws in (view, _roomy(gpu, nbytes)):
-        g = _sim(gpu, cfg, occ, n_peds, **wkw)
+        g = device_sim(gpu, cfg, occ, n_peds, **wkw)
         if layout == "packed-overflow-plane":
             assert "field_overflow" in g.t
         if layout == "packed-corridors-planned":
             assert "rect_table" in g.t and "costmap" in g.t
         g.t["regen_ws"] = ws
-        g.step(_act(gpu, cfg.n_envs, 1))
+        g.step(seeded_action(gpu, cfg.n_envs, 1))
         g.out["done"].fill_(1)
         goals = g.t["spawn_goal"].clone()
         g.regen()
         gpu.torch.cuda.synchronize()
         assert int((g.t["spawn_goal"] != goals).flatten(1).any(1).sum()) == cfg.regen_cap    # regen_cap arenas got a new world
-        g.step(_act(gpu, cfg.n_envs, 2))
+        g.step(seeded_action(gpu, cfg.n_envs, 2))
         sims.append(g)
     _guards_intact(gpu, buf, nbytes, "navsim_regen (%s)" % layout)
     _same(gpu, sims[0], sims[1], "navsim_regen (%s)" % layout)
@@ -155,10 +92,10 @@ def test_regen_stays_inside_the_queried_workspace(gpu, layout):
 
 def test_regen_stage_stays_inside_the_queried_workspace(gpu):
     """navsim_regen_stage_part through enable_pregen(): the pass takes count / list from the layout of ITS workspace."""
-    cfg, occ, n_peds, wkw = _regen_world(gpu, "packed-corridors-planned")
+    cfg, occ, n_peds, wkw = regen_layout(gpu, "packed-corridors-planned")
     sims, bufs = [], []
     for guarded in (True, False):
-        g = _sim(gpu, cfg, occ, n_peds, **wkw)
+        g = device_sim(gpu, cfg, occ, n_peds, **wkw)
         g.enable_pregen()
         nbytes = gpu.lib.load().navsim_regen_workspace_bytes(C.byref(g.stage_cfg))
         assert g.stage_ws.numel() == nbytes
@@ -168,11 +105,11 @@ def test_regen_stage_stays_inside_the_queried_workspace(gpu):
         for ln in g.stage_lane:
             ln["ws"] = ws
         for k in (1, 2):                                # the second swap installs what the guarded pass staged
-            g.step(_act(gpu, cfg.n_envs, k))
+            g.step(seeded_action(gpu, cfg.n_envs, k))
             g.out["done"].fill_(1)
             g.regen()
             g.pregen_sync()
-        g.step(_act(gpu, cfg.n_envs, 3))
+        g.step(seeded_action(gpu, cfg.n_envs, 3))
         sims.append(g); bufs.append((buf, nbytes))
     _guards_intact(gpu, bufs[0][0], bufs[0][1], "navsim_regen_stage_part")
     _same(gpu, sims[0], sims[1], "navsim_regen_stage_part")
@@ -192,10 +129,10 @@ def test_replan_stays_inside_the_queried_workspace(gpu, flags):
     buf, view = _guarded(gpu, nbytes)
     sims, replanned = [], 0
     for ws in (view, _roomy(gpu, nbytes)):
-        g = _sim(gpu, cfg, occ, N, plan_paths=True, v_pref_range=(0.5, 0.6))
+        g = device_sim(gpu, cfg, occ, N, plan_paths=True, v_pref_range=(0.5, 0.6))
         g.t["replan_ws_%d" % Q] = ws
         for t in range(150):
-            g.step(_act(gpu, E, t))
+            g.step(seeded_action(gpu, E, t))
             before = g.t["ped_n_waypoints"].clone(), g.t["ped_wp_head"].clone()
             g.replan(Q, flags=flags)
             replanned += int(((g.t["ped_n_waypoints"] != before[0]) | (g.t["ped_wp_head"] != before[1])).sum())
@@ -217,13 +154,13 @@ def test_ped_policy_stays_inside_the_queried_workspace(gpu, fused):
     buf, view = _guarded(gpu, nbytes)
     sims = []
     for ws in (view, _roomy(gpu, nbytes)):
-        g = _sim(gpu, cfg, occ, N)
+        g = device_sim(gpu, cfg, occ, N)
         g.set_policy(policy_weights(3))
         g.t["policy_ws"] = ws
         scans = gpu.torch.zeros((E, N, 512), dtype=gpu.torch.float32, device=gpu.dev)
         for t in range(3):
             g.ped_policy(fused=fused, scans_out=scans if fused else None)
-            g.step(_act(gpu, E, t))
+            g.step(seeded_action(gpu, E, t))
         g.t["scans_seen"] = scans if fused else g.ped_scans()
         sims.append(g)
     assert float(sims[0].t["ped_cmd"].abs().sum()) > 0.0

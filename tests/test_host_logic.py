@@ -356,7 +356,8 @@ import os, sys
 sys.path[:0] = [%(root)r + "/nav-gym_amd", %(root)r + "/oracle", %(root)r + "/tests"]
 import numpy as np, torch, torch.distributed as dist
 import ref
-from nav_gym_amd import abi, lib, robots, world
+from helpers import keti_thresholds
+from nav_gym_amd import abi, lib, world
 from nav_gym_amd.sharding import shard_range, gather_rows
 rank, ws = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 dist.init_process_group("gloo", rank=rank, world_size=ws)
@@ -369,8 +370,7 @@ def run(start, count):
     f = ref.build_dt(occ)
     a = world.make_world(cfg, occ, n_peds=2, device="cpu", field=torch.from_numpy(f), min_goal_dist=1.5, max_goal_dist=4, robot_clearance=0.6)
     host = {k: v.numpy() for k, v in a.items()}
-    host["scan_threshold"] = ref.scan_threshold(cfg, robots.footprint_array("keti", "threshold_footprint"))
-    host["scan_discomfort"] = ref.scan_threshold(cfg, robots.footprint_array("keti", "discomfort_threshold_footprint"))
+    host["scan_threshold"], host["scan_discomfort"] = keti_thresholds(cfg)
     sim = ref.RefSim(cfg, host); sim.reset_obs()
     rng = np.random.default_rng(3)
     acts = np.stack([rng.uniform(0, 0.5, (12, E_total)), rng.uniform(-0.6, 0.6, (12, E_total))], axis=2)

@@ -13,6 +13,7 @@ import pytest
 import dwa_spec
 import local_map_spec as spec
 import ref
+from helpers import struct_fields
 from nav_gym_amd import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -219,16 +220,6 @@ def test_population_of_the_device_tests_worlds():
 
 
 # ---- C ABI ------------------------------------------------------------------------------------------------------------------------
-def _struct_fields(header, name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        if decl.strip():
-            names += [re.match(r"\s*(\w+)", part).group(1) for part in decl.strip().split(None, 1)[1].split(",")]
-    return names
-
-
 def test_symbol_and_structure_in_header_library_and_exports():
     from nav_gym_amd import lib
     L = lib.load()
@@ -237,7 +228,7 @@ def test_symbol_and_structure_in_header_library_and_exports():
     assert C.sizeof(abi.NavsimConfig) == 624 == L.navsim_sizeof_config()         # no structure changed its size
     assert C.sizeof(abi.NavsimState) == L.navsim_sizeof_state() and C.sizeof(abi.NavsimStepIO) == L.navsim_sizeof_step_io()
     assert re.search(r"\bint navsim_local_map\(", header) and "navsim_local_map" in abi.EXPORTS and hasattr(L, "navsim_local_map")
-    fields = _struct_fields(header, "navsim_local_map_params")
+    fields = struct_fields(header, "navsim_local_map_params")
     assert fields == ["cell", "ahead", "cap", "ped_radius", "size", "channels"]
     assert [n for n, _ in abi.NavsimLocalMapParams._fields_] == fields
     assert C.sizeof(abi.NavsimLocalMapParams) == 4 * 8 + 2 * 4

@@ -8,7 +8,7 @@ import pytest
 from scipy import ndimage as ndi
 
 import ref
-from helpers import outdoor_map
+from helpers import keti_thresholds, outdoor_map
 from nav_gym_amd import abi
 
 
@@ -316,8 +316,7 @@ def test_regen_with_planning_properties():
                              ped_min_robot_dist=2.0, ped_min_goal_dist=4.0, regen_plan=1, obstacle_number=6)
     rng = np.random.default_rng(0)
     occ = np.stack([outdoor_map(rng, size) for _ in range(E)])
-    thr = ref.scan_threshold(cfg, robots.footprint_array("keti", "threshold_footprint"))
-    dthr = ref.scan_threshold(cfg, robots.footprint_array("keti", "discomfort_threshold_footprint"))
+    thr, dthr = keti_thresholds(cfg)
     r = ref.RefSim(cfg, finished_world(cfg, occ, ref.build_dt(occ), 5, (thr, dthr)))
     r.reset_obs()
     _, out = r.step(np.zeros((E, 2)))
@@ -400,8 +399,7 @@ def test_regen_indoor_maps_are_one_corridor_tree():
                              regen_indoor_ratio=1.0)
     rng = np.random.default_rng(0)
     occ = np.stack([outdoor_map(rng, size) for _ in range(E)])
-    thr = ref.scan_threshold(cfg, robots.footprint_array("keti", "threshold_footprint"))
-    dthr = ref.scan_threshold(cfg, robots.footprint_array("keti", "discomfort_threshold_footprint"))
+    thr, dthr = keti_thresholds(cfg)
     r = ref.RefSim(cfg, finished_world(cfg, occ, ref.build_dt(occ), 0, (thr, dthr)))
     r.reset_obs()
     _, out = r.step(np.zeros((E, 2)))
@@ -448,15 +446,13 @@ def test_short_episodes_restart_in_place():
     """cfg.regen_min_steps (build-defined; the reference draws a map at every reset): an arena whose episode ended after
     fewer steps keeps its map -- the step's restart from the spawn table stands -- and is counted; one that lasted long
     enough is regenerated.  The step records the length of the episode that ended (done_steps)."""
-    from nav_gym_amd import robots
     from helpers import finished_world
     E, size = 6, 200
     cfg = ref.default_config(n_envs=E, map_h=size, map_w=size, max_peds=1, ped_model=abi.PED_NONE, n_spawn=4, auto_reset=1,
                              seed=3, regen_cap=E, min_goal_dist=3.0, max_goal_dist=8.0, regen_min_steps=3)
     rng = np.random.default_rng(0)
     occ = np.stack([outdoor_map(rng, size) for _ in range(E)])
-    thr = ref.scan_threshold(cfg, robots.footprint_array("keti", "threshold_footprint"))
-    dthr = ref.scan_threshold(cfg, robots.footprint_array("keti", "discomfort_threshold_footprint"))
+    thr, dthr = keti_thresholds(cfg)
     r = ref.RefSim(cfg, finished_world(cfg, occ, ref.build_dt(occ), 0, (thr, dthr)))
     r.reset_obs()
     # every arena ends its episode in this step; pretend half of them had been running for a while
@@ -486,7 +482,6 @@ def test_short_episodes_restart_in_place():
 def test_native_thread_pool_equals_sequential_steps():
     """bench.py's CPU baseline (navsim_step_threads_cpu: POSIX threads inside the oracle, arenas split statically, no
     barrier between steps) computes exactly what step() after step() computes: observations, outputs and state."""
-    import copy
     from nav_gym_amd import lib, world
     E, size, N = 13, 120, 4
     cfg = lib.default_config(n_envs=E, map_h=size, map_w=size, max_peds=N, ped_model=abi.PED_SFM, n_spawn=4, auto_reset=1,
@@ -497,9 +492,7 @@ def test_native_thread_pool_equals_sequential_steps():
     arrays = world.make_world(cfg, occ, n_peds=3, device="cpu", field=torch.from_numpy(ref.build_dt(occ)), min_goal_dist=2.0,
                               max_goal_dist=4.0, robot_clearance=0.8)
     host = {k: v.numpy() for k, v in arrays.items()}
-    from nav_gym_amd import robots
-    host["scan_threshold"] = ref.scan_threshold(cfg, robots.footprint_array("keti", "threshold_footprint"))
-    host["scan_discomfort"] = ref.scan_threshold(cfg, robots.footprint_array("keti", "discomfort_threshold_footprint"))
+    host["scan_threshold"], host["scan_discomfort"] = keti_thresholds(cfg)
     a, b = ref.RefSim(cfg, host), ref.RefSim(cfg, host)
     assert np.array_equal(a.reset_obs(), b.reset_obs())
     rng = np.random.default_rng(1)

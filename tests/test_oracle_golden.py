@@ -5,14 +5,11 @@ stacking), a12/a13 (reward, terminals, info), a15 (xy->ij), and the orchestratio
 full reset()/step() traces of the reference's own code."""
 import os
 
-import os
-
 import numpy as np
 import pytest
 
 import ref
-from helpers import load_trace, trace_setup
-from nav_gym_amd import abi
+from helpers import crowd_golden, load_trace, trace_setup
 
 
 @pytest.fixture(scope="module")
@@ -263,19 +260,11 @@ def test_policy_control_block_vs_reference_trace(name):
         assert nw.max() > 16 and (r.a["ped_wp_head"][0] > 0).any()       # (ABI 5: a pop advances the head, the list stays)
 
 
-def _crowd_golden():
-    d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_crowd.npz"))
-    shape = tuple(int(x) for x in d["map_shape"])
-    maps = np.unpackbits(d["maps"])[: int(np.prod(shape))].reshape(shape)
-    params = {str(k): float(v) for k, v in zip(d["param_names"], d["params"])}
-    return d, maps, params
-
-
 def test_crowd_check_vs_reference_step():
     """the collision / goal / reward block of the reference's own CrowdSim.step
     (crowd_sim.py:808-949) on 600 random situations: info class and done flag exact, reward and Danger
     distance to 1e-12."""
-    d, maps, params = _crowd_golden()
+    d, maps, params = crowd_golden()
     reward, done, info, md = ref.crowd_check(params, maps, d["robot"], d["agents"], d["global_time"])
     assert np.array_equal(info, d["info"]) and np.array_equal(done, d["done"])
     assert np.abs(reward - d["reward"]).max() < 1e-12

@@ -12,18 +12,13 @@ import pytest
 
 import ped_observe_spec as spec
 import ref
+from helpers import struct_fields
 from nav_gym_amd import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- C ABI ------------------------------------------------------------------------------------------------------------------
-def _struct_fields(header, name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    return re.findall(r"(\w+)\s*;", body)
-
-
 def test_symbol_and_structures_in_header_library_and_exports():
     from nav_gym_amd import lib
     L = lib.load()
@@ -34,11 +29,11 @@ def test_symbol_and_structures_in_header_library_and_exports():
     assert C.sizeof(abi.NavsimStepIO) == L.navsim_sizeof_step_io()
     assert re.search(r"\bint navsim_ped_observe\(", header)
     assert "navsim_ped_observe" in abi.EXPORTS and hasattr(L, "navsim_ped_observe")
-    fields = _struct_fields(header, "navsim_ped_observe_params")
+    fields = struct_fields(header, "navsim_ped_observe_params")
     assert fields == ["ped_radius", "sensor_range", "max_obs", "rays", "occlusion", "fov"]
     assert [n for n, _ in abi.NavsimPedObserveParams._fields_] == fields
     assert C.sizeof(abi.NavsimPedObserveParams) == 2 * 8 + 4 * 4
-    fields = _struct_fields(header, "navsim_ped_observation")
+    fields = struct_fields(header, "navsim_ped_observation")
     assert fields == ["state", "index", "count", "visible"]
     assert [n for n, _ in abi.NavsimPedObservation._fields_] == fields == list(abi.PED_OBSERVATION)
     assert C.sizeof(abi.NavsimPedObservation) == 4 * C.sizeof(C.c_void_p)

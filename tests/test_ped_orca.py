@@ -11,7 +11,8 @@ import pytest
 
 import ped_orca_spec as spec
 import ref
-from nav_gym_amd import abi, robots, world
+from helpers import keti_thresholds
+from nav_gym_amd import abi, world
 
 CLOSE = 0.6 - 1e-4                  # the margin test_crowd_orca_properties uses for discs of 0.3 m
 
@@ -102,10 +103,10 @@ def _scene(starts, goals, v_pref, headings):
     wp = np.zeros((1, n, P, 2)); wp[0, :, 0] = goals
     pose = np.zeros((1, n, 3)); pose[0, :, :2] = starts; pose[0, :, 2] = headings
     rp = np.array([[1.5, 1.5, 0.0]])
+    thr, dthr = keti_thresholds(cfg)
     r = ref.RefSim(cfg, dict(
         field=ref.build_dt(occ), scan_noise_std=np.zeros(1, np.float32),
-        scan_threshold=ref.scan_threshold(cfg, robots.footprint_array("keti", "threshold_footprint")),
-        scan_discomfort=ref.scan_threshold(cfg, robots.footprint_array("keti", "discomfort_threshold_footprint")),
+        scan_threshold=thr, scan_discomfort=dthr,
         robot_pose=rp, robot_goal=np.array([[10.5, 10.5]]), prev_action=np.zeros((1, 2)), prev_pose=np.zeros((1, 3)),
         n_hist=np.zeros(1, np.int32), episode=np.zeros(1, np.int64), steps=np.zeros(1, np.int64),
         n_peds=np.full(1, n, np.int32), ped_pose=pose, ped_vel=np.zeros((1, n, 2)), ped_prev_yaw=np.zeros((1, n)),
@@ -164,8 +165,7 @@ def _random_world():
     a = world.make_world(cfg, occ, n_peds=6, device="cpu", field=torch.from_numpy(ref.build_dt(occ)), min_goal_dist=1.5,
                          max_goal_dist=4.0, v_pref_range=(0.3, 0.6))
     host = {k: v.numpy() for k, v in a.items()}
-    host["scan_threshold"] = ref.scan_threshold(cfg, robots.footprint_array("keti", "threshold_footprint"))
-    host["scan_discomfort"] = ref.scan_threshold(cfg, robots.footprint_array("keti", "discomfort_threshold_footprint"))
+    host["scan_threshold"], host["scan_discomfort"] = keti_thresholds(cfg)
     return cfg, host
 
 

@@ -9,12 +9,12 @@ import functools
 import numpy as np
 import pytest
 
-import orca_f64 as f64
 import ped_orca_spec as spec
 import ped_orca_walls_scenes as ws
 import ped_orca_walls_spec as wspec
 import ref
-from nav_gym_amd import abi, robots
+from helpers import keti_thresholds
+from nav_gym_amd import abi
 
 
 # ---- C ABI ------------------------------------------------------------------------------------------------------------------
@@ -202,10 +202,10 @@ def _through_boxes():
         pose[0, i, :2] = wp[0, i, 0]
         pose[0, i, 2] = 0.0 if along_x else np.pi / 2
     occ = ws.occupancy(1)
+    thr, dthr = keti_thresholds(cfg)
     r = ref.RefSim(cfg, dict(
         field=ref.build_dt(occ), scan_noise_std=np.zeros(1, np.float32),
-        scan_threshold=ref.scan_threshold(cfg, robots.footprint_array("keti", "threshold_footprint")),
-        scan_discomfort=ref.scan_threshold(cfg, robots.footprint_array("keti", "discomfort_threshold_footprint")),
+        scan_threshold=thr, scan_discomfort=dthr,
         robot_pose=np.array([[2.25, 3.75, 0.0]]), robot_goal=np.array([[3.75, 2.25]]), prev_action=np.zeros((1, 2)),
         prev_pose=np.zeros((1, 3)), n_hist=np.zeros(1, np.int32), episode=np.zeros(1, np.int64), steps=np.zeros(1, np.int64),
         n_peds=np.full(1, n, np.int32), ped_pose=pose, ped_vel=np.zeros((1, n, 2)), ped_prev_yaw=np.zeros((1, n)),

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import ref
+from gpu_support import gpu, keti_thresholds, random_actions  # noqa: F401  (gpu: the module's fixture)
 from nav_gym_amd import abi
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_reset.npz")
@@ -130,15 +131,6 @@ def test_oracle_spawn_decisions_equal_the_reference():
 
 
 # ---- the device ---------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from nav_gym_amd import lib, sim, world
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    lib.load()
-    return type("G", (), dict(torch=torch, lib=lib, sim=sim, world=world, dev=torch.device("cuda:0")))
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("fmt", [abi.FIELD_U16T, abi.FIELD_F32])
 def test_device_reset_on_supplied_draws_equals_the_reference(gpu, fmt):
@@ -213,7 +205,7 @@ def test_env_with_the_reference_map_sizes(gpu):
         refs.append((e, r))
     rng = np.random.default_rng(3)
     for t in range(5):
-        act = np.stack([rng.uniform(0, 0.5, E), rng.uniform(-0.64, 0.64, E)], axis=1)
+        act = random_actions(rng, E)
         obs, _, _, _ = env.step(act)
         og = obs["observation"].cpu().numpy()
         for e, r in refs:
@@ -227,8 +219,6 @@ def test_spawn_discomfort_check_changes_the_robot_start(gpu):
     """env.py:776-781: a start whose first scan has a beam inside the discomfort zone is dropped.  With the check the
     first observation of EVERY regenerated arena is clear of the discomfort threshold; without it some are not (so the
     check did something), and both variants equal the oracle."""
-    torch = gpu.torch
-    from nav_gym_amd import robots
     E, size = 64, 300
     worst = {}
     for check in (1, 0):
@@ -238,8 +228,7 @@ def test_spawn_discomfort_check_changes_the_robot_start(gpu):
                                      field_format=abi.FIELD_U16T)
         gpu.world.lidar_1081(cfg)
         arrays = gpu.world.empty_world(cfg, device=gpu.dev)
-        for key, name in (("scan_threshold", "threshold_footprint"), ("scan_discomfort", "discomfort_threshold_footprint")):
-            arrays[key] = gpu.sim.scan_threshold(cfg, torch.from_numpy(robots.footprint_array("keti", name)).to(gpu.dev))
+        arrays["scan_threshold"], arrays["scan_discomfort"] = keti_thresholds(gpu, cfg)
         s = gpu.sim.NavSim(cfg, arrays)
         s.out["done"].fill_(1)
         o = s.regen().cpu().numpy()
