@@ -574,6 +574,8 @@ class NavGymEnv(_EnvBase):
         plain_cap: cfg.regen_cap without the pipeline -- the constructor passes the library's default (64), the memory fallback
         of reset() passes nothing and gets min(num_envs, 64)."""
         regen = self.randomize_maps and self.auto_reset
+        # (corridor maps AND planned starts: the worlds whose navsim_regen forks -- sim.pregen_plan's `helper`; its `heavy` is the OR
+        #  of the two and decides another thing, the polled fallback and the two staging lanes)
         heavy = self.plan_paths and float(self.indoor_ratio) > 0.0
         self.pregen_pipeline = int(pipeline) if regen else 0
         if self.pregen_pipeline:

@@ -3,6 +3,7 @@
 torch is plumbing here: it owns the HBM buffers and the HIP stream; every computation of the hot
 path happens in libnavsim_hip.so.
 """
+import collections
 import ctypes as C
 import os
 
@@ -541,6 +542,86 @@ def concurrent_stream(device, priority=0, tries=8, beside=None):
     return best
 
 
+# ---- the reset path's mode: what NavSim.enable_pregen decides before it allocates anything (no torch, no library, no device) ----
+PregenPlan = collections.namedtuple("PregenPlan", (
+    "period",           # P: a staging pass every P steps (0: one between every two steps)
+    "install",          # step() is navsim_step_install: a finished arena's own workgroup installs its staged world
+    "shared_maps",      # live and staged state share the per-map arrays through slot tables
+    "fallback",         # navsim_regen for the arenas that finish before their world is staged (flags the step writes: NavSim.late)
+    "heavy",            # corridor maps OR planned starts: navsim_regen is the long chain of launches
+    "helper",           # corridor maps AND planned starts: navsim_regen forks, a helper stream for the fork
+    # side streams the passes alternate between.  KNOWN, NOT FIXED HERE: with 2 lanes a pass's part is
+    # pg_passes % 2, and pregen_sync / pregen_join reset pg_k but not pg_passes
+    "lanes",
+    "stage_cap",        # arenas one pass stages
+    "side_priority",    # of lane 0's side stream
+    # NEXT_STEP, worlds of outdoor maps without planning or costmap: NO fallback call at all -- an arena that finds nothing staged
+    # regenerates its own world inside the step's launch, in place of the step it does not take (include/navsim.h
+    # navsim_step_install with late = NULL; kernels_regen_dev.hpp regen_lone).  The library refuses (fewer than 256 threads per
+    # arena): _launch falls back to the flags + navsim_regen form.  KNOWN, NOT FIXED HERE: regen_min_steps
+    # is not consulted -- with 0 < regen_min_steps < 4 P the library runs rule-only and a late arena keeps its old map
+    "lone",
+    # NEXT_STEP (round 6): an arena learns when its episode ENDS whether the next world is staged; if not, the caller's
+    # navsim_regen generates it BESIDE the next step's launch, on a stream of its own (include/navsim.h
+    # navsim_step_install_next) -- nothing of the reset path is left on the steps' critical path, and no rule is needed
+    # MEASURED AND NOT THE DEFAULT (late_beside=True asks for it): c5, 512 arenas, no rule: 5.4 M env-steps/s against 6.9 M
+    # with the fallback's (mostly empty) launches behind the step on the same stream -- the two cross-stream waits per step
+    # cost more than the three launches they take off the critical path (profiles/r06_c5/README.md; the same finding as
+    # round 5's two-stream re-plan).  KNOWN, NOT FIXED HERE: in both next-step forms, this and `lone`,
+    # reset_arenas(mask) restarts an arena whose latest done flag is set a second time (the step has restarted it already)
+    "beside",
+    "poll",             # same-step: regen() reads "any late flag set?" back before it launches the fallback
+    "late_cap",         # arenas one fallback call serves (0: no fallback)
+    "late_defer_scan"))  # the fallback's configuration gets defer_reset_scan = 1 (the beside form)
+
+
+def late_cap_for(E, asked=None):
+    """Arenas one navsim_regen call of a fallback (the per-step one, reset_arenas' own) serves where nobody asks for a number."""
+    # (every launch of the fallback is sized by its cap whether anybody is late or not: with 16 slots the planner's
+    #  four launches alone dispatched 2 x 960 empty 1024-thread workgroups per step, 0.25 ms of a 0.38 ms step of the
+    #  reference's configuration, profiles/r05_refdef/timeline_pipeline8_no_rule_cap16.txt.  Late arenas are one in
+    #  ~100 steps of that loop; more of them than the cap in ONE step would restart in place, counted as regen_unserved.)
+    return int(min(E, asked if asked else max(8, E // 128)))
+
+
+def pregen_plan(cfg, next_step, has_costmap, pipeline=0, install=False, stage_cap=None, map_slots=True, fallback=None,
+                fallback_cap=None, late_beside=False, fallback_poll=None, stage_lanes=None):
+    """NavSim.enable_pregen's keyword arguments (described there), the world's configuration, its restart mode (NavSim.next_step)
+    and whether it has a costmap -> PregenPlan, or enable_pregen's ValueError."""
+    if not cfg.auto_reset:
+        raise ValueError("enable_pregen needs cfg.auto_reset = 1 (the step advances episode[e] when an arena finishes)")
+    E, P, install = cfg.n_envs, int(pipeline), bool(install)
+    fallback = bool(install and P > 0 and cfg.regen_min_steps < 4 * P if fallback is None else fallback)
+    if fallback and not install:
+        raise ValueError("enable_pregen(fallback=True) is a feature of install=True")
+    if P < 0 or (P > 0 and cfg.regen_min_steps < 4 * P and not fallback):
+        raise ValueError("enable_pregen(pipeline=%d) needs cfg.regen_min_steps >= %d (it is %d): an arena must not want its "
+                         "next world before the pass that stages it was waited for -- or fallback=True (install=True)"
+                         % (P, 4 * P, cfg.regen_min_steps))
+    if install and (not P or cfg.regen_cap < E):
+        raise ValueError("enable_pregen(install=True) needs pipeline >= 1 and cfg.regen_cap >= n_envs (every finished arena "
+                         "decides alone inside the step: there is no cap in index order)")
+    heavy = bool(cfg.regen_plan) or cfg.regen_indoor_ratio > 0.0
+    lanes = int(stage_lanes) if stage_lanes else (2 if (install and P and heavy) else 1)
+    if lanes not in (1, 2) or (lanes == 2 and not (install and P)):
+        raise ValueError("enable_pregen(stage_lanes=%r): 1, or 2 with install=True and pipeline > 0" % (stage_lanes,))
+    # a pipelined pass serves what the swaps of P steps marked: P caps' worth of arenas (twice that: what a pass leaves
+    # waits for the next one and would be late)
+    cap = cfg.regen_cap
+    if P:
+        # (install: every launch of a pass is sized by the cap, not by what it serves -- 512 slots for the ~35 arenas a pass
+        #  of the reference's configuration stages made its planner launches dispatch 30 000 empty workgroups, 367 us each)
+        per_step = max(8, E // 64) if install else cfg.regen_cap
+        cap = int(min(E, stage_cap if stage_cap else 2 * P * per_step))
+    beside = bool(fallback and next_step and late_beside)
+    return PregenPlan(
+        period=P, install=install, shared_maps=bool(install and map_slots), fallback=fallback, heavy=heavy,
+        helper=bool(cfg.regen_plan and cfg.regen_indoor_ratio > 0.0), lanes=lanes, stage_cap=cap, side_priority=0 if P else -1,
+        lone=bool(fallback and next_step and not late_beside and not heavy and not has_costmap), beside=beside,
+        poll=bool(fallback and (heavy if fallback_poll is None else fallback_poll) and not next_step),
+        late_cap=late_cap_for(E, fallback_cap) if fallback else 0, late_defer_scan=beside)
+
+
 class _StepProduct(object):
     """What one enable_* call of NavSim makes for a launch behind the step (observed pedestrians, goal path, local planner, local
     map): the parameters, two sets of outputs -- they flip with NavSim.cur, so what a call returned stays intact through the next
@@ -586,12 +667,13 @@ class NavSim(object):
         self.cfg = cfg.copy()
         self.device = torch.device(device)
         # everything the enable_* calls and the lazily made streams set, at its "not enabled" value
-        # staging (enable_pregen): the staged state, what a pass serves, the lanes (lane 0 = want / stage_io / stage_ws / side)
+        # staging (enable_pregen): pregen_plan()'s record of the mode, the staged state, what a pass serves, the lanes (lane 0 = want /
+        # stage_io / stage_ws / side)
         self.pregen = self.pg_install = False
         self.pg_period = self.pg_k = self.pg_passes = self.stage_cap = 0
         self.pg_open, self.pg_swapped, self.pg_staged, self.stage_lane = [], [], [], []
         self.stage_t, self.stage_st, self.stage_cfg, self.stage_obs, self.stage_io, self.stage_ws = {}, None, None, None, None, None
-        self.want = self.mark = self.ready = self.side = self.ev_swapped = self.ev_staged = None
+        self.pg_plan = self.want = self.mark = self.ready = self.side = self.ev_swapped = self.ev_staged = None
         # fallback: the arenas that finished before their world was staged (flags the step writes, navsim_regen for them)
         self.late, self.late_cfg, self.late_ws, self.late_cap = None, None, None, 0
         self.late_poll = self.lone = False
@@ -953,33 +1035,22 @@ class NavSim(object):
         and each has a slot table (navsim_state.map_slot); an install exchanges two table entries instead of copying the
         map -- numpy_state() resolves the table, code that indexes t['field'] by arena must go through t['map_slot']."""
         import torch
-        if not self.cfg.auto_reset:
-            raise ValueError("enable_pregen needs cfg.auto_reset = 1 (the step advances episode[e] when an arena finishes)")
-        E = self.cfg.n_envs
-        P = int(pipeline)
-        if fallback is None:
-            fallback = bool(install) and P > 0 and self.cfg.regen_min_steps < 4 * P
-        if fallback and not install:
-            raise ValueError("enable_pregen(fallback=True) is a feature of install=True")
-        if P < 0 or (P > 0 and self.cfg.regen_min_steps < 4 * P and not fallback):
-            raise ValueError("enable_pregen(pipeline=%d) needs cfg.regen_min_steps >= %d (it is %d): an arena must not want its "
-                             "next world before the pass that stages it was waited for -- or fallback=True (install=True)"
-                             % (P, 4 * P, self.cfg.regen_min_steps))
+        # the whole decision first (it raises what this call refuses): a refused call leaves the simulator as it was
+        plan = pregen_plan(self.cfg, self.next_step, "costmap" in self.t, pipeline, install, stage_cap, map_slots, fallback,
+                           fallback_cap, late_beside, fallback_poll, stage_lanes)
+        self.pg_plan = plan
+        E, P = self.cfg.n_envs, plan.period
         self.pg_period, self.pg_k = P, 0
-        if install and (not P or self.cfg.regen_cap < E):
-            raise ValueError("enable_pregen(install=True) needs pipeline >= 1 and cfg.regen_cap >= n_envs (every finished arena "
-                             "decides alone inside the step: there is no cap in index order)")
         self.ready = torch.zeros(2 * E, dtype=torch.int64, device=self.device) if P else None
         # (the per-map arrays of a slot-table world are allocated ONCE at twice the size below instead of cloned and then concatenated:
         #  fresh device memory is what the first reset() of a large world waits for -- 50 GB at 4096 arenas of 1000 x 1000 cells)
-        shared_maps = bool(install and map_slots)
-        self.stage_t = {k: self.t[k].clone() for k in self.STAGED if k in self.t and not (shared_maps and k in self.MAPS)}
+        self.stage_t = {k: self.t[k].clone() for k in self.STAGED if k in self.t and not (plan.shared_maps and k in self.MAPS)}
         self.stage_t["episode"] = self.t["episode"] + 1
         self.stage_st = abi.NavsimState()
         C.memmove(C.byref(self.stage_st), C.byref(self.st), C.sizeof(self.st))
         for k, v in self.stage_t.items():
             setattr(self.stage_st, k, v.data_ptr())
-        if install and map_slots:
+        if plan.shared_maps:
             for k in self.MAPS:
                 if k in self.t:
                     live = self.t[k]
@@ -1005,14 +1076,7 @@ class NavSim(object):
         self.stage_io.obs = self.stage_obs.data_ptr()
         self.stage_io.done = self.want.data_ptr()
         self._stage_all(scratch_bytes)
-        # a pipelined pass serves what the swaps of P steps marked: P caps' worth of arenas (twice that: what a pass leaves
-        # waits for the next one and would be late)
-        self.stage_cap = self.cfg.regen_cap
-        if P:
-            # (install: every launch of a pass is sized by the cap, not by what it serves -- 512 slots for the ~35 arenas a pass
-            #  of the reference's configuration stages made its planner launches dispatch 30 000 empty workgroups, 367 us each)
-            per_step = max(8, E // 64) if install else self.cfg.regen_cap
-            self.stage_cap = int(min(E, stage_cap if stage_cap else 2 * P * per_step))
+        self.stage_cap = plan.stage_cap
         self.stage_cfg = self.cfg.copy()
         self.stage_cfg.regen_cap = self.stage_cap
         nbytes = self.lib.navsim_regen_workspace_bytes(C.byref(self.stage_cfg))
@@ -1025,20 +1089,16 @@ class NavSim(object):
         # of slack -- and a process that has used a high-priority stream replays hipGraphs ~10 us per kernel slower from then
         # on: a reference-default environment built afterwards ran at 0.59 M env-steps/s instead of 0.87 M,
         # profiles/_diag/after_pregen.py.)
-        self.side = concurrent_stream(self.device, priority=0 if P else -1)
+        self.side = concurrent_stream(self.device, priority=plan.side_priority)
         # navsim_regen's helper stream (the distance transform of new corridor maps beside the searches): beside the steps AND
         # beside the passes -- three streams, three hardware queues
-        if self.cfg.regen_plan and self.cfg.regen_indoor_ratio > 0.0:
+        if plan.helper:
             self._regen_helper = concurrent_stream(self.device, beside=[torch.cuda.current_stream(self.device), self.side])
             check(self.lib.navsim_regen_helper(C.c_void_p(self._regen_helper.cuda_stream)), "navsim_regen_helper")
-        heavy = bool(self.cfg.regen_plan) or self.cfg.regen_indoor_ratio > 0.0
-        lanes = int(stage_lanes) if stage_lanes else (2 if (install and P and heavy) else 1)
-        if lanes not in (1, 2) or (lanes == 2 and not (install and P)):
-            raise ValueError("enable_pregen(stage_lanes=%r): 1, or 2 with install=True and pipeline > 0" % (stage_lanes,))
         # lane 0 = the objects above; lane 1: its own want[], io, workspace, stream and helper stream
         self.stage_lane = [dict(want=self.want, io=self.stage_io, ws=self.stage_ws, side=self.side,
                                 helper=self._regen_helper)]
-        if lanes == 2:
+        if plan.lanes == 2:
             want2 = torch.zeros(E, dtype=torch.uint8, device=self.device)
             io2 = abi.NavsimStepIO()
             C.memmove(C.byref(io2), C.byref(self.stage_io), C.sizeof(io2))
@@ -1055,41 +1115,23 @@ class NavSim(object):
         self.pg_swapped = [torch.cuda.Event() for _ in range(3)]      # pass j uses slot j % 3; step j P waits for pass j - 2
         self.pg_staged = [torch.cuda.Event() for _ in range(3)]
         self.pregen = True
-        self.pg_install = bool(install)
+        self.pg_install = plan.install
         self.pg_replan_cap, self.pg_replan_in_step = 0, True       # (set pg_replan_cap to re-plan inside the step's launch, _launch)
         # the fallback: flags the step writes, and a navsim_regen of its own size for the arenas they name
-        self.late = torch.zeros(E, dtype=torch.uint8, device=self.device) if fallback else None
-        # NEXT_STEP (round 6): an arena learns when its episode ENDS whether the next world is staged; if not, the caller's
-        # navsim_regen generates it BESIDE the next step's launch, on a stream of its own (include/navsim.h
-        # navsim_step_install_next) -- nothing of the reset path is left on the steps' critical path, and no rule is needed
-        # MEASURED AND NOT THE DEFAULT (late_beside=True asks for it): c5, 512 arenas, no rule: 5.4 M env-steps/s against 6.9 M
-        # with the fallback's (mostly empty) launches behind the step on the same stream -- the two cross-stream waits per step
-        # cost more than the three launches they take off the critical path (profiles/r06_c5/README.md; the same finding as
-        # round 5's two-stream re-plan)
-        # NEXT_STEP, worlds of outdoor maps without planning or costmap: NO fallback call at all -- an arena that finds nothing staged
-        # regenerates its own world inside the step's launch, in place of the step it does not take (include/navsim.h
-        # navsim_step_install with late = NULL; kernels_regen_dev.hpp regen_lone).  The library refuses (fewer than 256 threads per
-        # arena): _launch falls back to the flags + navsim_regen form.
-        self.lone = bool(fallback and self.next_step and not late_beside and not (self.cfg.regen_indoor_ratio > 0.0) and
-                         not self.cfg.regen_plan and "costmap" not in self.t)
+        self.late = torch.zeros(E, dtype=torch.uint8, device=self.device) if plan.fallback else None
+        self.lone = plan.lone
         self.late2 = None
-        if fallback and self.next_step and late_beside:
+        if plan.beside:
             self.late2 = [torch.zeros(E, dtype=torch.uint8, device=self.device) for _ in range(2)]
             self.urgent = concurrent_stream(self.device, beside=[torch.cuda.current_stream(self.device), self.side])
             self.ev_stepped, self.ev_urgent = torch.cuda.Event(), torch.cuda.Event()
             self.ev_stepped.record(torch.cuda.current_stream())
-        if fallback_poll is None:
-            fallback_poll = bool(self.cfg.regen_plan) or self.cfg.regen_indoor_ratio > 0.0
-        self.late_poll = bool(fallback and fallback_poll and not self.next_step)
-        if fallback:
+        self.late_poll = plan.poll
+        if plan.fallback:
             self.late_cfg = self.cfg.copy()
-            # (every launch of the fallback is sized by its cap whether anybody is late or not: with 16 slots the planner's
-            #  four launches alone dispatched 2 x 960 empty 1024-thread workgroups per step, 0.25 ms of a 0.38 ms step of the
-            #  reference's configuration, profiles/r05_refdef/timeline_pipeline8_no_rule_cap16.txt.  Late arenas are one in
-            #  ~100 steps of that loop; more of them than the cap in ONE step would restart in place, counted as regen_unserved.)
-            self.late_cap = int(min(E, fallback_cap if fallback_cap else max(8, E // 128)))
+            self.late_cap = plan.late_cap
             self.late_cfg.regen_cap = self.late_cap
-            if self.late2 is not None:
+            if plan.late_defer_scan:
                 self.late_cfg.defer_reset_scan = 1          # (the launch skips a flagged arena altogether: its row is navsim_regen's,
                                                             #  also when the arena lies beyond this call's cap and restarts in place)
             self.late_ws = torch.zeros(self.lib.navsim_regen_workspace_bytes(C.byref(self.late_cfg)), dtype=torch.uint8, device=self.device)
@@ -1379,7 +1421,7 @@ class NavSim(object):
                 ws, cap = self.late_ws, self.late_cap
             else:
                 if self.rs_ws is None:
-                    self.rs_cap = int(min(E, max(8, E // 128)))
+                    self.rs_cap = late_cap_for(E)
                     cfg = self.cfg.copy()
                     cfg.regen_cap = self.rs_cap
                     self.rs_ws = torch.zeros(self.lib.navsim_regen_workspace_bytes(C.byref(cfg)), dtype=torch.uint8, device=self.device)

@@ -53,3 +53,33 @@ def test_a_simulator_without_any_enable_call(gpu):
     torch.cuda.synchronize()
     assert torch.isfinite(obs).all() and g.pg_k == 3 and g.pg_passes == 3
     g.close()
+
+
+def test_a_refused_enable_pregen_leaves_the_simulator_as_it_was(gpu):
+    """enable_pregen decides everything (sim.pregen_plan) before it touches the object: a call it refuses -- the last of its
+    checks (stage_lanes) or an early one -- leaves every attribute at its "not enabled" value, no plan, no slot table and the
+    maps where they were; a valid call on the same object then works."""
+    torch = gpu.torch
+    cfg, occ, _, wkw = regen_layout(gpu, "float32-smallest")
+    E = 6
+    cfg.n_envs, cfg.regen_cap, cfg.max_peds, cfg.ped_model, cfg.field_format = E, E, 2, abi.PED_SFM, abi.FIELD_U16T
+    gpu.world.lidar_full_circle(cfg, 64)
+    g = device_sim(gpu, cfg, occ[:E], 2, **wkw)
+    field = g.t["field"]
+    for kw, text in ((dict(pipeline=1, install=True, stage_lanes=3), "stage_lanes=3"), (dict(fallback=True), "fallback=True")):
+        with pytest.raises(ValueError, match=text):
+            g.enable_pregen(**kw)
+        for k, v in OFF.items():
+            assert getattr(g, k) == v and type(getattr(g, k)) is type(v), (kw, k)
+        assert g.pg_plan is None and "map_slot" not in g.t and g.t["field"] is field
+    g.enable_pregen(pipeline=1, install=True)
+    assert g.pregen is True and g.pg_install is True and g.pg_period == 1 and len(g.stage_lane) == 1
+    assert g.pg_plan == gpu.sim.pregen_plan(g.cfg, False, False, pipeline=1, install=True)
+    assert g.pg_plan.fallback and g.late is not None and g.late_cap == g.pg_plan.late_cap == E and g.stage_cap == g.pg_plan.stage_cap == E
+    assert "map_slot" in g.t and g.stage_lane[0]["side"] is g.side and g.stage_lane[0]["ws"] is g.stage_ws
+    for k in (2, 3, 4):
+        obs, out = g.step(seeded_action(gpu, E, k))
+        g.regen()
+    torch.cuda.synchronize()
+    assert torch.isfinite(obs).all() and g.pg_k == 3 and g.pg_passes == 3
+    g.close()
