@@ -1337,6 +1337,65 @@ int navsim_local_map(const navsim_config* cfg, const navsim_state* st, const nav
                      const uint8_t* visible /* [E,N] or NULL */, const uint8_t* skip /* [E] or NULL */,
                      float* out /* [E,C,G,G] */, void* stream);
 
+/* ---- scan ground truth: the robot's scan without noise, and per beam what it fell on, from one launch ---------------------------
+ * What a 2D-lidar person / leg detector (the DROW / DR-SPAAM family) or a lidar tracker trains on, what a policy that masks or
+ * weights pedestrian returns reads, and what a scan denoiser takes as its target: the step's observation has walls, pedestrian
+ * bodies, pedestrian legs and (optionally) noise min-merged into one range per beam and keeps no record of which won.
+ * BUILD-DEFINED, all of it: the reference returns the merged scan alone (env.py:385-441).  The arithmetic is the one of
+ * robot_scan / gather_prims (oracle/navsim_ref.c:557-631), which restate env.py:385-435. */
+#define NAVSIM_BEAM_NONE     0   /* no return: the clipped range equals range_max (the beams that never receive noise) */
+#define NAVSIM_BEAM_WALL     1   /* the static map */
+#define NAVSIM_BEAM_PED_BODY 2   /* a side of a pedestrian's footprint rectangle */
+#define NAVSIM_BEAM_PED_LEG  3   /* a leg disc of a pedestrian with legs (cfg.lidar_legs) */
+typedef struct navsim_scan_labels_out {
+    float*   range;   /* [E,B] the robot's scan of the current state without noise: clipped to [0, range_max] */
+    uint8_t* label;   /* [E,B] NAVSIM_BEAM_NONE 0 | _WALL 1 | _PED_BODY 2 | _PED_LEG 3 */
+    int8_t*  index;   /* [E,B] pedestrian index for labels 2 and 3, else -1 */
+    int32_t* hits;    /* [E,N] beams labelled with pedestrian i; entries i >= n are 0; may be NULL */
+} navsim_scan_labels_out;
+
+/* ONE launch (a workgroup per arena; kernels_scan_labels.hpp), no device-to-host copy, nothing that blocks, no allocation.  Call
+ * it behind the step (and whatever follows it: navsim_regen, navsim_replan) on the same stream.  It reads st->robot_pose, the
+ * distance field of the arena's map slot (cfg.shared_field, st->map_slot, st->field_overflow, st->rect_table; both field formats)
+ * and, with a pedestrian model, n_peds, ped_pose, ped_dist and ped_has_legs; it writes EVERY element of `out`.  float32 unless
+ * stated, every operation rounded on its own (no fused multiply-add: DESIGN.md section 4); B = cfg.n_beams, N = cfg.max_peds.
+ * Per arena e:
+ *  1. skip && skip[e]: every range 0, every label 0, every index -1, every hits entry 0.  Nothing of the arena is read.
+ *  2. n = min(n_peds[e], N), or 0 with NAVSIM_PED_NONE.  The lidar pose (lx, ly, lth) is the float32 cast of robot_pose[e]
+ *     (env.py:386); the origin cell (i0, j0) = xy_to_ij_f32(lx, ly) (env.py:419).  Beam k's heading is
+ *     (float)(linspace_k(k) + (double)lth), its direction beam_dir(heading): the values the step uses.
+ *  3. candidate 0, the static ray: the restatement of range_libc's calc_range that navsim_cast_static runs, on the field of the
+ *     arena's map slot, from ((float)i0, (float)j0) along the beam, with cfg.march_rule and max_range = (float)((int64)H*W),
+ *     times (float)cfg.resolution (env.py:425-426).
+ *  4. candidates 1, 2, ... in gather_prims' order: first, for i = 0 .. n-1 ascending, the four sides v -> (v+1) mod 4 of every
+ *     pedestrian that is NOT (ped_has_legs[e,i] and cfg.lidar_legs) -- its corners the float64 rotation and translation of the
+ *     human footprint (+-0.22, +-0.19) by ped_pose[e,i], rounded to float32 --; then, for i ascending, the right and then the
+ *     left disc of every pedestrian that is: leg_centres on the float32 casts of ped_pose[e,i] and ped_dist[e,i], radius 0.03.
+ *  5. r starts as candidate 0's value.  Each further candidate, in order, replaces r iff its seg_merge / circle_merge accepts
+ *     (t >= 0 and, for a side, 0 <= u <= 1) and t < r, strictly.  The WINNER is the last candidate that lowered r, candidate 0
+ *     if none did -- which is the first candidate in order whose value equals the final r.
+ *  6. r is clipped to [0, range_max] (env.py:435): range[e,k] = r.  label = NAVSIM_BEAM_NONE iff r == (float)range_max; else
+ *     _WALL, _PED_BODY or _PED_LEG by the winner's kind.  index = the winner's pedestrian for _PED_BODY and _PED_LEG, else -1.
+ *  7. hits[e,i] = the number of beams k with index[e,k] == i (0 for i >= n).
+ * PROPERTY: with cfg.add_scan_noise == 0, range[e] equals the newest scan slot -- the last B floats ahead of the 7-float tail --
+ * of the observation row the step (or navsim_reset_obs) wrote for the same state, bit for bit.  With noise on the two differ
+ * by the noise alone, and only where label != NAVSIM_BEAM_NONE.
+ * How the kernel meets the sequential rule: its primitives lie in step 4's order; `range` comes from the step's own merge
+ * (merge_prims_culled_core: an atomic minimum per beam, in whatever order) after the step's own march (stopped at
+ * floor(range_max / resolution) + 4 cells and culled beyond range_max, neither of which changes a clipped range); a second pass
+ * then takes, per beam, the least candidate number whose t EQUALS the merged range, candidate 0 first -- the winner of step 5.
+ * Equality is by value: candidates of +0.0f and -0.0f on one beam (a lidar origin exactly on two primitives' lines) tie, the
+ * earlier one wins as in step 5, and the sign of that zero in `range` is the one the step's merge leaves in the observation.
+ * NAVSIM_E_ARG, before anything touches the device: cfg, st or out NULL; out->range, label or index NULL; st->robot_pose or
+ * st->field NULL; with a pedestrian model st->n_peds, ped_pose, ped_dist or ped_has_legs NULL; n_envs < 0; n_beams < 1; map_h or
+ * map_w < 1; max_peds outside 0 .. NAVSIM_MAX_PEDS (outside 1 .. with a pedestrian model); a march_rule that is none of
+ * NAVSIM_MARCH_*; st->map_slot with cfg.shared_field.  NAVSIM_E_UNSUPPORTED: a field_format that is neither NAVSIM_FIELD_F32 nor
+ * NAVSIM_FIELD_U16T; st->rect_table with a float32 field or a map above 1024 cells a side; with a pedestrian model a field of view
+ * angle_last - angle_min above 2 pi (the culled merge, as in navsim_step); beams x pedestrians beyond one compute unit's LDS
+ * (16 bytes per beam + 120 per pedestrian slot against 160 KB).  n_envs == 0: NAVSIM_OK, nothing is launched. */
+int navsim_scan_labels(const navsim_config* cfg, const navsim_state* st, const uint8_t* skip /* [E] or NULL */,
+                       const navsim_scan_labels_out* out, void* stream);
+
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);
 

@@ -24,6 +24,7 @@
 //   kernels_goal_path.hpp  distance-to-goal field per arena, the robot's path distance and steering sub-goal (navsim_goal_path)
 //   kernels_dwa.hpp  local planner: a dynamic-window action per arena (navsim_dwa)
 //   kernels_local_map.hpp  egocentric local map: wall and pedestrian grids per arena in the robot's frame (navsim_local_map)
+//   kernels_scan_labels.hpp  scan ground truth: the robot's clean scan and per-beam hit labels (navsim_scan_labels)
 //   step_plan.hpp        launch geometry of the fused step, the descriptors of a launch and the march-rule dispatch (shared by this
 //                        file and navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
 // Host code of this file, ahead of the C ABI: dispatch_step and the argument checks; the workspaces (Carver and one layout
@@ -51,6 +52,7 @@ namespace {
 #include "kernels_goal_path.hpp"
 #include "kernels_dwa.hpp"
 #include "kernels_local_map.hpp"
+#include "kernels_scan_labels.hpp"
 
 }  // namespace
 #include "step_plan.hpp"
@@ -512,6 +514,19 @@ int launch_local_map(const navsim_config* c, const navsim_state* st, const Local
     if (vec) local_map_kernel<F, 4><<<grid, block, 0, s>>>(*c, *st, a);
     else     local_map_kernel<F, 1><<<grid, block, 0, s>>>(*c, *st, a);
     return launch_status();
+}
+
+// navsim_scan_labels: a workgroup per arena; one kernel per (field type, march rule, rect records or not) as the pedestrian
+// scans have them (launch_ped_scan) -- eleven forms
+template <typename F, bool RECT>
+int launch_scan_labels(const navsim_config* c, const navsim_state* st, const ScanLabelsArgs& a, hipStream_t s) {
+    const size_t lds = scan_labels_lds_bytes(c);
+    return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
+        auto kernel = scan_labels_kernel<F, decltype(rule)::value, RECT>;
+        if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
+        kernel<<<c->n_envs, kScanLabelsBlock, lds, s>>>(*c, *st, a);
+        return launch_status();
+    });
 }
 
 }  // namespace
@@ -1601,6 +1616,30 @@ int navsim_local_map(const navsim_config* c, const navsim_state* st, const navsi
     a.p = *p; a.visible = p->channels > 1 ? visible : nullptr; a.skip = skip; a.out = out;
     hipStream_t s = (hipStream_t)stream;
     return with_field(c, st, [&](auto field) { return launch_local_map<typename decltype(field)::type>(c, st, a, s); });
+}
+
+int navsim_scan_labels(const navsim_config* c, const navsim_state* st, const uint8_t* skip, const navsim_scan_labels_out* out,
+                       void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !out || !out->range || !out->label || !out->index) return NAVSIM_E_ARG;
+    if (!st->robot_pose || !st->field) return NAVSIM_E_ARG;
+    const bool peds = c->ped_model != NAVSIM_PED_NONE;
+    if (peds && (!st->n_peds || !st->ped_pose || !st->ped_dist || !st->ped_has_legs)) return NAVSIM_E_ARG;
+    if (c->n_envs < 0 || c->n_beams < 1 || c->map_h < 1 || c->map_w < 1) return NAVSIM_E_ARG;
+    if (c->max_peds < (peds ? 1 : 0) || c->max_peds > NAVSIM_MAX_PEDS) return NAVSIM_E_ARG;
+    if (c->march_rule < NAVSIM_MARCH_F64 || c->march_rule > NAVSIM_MARCH_F32_FMA) return NAVSIM_E_ARG;
+    if (st->map_slot && c->shared_field) return NAVSIM_E_ARG;
+    if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
+    if (st->rect_table && (c->field_format != NAVSIM_FIELD_U16T || c->map_h > 1024 || c->map_w > 1024)) return NAVSIM_E_UNSUPPORTED;
+    if (peds && c->angle_last - c->angle_min > nv::kTwoPi) return NAVSIM_E_UNSUPPORTED;     // the culled merge: dispatch_step
+    if (scan_labels_lds_bytes(c) > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    ScanLabelsArgs a = {};
+    a.out = *out; a.skip = skip;
+    hipStream_t s = (hipStream_t)stream;
+    if (c->field_format == NAVSIM_FIELD_U16T)
+        return st->rect_table ? launch_scan_labels<FieldU16T, true>(c, st, a, s) : launch_scan_labels<FieldU16T, false>(c, st, a, s);
+    return launch_scan_labels<FieldF32, false>(c, st, a, s);
 }
 
 const char* navsim_step_kernel_name(void) { return "navsim_step_kernel"; }

@@ -260,6 +260,15 @@ class NavsimLocalMapParams(C.Structure):
 
 LOCAL_MAP_OUT = {"map": ("float32", ("C", "G", "G"))}       # (dtype, trailing shape behind E; C = channels, G = size)
 
+# navsim_scan_labels: the labels of a beam, and the four output arrays (dtype, trailing shape behind E; B = n_beams, N = max_peds)
+BEAM_NONE, BEAM_WALL, BEAM_PED_BODY, BEAM_PED_LEG = 0, 1, 2, 3
+SCAN_LABELS_OUT = {"range": ("float32", ("B",)), "label": ("uint8", ("B",)), "index": ("int8", ("B",)), "hits": ("int32", ("N",))}
+
+
+class NavsimScanLabelsOut(C.Structure):
+    _fields_ = [(name, _P) for name in SCAN_LABELS_OUT]
+
+
 ORCA_MAX_AGENTS = 64
 ORCA_MAX_EDGES = 128
 CROWD_MAX_VERTS = 8
@@ -475,6 +484,8 @@ def declare(lib, suffix=""):
         sig("navsim_dwa", [cfgp, stp, C.POINTER(NavsimDwaParams), _P, _P, C.POINTER(NavsimDwaOut), _P])
     if not suffix and hasattr(lib, "navsim_local_map"):                 # (likewise)
         sig("navsim_local_map", [cfgp, stp, C.POINTER(NavsimLocalMapParams), _P, _P, _P, _P])
+    if not suffix and hasattr(lib, "navsim_scan_labels"):               # (likewise)
+        sig("navsim_scan_labels", [cfgp, stp, _P, C.POINTER(NavsimScanLabelsOut), _P])
     sig("navsim_reset_obs", [cfgp, stp, iop, _P] + stream)
     sig("navsim_restart", [cfgp, stp, _P] + stream)
     return lib
@@ -494,6 +505,7 @@ EXPORTS = (
     "navsim_step", "navsim_step_sorted", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
     "navsim_episode_stats_update", "navsim_episode_stats_clear", "navsim_ped_observe",
     "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps", "navsim_dwa", "navsim_local_map",
+    "navsim_scan_labels",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

@@ -135,6 +135,18 @@ and default to the reference's behaviour for num_envs == 1:
                     info['final_observation'] carries no map.  env.local_map() returns the same tensor, also after reset() /
                     reset(mask).  num_envs > 1: a torch tensor with the lifetime below; num_envs == 1: a NumPy array [C, G, G]
                     from one device -> host copy.  None (default): nothing is allocated or launched.
+    scan_labels     True: the ground truth of the lidar, one launch behind the step (navsim_scan_labels; what a 2D-lidar person or
+                    leg detector, a tracker, a policy that masks pedestrian returns or a scan denoiser trains on) --
+                    info['scan_labels'] = {'range' [E,B] float32, the robot's scan of the current state WITHOUT noise; 'label'
+                    [E,B] uint8, abi.BEAM_NONE 0 (no return: range == range_max) / BEAM_WALL 1 / BEAM_PED_BODY 2 / BEAM_PED_LEG 3;
+                    'index' [E,B] int8, the pedestrian a beam of label 2 or 3 fell on, else -1; 'hits' [E,N] int32, the beams
+                    that see each pedestrian (only with a pedestrian model)}.  With scan noise off, 'range' equals the newest
+                    scan slot of the observation bit for bit; with noise on the two differ by the noise alone, and only where
+                    label != 0.  The rows describe the state the returned observation row describes; under next-step auto-reset
+                    an arena whose `done` is set is skipped (range 0, label 0, index -1, hits 0) until the step that resets it.
+                    env.scan_labels() returns the same dict, also after reset() / reset(mask).  num_envs > 1: torch views with
+                    the lifetime below; num_envs == 1: NumPy rows from one device -> host copy.  False (default): nothing is
+                    allocated or launched.
     reset(mask)     reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
                     [num_envs]; the others keep their state and their rows.  On the pipelined reset path the masked arenas install
                     their staged worlds in one launch: the same state and rows as with pregen_pipeline=0.
@@ -290,7 +302,8 @@ class NavGymEnv(_EnvBase):
                  regen_min_steps=0, pregen_pipeline=None, pregen_stage_cap=None, autoreset_mode="same_step",
                  final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None,
                  episode_stats=False, observe_humans=None, observe_params=None, goal_path=False, goal_path_params=None,
-                 local_planner=None, local_planner_params=None, observe_local_map=None, local_map_params=None):
+                 local_planner=None, local_planner_params=None, observe_local_map=None, local_map_params=None,
+                 scan_labels=False):
         # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
         self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
         from . import lib
@@ -514,6 +527,10 @@ class NavGymEnv(_EnvBase):
         self.observe_local_map = None if observe_local_map is None else int(observe_local_map)
         self.local_map_params = None if local_map_params is None else dict(local_map_params)
         self._local_map_visible = bool((local_map_params or {}).get("visible_only"))
+        # scan ground truth (navsim_scan_labels): the clean scan and per-beam hit labels, one launch behind the step
+        if not isinstance(scan_labels, (bool, np.bool_)):
+            raise ValueError("scan_labels must be True or False, not %r" % (scan_labels,))
+        self.scan_labels_on = bool(scan_labels)
         # the launches behind the step (and behind reset() / reset(mask) / load_state_dict), in the order they run -- the planner
         # reads the goal path's sub-goal, the local map the observer's `visible`.  _run_products() runs them; its latest result
         # and, per buffer parity, the views it handed out
@@ -521,7 +538,9 @@ class NavGymEnv(_EnvBase):
             (self.observe_humans, _Product("humans", "ped_observe", self._observe, tuple(abi.PED_OBSERVATION), self._humans_row)),
             (self.goal_path_on, _Product("goal_path", "goal_path", self._goal_path, tuple(abi.GOAL_PATH_OUT), None)),
             (self.local_planner, _Product("planner", "dwa", self._plan, self._PLANNER_KEYS, None)),
-            (self.observe_local_map, _Product("local_map", "local_map", self._local_map, ("map",), operator.itemgetter("map")))) if on]
+            (self.observe_local_map, _Product("local_map", "local_map", self._local_map, ("map",), operator.itemgetter("map"))),
+            (self.scan_labels_on, _Product("scan_labels", "scan_labels", self._scan_labels,
+                                           tuple(k for k in abi.SCAN_LABELS_OUT if k != "hits" or cfg.ped_model != abi.PED_NONE), None))) if on]
         self._product_out, self._product_views = {}, {}
         self.cfg = cfg
         self.sim = None
@@ -678,6 +697,8 @@ class NavGymEnv(_EnvBase):
             if self.observe_local_map:
                 self.sim.enable_local_map(self.observe_local_map, {k: v for k, v in (self.local_map_params or {}).items()
                                                                    if k != "visible_only"})
+            if self.scan_labels_on:
+                self.sim.enable_scan_labels()
         elif "policy_prev_actions" in self.sim.t:
             self.sim.t["policy_prev_actions"].zero_()           # env.py:739
         self._episode_batch += 1
@@ -900,6 +921,9 @@ class NavGymEnv(_EnvBase):
         sim = self.sim                                    # pedestrians that count)
         sim.local_map(skip=skip, visible=sim.products["ped_observe"].buf[sim.cur]["visible"] if self._local_map_visible else None)
 
+    def _scan_labels(self, skip, rebuild):
+        self.sim.scan_labels(skip=skip)
+
     def _latest(self, key, on, what, needs):
         """What info[key] of the latest step() holds; valid after reset() and reset(mask) too."""
         if not on:
@@ -912,6 +936,12 @@ class NavGymEnv(_EnvBase):
         """What info['local_map'] of the latest step() holds (observe_local_map=G); valid after reset() and reset(mask) too:
         float32 [E, C, G, G] in the robot's frame (num_envs == 1: a NumPy array [C, G, G])."""
         return self._latest("local_map", self.observe_local_map, "local_map", "observe_local_map=G")
+
+    def scan_labels(self):
+        """What info['scan_labels'] of the latest step() holds (scan_labels=True); valid after reset() and reset(mask) too:
+        {'range' [E,B] float32, the scan without noise; 'label' [E,B] uint8 (abi.BEAM_*); 'index' [E,B] int8, the pedestrian of
+        a beam with label 2 or 3, else -1; 'hits' [E,N] int32 with a pedestrian model}."""
+        return self._latest("scan_labels", self.scan_labels_on, "scan_labels", "scan_labels=True")
 
     def planner_action(self):
         """What info['planner'] of the latest step() holds (local_planner='dwa'); valid after reset() and reset(mask) too:

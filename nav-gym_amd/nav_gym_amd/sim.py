@@ -20,7 +20,7 @@ def _dtype(name):
     import torch
     if _TORCH_DTYPE is None:
         _TORCH_DTYPE = {"float32": torch.float32, "float64": torch.float64, "int32": torch.int32,
-                        "int64": torch.int64, "uint8": torch.uint8}
+                        "int64": torch.int64, "uint8": torch.uint8, "int8": torch.int8}
     return _TORCH_DTYPE[name]
 
 
@@ -627,7 +627,7 @@ class _StepProduct(object):
     map): the parameters, two sets of outputs -- they flip with NavSim.cur, so what a call returned stays intact through the next
     step like everything else a step returns -- and the arguments of the call, built here once: every buffer behind them is
     allocated once and only ever written in place.
-    params: the rule's ctypes struct.  layout: blob_layout()'s list; each set is ONE allocation (blob[i]) with the arrays carved
+    params: the rule's ctypes struct (None: a rule without parameters).  layout: blob_layout()'s list; each set is ONE allocation (blob[i]) with the arrays carved
     out of it (buf[i]: {name: tensor}), so that a caller who wants them on the host copies once (host()).
     cfg, st, par: byrefs of the simulator's config and state and of params.  out[i]: the call's output argument for set i -- the
     byref of an out_type filled with buf[i]'s pointers (struct[i]) or, without an out_type, the pointer of the blob itself (a
@@ -639,7 +639,7 @@ class _StepProduct(object):
         self.params, self.layout = params, layout
         self.blob = [torch.zeros(layout[-1][3], dtype=torch.uint8, device=sim.device) for _ in range(2)]
         self.buf = [{k: blob[lo:hi].view(_dtype(d)).view(shape) for k, d, lo, hi, shape in layout[:-1]} for blob in self.blob]
-        self.cfg, self.st, self.par = C.byref(sim.cfg), C.byref(sim.st), C.byref(params)
+        self.cfg, self.st, self.par = C.byref(sim.cfg), C.byref(sim.st), None if params is None else C.byref(params)
         self.struct = [out_type(**{k: v.data_ptr() for k, v in buf.items()}) if out_type else None for buf in self.buf]
         self.out = [C.byref(s) if out_type else C.c_void_p(blob.data_ptr()) for s, blob in zip(self.struct, self.blob)]
         self.extra, self.extra_struct = extra or {}, extra_struct
@@ -691,7 +691,7 @@ class NavSim(object):
         # episode statistics (enable_episode_stats): the accumulators, the totals, the two sets of published rows (they flip with
         # self.cur like out_buf) and, per parity, the arguments of navsim_episode_stats_update
         self.ep_acc, self.ep_totals, self.ep_buf, self._ep_args = None, None, None, {}
-        # the other launches behind the step: 'ped_observe', 'goal_path', 'dwa', 'local_map' -> the _StepProduct its enable_* call
+        # the other launches behind the step: 'ped_observe', 'goal_path', 'dwa', 'local_map', 'scan_labels' -> the _StepProduct its enable_* call
         # made (parameters, two sets of outputs, the call's arguments; the goal path's field, keys and rebuild counter as its extra)
         self.products = {}
         self.t = {}
@@ -1693,6 +1693,31 @@ class NavSim(object):
         if rc:
             check(rc, "navsim_local_map")
         return p.buf[cur]["map"]
+
+    # ---- scan ground truth: the robot's scan without noise and per beam what it fell on, one launch behind the step
+    # (include/navsim.h navsim_scan_labels)
+    def enable_scan_labels(self):
+        """Allocates two sets of outputs (range [E,B] float32, label [E,B] uint8, index [E,B] int8 and, with a pedestrian model,
+        hits [E,N] int32: they flip with self.cur like everything a step returns).  The rule has no parameters."""
+        cfg = self.cfg
+        omit = ("hits",) if cfg.ped_model == abi.PED_NONE else ()
+        self.products["scan_labels"] = _StepProduct(self, None, blob_layout(abi.SCAN_LABELS_OUT, cfg.n_envs,
+                                                                            {"B": cfg.n_beams, "N": cfg.max_peds}, omit=omit),
+                                                    abi.NavsimScanLabelsOut)
+
+    def scan_labels(self, skip=None):
+        """navsim_scan_labels of the current state on the current stream: one launch, no copy, no allocation.  skip: uint8 / bool
+        [E], arenas that are not read and come back empty (range 0, label 0, index -1, hits 0).  Returns the current set {'range',
+        'label', 'index'[, 'hits']}, intact through the next step.  label: abi.BEAM_NONE / BEAM_WALL / BEAM_PED_BODY / BEAM_PED_LEG."""
+        p, cur = self.products.get("scan_labels") or self._product("scan_labels"), self.cur
+        rc = self.lib.navsim_scan_labels(p.cfg, p.st, _ptr(skip), p.out[cur], _stream())
+        if rc:
+            check(rc, "navsim_scan_labels")
+        return p.buf[cur]
+
+    def scan_labels_host(self):
+        """The current set of scan_labels()'s outputs as NumPy arrays, from ONE device -> host copy."""
+        return self._product("scan_labels").host(self.cur)
 
     def occupancy(self, e=0):
         """uint8 [H, W] occupancy grid (1 = occupied) of arena e, read back from its distance field
