@@ -99,3 +99,13 @@ for _ in range(150):
     plan = info["planner"]
 print("planner-driven, 64 arenas x 150 steps: %d successes, %d crashes; now %d arenas blocked, clearance of arena 0 %.2f m"
       % (successes, crashes, int((plan["status"] == 2).sum()), float(plan["clearance"][0])))
+
+# ---- a safety shield: try K candidate actions before committing to one ---------------------------------------------------------
+# lookahead=K evaluates K candidate actions per arena in one launch that only reads the state: what step() would return for each.
+senv = nav_gym_env.make("NavGym-v0", num_envs=64, map_size=400, lookahead=4)
+senv.reset()
+for _ in range(50):
+    cand = torch.cat([actions[:256].reshape(64, 4, 2)[:, :3], torch.zeros(64, 1, 2, dtype=torch.float64, device="cuda:0")], dim=1).contiguous()
+    safe = (senv.lookahead(cand)["is_crash"] == 0).to(torch.uint8).argmax(dim=1)         # the first candidate that does not crash
+    obs, reward, done, info = senv.step(cand[torch.arange(64, device="cuda:0"), safe].contiguous())
+print("shielded, 64 arenas x 50 steps: %d crashes in the last step" % int((info["is_crash"] > 0).sum()))

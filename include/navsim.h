@@ -1396,6 +1396,85 @@ typedef struct navsim_scan_labels_out {
 int navsim_scan_labels(const navsim_config* cfg, const navsim_state* st, const uint8_t* skip /* [E] or NULL */,
                        const navsim_scan_labels_out* out, void* stream);
 
+/* ---- action lookahead: what navsim_step would return for each of K candidate actions of an arena, from one launch --------------
+ * What a safety shield, an action mask, a one-step Q-target or a "try before you commit" planner asks: if this arena took
+ * action a now, what would the step return?  Without this entry the answer costs a copy of the whole state, a step and a
+ * restore per candidate.  navsim_dwa does not give it: its disc model differs from the scan-based crash test by a cell or two,
+ * its pedestrians move at constant velocity, and it returns one action, not the outcomes of the caller's own.
+ * BUILD-DEFINED as an entry; every value is the step's own arithmetic (env.py:591-728 as DESIGN.md section 6 restates it). */
+#define NAVSIM_LOOKAHEAD_MAX 64
+typedef struct navsim_lookahead_params {
+    int32_t n_actions;   /* K, 1 .. NAVSIM_LOOKAHEAD_MAX */
+    double  range;       /* R: the scans' cap in metres (rule 5) */
+} navsim_lookahead_params;
+
+typedef struct navsim_lookahead_out {
+    double*  reward;      /* [E,K] */
+    uint8_t* done;        /* [E,K] success | crash | time limit */
+    float*   is_success;  /* [E,K] */
+    float*   is_crash;    /* [E,K] */
+    uint8_t* discomfort;  /* [E,K] */
+    double*  distance;    /* [E,K] */
+    float*   margin;      /* [E,K] */
+    double*  pose;        /* [E,K,3] pose the step would scan from (before any crash revert) */
+    uint8_t* status;      /* [E] 0 skipped, 1 evaluated */
+} navsim_lookahead_out;
+
+/* ONE launch (a workgroup per arena; kernels_lookahead.hpp), no device-to-host copy, nothing that blocks, no allocation, and it
+ * WRITES NOTHING BUT `out`: the state is read-only.  Call it wherever navsim_step could be called on the same stream.
+ * actions [E,K,2] is in cfg.action_kind's form.  ped_cmd [E,N,2] stands for st->ped_cmd under NAVSIM_PED_EXTERNAL (NULL: st->ped_cmd
+ * itself; ignored with the other models).  float32 / float64 as in the step, every operation rounded on its own; B = cfg.n_beams,
+ * N = cfg.max_peds, K = p->n_actions, R = p->range.  Per arena e:
+ *  1. skip && skip[e]: status[e] = 0 and every other element of the arena's rows 0.  Nothing of the arena is read.  Else status 1.
+ *  2. The pedestrians at t + 1 are what the fused step computes, exactly, under NAVSIM_PED_SFM and NAVSIM_PED_EXTERNAL, for
+ *     n = min(n_peds[e], N) pedestrians (0 with NAVSIM_PED_NONE): the waypoint pop (env.py:633-642) from ped_wp_head; the social
+ *     force with the robot at robot_pose[e] -- the pose of time t -- moving at prev_action[e][0], or
+ *     Human.set_vel on the pedestrian's command; then the leg odometry (env.py:237-255) with ped_prev_yaw.  Only the new pose
+ *     and the new ped_dist of a pedestrian are kept.  The new goal at a final waypoint, ped_wp_head, ped_due and everything else
+ *     the step stores for a pedestrian change neither this step's poses nor its scan: they are not computed and not written.
+ *  3. Candidate k: (a0, a1) = actions[e,k] goes through the step's phase 0 in its order -- under NAVSIM_ACTION_WHEELS
+ *     (wheel_radius (l + r) / 2, wheel_radius (r - l) / wheel_track); cfg.clamp_action; cfg.min_turning_radius (env.py:595-600);
+ *     KetiRobot.set_vel with cfg.axle_offset from robot_pose[e] (env.py:664).  The result is pose[e,k].  The lidar pose is its
+ *     float32 cast (env.py:386), the origin cell xy_to_ij_f32 of that (env.py:419).
+ *  4. The candidate's scan is rules 2 - 6 of navsim_scan_labels (range only) with two changes: the pedestrians are those of rule
+ *     2 here, seen from the candidate's lidar pose; and R stands for range_max in the march limit (floor(R / resolution) + 4
+ *     cells), in the primitive cull and in the clip to [0, R].  There is no noise.
+ *  5. R must satisfy max_k scan_discomfort[k] + 0.1 <= R <= range_max.  The thresholds live on the device only, so this entry
+ *     checks 0 < R <= range_max (NAVSIM_E_ARG otherwise) and the LOWER bound is the caller's to keep: NavSim.enable_lookahead
+ *     refuses an R below it (ValueError) and its default is the smallest multiple of 0.25 m that satisfies it.
+ *     Why the cap changes no outcome: a march stopped at floor(R / resolution) + 4 cells and a cull beyond R change no range
+ *     clipped to R (the step's argument for range_max, kernels_field.hpp march_limit), so a beam's capped value r' is
+ *     min(r, R) of its uncapped value r.  Every threshold lies below R - 0.1, so r' < threshold iff r < threshold: the flags
+ *     are the uncapped scan's.  A beam with r' = R has a discomfort ratio (R - thr) / ((dthr - thr) + 1e-6) above 1, its
+ *     uncapped ratio is larger still, and a beam below its discomfort threshold has a ratio below 1: whenever the ratio's minimum
+ *     is used (discomfort without crash) it is taken on a beam below R, where r' = r.  So the minimum is the uncapped scan's.
+ *  6. Outcomes of candidate k, r_k its clipped ranges: is_crash = any r_k < scan_threshold[k]; discomfort = any r_k <
+ *     scan_discomfort[k], and not crash; rmin = the minimum of nv::discomfort_ratio over all beams when discomfort (else
+ *     unused), as the step's phase 3; (reward, success, crash, distance) = the reference's reward (env.py:464-589) of
+ *     (prev_pose[e], pose[e,k], vel = prev_action[e], robot_goal[e], crash, discomfort, rmin) -- its velocity terms use the
+ *     PREVIOUS action (env.py:453) and are the same for every candidate; done = success or crash or, with
+ *     cfg.max_episode_steps > 0, steps[e] + 1 >= max_episode_steps; margin = min over beams of r_k - scan_threshold[k] in
+ *     float32: is_crash holds iff margin < 0.  margin depends on R (a beam clipped to R contributes R - threshold).
+ *  7. PROPERTY, with cfg.add_scan_noise == 0 or a noise standard deviation of 0: reward, done, is_success, is_crash and distance
+ *     of candidate k equal, bit for bit, what navsim_step with io.action[e] = actions[e,k] writes for arena e from the same
+ *     state.  With noise on they are the noise-free outcome.
+ * NAVSIM_E_ARG, before anything touches the device: cfg, st, p, actions or out NULL; any of out's nine arrays NULL; n_actions
+ * outside 1 .. NAVSIM_LOOKAHEAD_MAX; R not finite, not positive or above range_max; st->robot_pose, robot_goal, prev_action,
+ * prev_pose, steps, field, scan_threshold or scan_discomfort NULL; a ped_model that is none of NAVSIM_PED_*; with a pedestrian
+ * model st->n_peds, ped_pose, ped_vel, ped_prev_yaw, ped_dist or ped_has_legs NULL; with NAVSIM_PED_SFM ped_v_pref,
+ * ped_waypoints, ped_n_waypoints or ped_wp_head NULL or max_waypoints < 1; with NAVSIM_PED_EXTERNAL both ped_cmd and st->ped_cmd
+ * NULL; n_envs < 0; n_beams < 1; map_h or map_w < 1; max_peds outside 0 .. NAVSIM_MAX_PEDS (outside 1 .. with a pedestrian
+ * model); a march_rule that is none of NAVSIM_MARCH_*; resolution or time_step not positive and finite; an action_kind that is
+ * none of NAVSIM_ACTION_*, NAVSIM_ACTION_WHEELS with a wheel_radius that is not positive; st->map_slot with cfg.shared_field.
+ * NAVSIM_E_UNSUPPORTED: a field_format that is neither NAVSIM_FIELD_F32 nor NAVSIM_FIELD_U16T; st->rect_table with a float32
+ * field or a map above 1024 cells a side; with a pedestrian model a field of view angle_last - angle_min above 2 pi (the culled
+ * merge, as in navsim_step); LDS beyond one compute unit's 160 KB -- 12 bytes per beam, 56 per candidate and, with a pedestrian
+ * model, 144 per pedestrian slot + 32 and 16 (N (N - 1) / 2 + N) for the social force's pair table.
+ * n_envs == 0: NAVSIM_OK, nothing is launched. */
+int navsim_lookahead(const navsim_config* cfg, const navsim_state* st, const navsim_lookahead_params* p,
+                     const double* actions /* [E,K,2] */, const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */,
+                     const uint8_t* skip /* [E] or NULL */, const navsim_lookahead_out* out, void* stream);
+
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);
 

@@ -269,6 +269,23 @@ class NavsimScanLabelsOut(C.Structure):
     _fields_ = [(name, _P) for name in SCAN_LABELS_OUT]
 
 
+# navsim_lookahead: the rule's parameters and the nine output arrays (dtype, trailing shape behind E; K = n_actions; status is [E])
+LOOKAHEAD_MAX = 64
+
+
+class NavsimLookaheadParams(C.Structure):
+    _fields_ = [("n_actions", C.c_int32), ("range", C.c_double)]
+
+
+LOOKAHEAD_OUT = {"reward": ("float64", ("K",)), "done": ("uint8", ("K",)), "is_success": ("float32", ("K",)),
+                 "is_crash": ("float32", ("K",)), "discomfort": ("uint8", ("K",)), "distance": ("float64", ("K",)),
+                 "margin": ("float32", ("K",)), "pose": ("float64", ("K", 3)), "status": ("uint8", ())}
+
+
+class NavsimLookaheadOut(C.Structure):
+    _fields_ = [(name, _P) for name in LOOKAHEAD_OUT]
+
+
 ORCA_MAX_AGENTS = 64
 ORCA_MAX_EDGES = 128
 CROWD_MAX_VERTS = 8
@@ -486,6 +503,8 @@ def declare(lib, suffix=""):
         sig("navsim_local_map", [cfgp, stp, C.POINTER(NavsimLocalMapParams), _P, _P, _P, _P])
     if not suffix and hasattr(lib, "navsim_scan_labels"):               # (likewise)
         sig("navsim_scan_labels", [cfgp, stp, _P, C.POINTER(NavsimScanLabelsOut), _P])
+    if not suffix and hasattr(lib, "navsim_lookahead"):                 # (likewise)
+        sig("navsim_lookahead", [cfgp, stp, C.POINTER(NavsimLookaheadParams), _P, _P, _P, C.POINTER(NavsimLookaheadOut), _P])
     sig("navsim_reset_obs", [cfgp, stp, iop, _P] + stream)
     sig("navsim_restart", [cfgp, stp, _P] + stream)
     return lib
@@ -505,7 +524,7 @@ EXPORTS = (
     "navsim_step", "navsim_step_sorted", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
     "navsim_episode_stats_update", "navsim_episode_stats_clear", "navsim_ped_observe",
     "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps", "navsim_dwa", "navsim_local_map",
-    "navsim_scan_labels",
+    "navsim_scan_labels", "navsim_lookahead",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

@@ -147,6 +147,13 @@ and default to the reference's behaviour for num_envs == 1:
                     env.scan_labels() returns the same dict, also after reset() / reset(mask).  num_envs > 1: torch views with
                     the lifetime below; num_envs == 1: NumPy rows from one device -> host copy.  False (default): nothing is
                     allocated or launched.
+    lookahead       K in 1 .. 64: env.lookahead(actions) returns what step() would return for each of K candidate actions per
+                    arena -- reward, done, is_success, is_crash, discomfort, distance, the crash margin and the pose -- from one
+                    launch that only reads the state (navsim_lookahead): what a safety shield, an action mask or a one-step
+                    Q-target asks.  With scan noise off the five values step() also returns are bit-identical to that step's.
+                    lookahead_params: dict(range=), the candidates' scan cap in metres (default: the smallest multiple of 0.25 m
+                    that lies 0.1 m above the largest discomfort threshold).  Not with pedestrian_model 'orca' or 'policy', whose
+                    commands come from a launch in front of the step.  None (default): nothing is allocated or launched.
     reset(mask)     reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
                     [num_envs]; the others keep their state and their rows.  On the pipelined reset path the masked arenas install
                     their staged worlds in one launch: the same state and rows as with pregen_pipeline=0.
@@ -303,7 +310,7 @@ class NavGymEnv(_EnvBase):
                  final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None,
                  episode_stats=False, observe_humans=None, observe_params=None, goal_path=False, goal_path_params=None,
                  local_planner=None, local_planner_params=None, observe_local_map=None, local_map_params=None,
-                 scan_labels=False):
+                 scan_labels=False, lookahead=None, lookahead_params=None):
         # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
         self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
         from . import lib
@@ -531,6 +538,16 @@ class NavGymEnv(_EnvBase):
         if not isinstance(scan_labels, (bool, np.bool_)):
             raise ValueError("scan_labels must be True or False, not %r" % (scan_labels,))
         self.scan_labels_on = bool(scan_labels)
+        # action lookahead (navsim_lookahead): the step's outcomes for K candidate actions per arena, on request (env.lookahead())
+        _check_params("lookahead_params", lookahead_params, lookahead is not None, "lookahead=K", _simmod.LOOKAHEAD_KEYS)
+        if lookahead is not None:
+            if not (isinstance(lookahead, numbers.Integral) and not isinstance(lookahead, bool) and 1 <= lookahead <= abi.LOOKAHEAD_MAX):
+                raise ValueError("lookahead must be None or an int in 1 .. %d, not %r" % (abi.LOOKAHEAD_MAX, lookahead))
+            if pedestrian_model in ("orca", "policy"):
+                raise ValueError("lookahead is not available with pedestrian_model=%r: the pedestrians' commands come from a launch in "
+                                 "front of the step that has not run yet" % pedestrian_model)
+        self.lookahead_k = None if lookahead is None else int(lookahead)
+        self.lookahead_params = None if lookahead_params is None else dict(lookahead_params)
         # the launches behind the step (and behind reset() / reset(mask) / load_state_dict), in the order they run -- the planner
         # reads the goal path's sub-goal, the local map the observer's `visible`.  _run_products() runs them; its latest result
         # and, per buffer parity, the views it handed out
@@ -699,6 +716,8 @@ class NavGymEnv(_EnvBase):
                                                                    if k != "visible_only"})
             if self.scan_labels_on:
                 self.sim.enable_scan_labels()
+            if self.lookahead_k:
+                self.sim.enable_lookahead(self.lookahead_k, self.lookahead_params)
         elif "policy_prev_actions" in self.sim.t:
             self.sim.t["policy_prev_actions"].zero_()           # env.py:739
         self._episode_batch += 1
@@ -942,6 +961,40 @@ class NavGymEnv(_EnvBase):
         {'range' [E,B] float32, the scan without noise; 'label' [E,B] uint8 (abi.BEAM_*); 'index' [E,B] int8, the pedestrian of
         a beam with label 2 or 3, else -1; 'hits' [E,N] int32 with a pedestrian model}."""
         return self._latest("scan_labels", self.scan_labels_on, "scan_labels", "scan_labels=True")
+
+    _LOOKAHEAD_BOOL = ("done", "discomfort")
+
+    def lookahead(self, actions, human_actions=None):
+        """What step() would return for each of K candidate actions per arena, from the current state, which is only read
+        (NavGymEnv(lookahead=K); navsim_lookahead, one launch): {'reward' [E,K] float64, 'done' [E,K] bool (success, crash or time
+        limit), 'is_success', 'is_crash' [E,K] float32, 'discomfort' [E,K] bool, 'distance' [E,K] float64, 'margin' [E,K] float32
+        (the least range minus crash threshold over the beams: negative iff is_crash), 'pose' [E,K,3] float64 (the pose the step
+        would scan from), 'status' [E] uint8 (0 = skipped)}.  With scan noise on the values are the noise-free outcome.
+        actions: a float64 device tensor [E,K,2], or an array-like [K,2] that every arena takes, in action_kind's form.
+        human_actions: [E,N,2] with pedestrian_model='external' (required there: the commands the step would be given).
+        Next-step auto-reset: an arena whose `done` is set is skipped (status 0, rows 0) until the step that resets it.
+        num_envs > 1: torch views, intact through the next step(); num_envs == 1: NumPy rows [K,...] from one device -> host copy."""
+        if self.lookahead_k is None:
+            raise RuntimeError("lookahead() needs NavGymEnv(lookahead=K)")
+        if self.pedestrian_model == "external" and human_actions is None:
+            raise ValueError("lookahead() with pedestrian_model='external' needs human_actions")
+        if self.sim is None:
+            raise RuntimeError("call reset() before lookahead()")
+        import torch
+        sim, E, K = self.sim, self.num_envs, self.lookahead_k
+        if not hasattr(actions, "is_cuda"):
+            a = np.asarray(actions, dtype=np.float64)
+            if a.shape == (K, 2):
+                a = np.broadcast_to(a, (E, K, 2))
+            actions = torch.from_numpy(np.array(a.reshape(E, K, 2), dtype=np.float64, order="C"))    # (a writable copy)
+        elif tuple(actions.shape) == (K, 2):
+            actions = actions.expand(E, K, 2)
+        skip = sim.out["done"] if self.auto_reset and self.autoreset_mode == "next_step" and sim.out is not None else None
+        out = sim.lookahead(actions, ped_cmd=human_actions if self.pedestrian_model == "external" else None, skip=skip)
+        if E == 1:
+            host = sim.lookahead_host()
+            return {k: (v[0].astype(bool) if k in self._LOOKAHEAD_BOOL else v[0]) for k, v in host.items()}
+        return {k: (v.view(self._bool) if k in self._LOOKAHEAD_BOOL else v) for k, v in out.items()}
 
     def planner_action(self):
         """What info['planner'] of the latest step() holds (local_planner='dwa'); valid after reset() and reset(mask) too:

@@ -412,6 +412,21 @@ def local_map_params(cfg, params=None, size=None):
     return p
 
 
+LOOKAHEAD_KEYS = ("range",)
+
+
+def lookahead_range_min(discomfort_max):
+    """The least cap R that navsim_lookahead's rule 5 allows for thresholds up to discomfort_max: 0.1 m above them."""
+    return float(discomfort_max) + 0.1
+
+
+def lookahead_defaults(cfg, discomfort_max=0.0):
+    """The parameters of navsim_lookahead as a dict: range, the candidates' scan cap R -- the smallest multiple of 0.25 m that
+    lies 0.1 m above the largest discomfort threshold (discomfort_max, metres; NavSim.enable_lookahead reads it from the state),
+    never above the lidar's range."""
+    return dict(range=min(float(cfg.range_max), float(np.ceil(lookahead_range_min(discomfort_max) / 0.25)) * 0.25))
+
+
 def ped_observation_layout(E, K, N):
     """Where navsim_ped_observation's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in
     abi.PED_OBSERVATION's order, each start rounded up to 16 bytes, and a last entry whose end byte is the blob's size."""
@@ -1718,6 +1733,56 @@ class NavSim(object):
     def scan_labels_host(self):
         """The current set of scan_labels()'s outputs as NumPy arrays, from ONE device -> host copy."""
         return self._product("scan_labels").host(self.cur)
+
+    # ---- action lookahead: what step() would return for each of K candidate actions per arena, one launch that only reads the
+    # state (include/navsim.h navsim_lookahead)
+    def enable_lookahead(self, K, params=None):
+        """Allocates two sets of outputs (abi.LOOKAHEAD_OUT, [E,K,...] and status [E]: they flip with self.cur like everything a
+        step returns), an action buffer float64 [E,K,2] and a command buffer float64 [E,N,2].  params: a dict of overrides of
+        lookahead_defaults(cfg), or None.  The thresholds live on the device, so rule 5's lower bound on the cap is checked here
+        (one device -> host copy of their maximum): a range outside [max scan_discomfort + 0.1, range_max] raises ValueError."""
+        import torch
+        cfg = self.cfg
+        if not 1 <= int(K) <= abi.LOOKAHEAD_MAX:
+            raise ValueError("lookahead evaluates 1 .. %d actions per arena, not %r" % (abi.LOOKAHEAD_MAX, K))
+        dmax = float(self.t["scan_discomfort"].max().item())
+        d = _overridden(lookahead_defaults(cfg, dmax), params, "lookahead", LOOKAHEAD_KEYS)
+        R = float(d["range"])
+        if not lookahead_range_min(dmax) <= R <= cfg.range_max:
+            raise ValueError("the lookahead's range must lie in [%g, %g] (0.1 m above the largest discomfort threshold .. range_max), "
+                             "not %g" % (lookahead_range_min(dmax), cfg.range_max, R))
+        p = abi.NavsimLookaheadParams(n_actions=int(K), range=R)
+        extra = dict(actions=torch.zeros((cfg.n_envs, int(K), 2), dtype=torch.float64, device=self.device),
+                     ped_cmd=torch.zeros((cfg.n_envs, max(cfg.max_peds, 1), 2), dtype=torch.float64, device=self.device))
+        self.products["lookahead"] = _StepProduct(self, p, blob_layout(abi.LOOKAHEAD_OUT, cfg.n_envs, {"K": int(K)}),
+                                                  abi.NavsimLookaheadOut, extra=extra)
+
+    def lookahead(self, actions, ped_cmd=None, skip=None):
+        """navsim_lookahead of the current state on the current stream: one launch, no device -> host copy, no allocation, and the
+        state is only read.  actions: [E,K,2] in cfg.action_kind's form (copied into the product's buffer unless it already is a
+        contiguous float64 tensor on the device); ped_cmd: [E,N,2] commands that stand for the state's under PED_EXTERNAL (None:
+        the state's own); skip: uint8 / bool [E], arenas that are not read and come back all 0 with status 0.  Returns the current
+        set {'reward', 'done', 'is_success', 'is_crash', 'discomfort', 'distance', 'margin', 'pose', 'status'}, intact through
+        the next step."""
+        import torch
+        p, cur = self.products.get("lookahead") or self._product("lookahead"), self.cur
+        buf = p.extra["actions"]
+        if not (torch.is_tensor(actions) and actions.device == buf.device and actions.dtype == buf.dtype and actions.is_contiguous()
+                and actions.shape == buf.shape):
+            buf.copy_(torch.as_tensor(actions).to(device=buf.device, dtype=buf.dtype).reshape(buf.shape), non_blocking=True)
+            actions = buf
+        if ped_cmd is not None:
+            cmd = p.extra["ped_cmd"]
+            cmd.copy_(torch.as_tensor(ped_cmd).to(device=cmd.device, dtype=cmd.dtype).reshape(cmd.shape), non_blocking=True)
+            ped_cmd = cmd
+        rc = self.lib.navsim_lookahead(p.cfg, p.st, p.par, _ptr(actions), _ptr(ped_cmd), _ptr(skip), p.out[cur], _stream())
+        if rc:
+            check(rc, "navsim_lookahead")
+        return p.buf[cur]
+
+    def lookahead_host(self):
+        """The current set of lookahead()'s outputs as NumPy arrays, from ONE device -> host copy."""
+        return self._product("lookahead").host(self.cur)
 
     def occupancy(self, e=0):
         """uint8 [H, W] occupancy grid (1 = occupied) of arena e, read back from its distance field
