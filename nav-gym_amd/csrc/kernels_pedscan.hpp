@@ -350,6 +350,13 @@ __global__ void math_kernel(int fn, const double* x, const double* x2, double* o
             out[i] = ok ? 0.0 : 1.0;
             break;
         }
+        case 17: {
+            // nv::gauss_noise alone (tests/scan_noise_f64.py is its float64 model): the stream's low word in x, its high word
+            // in x2 (absent: 0), both whole numbers below 2^32; the beam is the element's index
+            const uint64_t lo = (uint64_t)(uint32_t)x[i], hi = x2 ? (uint64_t)(uint32_t)x2[i] : 0ull;
+            out[i] = (double)nv::gauss_noise(lo | (hi << 32), (uint32_t)i);
+            break;
+        }
         default: out[i] = 0.0;
     }
 }

@@ -270,7 +270,8 @@ __device__ __forceinline__ float log_normal(float x) {
 
 // Gaussian scan noise (env.py:437-440).  Counter-based -- keyed by (seed, global arena, episode / step / scan, beam)
 // -- so results do not depend on the launch geometry; not bit-comparable with numpy's global Mersenne stream
-// (tested statistically).  noise_stream() is the per-scan part of the key, evaluated once per thread.
+// (checked draw by draw against the float64 model tests/scan_noise_f64.py).  noise_stream() is the per-scan part of the key,
+// evaluated once per thread.
 __device__ __forceinline__ uint64_t noise_stream(uint64_t seed, uint64_t genv, uint64_t scan_key) {
     return hash4(seed ^ scan_key, genv, scan_key, 0x6E6F697365ULL);
 }

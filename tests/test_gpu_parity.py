@@ -1762,18 +1762,20 @@ def test_config1_single_env_64_beams(gpu):
 
 def test_scan_noise_statistics(gpu):
     """Noise cannot be bit-compared with numpy's global stream: check that it is
-    zero-mean with the requested std, applied only where range != range_max (env.py:437-440)."""
-    E, size = 64, 200
-    cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, n_spawn=4, add_scan_noise=1, seed=99)
+    zero-mean with the requested std, applied only where range != range_max (env.py:437-440).  The lidar reaches 4 m on these
+    10 m maps, so that beams at range_max exist (at the robot's own 25 m none did, and the comparison was one of empty arrays)."""
+    E, size, rmax = 64, 200, np.float32(4.0)
+    cfg = gpu.lib.default_config(n_envs=E, map_h=size, map_w=size, n_spawn=4, add_scan_noise=1, seed=99, range_max=float(rmax))
     gpu.world.lidar_1081(cfg)
     occ = gpu.world.make_maps(E, size, 99)
     arrays = device_world(gpu, cfg, occ, 0, noise_std_range=(0.03, 0.03))
     noisy = gpu.sim.NavSim(cfg, arrays).reset_obs().cpu().numpy()[:, :1081]
     cfg.add_scan_noise = 0
     clean = gpu.sim.NavSim(cfg, arrays).reset_obs().cpu().numpy()[:, :1081]
-    d = (noisy - clean)[clean != 25.0]
+    d = (noisy - clean)[clean != rmax]
     assert abs(d.mean()) < 1e-3 and abs(d.std() - 0.03) < 1e-3
-    assert np.array_equal(noisy[clean == 25.0], clean[clean == 25.0])
+    assert (clean == rmax).sum() > 1000 and (clean != rmax).sum() > 1000
+    assert np.array_equal(noisy[clean == rmax], clean[clean == rmax])
     k = np.mean(d ** 4) / d.var() ** 2
     assert 2.8 < k < 3.2                              # Gaussian kurtosis
 
