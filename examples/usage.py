@@ -109,3 +109,15 @@ for _ in range(50):
     safe = (senv.lookahead(cand)["is_crash"] == 0).to(torch.uint8).argmax(dim=1)         # the first candidate that does not crash
     obs, reward, done, info = senv.step(cand[torch.arange(64, device="cuda:0"), safe].contiguous())
 print("shielded, 64 arenas x 50 steps: %d crashes in the last step" % int((info["is_crash"] > 0).sum()))
+
+# ---- random shooting: roll K action sequences H steps ahead, execute the first action of the best one --------------------------------
+# rollout=K evaluates K sequences per arena over the next H steps in one launch that only reads the state: what step() would return.
+renv = nav_gym_env.make("NavGym-v0", num_envs=64, map_size=400, rollout=8, rollout_params=dict(horizon=6))
+renv.reset()
+for _ in range(50):
+    seq = torch.rand(64, 8, 6, 2, dtype=torch.float64, device="cuda:0") * torch.tensor([0.5, 1.28], device="cuda:0") - torch.tensor([0.0, 0.64], device="cuda:0")
+    seq[:, -1] = 0.0                                                                     # standing still is always on offer
+    out = renv.rollout(seq)                                                            # 'ret' [E,K], 'outcome' [E,K] (bit 1: crash), ...
+    best = torch.where((out["outcome"] & 2) == 0, out["ret"], torch.full_like(out["ret"], -1e300)).argmax(dim=1)
+    obs, reward, done, info = renv.step(seq[torch.arange(64, device="cuda:0"), best, 0].contiguous())
+print("random shooting, 64 arenas x 50 steps: %d crashes in the last step" % int((info["is_crash"] > 0).sum()))

@@ -1475,6 +1475,100 @@ int navsim_lookahead(const navsim_config* cfg, const navsim_state* st, const nav
                      const double* actions /* [E,K,2] */, const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */,
                      const uint8_t* skip /* [E] or NULL */, const navsim_lookahead_out* out, void* stream);
 
+/* ---- action-sequence rollout: what the next H navsim_step calls would return for each of K action sequences of an arena ---------
+ * The question behind a sampling-based model-predictive controller (random shooting, MPPI, CEM), an n-step return target or a
+ * multi-step shield: if this arena executed the actions a_0 .. a_{H-1}, what would the next H steps return?  Without this entry
+ * the answer costs a copy of the whole state, H steps of EVERY arena and a restore per sequence.  navsim_lookahead answers it for
+ * one step; navsim_dwa looks ahead with a model of its own (two discs, pedestrians at constant velocity) and returns one action.
+ * BUILD-DEFINED as an entry; every value is the step's own arithmetic (env.py:591-728 as DESIGN.md section 6 restates it). */
+#define NAVSIM_ROLLOUT_MAX_K 256
+#define NAVSIM_ROLLOUT_MAX_H 32
+typedef struct navsim_rollout_params {
+    int32_t n_seq;       /* K, 1 .. NAVSIM_ROLLOUT_MAX_K */
+    int32_t horizon;     /* H, 1 .. NAVSIM_ROLLOUT_MAX_H */
+    double  range;       /* R: the scans' cap in metres, as navsim_lookahead's (its rule 5) */
+    double  gamma;       /* discount of `ret`, 0 .. 1 */
+} navsim_rollout_params;
+
+typedef struct navsim_rollout_out {
+    double*  reward;           /* [E,K,H]   the step's reward at step h; 0 behind the sequence's last evaluated step */
+    double*  pose;             /* [E,K,H,3] the pose the step scans from at step h (before any crash revert); 0 behind the end */
+    double*  ret;              /* [E,K]     g = 1, ret = 0; for h < length: ret = ret + g * reward[h]; g = g * gamma  (no fma) */
+    int32_t* length;           /* [E,K]     steps evaluated: index of the first done step + 1, else H */
+    uint8_t* outcome;          /* [E,K]     of the last evaluated step: bit 0 success, bit 1 crash, bit 2 time limit (episode_stats' bits) */
+    int32_t* discomfort_steps; /* [E,K]     evaluated steps with discomfort and no crash */
+    float*   min_margin;       /* [E,K]     min over evaluated steps of the lookahead's margin */
+    double*  distance;         /* [E,K]     the step's distance at the last evaluated step */
+    int32_t* exact_steps;      /* [E,K]     see rule 8 */
+    uint8_t* status;           /* [E]       0 skipped, 1 evaluated */
+} navsim_rollout_out;
+
+/* ONE launch (a workgroup per arena and sequence; kernels_rollout.hpp), no device-to-host copy, nothing that blocks, no
+ * allocation, and it WRITES NOTHING BUT `out`: the state is read-only.  Call it wherever navsim_step could be called on the same
+ * stream.  actions [E,K,H,2] is in cfg.action_kind's form.  ped_cmd [E,N,2] stands for st->ped_cmd under NAVSIM_PED_EXTERNAL
+ * (NULL: st->ped_cmd itself; ignored with the other models).  float32 / float64 as in the step, every operation rounded on its
+ * own; B = cfg.n_beams, N = cfg.max_peds, K = p->n_seq, H = p->horizon, R = p->range.  Per arena e and sequence k, for
+ * h = 0 .. H-1:
+ *  1. Step h = 0 is exactly rules 2 - 6 of navsim_lookahead with candidate action actions[e,k,0]: pose[e,k,0] is its pose,
+ *     reward[e,k,0] its reward, the step's margin its margin, and so on.
+ *  2. The carry.  What the fused step stores for its next call (kernels_step.hpp phase 6 and ped_finish) is carried from step h
+ *     to step h + 1: the robot's pose (the pose the step scanned from: a step that is carried over did not crash); prev_pose =
+ *     that pose (its xy is all the reward reads); prev_action = the action of step h as the step stores it -- after wheels to
+ *     twist, cfg.clamp_action and cfg.min_turning_radius; steps + 1; and per pedestrian its pose, its velocity, ped_prev_yaw =
+ *     wrap_pi(new yaw), ped_dist after the leg odometry, and ped_wp_head after the waypoint pop.
+ *  3. Steps h >= 1 repeat rules 2 - 6 of navsim_lookahead on the carried values with action actions[e,k,h]: the waypoint pop
+ *     starts at the carried head; the social force sees the carried robot pose moving at the carried prev_action[0]; the leg
+ *     odometry uses the carried ped_prev_yaw and ped_dist; the reward's velocity terms use the carried prev_action and its
+ *     progress term the carried prev_pose; the time limit tests the carried steps + 1 against cfg.max_episode_steps.
+ *  4. A sequence ends at its first done step -- success, crash, or the time limit (bit 2 of outcome: set only without success
+ *     and crash, as io.truncated).  length[e,k] = that step's index + 1, or H.  Nothing behind it is evaluated: reward and pose
+ *     rows h >= length are 0; the crash revert and any restart are not modelled.  ret, discomfort_steps and min_margin run over
+ *     the evaluated steps, outcome and distance are the last evaluated step's.  skip && skip[e]: status[e] = 0 and every other
+ *     element of the arena's rows 0, nothing of the arena is read; else status 1.
+ *  5. No scan noise, as in the lookahead: with noise on the values are the noise-free outcome.
+ *  6. NAVSIM_PED_EXTERNAL: the commands of the call are held for all H steps.  NAVSIM_PED_NONE: no pedestrians.
+ *  7. What the rollout leaves out: the real step gives a pedestrian that comes within 0.5 m of its LAST waypoint a new goal and
+ *     a new route (env.py:666-680: a draw from the spawn table inside the step, or st->ped_due and the navsim_replan launch).  The
+ *     rollout draws nothing and plans nothing: that pedestrian keeps heading for its last waypoint.
+ *  8. Exactness.  exact_steps[e,k] is the number of leading steps for which every carried value is what the real step sequence
+ *     would hold.  The step raises ped_due for pedestrian i (ped_finish) iff, with (x, y) its pose AFTER this step's move and
+ *     (wx, wy) = ped_waypoints[e,i,ped_n_waypoints[e,i] - 1], sqrt((x - wx)^2 + (y - wy)^2) < 0.5 in float64, every operation
+ *     rounded on its own.  The rollout evaluates the same predicate on its carried pedestrians under NAVSIM_PED_SFM (with the
+ *     other models no waypoint is read and the predicate is never true): exact_steps = H unless it holds for some pedestrian at
+ *     an evaluated step h; then exact_steps = h + 1 for the first such h -- the new route takes effect from the next step on.
+ * R: rule 5 of navsim_lookahead, unchanged (max_k scan_discomfort[k] + 0.1 <= R <= range_max; this entry checks 0 < R <=
+ * range_max, NavSim.enable_rollout the lower bound).  margin depends on R, nothing else does.
+ * PROPERTY, with cfg.add_scan_noise == 0 or a noise standard deviation of 0: for every h < min(length, exact_steps),
+ * reward[e,k,h] and pose[e,k,h], and -- when the last evaluated step length - 1 is < exact_steps -- outcome and distance, equal
+ * bit for bit what H consecutive navsim_step calls with io.action[e] = actions[e,k,h] write for arena e from the same state
+ * (pose: st->robot_pose behind a step that did not crash), the re-plan launches running between them as the caller's step path
+ * runs them.  With H = 1 every output equals navsim_lookahead's for the same actions, R and state: reward, pose, distance;
+ * outcome = is_success | is_crash << 1 | (done and neither) << 2; discomfort_steps = discomfort; min_margin = margin;
+ * length = exact_steps = 1; ret = reward.
+ * NAVSIM_E_ARG, before anything touches the device: cfg, st, p, actions or out NULL; any of out's ten arrays NULL; n_seq outside
+ * 1 .. NAVSIM_ROLLOUT_MAX_K; horizon outside 1 .. NAVSIM_ROLLOUT_MAX_H; R not finite, not positive or above range_max; gamma
+ * outside 0 .. 1 (NaN included); st->robot_pose, robot_goal, prev_action, prev_pose, steps, field, scan_threshold or
+ * scan_discomfort NULL; a ped_model that is none of NAVSIM_PED_*; with a pedestrian model st->n_peds, ped_pose, ped_vel,
+ * ped_prev_yaw, ped_dist or ped_has_legs NULL; with NAVSIM_PED_SFM ped_v_pref, ped_waypoints, ped_n_waypoints or ped_wp_head
+ * NULL or max_waypoints outside 1 .. NAVSIM_MAX_WAYPOINTS; with NAVSIM_PED_EXTERNAL both ped_cmd and st->ped_cmd NULL;
+ * n_envs < 0; n_beams < 1; map_h or map_w < 1; max_peds outside 0 .. NAVSIM_MAX_PEDS (outside 1 .. with a pedestrian model); a
+ * march_rule that is none of NAVSIM_MARCH_*; resolution or time_step not positive and finite; an action_kind that is none of
+ * NAVSIM_ACTION_*, NAVSIM_ACTION_WHEELS with a wheel_radius that is not positive; st->map_slot with cfg.shared_field.
+ * NAVSIM_E_UNSUPPORTED: a field_format that is neither NAVSIM_FIELD_F32 nor NAVSIM_FIELD_U16T; st->rect_table with a float32
+ * field or a map above 1024 cells a side; with a pedestrian model a field of view angle_last - angle_min above 2 pi (the culled
+ * merge, as in navsim_step); LDS beyond one compute unit's 160 KB -- per workgroup 12 bytes per beam and, with a pedestrian
+ * model, 144 per pedestrian slot + 32 and 16 (N (N - 1) / 2 + N) for the social force's pair table (18.8 KB at 1081 beams and 20
+ * pedestrians); n_envs x n_seq above 2^31 - 1 workgroups.  n_envs == 0: NAVSIM_OK, nothing is launched.
+ * Cost, measured on an MI355X (profiles/r23_rollout/summary.txt; 4096 arenas x 1081 beams, R = 1.75 m, kernel times from a
+ * kernel trace): linear in K H -- one sequence-step of the whole batch takes 37.6 - 39.7 us without pedestrians and 76.5 - 79.3 us
+ * with twenty an arena, about half of the step kernel's time for one real step of the same arenas (80.6 / 145.8 us); (K, H) =
+ * (16, 8) is 5.08 / 10.15 ms, (64, 16) 38.5 / 78.3 ms: x 1.44 - 1.53 resp. x 2.39 - 2.76 of H navsim_lookahead launches at the same K.
+ * Out of scope: pedestrians driven by navsim_ped_orca or navsim_ped_policy (their commands come from launches of their own);
+ * re-plans inside the horizon (rules 7 and 8); anything behind an episode's end (rule 4). */
+int navsim_rollout(const navsim_config* cfg, const navsim_state* st, const navsim_rollout_params* p,
+                   const double* actions /* [E,K,H,2] */, const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */,
+                   const uint8_t* skip /* [E] or NULL */, const navsim_rollout_out* out, void* stream);
+
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);
 

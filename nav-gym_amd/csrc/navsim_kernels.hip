@@ -26,6 +26,7 @@
 //   kernels_local_map.hpp  egocentric local map: wall and pedestrian grids per arena in the robot's frame (navsim_local_map)
 //   kernels_scan_labels.hpp  scan ground truth: the robot's clean scan and per-beam hit labels (navsim_scan_labels)
 //   kernels_lookahead.hpp    action lookahead: the step's outcomes for K candidate actions per arena (navsim_lookahead)
+//   kernels_rollout.hpp      action-sequence rollout: the next H steps' outcomes for K action sequences per arena (navsim_rollout)
 //   step_plan.hpp        launch geometry of the fused step, the descriptors of a launch and the march-rule dispatch (shared by this
 //                        file and navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
 // Host code of this file, ahead of the C ABI: dispatch_step and the argument checks; the workspaces (Carver and one layout
@@ -55,6 +56,7 @@ namespace {
 #include "kernels_local_map.hpp"
 #include "kernels_scan_labels.hpp"
 #include "kernels_lookahead.hpp"
+#include "kernels_rollout.hpp"
 
 }  // namespace
 #include "step_plan.hpp"
@@ -539,6 +541,18 @@ int launch_lookahead(const navsim_config* c, const navsim_state* st, const Looka
         auto kernel = lookahead_kernel<F, decltype(rule)::value, RECT>;
         if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
         kernel<<<c->n_envs, kLookaheadBlock, lds, s>>>(*c, *st, a);
+        return launch_status();
+    });
+}
+
+// navsim_rollout: a workgroup per (arena, sequence), the forms of launch_scan_labels
+template <typename F, bool RECT>
+int launch_rollout(const navsim_config* c, const navsim_state* st, const RolloutArgs& a, hipStream_t s) {
+    const size_t lds = rollout_lds_bytes(c);
+    return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
+        auto kernel = rollout_kernel<F, decltype(rule)::value, RECT>;
+        if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
+        kernel<<<(unsigned)((size_t)c->n_envs * a.K), kRolloutBlock, lds, s>>>(*c, *st, a);
         return launch_status();
     });
 }
@@ -1694,6 +1708,49 @@ int navsim_lookahead(const navsim_config* c, const navsim_state* st, const navsi
     if (c->field_format == NAVSIM_FIELD_U16T)
         return st->rect_table ? launch_lookahead<FieldU16T, true>(c, st, a, s) : launch_lookahead<FieldU16T, false>(c, st, a, s);
     return launch_lookahead<FieldF32, false>(c, st, a, s);
+}
+
+int navsim_rollout(const navsim_config* c, const navsim_state* st, const navsim_rollout_params* p, const double* actions,
+                   const double* ped_cmd, const uint8_t* skip, const navsim_rollout_out* out, void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !p || !actions || !out) return NAVSIM_E_ARG;
+    if (!out->reward || !out->pose || !out->ret || !out->length || !out->outcome || !out->discomfort_steps || !out->min_margin ||
+        !out->distance || !out->exact_steps || !out->status)
+        return NAVSIM_E_ARG;
+    if (p->n_seq < 1 || p->n_seq > NAVSIM_ROLLOUT_MAX_K || p->horizon < 1 || p->horizon > NAVSIM_ROLLOUT_MAX_H) return NAVSIM_E_ARG;
+    if (!std::isfinite(p->range) || !(p->range > 0.0) || !(p->range <= c->range_max)) return NAVSIM_E_ARG;
+    if (!(p->gamma >= 0.0) || !(p->gamma <= 1.0)) return NAVSIM_E_ARG;
+    if (!st->robot_pose || !st->robot_goal || !st->prev_action || !st->prev_pose || !st->steps || !st->field ||
+        !st->scan_threshold || !st->scan_discomfort)
+        return NAVSIM_E_ARG;
+    if (c->ped_model != NAVSIM_PED_NONE && c->ped_model != NAVSIM_PED_EXTERNAL && c->ped_model != NAVSIM_PED_SFM) return NAVSIM_E_ARG;
+    const bool peds = c->ped_model != NAVSIM_PED_NONE;
+    if (peds && (!st->n_peds || !st->ped_pose || !st->ped_vel || !st->ped_prev_yaw || !st->ped_dist || !st->ped_has_legs)) return NAVSIM_E_ARG;
+    if (c->ped_model == NAVSIM_PED_SFM && (!st->ped_v_pref || !st->ped_waypoints || !st->ped_n_waypoints || !st->ped_wp_head ||
+                                           c->max_waypoints < 1 || c->max_waypoints > NAVSIM_MAX_WAYPOINTS))
+        return NAVSIM_E_ARG;
+    if (c->ped_model == NAVSIM_PED_EXTERNAL && !ped_cmd && !st->ped_cmd) return NAVSIM_E_ARG;
+    if (c->n_envs < 0 || c->n_beams < 1 || c->map_h < 1 || c->map_w < 1) return NAVSIM_E_ARG;
+    if (c->max_peds < (peds ? 1 : 0) || c->max_peds > NAVSIM_MAX_PEDS) return NAVSIM_E_ARG;
+    if (c->march_rule < NAVSIM_MARCH_F64 || c->march_rule > NAVSIM_MARCH_F32_FMA) return NAVSIM_E_ARG;
+    if (!(c->resolution > 0.0) || !std::isfinite(c->resolution) || !(c->time_step > 0.0) || !std::isfinite(c->time_step)) return NAVSIM_E_ARG;
+    if (c->action_kind != NAVSIM_ACTION_TWIST && c->action_kind != NAVSIM_ACTION_WHEELS) return NAVSIM_E_ARG;
+    if (c->action_kind == NAVSIM_ACTION_WHEELS && (!(c->wheel_radius > 0.0) || !std::isfinite(c->wheel_radius) || !std::isfinite(c->wheel_track)))
+        return NAVSIM_E_ARG;
+    if (st->map_slot && c->shared_field) return NAVSIM_E_ARG;
+    if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
+    if (st->rect_table && (c->field_format != NAVSIM_FIELD_U16T || c->map_h > 1024 || c->map_w > 1024)) return NAVSIM_E_UNSUPPORTED;
+    if (peds && c->angle_last - c->angle_min > nv::kTwoPi) return NAVSIM_E_UNSUPPORTED;     // the culled merge: dispatch_step
+    if (rollout_lds_bytes(c) > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;
+    if ((long long)c->n_envs * p->n_seq > 0x7FFFFFFFLL) return NAVSIM_E_UNSUPPORTED;         // one workgroup per (arena, sequence)
+    if (c->n_envs == 0) return NAVSIM_OK;
+    RolloutArgs a = {};
+    a.out = *out; a.actions = actions; a.ped_cmd = c->ped_model == NAVSIM_PED_EXTERNAL ? ped_cmd : nullptr; a.skip = skip;
+    a.K = p->n_seq; a.H = p->horizon; a.range = p->range; a.gamma = p->gamma;
+    hipStream_t s = (hipStream_t)stream;
+    if (c->field_format == NAVSIM_FIELD_U16T)
+        return st->rect_table ? launch_rollout<FieldU16T, true>(c, st, a, s) : launch_rollout<FieldU16T, false>(c, st, a, s);
+    return launch_rollout<FieldF32, false>(c, st, a, s);
 }
 
 const char* navsim_step_kernel_name(void) { return "navsim_step_kernel"; }

@@ -286,6 +286,26 @@ class NavsimLookaheadOut(C.Structure):
     _fields_ = [(name, _P) for name in LOOKAHEAD_OUT]
 
 
+# navsim_rollout: the rule's parameters and the ten output arrays (dtype, trailing shape behind E; K = n_seq, H = horizon; status is [E])
+ROLLOUT_MAX_K = 256
+ROLLOUT_MAX_H = 32
+OUTCOME_SUCCESS, OUTCOME_CRASH, OUTCOME_TIME_LIMIT = 1, 2, 4      # bits of navsim_rollout's outcome (navsim_episode_stats' ep_outcome)
+
+
+class NavsimRolloutParams(C.Structure):
+    _fields_ = [("n_seq", C.c_int32), ("horizon", C.c_int32), ("range", C.c_double), ("gamma", C.c_double)]
+
+
+ROLLOUT_OUT = {"reward": ("float64", ("K", "H")), "pose": ("float64", ("K", "H", 3)), "ret": ("float64", ("K",)),
+               "length": ("int32", ("K",)), "outcome": ("uint8", ("K",)), "discomfort_steps": ("int32", ("K",)),
+               "min_margin": ("float32", ("K",)), "distance": ("float64", ("K",)), "exact_steps": ("int32", ("K",)),
+               "status": ("uint8", ())}
+
+
+class NavsimRolloutOut(C.Structure):
+    _fields_ = [(name, _P) for name in ROLLOUT_OUT]
+
+
 ORCA_MAX_AGENTS = 64
 ORCA_MAX_EDGES = 128
 CROWD_MAX_VERTS = 8
@@ -505,6 +525,8 @@ def declare(lib, suffix=""):
         sig("navsim_scan_labels", [cfgp, stp, _P, C.POINTER(NavsimScanLabelsOut), _P])
     if not suffix and hasattr(lib, "navsim_lookahead"):                 # (likewise)
         sig("navsim_lookahead", [cfgp, stp, C.POINTER(NavsimLookaheadParams), _P, _P, _P, C.POINTER(NavsimLookaheadOut), _P])
+    if not suffix and hasattr(lib, "navsim_rollout"):                   # (likewise)
+        sig("navsim_rollout", [cfgp, stp, C.POINTER(NavsimRolloutParams), _P, _P, _P, C.POINTER(NavsimRolloutOut), _P])
     sig("navsim_reset_obs", [cfgp, stp, iop, _P] + stream)
     sig("navsim_restart", [cfgp, stp, _P] + stream)
     return lib
@@ -524,7 +546,7 @@ EXPORTS = (
     "navsim_step", "navsim_step_sorted", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
     "navsim_episode_stats_update", "navsim_episode_stats_clear", "navsim_ped_observe",
     "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps", "navsim_dwa", "navsim_local_map",
-    "navsim_scan_labels", "navsim_lookahead",
+    "navsim_scan_labels", "navsim_lookahead", "navsim_rollout",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

@@ -154,7 +154,16 @@ and default to the reference's behaviour for num_envs == 1:
                     lookahead_params: dict(range=), the candidates' scan cap in metres (default: the smallest multiple of 0.25 m
                     that lies 0.1 m above the largest discomfort threshold).  Not with pedestrian_model 'orca' or 'policy', whose
                     commands come from a launch in front of the step.  None (default): nothing is allocated or launched.
-    reset(mask)     reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
+    rollout         K in 1 .. 256: env.rollout(actions) returns what the next H step() calls would return if an arena executed each
+                    of K action sequences -- per step reward and pose; per sequence the discounted return, the steps evaluated,
+                    the outcome bits (1 success, 2 crash, 4 time limit), discomfort steps, the least crash margin, the final
+                    distance and exact_steps -- from one launch that only reads the state (navsim_rollout): what random shooting,
+                    MPPI, CEM, an n-step target or a multi-step shield asks.  A sequence ends at its first done step; a pedestrian
+                    that reaches its last waypoint inside the horizon is not re-planned, and exact_steps says up to which step the
+                    rows are the step's own, bit for bit with scan noise off (without pedestrians: the whole horizon).
+                    rollout_params: dict(horizon=8, range=, gamma=1.0); range as lookahead_params'.  Not with pedestrian_model
+                    'orca' or 'policy'.  None (default): nothing is allocated or launched.
+    reset(mask)    reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
                     [num_envs]; the others keep their state and their rows.  On the pipelined reset path the masked arenas install
                     their staged worlds in one launch: the same state and rows as with pregen_pipeline=0.
 
@@ -310,7 +319,7 @@ class NavGymEnv(_EnvBase):
                  final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None,
                  episode_stats=False, observe_humans=None, observe_params=None, goal_path=False, goal_path_params=None,
                  local_planner=None, local_planner_params=None, observe_local_map=None, local_map_params=None,
-                 scan_labels=False, lookahead=None, lookahead_params=None):
+                 scan_labels=False, lookahead=None, lookahead_params=None, rollout=None, rollout_params=None):
         # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
         self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
         from . import lib
@@ -548,6 +557,23 @@ class NavGymEnv(_EnvBase):
                                  "front of the step that has not run yet" % pedestrian_model)
         self.lookahead_k = None if lookahead is None else int(lookahead)
         self.lookahead_params = None if lookahead_params is None else dict(lookahead_params)
+        # action-sequence rollout (navsim_rollout): the next H steps' outcomes for K action sequences per arena, on request (env.rollout())
+        _check_params("rollout_params", rollout_params, rollout is not None, "rollout=K", ("horizon",) + _simmod.ROLLOUT_KEYS)
+        if rollout is not None:
+            if not (isinstance(rollout, numbers.Integral) and not isinstance(rollout, bool) and 1 <= rollout <= abi.ROLLOUT_MAX_K):
+                raise ValueError("rollout must be None or an int in 1 .. %d, not %r" % (abi.ROLLOUT_MAX_K, rollout))
+            horizon = (rollout_params or {}).get("horizon", self._ROLLOUT_HORIZON)
+            if not (isinstance(horizon, numbers.Integral) and not isinstance(horizon, bool) and 1 <= horizon <= abi.ROLLOUT_MAX_H):
+                raise ValueError("rollout_params: horizon must be an int in 1 .. %d, not %r" % (abi.ROLLOUT_MAX_H, horizon))
+            gamma = (rollout_params or {}).get("gamma", 1.0)
+            if not (isinstance(gamma, numbers.Real) and not isinstance(gamma, bool) and 0.0 <= gamma <= 1.0):
+                raise ValueError("rollout_params: gamma must lie in [0, 1], not %r" % (gamma,))
+            if pedestrian_model in ("orca", "policy"):
+                raise ValueError("rollout is not available with pedestrian_model=%r: the pedestrians' commands come from a launch in "
+                                 "front of the step that has not run yet" % pedestrian_model)
+        self.rollout_k = None if rollout is None else int(rollout)
+        self.rollout_h = None if rollout is None else int((rollout_params or {}).get("horizon", self._ROLLOUT_HORIZON))
+        self.rollout_params = None if rollout_params is None else dict(rollout_params)
         # the launches behind the step (and behind reset() / reset(mask) / load_state_dict), in the order they run -- the planner
         # reads the goal path's sub-goal, the local map the observer's `visible`.  _run_products() runs them; its latest result
         # and, per buffer parity, the views it handed out
@@ -718,6 +744,9 @@ class NavGymEnv(_EnvBase):
                 self.sim.enable_scan_labels()
             if self.lookahead_k:
                 self.sim.enable_lookahead(self.lookahead_k, self.lookahead_params)
+            if self.rollout_k:
+                self.sim.enable_rollout(self.rollout_k, self.rollout_h,
+                                        {k: v for k, v in (self.rollout_params or {}).items() if k != "horizon"})
         elif "policy_prev_actions" in self.sim.t:
             self.sim.t["policy_prev_actions"].zero_()           # env.py:739
         self._episode_batch += 1
@@ -995,6 +1024,51 @@ class NavGymEnv(_EnvBase):
             host = sim.lookahead_host()
             return {k: (v[0].astype(bool) if k in self._LOOKAHEAD_BOOL else v[0]) for k, v in host.items()}
         return {k: (v.view(self._bool) if k in self._LOOKAHEAD_BOOL else v) for k, v in out.items()}
+
+    _ROLLOUT_HORIZON = 8
+
+    def rollout(self, actions, human_actions=None):
+        """What the next H step() calls would return if an arena executed each of K action sequences, from the current state, which
+        is only read (NavGymEnv(rollout=K, rollout_params=dict(horizon=H)); navsim_rollout, one launch): {'reward' [E,K,H] float64
+        and 'pose' [E,K,H,3] float64 (the pose the step scans from), both 0 behind the sequence's last evaluated step; 'ret' [E,K]
+        float64, the rewards discounted by gamma; 'length' [E,K] int32, the steps evaluated (a sequence ends at its first done
+        step); 'outcome' [E,K] uint8 of the last evaluated step (1 success | 2 crash | 4 time limit); 'discomfort_steps' [E,K]
+        int32; 'min_margin' [E,K] float32 (negative iff a step crashed); 'distance' [E,K] float64; 'exact_steps' [E,K] int32 (the
+        leading steps whose rows are the step's own -- H unless a pedestrian reaches its last waypoint inside the horizon, where
+        the real step would re-plan it); 'status' [E] uint8 (0 = skipped)}.  With scan noise on the values are the noise-free
+        outcome.
+        actions: a float64 device tensor [E,K,H,2], or an array-like [K,H,2] that every arena takes, in action_kind's form.
+        human_actions: [E,N,2] with pedestrian_model='external' (required there), held for the whole horizon.
+        Next-step auto-reset: an arena whose `done` is set is skipped (status 0, rows 0) until the step that resets it.
+        num_envs > 1: torch views, intact through the next step(); num_envs == 1: NumPy rows [K,...] from one device -> host copy."""
+        if self.rollout_k is None:
+            raise RuntimeError("rollout() needs NavGymEnv(rollout=K)")
+        if self.pedestrian_model == "external" and human_actions is None:
+            raise ValueError("rollout() with pedestrian_model='external' needs human_actions")
+        if self.sim is None:
+            raise RuntimeError("call reset() before rollout()")
+        import torch
+        sim, E = self.sim, self.num_envs
+        actions = self._rollout_actions(actions, E, self.rollout_k, self.rollout_h)
+        skip = sim.out["done"] if self.auto_reset and self.autoreset_mode == "next_step" and sim.out is not None else None
+        out = sim.rollout(actions, ped_cmd=human_actions if self.pedestrian_model == "external" else None, skip=skip)
+        if E == 1:
+            return {k: v[0] for k, v in sim.rollout_host().items()}
+        return dict(out)
+
+    @staticmethod
+    def _rollout_actions(actions, E, K, H):
+        """rollout()'s actions as [E,K,H,2]: a device tensor stays one ([K,H,2] expanded), an array-like becomes a float64 host
+        tensor ([K,H,2] broadcast over the arenas)."""
+        import torch
+        if hasattr(actions, "is_cuda"):
+            return actions.expand(E, K, H, 2) if tuple(actions.shape) == (K, H, 2) else actions
+        a = np.asarray(actions, dtype=np.float64)
+        if a.shape == (K, H, 2):
+            a = np.broadcast_to(a, (E, K, H, 2))
+        if a.shape != (E, K, H, 2):
+            raise ValueError("rollout() takes actions of shape (%d, %d, %d, 2) or (%d, %d, 2), not %r" % (E, K, H, K, H, a.shape))
+        return torch.from_numpy(np.array(a, dtype=np.float64, order="C"))               # (a writable copy)
 
     def planner_action(self):
         """What info['planner'] of the latest step() holds (local_planner='dwa'); valid after reset() and reset(mask) too:

@@ -427,6 +427,16 @@ def lookahead_defaults(cfg, discomfort_max=0.0):
     return dict(range=min(float(cfg.range_max), float(np.ceil(lookahead_range_min(discomfort_max) / 0.25)) * 0.25))
 
 
+ROLLOUT_KEYS = ("range", "gamma")
+
+
+def rollout_defaults(cfg, discomfort_max=0.0):
+    """The parameters of navsim_rollout as a dict: range, the scans' cap R with the lookahead's default and lower bound
+    (lookahead_defaults, lookahead_range_min), and gamma, the discount of `ret` (1.0: the plain sum of rewards).  The sequence
+    count K and the horizon H are arguments of NavSim.enable_rollout."""
+    return dict(range=lookahead_defaults(cfg, discomfort_max)["range"], gamma=1.0)
+
+
 def ped_observation_layout(E, K, N):
     """Where navsim_ped_observation's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in
     abi.PED_OBSERVATION's order, each start rounded up to 16 bytes, and a last entry whose end byte is the blob's size."""
@@ -1783,6 +1793,59 @@ class NavSim(object):
     def lookahead_host(self):
         """The current set of lookahead()'s outputs as NumPy arrays, from ONE device -> host copy."""
         return self._product("lookahead").host(self.cur)
+
+    # ---- action-sequence rollout: what the next H step() calls would return for each of K action sequences per arena, one launch
+    # that only reads the state (include/navsim.h navsim_rollout)
+    def enable_rollout(self, K, H, params=None):
+        """Allocates two sets of outputs (abi.ROLLOUT_OUT, [E,K,...] and status [E]: they flip with self.cur like everything a
+        step returns), an action buffer float64 [E,K,H,2] and a command buffer float64 [E,N,2].  params: a dict of overrides of
+        rollout_defaults(cfg) -- range, gamma -- or None.  The lower bound on the cap is the lookahead's and is checked here the
+        same way: a range outside [max scan_discomfort + 0.1, range_max] or a gamma outside [0, 1] raises ValueError."""
+        import torch
+        cfg = self.cfg
+        if not 1 <= int(K) <= abi.ROLLOUT_MAX_K:
+            raise ValueError("rollout evaluates 1 .. %d sequences per arena, not %r" % (abi.ROLLOUT_MAX_K, K))
+        if not 1 <= int(H) <= abi.ROLLOUT_MAX_H:
+            raise ValueError("rollout looks 1 .. %d steps ahead, not %r" % (abi.ROLLOUT_MAX_H, H))
+        dmax = float(self.t["scan_discomfort"].max().item())
+        d = _overridden(rollout_defaults(cfg, dmax), params, "rollout", ROLLOUT_KEYS)
+        R, gamma = float(d["range"]), float(d["gamma"])
+        if not lookahead_range_min(dmax) <= R <= cfg.range_max:
+            raise ValueError("the rollout's range must lie in [%g, %g] (0.1 m above the largest discomfort threshold .. range_max), "
+                             "not %g" % (lookahead_range_min(dmax), cfg.range_max, R))
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError("the rollout's gamma must lie in [0, 1], not %g" % gamma)
+        p = abi.NavsimRolloutParams(n_seq=int(K), horizon=int(H), range=R, gamma=gamma)
+        extra = dict(actions=torch.zeros((cfg.n_envs, int(K), int(H), 2), dtype=torch.float64, device=self.device),
+                     ped_cmd=torch.zeros((cfg.n_envs, max(cfg.max_peds, 1), 2), dtype=torch.float64, device=self.device))
+        self.products["rollout"] = _StepProduct(self, p, blob_layout(abi.ROLLOUT_OUT, cfg.n_envs, {"K": int(K), "H": int(H)}),
+                                                abi.NavsimRolloutOut, extra=extra)
+
+    def rollout(self, actions, ped_cmd=None, skip=None):
+        """navsim_rollout of the current state on the current stream: one launch, no device -> host copy, no allocation, and the
+        state is only read.  actions: [E,K,H,2] in cfg.action_kind's form (copied into the product's buffer unless it already is a
+        contiguous float64 tensor on the device); ped_cmd: [E,N,2] commands held for the whole horizon under PED_EXTERNAL (None:
+        the state's own); skip: uint8 / bool [E], arenas that are not read and come back all 0 with status 0.  Returns the current
+        set (abi.ROLLOUT_OUT's keys), intact through the next step."""
+        import torch
+        p, cur = self.products.get("rollout") or self._product("rollout"), self.cur
+        buf = p.extra["actions"]
+        if not (torch.is_tensor(actions) and actions.device == buf.device and actions.dtype == buf.dtype and actions.is_contiguous()
+                and actions.shape == buf.shape):
+            buf.copy_(torch.as_tensor(actions).to(device=buf.device, dtype=buf.dtype).reshape(buf.shape), non_blocking=True)
+            actions = buf
+        if ped_cmd is not None:
+            cmd = p.extra["ped_cmd"]
+            cmd.copy_(torch.as_tensor(ped_cmd).to(device=cmd.device, dtype=cmd.dtype).reshape(cmd.shape), non_blocking=True)
+            ped_cmd = cmd
+        rc = self.lib.navsim_rollout(p.cfg, p.st, p.par, _ptr(actions), _ptr(ped_cmd), _ptr(skip), p.out[cur], _stream())
+        if rc:
+            check(rc, "navsim_rollout")
+        return p.buf[cur]
+
+    def rollout_host(self):
+        """The current set of rollout()'s outputs as NumPy arrays, from ONE device -> host copy."""
+        return self._product("rollout").host(self.cur)
 
     def occupancy(self, e=0):
         """uint8 [H, W] occupancy grid (1 = occupied) of arena e, read back from its distance field
