@@ -121,3 +121,16 @@ for _ in range(50):
     best = torch.where((out["outcome"] & 2) == 0, out["ret"], torch.full_like(out["ret"], -1e300)).argmax(dim=1)
     obs, reward, done, info = renv.step(seq[torch.arange(64, device="cuda:0"), best, 0].contiguous())
 print("random shooting, 64 arenas x 50 steps: %d crashes in the last step" % int((info["is_crash"] > 0).sum()))
+
+# ---- MPPI: the planner on top of the rollout, all on the device -------------------------------------------------------------------
+# local_planner='mppi' keeps a plan per arena, samples K sequences around it, rolls them out with the step's own arithmetic and
+# takes the weighted mean; with goal_path=True the cost's distance follows the goal field around the walls.
+menv = nav_gym_env.make("NavGym-v0", num_envs=64, map_size=400, goal_path=True, local_planner="mppi")
+menv.reset()
+reached = torch.zeros(64, dtype=torch.bool, device="cuda:0")
+for _ in range(100):
+    plan = menv.planner_action()                                                       # valid after reset() too
+    obs, reward, done, info = menv.step(plan["action"].clone())
+    reached |= info["is_success"] > 0
+print("MPPI, 64 arenas x 100 steps: %d reached a goal, %d crashes in the last step, mean effective sample size %.1f"
+      % (int(reached.sum()), int((info["is_crash"] > 0).sum()), float(info["planner"]["ess"].mean())))

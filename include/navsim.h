@@ -1569,6 +1569,94 @@ int navsim_rollout(const navsim_config* cfg, const navsim_state* st, const navsi
                    const double* actions /* [E,K,H,2] */, const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */,
                    const uint8_t* skip /* [E] or NULL */, const navsim_rollout_out* out, void* stream);
 
+/* ---- MPPI local planner: sampled plans, navsim_rollout and the importance-weighted update, all on the device ------------------
+ * A sampling-based model-predictive controller on the batch: every arena keeps a plan of H actions, perturbs it K times with
+ * time-correlated Gaussian noise, evaluates the K sequences with the step's own arithmetic (navsim_rollout), weights them by
+ * exp(-cost / lambda) and takes the weighted mean as its new plan.  BUILD-DEFINED, all of it: the reference has no controller. */
+typedef struct navsim_mppi_params {
+    int32_t n_samples;       /* K, 1 .. NAVSIM_ROLLOUT_MAX_K */
+    int32_t horizon;         /* H, 1 .. NAVSIM_ROLLOUT_MAX_H */
+    int32_t iterations;      /* 1 .. 8 */
+    int32_t stop_sample;     /* 0 / 1: sequence 1 is the all-zero action (needs 0 inside the box) */
+    int32_t select;          /* 0: out->action is the new plan's first action; 1: the best sequence's first action */
+    int32_t pad_;
+    double  range, gamma;    /* navsim_rollout_params' */
+    double  sigma[2];        /* >= 0: standard deviation of the perturbation per action component */
+    double  lo[2], hi[2];    /* lo <= hi: the action box, in cfg.action_kind's form */
+    double  init_action[2];  /* inside the box: what a fresh plan holds */
+    double  beta, alpha;     /* beta in [0, 1): the noise's AR(1) coefficient; alpha = sqrt(1 - beta * beta), computed by the caller */
+    double  lambda;          /* > 0: the temperature */
+    double  w_goal, w_crash, off_field_cost;   /* >= 0 */
+} navsim_mppi_params;
+
+typedef struct navsim_mppi_ws {     /* caller-allocated, persists between calls */
+    double*  plan;           /* [E,H,2] */
+    int64_t* plan_key;       /* [E,2] (episode, steps) the plan was made for; the caller initialises plan_key[e,0] = -1 */
+    double*  actions;        /* [E,K,H,2] the sampled sequences of the last iteration */
+    navsim_rollout_out roll; /* all ten arrays: navsim_rollout's outputs for `actions` */
+    double*  cost;           /* [E,K] */
+} navsim_mppi_ws;
+
+typedef struct navsim_mppi_out {
+    double*  action;         /* [E,2] in cfg.action_kind's form: feed it to the next navsim_step */
+    int32_t* best;           /* [E]   the best sequence (rule 7) */
+    double*  cost_best;      /* [E]   its cost */
+    double*  ess;            /* [E]   effective sample size S^2 / Q, 1 .. K */
+    uint8_t* status;         /* [E]   0 skipped, NAVSIM_MPPI_OK 1, NAVSIM_MPPI_ALL_CRASH 2 */
+} navsim_mppi_out;
+
+#define NAVSIM_MPPI_OK        1
+#define NAVSIM_MPPI_ALL_CRASH 2   /* every sequence crashed inside the horizon */
+
+/* 3 x iterations launches (sample, navsim_rollout's own, update; kernels_mppi.hpp), no device-to-host copy, nothing that blocks, no
+ * allocation; the state is only read and nothing but `ws` and `out` is written.  Call it wherever navsim_rollout could be called,
+ * on the same stream.  `field` (with `gp`, the parameters it was built with) is the goal field the caller's navsim_goal_path
+ * built for THIS state: it is only read, its keys are not looked at -- a stale field is the caller's business; NULL: the
+ * straight-line distance.  ped_cmd and skip are navsim_rollout's.  Float64, every operation rounded on its own, no fused
+ * multiply-add; B, N and the state as in navsim_rollout; genv = cfg.env_index_base + e.  Per arena e:
+ *  1. skip && skip[e]: every element of out's row is 0 (status 0); the arena's rows of ws->actions, ws->cost and ws->roll are 0
+ *     (ws->roll as navsim_rollout leaves a skipped arena); nothing of the arena is read; ws->plan and ws->plan_key stay untouched.
+ *  2. Warm start, once per call.  (ep, s) = (st->episode[e], st->steps[e]).  plan_key[e] == (ep, s): the plan stays.
+ *     plan_key[e] == (ep, s - 1): plan[h] = plan[h+1] for h < H-1, plan[H-1] stays.  Otherwise plan[h] = init_action for all h.
+ *     Then plan_key[e] = (ep, s).  (A restart, a reset of some arenas, an installed world, a missed step: all show in the two
+ *     counters, no host logic decides.)
+ *  3. For it = 0 .. iterations-1 do 4 - 8.
+ *  4. Sample.  key = ((uint64)ep << 32) + ((uint64)s << 3) + it.  For sequence k: stream_k = nv::hash4(cfg.seed ^ key, genv, key,
+ *     0x6D707069 + ((uint64)k << 32));  g(k,h,c) = (double)nv::gauss_noise(stream_k, 2h + c);  eps(k,0,c) = g(k,0,c),
+ *     eps(k,h,c) = beta * eps(k,h-1,c) + alpha * g(k,h,c);
+ *     actions[e,k,h,c] = min(max(plan[h,c] + sigma[c] * eps(k,h,c), lo[c]), hi[c]).
+ *     Two exceptions: k = 0 is the plan itself, min(max(plan[h,c], lo[c]), hi[c]); with stop_sample and K >= 2, k = 1 is
+ *     min(max(0, lo[c]), hi[c]) throughout.  The draw depends on (seed, genv, ep, s, it, k, h, c) alone.
+ *  5. navsim_rollout's launch on ws->actions into ws->roll, with (K, H, range, gamma), ped_cmd and skip.
+ *  6. Cost.  L = length[e,k], crash_k = outcome[e,k] & 2, (x, y) = pose[e,k,L-1,0..1].  Without field: D_k = distance[e,k].
+ *     With field: D_k = (double) of the float32 distance that rules 3 - 6 of navsim_goal_path give for a robot standing at
+ *     (x, y) on arena e's field with gp's look-ahead and hard clearance; where that rule's status is OFF_FIELD,
+ *     D_k = D_k + off_field_cost.  J_k = w_goal * D_k - ret[e,k]; if (crash_k) J_k = J_k + w_crash; cost[e,k] = J_k.
+ *  7. jmin = the least J_k, scanning k upward.  best = the least (crash_k != 0, J_k, k) lexicographically: a sequence that did
+ *     not crash whenever there is one.  w_k = nv::exp_neg(-((J_k - jmin) / lambda)).  S = 0; for k = 0 .. K-1: S = S + w_k.
+ *     Q = 0; Q = Q + w_k * w_k likewise.  For every (h, c): m = 0; for k upward: m = m + w_k * actions[e,k,h,c];
+ *     plan[h,c] = min(max(m / S, lo[c]), hi[c]).  (S >= 1: the sequence at jmin has weight exactly 1.)
+ *  8. Outputs, of the LAST iteration: action = plan[0] (select 0) or actions[e,best,0] (select 1); cost_best = J_best;
+ *     ess = S * S / Q; status = NAVSIM_MPPI_OK, or NAVSIM_MPPI_ALL_CRASH when every sequence crashed.
+ * NAVSIM_E_ARG, before anything touches the device: cfg, st, p, ws or out NULL; any array of ws (its ten rollout arrays
+ * included) or of out NULL; n_samples, horizon or iterations outside their ranges; stop_sample or select outside 0 / 1; a sigma
+ * that is negative or not finite; lo, hi or init_action not finite, lo > hi, init_action outside the box; stop_sample with 0
+ * outside the box; beta outside [0, 1); alpha further than 1e-12 from sqrt(1 - beta^2); lambda not positive and finite; w_goal,
+ * w_crash or off_field_cost negative or not finite (NaN fails every one of these); field without gp, field->dist NULL, gp's
+ * hard_clearance or lookahead not finite, hard_clearance < 3 resolution, lookahead < 0, map_h / 5 < 1 or map_w / 5 < 1;
+ * st->episode NULL.  Everything navsim_rollout refuses for (n_samples, horizon, range, gamma), ws->actions and ws->roll is refused
+ * with navsim_rollout's code (its pedestrian models too: navsim_ped_orca / navsim_ped_policy worlds are out of scope for its
+ * reason).  n_envs == 0: NAVSIM_OK, nothing is launched.
+ * Cost, measured on an MI355X (profiles/r24_mppi/summary.txt; 4096 arenas x 1081 beams, goal field on): the sample kernel 21 - 24 us
+ * and the update kernel 49 - 90 us a launch (K = 32 / 64; rule 7's sums are sequential in k by specification), 0.03 - 0.22 % of an
+ * iteration beside navsim_rollout's launch: (K, H) = (32, 24) 28.9 ms without pedestrians and 59.2 ms with twenty an arena,
+ * (64, 16) 38.6 / 78.6 ms.
+ * Out of scope: covariance adaptation (CEM), noise-aware outcomes, pedestrians driven by navsim_ped_orca or navsim_ped_policy. */
+int navsim_mppi(const navsim_config* cfg, const navsim_state* st, const navsim_mppi_params* p,
+                const navsim_goal_field* field /* or NULL */, const navsim_goal_path_params* gp /* with field */,
+                const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */, const uint8_t* skip /* [E] or NULL */,
+                const navsim_mppi_ws* ws, const navsim_mppi_out* out, void* stream);
+
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);
 

@@ -41,7 +41,8 @@
 //                      its loops are flat and never unrolled: with navsim_config / navsim_state as parameters, loops nested per row
 //                      and column and the compiler's unrolling, the loop-invariant scalars did not fit 102 SGPRs (4 - 17 spilled
 //                      to vector-register lanes).
-//   goal_query_kernel  VGPRs 48 / 51 / 48, SGPRs 48 / 50 / 47, no scratch, no spill, no LDS, 8 waves per SIMD.
+//   goal_query_kernel  VGPRs 45 / 48 / 46, SGPRs 46 / 47 / 45, no scratch, no spill, no LDS, 8 waves per SIMD (its walk is the device
+//                      function goal_walk, which kernels_mppi.hpp's update kernel calls too).
 // ============================================================================================
 constexpr int kGoalBlock = 1024;         // threads of a rebuilding workgroup
 constexpr int kGoalWaves = 4;            // wavefronts per workgroup of the query
@@ -208,37 +209,33 @@ __global__ __launch_bounds__(kGoalBlock) void goal_field_kernel(GoalFieldArgs a)
     }
 }
 
+// Steps 3 - 5 of navsim_goal_path for a robot at (rx, ry) on the field `dist` whose goal is (gx, gy): EIGHT lanes per walker --
+// lane k of a group = neighbour k -- and every lane of the wavefront calls it (ballots and shuffles; the hop loop is
+// wave-uniform).  `active`: this group has a walker.  All eight lanes of a group return the same values: the walk's last cell
+// (ci, cj), the goal's cell (gi, gj), dcur = dist[cur] and `off` (step 3).  goal_query_kernel and mppi_update_kernel
+// (kernels_mppi.hpp) call it.
 template <typename Field>
-__global__ __launch_bounds__(64 * kGoalWaves) void goal_query_kernel(navsim_config c, navsim_state st, GoalPathArgs a) {
-    const int lane = threadIdx.x & 63, k = lane & 7;
-    const int e = ((int)blockIdx.x * kGoalWaves + (int)(threadIdx.x >> 6)) * 8 + (lane >> 3);
-    if (e - (lane >> 3) >= c.n_envs) return;                             // wave-uniform: no arena on this wavefront
-    const bool in = e < c.n_envs;
-    const bool skipped = in && a.skip && a.skip[e] != 0;                 // step 1
-    const int Hc = a.Hc, Wc = a.Wc;
+__device__ __forceinline__ void goal_walk(const Field& field, const uint16_t* dist, int Hc, int Wc, float hard, int lookahead_cells,
+                                          float ox, float oy, float res, int map_h, int map_w, int lane, bool active,
+                                          double rx, double ry, double gx, double gy,
+                                          int& ci, int& cj, int& gi, int& gj, unsigned& dcur, bool& off) {
+    const int k = lane & 7;
     // neighbour k of the fixed order: (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (+1,-1) (-1,+1) (-1,-1)
     const int di = k < 2 ? 1 - 2 * k : (k < 4 ? 0 : (k < 6 ? 1 : -1));
     const int dj = k < 2 ? 0 : (k < 4 ? 5 - 2 * k : ((k & 1) ? -1 : 1));
     const unsigned w = k < 4 ? 5u : 7u;
     const unsigned need_bits = k < 4 ? 0u : ((di > 0 ? 1u : 2u) | (dj > 0 ? 4u : 8u));      // a diagonal's two orthogonal cells
-    double rx = 0.0, ry = 0.0, th = 0.0, gx = 0.0, gy = 0.0;
-    int ci = 0, cj = 0, gi = 0, gj = 0;
-    unsigned dcur = kGoalInf;
-    const size_t ee = in ? (size_t)e : 0;
-    const uint16_t* dist = a.field.dist + ee * Hc * Wc;
-    const Field field(st.field, st.field_overflow, (in && !skipped) ? map_slot_of(c, st, e) : 0, c.map_h, c.map_w);
-    if (in && !skipped) {                                                // step 2
-        rx = st.robot_pose[3 * ee]; ry = st.robot_pose[3 * ee + 1]; th = st.robot_pose[3 * ee + 2];
-        gx = st.robot_goal[2 * ee]; gy = st.robot_goal[2 * ee + 1];
-        const float ox = (float)c.origin_x, oy = (float)c.origin_y, res = (float)c.resolution;
-        goal_nav_cell((float)gx, (float)gy, ox, oy, res, c.map_h, c.map_w, Hc, Wc, gi, gj);
-        goal_nav_cell((float)rx, (float)ry, ox, oy, res, c.map_h, c.map_w, Hc, Wc, ci, cj);
+    ci = 0; cj = 0; gi = 0; gj = 0;
+    dcur = kGoalInf;
+    if (active) {                                                        // step 2
+        goal_nav_cell((float)gx, (float)gy, ox, oy, res, map_h, map_w, Hc, Wc, gi, gj);
+        goal_nav_cell((float)rx, (float)ry, ox, oy, res, map_h, map_w, Hc, Wc, ci, cj);
         dcur = dist[cj * Wc + ci];
     }
-    const bool off = in && !skipped && dcur == kGoalInf;                 // step 3
-    bool walking = in && !skipped && !off;
+    off = active && dcur == kGoalInf;                                    // step 3
+    bool walking = active && !off;
     int walked = 0;
-    const int by_look = a.lookahead_cells / 5, by_grid = Hc * Wc;
+    const int by_look = lookahead_cells / 5, by_grid = Hc * Wc;
     const int max_hops = by_look < by_grid ? by_look : by_grid;
     for (int hop = 0; hop < max_hops; ++hop) {                           // step 4; wave-uniform
         walking = walking && !(ci == gi && cj == gj);
@@ -248,9 +245,9 @@ __global__ __launch_bounds__(64 * kGoalWaves) void goal_query_kernel(navsim_conf
         bool pass = false;
         if (walking && ni >= 0 && ni < Wc && nj >= 0 && nj < Hc) {
             dn = dist[nj * Wc + ni];
-            pass = (ni == gi && nj == gj) || !(field.at(5 * ni + 2, 5 * nj + 2) < a.hard);
+            pass = (ni == gi && nj == gj) || !(field.at(5 * ni + 2, 5 * nj + 2) < hard);
         }
-        const unsigned bits = (unsigned)(__ballot(pass) >> (lane & 56)) & 0xFFu;      // the eight neighbours of this arena
+        const unsigned bits = (unsigned)(__ballot(pass) >> (lane & 56)) & 0xFFu;      // the eight neighbours of this walker
         const bool adm = pass && (bits & need_bits) == need_bits;
         int key = adm ? (int)((dn + w) * 8u + (unsigned)k) : 0x7FFFFFFF;
         int o = __shfl_xor(key, 1); key = o < key ? o : key;
@@ -258,7 +255,7 @@ __global__ __launch_bounds__(64 * kGoalWaves) void goal_query_kernel(navsim_conf
         o = __shfl_xor(key, 4); key = o < key ? o : key;
         if (walking) {
             const int kk = key & 7, ww = kk < 4 ? 5 : 7;
-            if (key == 0x7FFFFFFF || walked + ww > a.lookahead_cells) {
+            if (key == 0x7FFFFFFF || walked + ww > lookahead_cells) {
                 walking = false;
             } else {
                 ci += kk < 2 ? 1 - 2 * kk : (kk < 4 ? 0 : (kk < 6 ? 1 : -1));
@@ -268,6 +265,43 @@ __global__ __launch_bounds__(64 * kGoalWaves) void goal_query_kernel(navsim_conf
             }
         }
     }
+}
+
+// Steps 5 and 6 behind goal_walk: the target (tx, ty) and the float32 distance; dx, dy = target - robot for the caller's sub-goal
+__device__ __forceinline__ float goal_distance(double origin_x, double origin_y, double resolution, bool off, bool reached, int ci, int cj,
+                                               unsigned dcur, double rx, double ry, double gx, double gy, double& dx, double& dy) {
+    double tx = gx, ty = gy;
+    unsigned rem = 0u;
+    if (!off && !reached) {
+        tx = origin_x + ((double)(5 * ci) + 2.5) * resolution;
+        ty = origin_y + ((double)(5 * cj) + 2.5) * resolution;
+        rem = dcur;
+    }
+    dx = tx - rx; dy = ty - ry;
+    return (float)(sqrt(dx * dx + dy * dy) + (double)rem * resolution);
+}
+
+template <typename Field>
+__global__ __launch_bounds__(64 * kGoalWaves) void goal_query_kernel(navsim_config c, navsim_state st, GoalPathArgs a) {
+    const int lane = threadIdx.x & 63, k = lane & 7;
+    const int e = ((int)blockIdx.x * kGoalWaves + (int)(threadIdx.x >> 6)) * 8 + (lane >> 3);
+    if (e - (lane >> 3) >= c.n_envs) return;                             // wave-uniform: no arena on this wavefront
+    const bool in = e < c.n_envs;
+    const bool skipped = in && a.skip && a.skip[e] != 0;                 // step 1
+    const int Hc = a.Hc, Wc = a.Wc;
+    double rx = 0.0, ry = 0.0, th = 0.0, gx = 0.0, gy = 0.0;
+    const size_t ee = in ? (size_t)e : 0;
+    const uint16_t* dist = a.field.dist + ee * Hc * Wc;
+    const Field field(st.field, st.field_overflow, (in && !skipped) ? map_slot_of(c, st, e) : 0, c.map_h, c.map_w);
+    if (in && !skipped) {                                                // step 2
+        rx = st.robot_pose[3 * ee]; ry = st.robot_pose[3 * ee + 1]; th = st.robot_pose[3 * ee + 2];
+        gx = st.robot_goal[2 * ee]; gy = st.robot_goal[2 * ee + 1];
+    }
+    int ci, cj, gi, gj;
+    unsigned dcur;
+    bool off;
+    goal_walk(field, dist, Hc, Wc, a.hard, a.lookahead_cells, (float)c.origin_x, (float)c.origin_y, (float)c.resolution, c.map_h,
+              c.map_w, lane, in && !skipped, rx, ry, gx, gy, ci, cj, gi, gj, dcur, off);
     if (!in || k != 0) return;
     float* sub = a.out.subgoal + 2 * ee;
     if (skipped) {
@@ -276,17 +310,11 @@ __global__ __launch_bounds__(64 * kGoalWaves) void goal_query_kernel(navsim_conf
     }
     // ---- steps 5 and 6
     const bool reached = !off && ci == gi && cj == gj;
-    double tx = gx, ty = gy;
-    unsigned rem = 0u;
-    if (!off && !reached) {
-        tx = c.origin_x + ((double)(5 * ci) + 2.5) * c.resolution;
-        ty = c.origin_y + ((double)(5 * cj) + 2.5) * c.resolution;
-        rem = dcur;
-    }
-    const double dx = tx - rx, dy = ty - ry;
+    double dx, dy;
+    const float distance = goal_distance(c.origin_x, c.origin_y, c.resolution, off, reached, ci, cj, dcur, rx, ry, gx, gy, dx, dy);
     double sn, cs;
     nv::sincos(th, sn, cs);
-    a.out.distance[e] = (float)(sqrt(dx * dx + dy * dy) + (double)rem * c.resolution);
+    a.out.distance[e] = distance;
     sub[0] = (float)(cs * dx + sn * dy);
     sub[1] = (float)(cs * dy - sn * dx);
     a.out.status[e] = (uint8_t)(off ? NAVSIM_GOAL_PATH_OFF_FIELD

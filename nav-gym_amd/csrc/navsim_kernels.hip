@@ -27,6 +27,7 @@
 //   kernels_scan_labels.hpp  scan ground truth: the robot's clean scan and per-beam hit labels (navsim_scan_labels)
 //   kernels_lookahead.hpp    action lookahead: the step's outcomes for K candidate actions per arena (navsim_lookahead)
 //   kernels_rollout.hpp      action-sequence rollout: the next H steps' outcomes for K action sequences per arena (navsim_rollout)
+//   kernels_mppi.hpp         MPPI local planner: sampled plans, the rollout's launch, the weighted update (navsim_mppi)
 //   step_plan.hpp        launch geometry of the fused step, the descriptors of a launch and the march-rule dispatch (shared by this
 //                        file and navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
 // Host code of this file, ahead of the C ABI: dispatch_step and the argument checks; the workspaces (Carver and one layout
@@ -57,6 +58,7 @@ namespace {
 #include "kernels_scan_labels.hpp"
 #include "kernels_lookahead.hpp"
 #include "kernels_rollout.hpp"
+#include "kernels_mppi.hpp"
 
 }  // namespace
 #include "step_plan.hpp"
@@ -1710,9 +1712,9 @@ int navsim_lookahead(const navsim_config* c, const navsim_state* st, const navsi
     return launch_lookahead<FieldF32, false>(c, st, a, s);
 }
 
-int navsim_rollout(const navsim_config* c, const navsim_state* st, const navsim_rollout_params* p, const double* actions,
-                   const double* ped_cmd, const uint8_t* skip, const navsim_rollout_out* out, void* stream) {
-    (void)hipGetLastError();
+// what navsim_rollout refuses, before anything touches the device (navsim_mppi refuses the same with the same codes)
+static int rollout_check(const navsim_config* c, const navsim_state* st, const navsim_rollout_params* p, const double* actions,
+                         const double* ped_cmd, const navsim_rollout_out* out) {
     if (!c || !st || !p || !actions || !out) return NAVSIM_E_ARG;
     if (!out->reward || !out->pose || !out->ret || !out->length || !out->outcome || !out->discomfort_steps || !out->min_margin ||
         !out->distance || !out->exact_steps || !out->status)
@@ -1743,14 +1745,91 @@ int navsim_rollout(const navsim_config* c, const navsim_state* st, const navsim_
     if (peds && c->angle_last - c->angle_min > nv::kTwoPi) return NAVSIM_E_UNSUPPORTED;     // the culled merge: dispatch_step
     if (rollout_lds_bytes(c) > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;
     if ((long long)c->n_envs * p->n_seq > 0x7FFFFFFFLL) return NAVSIM_E_UNSUPPORTED;         // one workgroup per (arena, sequence)
-    if (c->n_envs == 0) return NAVSIM_OK;
+    return NAVSIM_OK;
+}
+
+// navsim_rollout's launch behind rollout_check
+static int rollout_launch(const navsim_config* c, const navsim_state* st, const navsim_rollout_params* p, const double* actions,
+                          const double* ped_cmd, const uint8_t* skip, const navsim_rollout_out* out, hipStream_t s) {
     RolloutArgs a = {};
     a.out = *out; a.actions = actions; a.ped_cmd = c->ped_model == NAVSIM_PED_EXTERNAL ? ped_cmd : nullptr; a.skip = skip;
     a.K = p->n_seq; a.H = p->horizon; a.range = p->range; a.gamma = p->gamma;
-    hipStream_t s = (hipStream_t)stream;
     if (c->field_format == NAVSIM_FIELD_U16T)
         return st->rect_table ? launch_rollout<FieldU16T, true>(c, st, a, s) : launch_rollout<FieldU16T, false>(c, st, a, s);
     return launch_rollout<FieldF32, false>(c, st, a, s);
+}
+
+int navsim_rollout(const navsim_config* c, const navsim_state* st, const navsim_rollout_params* p, const double* actions,
+                   const double* ped_cmd, const uint8_t* skip, const navsim_rollout_out* out, void* stream) {
+    (void)hipGetLastError();
+    const int rc = rollout_check(c, st, p, actions, ped_cmd, out);
+    if (rc != NAVSIM_OK) return rc;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    return rollout_launch(c, st, p, actions, ped_cmd, skip, out, (hipStream_t)stream);
+}
+
+int navsim_mppi(const navsim_config* c, const navsim_state* st, const navsim_mppi_params* p, const navsim_goal_field* field,
+                const navsim_goal_path_params* gp, const double* ped_cmd, const uint8_t* skip, const navsim_mppi_ws* ws,
+                const navsim_mppi_out* out, void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !p || !ws || !out) return NAVSIM_E_ARG;
+    if (!ws->plan || !ws->plan_key || !ws->actions || !ws->cost) return NAVSIM_E_ARG;
+    if (!out->action || !out->best || !out->cost_best || !out->ess || !out->status) return NAVSIM_E_ARG;
+    if (p->n_samples < 1 || p->n_samples > NAVSIM_ROLLOUT_MAX_K || p->horizon < 1 || p->horizon > NAVSIM_ROLLOUT_MAX_H) return NAVSIM_E_ARG;
+    if (p->iterations < 1 || p->iterations > 8) return NAVSIM_E_ARG;
+    if ((p->stop_sample != 0 && p->stop_sample != 1) || (p->select != 0 && p->select != 1)) return NAVSIM_E_ARG;
+    for (int i = 0; i < 2; ++i) {
+        if (!std::isfinite(p->sigma[i]) || p->sigma[i] < 0.0) return NAVSIM_E_ARG;
+        if (!std::isfinite(p->lo[i]) || !std::isfinite(p->hi[i]) || !std::isfinite(p->init_action[i])) return NAVSIM_E_ARG;
+        if (!(p->lo[i] <= p->hi[i]) || !(p->lo[i] <= p->init_action[i]) || !(p->init_action[i] <= p->hi[i])) return NAVSIM_E_ARG;
+        if (p->stop_sample && !(p->lo[i] <= 0.0 && 0.0 <= p->hi[i])) return NAVSIM_E_ARG;
+    }
+    if (!(p->beta >= 0.0) || !(p->beta < 1.0)) return NAVSIM_E_ARG;
+    if (!(fabs(p->alpha - sqrt(1.0 - p->beta * p->beta)) <= 1e-12)) return NAVSIM_E_ARG;
+    if (!std::isfinite(p->lambda) || !(p->lambda > 0.0)) return NAVSIM_E_ARG;
+    const double nonneg[] = {p->w_goal, p->w_crash, p->off_field_cost};
+    for (double x : nonneg)
+        if (!std::isfinite(x) || x < 0.0) return NAVSIM_E_ARG;
+    if (!st->episode) return NAVSIM_E_ARG;
+    if (field) {
+        if (!gp || !field->dist) return NAVSIM_E_ARG;
+        if (!std::isfinite(gp->hard_clearance) || !std::isfinite(gp->lookahead) || gp->lookahead < 0.0) return NAVSIM_E_ARG;
+        if (!(c->resolution > 0.0) || !std::isfinite(c->resolution) || gp->hard_clearance < 3.0 * c->resolution) return NAVSIM_E_ARG;
+        if (c->map_h / 5 < 1 || c->map_w / 5 < 1) return NAVSIM_E_ARG;
+    }
+    const navsim_rollout_params rp = {p->n_samples, p->horizon, p->range, p->gamma};
+    const int rc = rollout_check(c, st, &rp, ws->actions, ped_cmd, &ws->roll);
+    if (rc != NAVSIM_OK) return rc;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    MppiArgs a = {};
+    a.p = *p; a.ws = *ws; a.out = *out; a.skip = skip;
+    a.episode = st->episode; a.steps = st->steps; a.robot_goal = st->robot_goal;
+    a.field = st->field; a.overflow = st->field_overflow; a.map_slot = st->map_slot;
+    a.seed = c->seed; a.origin_x = c->origin_x; a.origin_y = c->origin_y; a.resolution = c->resolution;
+    a.env_index_base = c->env_index_base; a.map_h = c->map_h; a.map_w = c->map_w; a.shared_field = c->shared_field;
+    if (field) {
+        a.goal_dist = field->dist;
+        a.Hc = c->map_h / 5; a.Wc = c->map_w / 5;
+        a.hard = (float)(gp->hard_clearance / c->resolution);
+        const double look = floor(gp->lookahead / c->resolution);
+        a.lookahead_cells = (int)(look < 1048576.0 ? look : 1048576.0);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int block = 64 * ((2 * p->n_samples + 63) / 64);
+    for (int it = 0; it < p->iterations; ++it) {
+        a.it = it; a.last = it == p->iterations - 1;
+        mppi_sample_kernel<<<c->n_envs, block, 0, s>>>(a);
+        int rc2 = launch_status();
+        if (rc2 != NAVSIM_OK) return rc2;
+        rc2 = rollout_launch(c, st, &rp, ws->actions, ped_cmd, skip, &ws->roll, s);
+        if (rc2 != NAVSIM_OK) return rc2;
+        rc2 = with_field(c, st, [&](auto f) {
+            mppi_update_kernel<typename decltype(f)::type><<<c->n_envs, kMppiUpdateBlock, 0, s>>>(a);
+            return launch_status();
+        });
+        if (rc2 != NAVSIM_OK) return rc2;
+    }
+    return NAVSIM_OK;
 }
 
 const char* navsim_step_kernel_name(void) { return "navsim_step_kernel"; }

@@ -306,6 +306,36 @@ class NavsimRolloutOut(C.Structure):
     _fields_ = [(name, _P) for name in ROLLOUT_OUT]
 
 
+# navsim_mppi: the rule's parameters, the persistent workspace (with navsim_rollout's ten arrays inside) and the five output arrays
+# (dtype, trailing shape behind E; K = n_samples, H = horizon)
+MPPI_MAX_ITERATIONS = 8
+MPPI_OK, MPPI_ALL_CRASH = 1, 2
+
+
+class NavsimMppiParams(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("horizon", C.c_int32), ("iterations", C.c_int32), ("stop_sample", C.c_int32),
+                ("select", C.c_int32), ("pad_", C.c_int32), ("range", C.c_double), ("gamma", C.c_double),
+                ("sigma", C.c_double * 2), ("lo", C.c_double * 2), ("hi", C.c_double * 2), ("init_action", C.c_double * 2),
+                ("beta", C.c_double), ("alpha", C.c_double), ("lam", C.c_double), ("w_goal", C.c_double),
+                ("w_crash", C.c_double), ("off_field_cost", C.c_double)]       # lam: the header's `lambda`
+
+
+MPPI_WS = {"plan": ("float64", ("H", 2)), "plan_key": ("int64", (2,)), "actions": ("float64", ("K", "H", 2)),
+           "cost": ("float64", ("K",))}                                       # (+ ROLLOUT_OUT's arrays, in the struct's `roll`)
+
+
+class NavsimMppiWs(C.Structure):
+    _fields_ = [("plan", _P), ("plan_key", _P), ("actions", _P), ("roll", NavsimRolloutOut), ("cost", _P)]
+
+
+MPPI_OUT = {"action": ("float64", (2,)), "best": ("int32", ()), "cost_best": ("float64", ()), "ess": ("float64", ()),
+            "status": ("uint8", ())}
+
+
+class NavsimMppiOut(C.Structure):
+    _fields_ = [(name, _P) for name in MPPI_OUT]
+
+
 ORCA_MAX_AGENTS = 64
 ORCA_MAX_EDGES = 128
 CROWD_MAX_VERTS = 8
@@ -527,6 +557,9 @@ def declare(lib, suffix=""):
         sig("navsim_lookahead", [cfgp, stp, C.POINTER(NavsimLookaheadParams), _P, _P, _P, C.POINTER(NavsimLookaheadOut), _P])
     if not suffix and hasattr(lib, "navsim_rollout"):                   # (likewise)
         sig("navsim_rollout", [cfgp, stp, C.POINTER(NavsimRolloutParams), _P, _P, _P, C.POINTER(NavsimRolloutOut), _P])
+    if not suffix and hasattr(lib, "navsim_mppi"):                      # (likewise)
+        sig("navsim_mppi", [cfgp, stp, C.POINTER(NavsimMppiParams), C.POINTER(NavsimGoalField), C.POINTER(NavsimGoalPathParams),
+                            _P, _P, C.POINTER(NavsimMppiWs), C.POINTER(NavsimMppiOut), _P])
     sig("navsim_reset_obs", [cfgp, stp, iop, _P] + stream)
     sig("navsim_restart", [cfgp, stp, _P] + stream)
     return lib
@@ -546,7 +579,7 @@ EXPORTS = (
     "navsim_step", "navsim_step_sorted", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
     "navsim_episode_stats_update", "navsim_episode_stats_clear", "navsim_ped_observe",
     "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps", "navsim_dwa", "navsim_local_map",
-    "navsim_scan_labels", "navsim_lookahead", "navsim_rollout",
+    "navsim_scan_labels", "navsim_lookahead", "navsim_rollout", "navsim_mppi",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

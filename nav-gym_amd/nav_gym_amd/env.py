@@ -122,6 +122,20 @@ and default to the reference's behaviour for num_envs == 1:
                     the step that resets it.  env.planner_action() returns the same dict, also after reset() / reset(mask).
                     num_envs > 1: torch views with the lifetime below; num_envs == 1: NumPy values from one device -> host copy.
                     None (default): nothing is allocated or launched.
+                    'mppi': a sampling-based model-predictive controller on the device (navsim_mppi, 3 launches per iteration
+                    behind the step and behind navsim_goal_path): every arena keeps a plan of H actions, perturbs it K times with
+                    time-correlated Gaussian noise, evaluates the sequences with the STEP'S OWN arithmetic (navsim_rollout: the
+                    scan-based crash test, the social force per sequence), weights them by exp(-cost / lam) and takes the
+                    weighted mean as its new plan; the plan is shifted by one action from step to step and starts afresh when
+                    the arena's (episode, steps) say it restarted.  cost = w_goal x the distance to the goal at the horizon's
+                    end -- along the goal field with goal_path=True, else the straight line -- minus the rollout's return,
+                    + w_crash for a crash.  info['planner'] = {'action' [E,2] float64: feed it to the next step(); 'best' [E]
+                    the best sequence, one that did not crash whenever there is one; 'cost_best' [E]; 'ess' [E] the effective
+                    sample size; 'status' [E] uint8: 1 = ok, 2 = every sequence crashed, 0 = skipped}.  local_planner_params
+                    overrides sim.mppi_defaults: n_samples (32), horizon (24), iterations (1), sigma, lam, beta, w_goal, w_crash,
+                    off_field_cost, stop_sample, select ('mean': the new plan's first action, 'best': the best sequence's),
+                    range, gamma, init_action; the action box is action_space.  env.planner_plan() returns the plans [E,H,2].
+                    Not with pedestrian_model 'orca' or 'policy'; 'external': the state's own commands are held.
     observe_local_map  G (1 .. 128): an egocentric grid map per arena, one launch behind the step (navsim_local_map; what a CNN
                     policy over a local costmap or a DRL-VO style pedestrian map reads) -- info['local_map'] = float32
                     [E, C, G, G] in the robot's frame, row r counting forward along the body's x axis and column q to its left,
@@ -520,9 +534,17 @@ class NavGymEnv(_EnvBase):
         self.goal_path_params = None if goal_path_params is None else dict(goal_path_params)
         self._goal_all = None                               # the goal path's rebuild mask of a reset(): every arena
         # local planner (navsim_dwa): an action per arena, one launch behind the step (and behind the goal path)
-        if local_planner not in (None, "dwa"):
-            raise ValueError("local_planner must be None or 'dwa', not %r" % (local_planner,))
-        _check_params("local_planner_params", local_planner_params, local_planner is not None, "local_planner='dwa'", _simmod.DWA_KEYS)
+        if local_planner not in (None, "dwa", "mppi"):
+            raise ValueError("local_planner must be None or 'dwa' or 'mppi', not %r" % (local_planner,))
+        _check_params("local_planner_params", local_planner_params, local_planner is not None, "local_planner='dwa' or 'mppi'",
+                      self._MPPI_KEYS if local_planner == "mppi" else _simmod.DWA_KEYS)
+        if local_planner == "mppi":
+            # (navsim_mppi, behind the goal path: its rollouts run the pedestrians' own model, which needs their commands)
+            if pedestrian_model in ("orca", "policy"):
+                raise ValueError("rollout is not available with pedestrian_model=%r: the pedestrians' commands come from a launch in "
+                                 "front of the step that has not run yet (local_planner='mppi' plans with navsim_rollout)"
+                                 % pedestrian_model)
+            _simmod.mppi_params(cfg, self._mppi_overrides(local_planner_params, linvel_range, rotvel_range, cfg), robot_type)
         self.local_planner = local_planner
         self.local_planner_params = None if local_planner_params is None else dict(local_planner_params)
         # local map (navsim_local_map): a G x G grid per arena in the robot's frame, one launch behind the step
@@ -580,7 +602,8 @@ class NavGymEnv(_EnvBase):
         self._products = [row for on, row in (
             (self.observe_humans, _Product("humans", "ped_observe", self._observe, tuple(abi.PED_OBSERVATION), self._humans_row)),
             (self.goal_path_on, _Product("goal_path", "goal_path", self._goal_path, tuple(abi.GOAL_PATH_OUT), None)),
-            (self.local_planner, _Product("planner", "dwa", self._plan, self._PLANNER_KEYS, None)),
+            (self.local_planner == "dwa", _Product("planner", "dwa", self._plan, self._PLANNER_KEYS, None)),
+            (self.local_planner == "mppi", _Product("planner", "mppi", self._plan_mppi, tuple(abi.MPPI_OUT), None)),
             (self.observe_local_map, _Product("local_map", "local_map", self._local_map, ("map",), operator.itemgetter("map"))),
             (self.scan_labels_on, _Product("scan_labels", "scan_labels", self._scan_labels,
                                            tuple(k for k in abi.SCAN_LABELS_OUT if k != "hits" or cfg.ped_model != abi.PED_NONE), None))) if on]
@@ -735,8 +758,11 @@ class NavGymEnv(_EnvBase):
             if self.goal_path_on:
                 self.sim.enable_goal_path(self.goal_path_params)
                 self._goal_all = torch.ones(self.num_envs, dtype=torch.uint8, device=dev)
-            if self.local_planner:
+            if self.local_planner == "dwa":
                 self.sim.enable_dwa(self.local_planner_params, robot_type=self.robot_type)
+            if self.local_planner == "mppi":
+                self.sim.enable_mppi(self._mppi_overrides(self.local_planner_params, self.linvel_range, self.rotvel_range, cfg),
+                                     robot_type=self.robot_type)
             if self.observe_local_map:
                 self.sim.enable_local_map(self.observe_local_map, {k: v for k, v in (self.local_map_params or {}).items()
                                                                    if k != "visible_only"})
@@ -965,6 +991,38 @@ class NavGymEnv(_EnvBase):
         sim = self.sim                                    # goal_path the arena's goal)
         sim.dwa(subgoal=sim.products["goal_path"].buf[sim.cur]["subgoal"] if self.goal_path_on else None, skip=skip)
 
+    # local_planner_params under 'mppi': sim.MPPI_KEYS without the action box, which is the environment's own action_space
+    _MPPI_KEYS = ("n_samples", "horizon", "iterations", "sigma", "lam", "beta", "w_goal", "w_crash", "off_field_cost", "stop_sample",
+                  "select", "range", "gamma", "init_action")
+
+    @staticmethod
+    def _mppi_overrides(params, linvel_range, rotvel_range, cfg):
+        """local_planner_params with the action box of this environment's action_space added (lo, hi of sim.mppi_defaults)."""
+        if cfg.action_kind == abi.ACTION_WHEELS:
+            corners = [robots.wheels_from_twist(v, w, cfg.wheel_radius, cfg.wheel_track) for v in linvel_range for w in rotvel_range]
+            lo, hi = (float(np.min(corners)),) * 2, (float(np.max(corners)),) * 2
+        else:
+            lo, hi = (float(linvel_range[0]), float(rotvel_range[0])), (float(linvel_range[1]), float(rotvel_range[1]))
+        d = dict(params or {}, lo=lo, hi=hi)
+        if "sigma" not in d:
+            d["sigma"] = tuple(0.5 * (h - l) for l, h in zip(lo, hi))
+        if "init_action" not in d:
+            d["init_action"] = tuple(min(max(0.0, l), h) for l, h in zip(lo, hi))
+        return d
+
+    def _plan_mppi(self, skip, rebuild):                 # (with goal_path the field that launch just brought up to date is the
+        self.sim.mppi(field=self.goal_path_on, skip=skip)  # terminal cost; 'external' pedestrians: the state's own commands)
+
+    def planner_plan(self):
+        """The planner's current plans (local_planner='mppi'): float64 [E,H,2] on the device, in action_kind's form; row 0 is
+        what info['planner']['action'] holds under select='mean' (num_envs == 1: a NumPy array [H,2])."""
+        if self.local_planner != "mppi":
+            raise RuntimeError("planner_plan() needs NavGymEnv(local_planner='mppi')")
+        if self.sim is None:
+            raise RuntimeError("call reset() before planner_plan()")
+        plan = self.sim.mppi_plan()
+        return plan[0].cpu().numpy() if self.num_envs == 1 else plan
+
     def _local_map(self, skip, rebuild):                 # (visible_only: the observer's `visible` of the current buffer set is the
         sim = self.sim                                    # pedestrians that count)
         sim.local_map(skip=skip, visible=sim.products["ped_observe"].buf[sim.cur]["visible"] if self._local_map_visible else None)
@@ -1073,8 +1131,9 @@ class NavGymEnv(_EnvBase):
     def planner_action(self):
         """What info['planner'] of the latest step() holds (local_planner='dwa'); valid after reset() and reset(mask) too:
         {'action' [E,2] float64 in action_kind's form, 'twist' [E,2] float64 (v, omega), 'clearance' [E] float32 metres, 'best' [E]
-        int32, 'status' [E] uint8}."""
-        return self._latest("planner", self.local_planner, "planner_action", "local_planner='dwa'")
+        int32, 'status' [E] uint8}.  local_planner='mppi': {'action' [E,2], 'best' [E] int32, 'cost_best' [E] float64, 'ess' [E]
+        float64, 'status' [E] uint8 (1 ok, 2 every sequence crashed, 0 skipped)}."""
+        return self._latest("planner", self.local_planner, "planner_action", "local_planner='dwa' or 'mppi'")
 
     def goal_path(self):
         """What info['goal_path'] of the latest step() holds (goal_path=True); valid after reset() and reset(mask) too:

@@ -437,6 +437,80 @@ def rollout_defaults(cfg, discomfort_max=0.0):
     return dict(range=lookahead_defaults(cfg, discomfort_max)["range"], gamma=1.0)
 
 
+MPPI_KEYS = ("n_samples", "horizon", "iterations", "sigma", "lam", "beta", "w_goal", "w_crash", "off_field_cost", "stop_sample",
+             "select", "range", "gamma", "init_action", "lo", "hi")
+MPPI_SELECT = {"mean": 0, "best": 1, 0: 0, 1: 1}
+
+
+def mppi_defaults(cfg, robot_type="keti", discomfort_max=0.0):
+    """The parameters of navsim_mppi as a dict.  The action box lo / hi: the robot's linvel_range / rotvel_range (robots.py), or
+    under ACTION_WHEELS the least and the greatest wheel speed over the corners of that box, as NavGymEnv builds its
+    action_space.  K = 32 sequences over H = 24 steps, one iteration; sigma half of the box per component, the noise strongly
+    correlated over the horizon (beta = 0.9: a sequence is a manoeuvre, not a jitter); the plan starts at the action nearest to
+    0; sequence 1 stands still (stop_sample); the cost is w_goal = 3 per metre of goal distance at the horizon's end minus the
+    rollout's return, + w_crash = 100 for a crash, + off_field_cost = 10 m for an end pose off the goal field; temperature
+    lam = 0.05; select 'mean' (the new plan's first action; 'best': the best sequence's).  range / gamma: rollout_defaults'.
+    Tuning, not correctness, from the behaviour run of profiles/r24_mppi/summary.txt (64 outdoor arenas, 150 steps, goal_path on,
+    select='best'): the robot turns at 0.64 rad/s at most, so a horizon of 8 steps (1.6 s) sees no progress behind a turn and
+    stands still -- 13 of 64 arenas reach their goal; H = 16 with beta = 0.9 and the wider sigma: 33; w_goal = 3: 44; H = 24: 58.
+    No setting crashed without pedestrians."""
+    from . import robots
+    spec = robots.ROBOTS[robot_type]
+    (v0, v1), (w0, w1) = spec["linvel_range"], spec["rotvel_range"]
+    if cfg.action_kind == abi.ACTION_WHEELS:
+        corners = [robots.wheels_from_twist(v, w, cfg.wheel_radius, cfg.wheel_track) for v in (v0, v1) for w in (w0, w1)]
+        lo = (float(np.min(corners)),) * 2
+        hi = (float(np.max(corners)),) * 2
+    else:
+        lo, hi = (float(v0), float(w0)), (float(v1), float(w1))
+    d = dict(n_samples=32, horizon=24, iterations=1, sigma=tuple(0.5 * (h - l) for l, h in zip(lo, hi)), lam=0.05, beta=0.9,
+             w_goal=3.0, w_crash=100.0, off_field_cost=10.0, stop_sample=1, select="mean",
+             init_action=tuple(min(max(0.0, l), h) for l, h in zip(lo, hi)), lo=lo, hi=hi)
+    d.update(rollout_defaults(cfg, discomfort_max))
+    return d
+
+
+def mppi_params(cfg, params=None, robot_type="keti", discomfort_max=0.0):
+    """abi.NavsimMppiParams of mppi_defaults(cfg, robot_type) overridden by the dict `params`; an unknown key or a value
+    navsim_mppi would refuse raises ValueError.  alpha = sqrt(1 - beta * beta) is computed here, in float64."""
+    d = _overridden(mppi_defaults(cfg, robot_type, discomfort_max), params, "planner", MPPI_KEYS)
+    if d["select"] not in MPPI_SELECT:
+        raise ValueError("select must be 'mean' or 'best', not %r" % (d["select"],))
+    p = abi.NavsimMppiParams()
+    p.n_samples, p.horizon, p.iterations = int(d["n_samples"]), int(d["horizon"]), int(d["iterations"])
+    p.stop_sample, p.select = int(bool(d["stop_sample"])), MPPI_SELECT[d["select"]]
+    p.range, p.gamma = float(d["range"]), float(d["gamma"])
+    for k in ("sigma", "lo", "hi", "init_action"):
+        v = np.asarray(d[k], np.float64).reshape(-1)
+        if v.shape != (2,):
+            raise ValueError("%s holds two values (one per action component), not %r" % (k, d[k]))
+        getattr(p, k)[:] = [float(v[0]), float(v[1])]
+    p.beta, p.lam = float(d["beta"]), float(d["lam"])
+    p.w_goal, p.w_crash, p.off_field_cost = float(d["w_goal"]), float(d["w_crash"]), float(d["off_field_cost"])
+    if not 1 <= p.n_samples <= abi.ROLLOUT_MAX_K:
+        raise ValueError("the planner samples 1 .. %d sequences per arena, not %r" % (abi.ROLLOUT_MAX_K, d["n_samples"]))
+    if not 1 <= p.horizon <= abi.ROLLOUT_MAX_H:
+        raise ValueError("the planner looks 1 .. %d steps ahead, not %r" % (abi.ROLLOUT_MAX_H, d["horizon"]))
+    if not 1 <= p.iterations <= abi.MPPI_MAX_ITERATIONS:
+        raise ValueError("the planner runs 1 .. %d iterations, not %r" % (abi.MPPI_MAX_ITERATIONS, d["iterations"]))
+    if not 0.0 <= p.beta < 1.0:
+        raise ValueError("beta must lie in [0, 1), not %r" % (d["beta"],))
+    if not (p.lam > 0.0 and np.isfinite(p.lam)):
+        raise ValueError("lam must be positive, not %r" % (d["lam"],))
+    for i in range(2):
+        if not (np.isfinite(p.sigma[i]) and p.sigma[i] >= 0.0):
+            raise ValueError("sigma must not be negative, not %r" % (d["sigma"],))
+        if not (np.isfinite(p.lo[i]) and np.isfinite(p.hi[i]) and p.lo[i] <= p.init_action[i] <= p.hi[i]):
+            raise ValueError("init_action must lie inside the action box [%r, %r], not %r" % (d["lo"], d["hi"], d["init_action"]))
+        if p.stop_sample and not p.lo[i] <= 0.0 <= p.hi[i]:
+            raise ValueError("stop_sample needs the action 0 inside the box [%r, %r]" % (d["lo"], d["hi"]))
+    for k in ("w_goal", "w_crash", "off_field_cost"):
+        if not (np.isfinite(getattr(p, k)) and getattr(p, k) >= 0.0):
+            raise ValueError("%s must not be negative, not %r" % (k, d[k]))
+    p.alpha = float(np.sqrt(np.float64(1.0) - np.float64(p.beta) * np.float64(p.beta)))
+    return p
+
+
 def ped_observation_layout(E, K, N):
     """Where navsim_ped_observation's arrays lie in one byte blob: [(name, dtype, first byte, end byte, shape), ...] in
     abi.PED_OBSERVATION's order, each start rounded up to 16 bytes, and a last entry whose end byte is the blob's size."""
@@ -1846,6 +1920,64 @@ class NavSim(object):
     def rollout_host(self):
         """The current set of rollout()'s outputs as NumPy arrays, from ONE device -> host copy."""
         return self._product("rollout").host(self.cur)
+
+    # ---- MPPI local planner: sampled plans, the rollout's launch and the weighted update on the device, 3 launches an iteration
+    # (include/navsim.h navsim_mppi).  Independent of enable_rollout: its K and H are its own
+    def enable_mppi(self, params=None, robot_type="keti"):
+        """Allocates the workspace ONCE -- plan [E,H,2], plan_key [E,2] (-1: no plan yet), actions [E,K,H,2], cost [E,K] and
+        navsim_rollout's ten arrays: it persists from call to call -- and two sets of outputs (abi.MPPI_OUT: they flip with
+        self.cur like everything a step returns).  params: an abi.NavsimMppiParams, a dict of overrides of mppi_defaults(cfg,
+        robot_type), or None.  The lower bound on the rollout's cap is checked here as enable_rollout checks it."""
+        import torch
+        cfg, E = self.cfg, self.cfg.n_envs
+        dmax = float(self.t["scan_discomfort"].max().item())
+        p = params if isinstance(params, abi.NavsimMppiParams) else mppi_params(cfg, params, robot_type, dmax)
+        if not lookahead_range_min(dmax) <= p.range <= cfg.range_max:
+            raise ValueError("the planner's range must lie in [%g, %g] (0.1 m above the largest discomfort threshold .. range_max), "
+                             "not %g" % (lookahead_range_min(dmax), cfg.range_max, p.range))
+        if not 0.0 <= p.gamma <= 1.0:
+            raise ValueError("the planner's gamma must lie in [0, 1], not %g" % p.gamma)
+        sym = {"K": p.n_samples, "H": p.horizon}
+        ws = {k: torch.zeros((E,) + tuple(sym.get(s, s) for s in shape), dtype=_dtype(d), device=self.device)
+              for k, (d, shape) in abi.MPPI_WS.items()}
+        ws["plan_key"][:, 0] = -1
+        roll_blob = torch.zeros(blob_layout(abi.ROLLOUT_OUT, E, sym)[-1][3], dtype=torch.uint8, device=self.device)
+        roll = {k: roll_blob[lo:hi].view(_dtype(d)).view(shape) for k, d, lo, hi, shape in blob_layout(abi.ROLLOUT_OUT, E, sym)[:-1]}
+        struct = abi.NavsimMppiWs(roll=abi.NavsimRolloutOut(**{k: v.data_ptr() for k, v in roll.items()}),
+                                  **{k: v.data_ptr() for k, v in ws.items()})
+        extra = dict(ws, roll=roll, roll_blob=roll_blob,
+                     ped_cmd=torch.zeros((E, max(cfg.max_peds, 1), 2), dtype=torch.float64, device=self.device))
+        self.products["mppi"] = _StepProduct(self, p, blob_layout(abi.MPPI_OUT, E), abi.NavsimMppiOut, extra=extra, extra_struct=struct)
+
+    def mppi(self, field=None, ped_cmd=None, skip=None):
+        """navsim_mppi of the current state on the current stream: 3 launches per iteration, no device -> host copy, no
+        allocation; the state is only read.  field: True = the terminal cost reads the goal field of enable_goal_path() -- call
+        goal_path() for this state first, the field's keys are not looked at here --, None / False = the straight-line distance;
+        ped_cmd: [E,N,2] commands held for the whole horizon under PED_EXTERNAL (None: the state's own); skip: uint8 / bool [E],
+        arenas that are not read, whose plan stays and whose rows come back all 0.  Returns the current set {'action', 'best',
+        'cost_best', 'ess', 'status'}, intact through the next step."""
+        import torch
+        p, cur = self.products.get("mppi") or self._product("mppi"), self.cur
+        gf = gp = None
+        if field:
+            g = self.products.get("goal_path") or self._product("goal_path")
+            gf, gp = g.extra_ref, g.par
+        if ped_cmd is not None:
+            cmd = p.extra["ped_cmd"]
+            cmd.copy_(torch.as_tensor(ped_cmd).to(device=cmd.device, dtype=cmd.dtype).reshape(cmd.shape), non_blocking=True)
+            ped_cmd = cmd
+        rc = self.lib.navsim_mppi(p.cfg, p.st, p.par, gf, gp, _ptr(ped_cmd), _ptr(skip), p.extra_ref, p.out[cur], _stream())
+        if rc:
+            check(rc, "navsim_mppi")
+        return p.buf[cur]
+
+    def mppi_host(self):
+        """The current set of mppi()'s outputs as NumPy arrays, from ONE device -> host copy."""
+        return self._product("mppi").host(self.cur)
+
+    def mppi_plan(self):
+        """The plans on the device: float64 [E,H,2], as the latest mppi() left them."""
+        return self._product("mppi").extra["plan"]
 
     def occupancy(self, e=0):
         """uint8 [H, W] occupancy grid (1 = occupied) of arena e, read back from its distance field
