@@ -134,3 +134,17 @@ for _ in range(100):
     reached |= info["is_success"] > 0
 print("MPPI, 64 arenas x 100 steps: %d reached a goal, %d crashes in the last step, mean effective sample size %.1f"
       % (int(reached.sum()), int((info["is_crash"] > 0).sum()), float(info["planner"]["ess"].mean())))
+
+# ---- pedestrian forecast: where the crowd will be over the next H steps ---------------------------------------------------------------
+# ped_forecast=H puts every pedestrian's next H poses into info['ped_forecast'], time-major [E,H,N,...], from one launch behind the
+# step: the step's own pedestrian model (model='true', bit-equal to the next steps up to 'exact_steps') or the constant-velocity
+# baseline (model='const_vel'); 'rel' is the position in the robot's current frame, 'min_dist' the predicted closest approach.
+fenv = nav_gym_env.make("NavGym-v0", num_envs=64, map_size=400, num_humans=8, ped_forecast=8, observe_humans=4)
+fenv.reset()
+for _ in range(20):
+    obs, reward, done, info = fenv.step(actions[:64].contiguous())
+f = info["ped_forecast"]                                                               # = fenv.ped_forecast()
+near = f["min_dist"].min(dim=1).values                                                 # +inf in an arena without pedestrians
+print("forecast, 64 arenas: closest predicted approach within 1.6 s %.2f m; futures of the observed pedestrians %s; a query with "
+      "the robot standing still: %s" % (float(near.min()), tuple(f["humans_rel"].shape),
+                                        tuple(fenv.ped_forecast(actions=torch.zeros(8, 2, dtype=torch.float64))["pose"].shape)))

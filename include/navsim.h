@@ -1657,6 +1657,110 @@ int navsim_mppi(const navsim_config* cfg, const navsim_state* st, const navsim_m
                 const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */, const uint8_t* skip /* [E] or NULL */,
                 const navsim_mppi_ws* ws, const navsim_mppi_out* out, void* stream);
 
+/* ---- pedestrian forecast: where the pedestrians of an arena will be after each of the next H navsim_step calls, one launch ------
+ * What a prediction-aware crowd-navigation policy observes (the pedestrians' future trajectories: pred_method 'truth' or
+ * 'const_vel' of the CrowdNav++ / intention-aware family), what a trajectory predictor is trained on and compared with (the
+ * simulator's own futures; the constant-velocity baseline), and what a risk signal reads (each pedestrian's predicted closest
+ * approach).  Without this entry a future costs a copy of the whole state, H steps of every arena and a restore; navsim_rollout
+ * carries exactly these pedestrians forward, one copy per sequence, and throws them away -- beside a scan per step that a
+ * forecast does not need.  BUILD-DEFINED as an entry; every value under NAVSIM_FORECAST_TRUE is the step's own arithmetic. */
+#define NAVSIM_FORECAST_MAX_H 32          /* = NAVSIM_ROLLOUT_MAX_H: a plan of navsim_mppi fits */
+#define NAVSIM_FORECAST_HOLD      0       /* robot: the state's prev_action, repeated */
+#define NAVSIM_FORECAST_STOP      1       /* robot: the zero twist */
+#define NAVSIM_FORECAST_ACTIONS   2       /* robot: `actions` [E,H,2] in cfg.action_kind's form */
+#define NAVSIM_FORECAST_TRUE      0       /* model: the configured pedestrian model (social force, or external commands held) */
+#define NAVSIM_FORECAST_CONST_VEL 1       /* model: every pedestrian keeps its velocity */
+typedef struct navsim_ped_forecast_params {
+    int32_t horizon;     /* H, 1 .. NAVSIM_FORECAST_MAX_H */
+    int32_t robot;       /* NAVSIM_FORECAST_HOLD / STOP / ACTIONS: what the robot is assumed to do over the horizon */
+    int32_t model;       /* NAVSIM_FORECAST_TRUE / CONST_VEL */
+    int32_t pad_;
+} navsim_ped_forecast_params;
+
+typedef struct navsim_ped_forecast_out {    /* time-major: at step h the N slots of an arena are N adjacent rows */
+    double*  pose;         /* [E,H,N,3] pedestrian i after forecast step h */
+    double*  vel;          /* [E,H,N,2] its velocity */
+    float*   rel;          /* [E,H,N,2] its position in the robot's CURRENT frame (the pose at time t): rule 6 */
+    double*  robot_pose;   /* [E,H,3]   the robot pose assumed after step h */
+    double*  min_dist;     /* [E,N]     least centre distance between robot_pose[h] and pose[h,i] over the horizon; +inf for an unused slot */
+    int32_t* min_step;     /* [E,N]     the first h that attains min_dist; -1 for an unused slot */
+    int32_t* exact_steps;  /* [E]       see rule 5 */
+    uint8_t* status;       /* [E]       0 skipped, 1 forecast */
+} navsim_ped_forecast_out;
+
+/* ONE launch (a wavefront per arena, a lane per pedestrian, the horizon loop inside; kernels_ped_forecast.hpp), no device-to-host
+ * copy, nothing that blocks, no allocation, and it WRITES NOTHING BUT `out`: the state is read-only.  Call it wherever navsim_step
+ * could be called on the same stream.  actions [E,H,2] is in cfg.action_kind's form (read under NAVSIM_FORECAST_ACTIONS only).
+ * ped_cmd [E,N,2] stands for st->ped_cmd under NAVSIM_PED_EXTERNAL with NAVSIM_FORECAST_TRUE (NULL: st->ped_cmd itself; ignored
+ * otherwise).  Float64, every operation rounded on its own, no fused multiply-add; N = cfg.max_peds, H = p->horizon,
+ * n = min(n_peds[e], N), dt = cfg.time_step.  Per arena e:
+ *  1. skip && skip[e]: status[e] = 0 and EVERY other element of the arena's rows is 0 (min_dist and min_step too).  Nothing of
+ *     the arena is read.  Else status 1.
+ *  2. The robot, for h = 0 .. H-1, from p = robot_pose[e] and prev_v = prev_action[e][0]: the action (a0, a1) of step h is
+ *     prev_action[e] (HOLD), (0, 0) (STOP) or actions[e,h] (ACTIONS).  It goes through the step's phase 0, operation for
+ *     operation as navsim_rollout's rule 3 (navsim_lookahead's rule 3): under ACTIONS with NAVSIM_ACTION_WHEELS
+ *     (wheel_radius (l + r) / 2, wheel_radius (r - l) / wheel_track) -- HOLD and STOP are twists already and skip only this
+ *     conversion --; cfg.clamp_action; cfg.min_turning_radius (env.py:595-600); KetiRobot.set_vel with cfg.axle_offset from p
+ *     (env.py:664).  The result is robot_pose[e,h] and the next p; prev_v = a0 as the step would store it (after clamp and
+ *     turning radius).  The robot's crash, its crash revert, the episode's end and a restart are NOT modelled.
+ *     Clamp and turning radius are idempotent on a prev_action the step stored, so HOLD equals ACTIONS with that twist under
+ *     NAVSIM_ACTION_TWIST: a clamped value lies inside its interval and stays; with lim = |a1| min_turning_radius computed from
+ *     the same a1, the stored a0 satisfies a0 >= lim (a0 >= 0) or a0 <= -lim (a0 < 0), so the rule selects a0 again or a lim
+ *     equal to it; and where the radius rule pushed a0 out of [linvel_lo, linvel_hi], a0 IS lim: the clamp pulls it in and the
+ *     radius rule returns the same lim.
+ *  3. NAVSIM_FORECAST_TRUE, step h, for the n pedestrians, over the step's own functions (kernels_step.hpp):
+ *       1. pop waypoints from the carried head (ped_pop_waypoints; NAVSIM_PED_SFM);
+ *       2. stage the agents of time t + h: the carried pedestrians, and the robot at its carried pose p with speed prev_v along
+ *          its heading -- (p.x, p.y, prev_v cos p.th, prev_v sin p.th), exactly as ped_stage_wave does;
+ *       3. compute the pair terms (ped_pair_term);
+ *       4. ped_sfm_step towards the waypoint at the head, or under NAVSIM_PED_EXTERNAL nv::set_vel on the pedestrian's command
+ *          of the call, held for the whole horizon (navsim_rollout's rule 6);
+ *       5. the robot moves by rule 2 on this step's action.
+ *     Carried per pedestrian: pose, velocity, waypoint head; for the robot: pose and prev_action as the step would store it.
+ *     pose[e,h,i] / vel[e,h,i] are the pedestrian's after step 4.  Leg odometry, ped_prev_yaw and the scan are not needed and
+ *     not computed; nothing is drawn and nothing is planned.
+ *  4. NAVSIM_FORECAST_CONST_VEL: with (x, y, yaw) = ped_pose[e,i] and (vx, vy) = ped_vel[e,i],
+ *     pose[e,h,i] = (x + vx * ((double)(h + 1) * dt), y + vy * ((double)(h + 1) * dt), yaw), vel[e,h,i] = (vx, vy).  It reads
+ *     only ped_pose / ped_vel and is valid with every pedestrian model.  The robot still moves by rule 2, and rules 6 and 7
+ *     use that pose.  exact_steps = 0.
+ *  5. Exactness (navsim_rollout's rule 8).  exact_steps[e] is the number of leading steps that are the step's own.  The step
+ *     raises ped_due for pedestrian i (ped_finish) iff, with (x, y) its pose AFTER this step's move and (wx, wy) =
+ *     ped_waypoints[e,i,ped_n_waypoints[e,i] - 1], sqrt((x - wx)^2 + (y - wy)^2) < 0.5 in float64, every operation rounded on
+ *     its own: the real step then gives the pedestrian a new goal and a new route (env.py:666-680).  Under NAVSIM_PED_SFM
+ *     exact_steps = H unless the predicate holds for some pedestrian at a step h; then exact_steps = h + 1 for the first such
+ *     h -- the new route takes effect from the next step on -- and the forecast GOES ON without the re-plan: that pedestrian
+ *     keeps heading for its last waypoint, and all H rows are filled.  Always H under NAVSIM_PED_EXTERNAL.
+ *  6. rel[e,h,i], navsim_ped_observe's frame convention (its rule 3) with the robot pose of time t, (rx, ry, th) =
+ *     robot_pose[e] of the state: c = nv::cos(th), s = nv::sin(th); ax = pose[e,h,i].x - rx, ay = pose[e,h,i].y - ry;
+ *     rel = ((float)(c*ax + s*ay), (float)(c*ay - s*ax)): float64 in this order, rounded once.
+ *  7. d_h = sqrt(dx*dx + dy*dy) with dx = pose[e,h,i].x - robot_pose[e,h].x, dy likewise.  min_dist[e,i] = the least d_h,
+ *     min_step[e,i] = the first h that attains it (d_h < the minimum so far, starting from +inf).
+ *  8. Slots i >= n: every row 0, min_dist = +inf, min_step = -1.
+ * PROPERTY: under NAVSIM_FORECAST_TRUE with NAVSIM_FORECAST_ACTIONS, for every h below both exact_steps[e] and the first step
+ * at which the arena's episode ends, pose[e,h,:n], vel[e,h,:n] and robot_pose[e,h] equal bit for bit st->ped_pose, st->ped_vel
+ * and st->robot_pose after h + 1 consecutive navsim_step calls with io.action[e] = actions[e,h] from the same state, the
+ * re-plan launches running between them as the caller's step path runs them.  Scan noise plays no part.  The rows of a
+ * horizon H are the leading rows of every longer horizon.
+ * NAVSIM_E_ARG, before anything touches the device: cfg, st, p or out NULL; any of out's eight arrays NULL; horizon outside
+ * 1 .. NAVSIM_FORECAST_MAX_H; a robot that is none of HOLD / STOP / ACTIONS, a model that is none of TRUE / CONST_VEL;
+ * NAVSIM_FORECAST_ACTIONS without actions; cfg.ped_model == NAVSIM_PED_NONE or none of NAVSIM_PED_*; max_peds outside
+ * 1 .. NAVSIM_MAX_PEDS; st->robot_pose, prev_action, n_peds, ped_pose or ped_vel NULL; under NAVSIM_FORECAST_TRUE with
+ * NAVSIM_PED_SFM st->field, ped_v_pref, ped_waypoints, ped_n_waypoints or ped_wp_head NULL or max_waypoints outside
+ * 1 .. NAVSIM_MAX_WAYPOINTS, with NAVSIM_PED_EXTERNAL both ped_cmd and st->ped_cmd NULL; n_envs < 0; map_h or map_w < 1;
+ * resolution or time_step not positive and finite; an action_kind that is none of NAVSIM_ACTION_*, NAVSIM_ACTION_WHEELS with a
+ * wheel_radius that is not positive; st->map_slot with cfg.shared_field.  NAVSIM_E_UNSUPPORTED: a field_format that is neither
+ * NAVSIM_FIELD_F32 nor NAVSIM_FIELD_U16T; st->rect_table with a float32 field or a map above 1024 cells a side (the field-format
+ * cases navsim_rollout refuses).  n_envs == 0: NAVSIM_OK, nothing is launched.
+ * Cost, measured on an MI355X (profiles/r25_ped_forecast/summary.txt; 4096 arenas x 20 pedestrians, kernel times from a kernel
+ * trace, the step kernel at 145.4 us in the same trace): linear in H -- 25.4 - 26.6 us a forecast step under NAVSIM_FORECAST_TRUE
+ * (H = 8 / 16 / 32: 213 / 419 / 814 us), 2.4 - 3.0 us under NAVSIM_FORECAST_CONST_VEL (23.8 / 41.0 / 75.7 us).
+ * Out of scope: pedestrians driven by navsim_ped_orca or navsim_ped_policy under NAVSIM_FORECAST_TRUE (their commands come
+ * from launches of their own: the caller passes the commands it wants held, or asks for NAVSIM_FORECAST_CONST_VEL); re-plans
+ * inside the horizon (rule 5); the robot's crash and anything behind an episode's end (rule 2). */
+int navsim_ped_forecast(const navsim_config* cfg, const navsim_state* st, const navsim_ped_forecast_params* p,
+                        const double* actions /* [E,H,2] or NULL */, const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */,
+                        const uint8_t* skip /* [E] or NULL */, const navsim_ped_forecast_out* out, void* stream);
+
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);
 

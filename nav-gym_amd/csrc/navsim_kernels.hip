@@ -28,6 +28,7 @@
 //   kernels_lookahead.hpp    action lookahead: the step's outcomes for K candidate actions per arena (navsim_lookahead)
 //   kernels_rollout.hpp      action-sequence rollout: the next H steps' outcomes for K action sequences per arena (navsim_rollout)
 //   kernels_mppi.hpp         MPPI local planner: sampled plans, the rollout's launch, the weighted update (navsim_mppi)
+//   kernels_ped_forecast.hpp pedestrian forecast: the pedestrians' next H poses per arena, one launch (navsim_ped_forecast)
 //   step_plan.hpp        launch geometry of the fused step, the descriptors of a launch and the march-rule dispatch (shared by this
 //                        file and navsim_step_inst.hip; included behind the namespace, its two descriptors are global types)
 // Host code of this file, ahead of the C ABI: dispatch_step and the argument checks; the workspaces (Carver and one layout
@@ -59,6 +60,7 @@ namespace {
 #include "kernels_lookahead.hpp"
 #include "kernels_rollout.hpp"
 #include "kernels_mppi.hpp"
+#include "kernels_ped_forecast.hpp"
 
 }  // namespace
 #include "step_plan.hpp"
@@ -557,6 +559,16 @@ int launch_rollout(const navsim_config* c, const navsim_state* st, const Rollout
         kernel<<<(unsigned)((size_t)c->n_envs * a.K), kRolloutBlock, lds, s>>>(*c, *st, a);
         return launch_status();
     });
+}
+
+// navsim_ped_forecast: a workgroup per arena; one kernel per field type -- three forms (nothing is marched)
+template <typename F>
+int launch_ped_forecast(const navsim_config* c, const navsim_state* st, const PedForecastArgs& a, hipStream_t s) {
+    const size_t lds = ped_forecast_lds_bytes(c, a.model);
+    auto kernel = ped_forecast_kernel<F>;
+    if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return NAVSIM_E_UNSUPPORTED;
+    kernel<<<c->n_envs, kForecastBlock, lds, s>>>(*c, *st, a);
+    return launch_status();
 }
 
 }  // namespace
@@ -1766,6 +1778,41 @@ int navsim_rollout(const navsim_config* c, const navsim_state* st, const navsim_
     if (rc != NAVSIM_OK) return rc;
     if (c->n_envs == 0) return NAVSIM_OK;
     return rollout_launch(c, st, p, actions, ped_cmd, skip, out, (hipStream_t)stream);
+}
+
+int navsim_ped_forecast(const navsim_config* c, const navsim_state* st, const navsim_ped_forecast_params* p, const double* actions,
+                        const double* ped_cmd, const uint8_t* skip, const navsim_ped_forecast_out* out, void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !p || !out) return NAVSIM_E_ARG;
+    if (!out->pose || !out->vel || !out->rel || !out->robot_pose || !out->min_dist || !out->min_step || !out->exact_steps || !out->status)
+        return NAVSIM_E_ARG;
+    if (p->horizon < 1 || p->horizon > NAVSIM_FORECAST_MAX_H) return NAVSIM_E_ARG;
+    if (p->robot != NAVSIM_FORECAST_HOLD && p->robot != NAVSIM_FORECAST_STOP && p->robot != NAVSIM_FORECAST_ACTIONS) return NAVSIM_E_ARG;
+    if (p->model != NAVSIM_FORECAST_TRUE && p->model != NAVSIM_FORECAST_CONST_VEL) return NAVSIM_E_ARG;
+    if (p->robot == NAVSIM_FORECAST_ACTIONS && !actions) return NAVSIM_E_ARG;
+    if (c->ped_model != NAVSIM_PED_EXTERNAL && c->ped_model != NAVSIM_PED_SFM) return NAVSIM_E_ARG;      // NAVSIM_PED_NONE: nobody to forecast
+    if (c->max_peds < 1 || c->max_peds > NAVSIM_MAX_PEDS) return NAVSIM_E_ARG;
+    if (!st->robot_pose || !st->prev_action || !st->n_peds || !st->ped_pose || !st->ped_vel) return NAVSIM_E_ARG;
+    const bool truth = p->model == NAVSIM_FORECAST_TRUE;
+    if (truth && c->ped_model == NAVSIM_PED_SFM && (!st->field || !st->ped_v_pref || !st->ped_waypoints || !st->ped_n_waypoints ||
+                                                    !st->ped_wp_head || c->max_waypoints < 1 || c->max_waypoints > NAVSIM_MAX_WAYPOINTS))
+        return NAVSIM_E_ARG;
+    if (truth && c->ped_model == NAVSIM_PED_EXTERNAL && !ped_cmd && !st->ped_cmd) return NAVSIM_E_ARG;
+    if (c->n_envs < 0 || c->map_h < 1 || c->map_w < 1) return NAVSIM_E_ARG;
+    if (!(c->resolution > 0.0) || !std::isfinite(c->resolution) || !(c->time_step > 0.0) || !std::isfinite(c->time_step)) return NAVSIM_E_ARG;
+    if (c->action_kind != NAVSIM_ACTION_TWIST && c->action_kind != NAVSIM_ACTION_WHEELS) return NAVSIM_E_ARG;
+    if (c->action_kind == NAVSIM_ACTION_WHEELS && (!(c->wheel_radius > 0.0) || !std::isfinite(c->wheel_radius) || !std::isfinite(c->wheel_track)))
+        return NAVSIM_E_ARG;
+    if (st->map_slot && c->shared_field) return NAVSIM_E_ARG;
+    if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
+    if (st->rect_table && (c->field_format != NAVSIM_FIELD_U16T || c->map_h > 1024 || c->map_w > 1024)) return NAVSIM_E_UNSUPPORTED;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    PedForecastArgs a = {};
+    a.out = *out; a.actions = p->robot == NAVSIM_FORECAST_ACTIONS ? actions : nullptr;
+    a.ped_cmd = truth && c->ped_model == NAVSIM_PED_EXTERNAL ? ped_cmd : nullptr; a.skip = skip;
+    a.H = p->horizon; a.robot = p->robot; a.model = p->model;
+    hipStream_t s = (hipStream_t)stream;
+    return with_field(c, st, [&](auto field) { return launch_ped_forecast<typename decltype(field)::type>(c, st, a, s); });
 }
 
 int navsim_mppi(const navsim_config* c, const navsim_state* st, const navsim_mppi_params* p, const navsim_goal_field* field,

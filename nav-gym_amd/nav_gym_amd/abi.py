@@ -336,6 +336,26 @@ class NavsimMppiOut(C.Structure):
     _fields_ = [(name, _P) for name in MPPI_OUT]
 
 
+# navsim_ped_forecast: the rule's parameters and the eight output arrays (dtype, trailing shape behind E; H = horizon, N = max_peds;
+# exact_steps and status are [E]).  Time-major: a consumer that wants [E,N,H,.] takes a transposed view
+FORECAST_MAX_H = 32
+FORECAST_HOLD, FORECAST_STOP, FORECAST_ACTIONS = 0, 1, 2          # navsim_ped_forecast_params.robot
+FORECAST_TRUE, FORECAST_CONST_VEL = 0, 1                          # navsim_ped_forecast_params.model
+
+
+class NavsimPedForecastParams(C.Structure):
+    _fields_ = [("horizon", C.c_int32), ("robot", C.c_int32), ("model", C.c_int32), ("pad_", C.c_int32)]
+
+
+FORECAST_OUT = {"pose": ("float64", ("H", "N", 3)), "vel": ("float64", ("H", "N", 2)), "rel": ("float32", ("H", "N", 2)),
+                "robot_pose": ("float64", ("H", 3)), "min_dist": ("float64", ("N",)), "min_step": ("int32", ("N",)),
+                "exact_steps": ("int32", ()), "status": ("uint8", ())}
+
+
+class NavsimPedForecastOut(C.Structure):
+    _fields_ = [(name, _P) for name in FORECAST_OUT]
+
+
 ORCA_MAX_AGENTS = 64
 ORCA_MAX_EDGES = 128
 CROWD_MAX_VERTS = 8
@@ -560,6 +580,8 @@ def declare(lib, suffix=""):
     if not suffix and hasattr(lib, "navsim_mppi"):                      # (likewise)
         sig("navsim_mppi", [cfgp, stp, C.POINTER(NavsimMppiParams), C.POINTER(NavsimGoalField), C.POINTER(NavsimGoalPathParams),
                             _P, _P, C.POINTER(NavsimMppiWs), C.POINTER(NavsimMppiOut), _P])
+    if not suffix and hasattr(lib, "navsim_ped_forecast"):              # (likewise)
+        sig("navsim_ped_forecast", [cfgp, stp, C.POINTER(NavsimPedForecastParams), _P, _P, _P, C.POINTER(NavsimPedForecastOut), _P])
     sig("navsim_reset_obs", [cfgp, stp, iop, _P] + stream)
     sig("navsim_restart", [cfgp, stp, _P] + stream)
     return lib
@@ -579,7 +601,7 @@ EXPORTS = (
     "navsim_step", "navsim_step_sorted", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
     "navsim_episode_stats_update", "navsim_episode_stats_clear", "navsim_ped_observe",
     "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps", "navsim_dwa", "navsim_local_map",
-    "navsim_scan_labels", "navsim_lookahead", "navsim_rollout", "navsim_mppi",
+    "navsim_scan_labels", "navsim_lookahead", "navsim_rollout", "navsim_mppi", "navsim_ped_forecast",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

@@ -177,6 +177,23 @@ and default to the reference's behaviour for num_envs == 1:
                     rows are the step's own, bit for bit with scan noise off (without pedestrians: the whole horizon).
                     rollout_params: dict(horizon=8, range=, gamma=1.0); range as lookahead_params'.  Not with pedestrian_model
                     'orca' or 'policy'.  None (default): nothing is allocated or launched.
+    ped_forecast    H in 1 .. 32: info['ped_forecast'] holds where every pedestrian will be after each of the next H step() calls,
+                    time-major -- 'pose' [E,H,N,3], 'vel' [E,H,N,2], 'rel' [E,H,N,2] (the position in the robot's CURRENT frame),
+                    'robot_pose' [E,H,3] (the robot pose assumed after step h), 'min_dist' / 'min_step' [E,N] (the predicted
+                    closest approach and its step), 'exact_steps' [E], 'status' [E] -- from one launch behind the step that only
+                    reads the state (navsim_ped_forecast): the observation of a prediction-aware policy, the labels and the
+                    constant-velocity baseline of a trajectory predictor, a risk signal.  ped_forecast_params: dict(robot='hold' |
+                    'stop' | 'plan', model='true' | 'const_vel').  robot: what the robot is assumed to do -- repeat its previous
+                    action, stand still, or execute the first H actions of the MPPI planner's plan (needs local_planner='mppi' with
+                    a plan horizon >= H; the launch then runs behind the planner's).  model 'true': the pedestrians' own model with
+                    the step's arithmetic -- the rows below exact_steps equal the next steps' states bit for bit; a pedestrian that
+                    reaches its last waypoint inside the horizon is not re-planned --; 'const_vel': every pedestrian keeps its
+                    velocity (exact_steps 0).  Defaults 'hold' and 'true'; with pedestrian_model 'orca' or 'policy', whose
+                    commands come from a launch in front of the step, the default is 'const_vel' and 'true' raises ValueError.
+                    With observe_humans=K also 'humans_rel' [E,H,K,2]: `rel` of the observed pedestrians, in info['humans']'s row
+                    order.  env.ped_forecast() returns the same dict, also after reset() / reset(mask);
+                    env.ped_forecast(actions=, human_actions=) is an explicit query.  None (default): nothing is allocated or
+                    launched.
     reset(mask)    reset() of SOME arenas (the reference's reset() is per environment, env.py:730-831): a bool / 0-1 array
                     [num_envs]; the others keep their state and their rows.  On the pipelined reset path the masked arenas install
                     their staged worlds in one launch: the same state and rows as with pregen_pipeline=0.
@@ -333,7 +350,8 @@ class NavGymEnv(_EnvBase):
                  final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None,
                  episode_stats=False, observe_humans=None, observe_params=None, goal_path=False, goal_path_params=None,
                  local_planner=None, local_planner_params=None, observe_local_map=None, local_map_params=None,
-                 scan_labels=False, lookahead=None, lookahead_params=None, rollout=None, rollout_params=None):
+                 scan_labels=False, lookahead=None, lookahead_params=None, rollout=None, rollout_params=None,
+                 ped_forecast=None, ped_forecast_params=None):
         # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
         self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
         from . import lib
@@ -596,6 +614,37 @@ class NavGymEnv(_EnvBase):
         self.rollout_k = None if rollout is None else int(rollout)
         self.rollout_h = None if rollout is None else int((rollout_params or {}).get("horizon", self._ROLLOUT_HORIZON))
         self.rollout_params = None if rollout_params is None else dict(rollout_params)
+        # pedestrian forecast (navsim_ped_forecast): the pedestrians' next H poses per arena, one launch behind the step
+        _check_params("ped_forecast_params", ped_forecast_params, ped_forecast is not None, "ped_forecast=H", self._FORECAST_KEYS)
+        self.ped_forecast_h = self.ped_forecast_robot = self.ped_forecast_model = None
+        if ped_forecast is not None:
+            if not (isinstance(ped_forecast, numbers.Integral) and not isinstance(ped_forecast, bool) and
+                    1 <= ped_forecast <= abi.FORECAST_MAX_H):
+                raise ValueError("ped_forecast must be None or an int in 1 .. %d, not %r" % (abi.FORECAST_MAX_H, ped_forecast))
+            if cfg.ped_model == abi.PED_NONE:
+                raise ValueError("ped_forecast needs pedestrians: pedestrian_model=%r with at most %d of them has none"
+                                 % (pedestrian_model, nh_hi))
+            launched = pedestrian_model in ("orca", "policy")       # their commands come from a launch in front of the step
+            robot = (ped_forecast_params or {}).get("robot", "hold")
+            model = (ped_forecast_params or {}).get("model", "const_vel" if launched else "true")
+            if robot not in self._FORECAST_ROBOT:
+                raise ValueError("ped_forecast_params: robot must be one of %s, not %r" % (", ".join(map(repr, self._FORECAST_ROBOT)), robot))
+            if model not in _simmod.PED_FORECAST_MODEL:
+                raise ValueError("ped_forecast_params: model must be 'true' or 'const_vel', not %r" % (model,))
+            if model == "true" and launched:
+                raise ValueError("ped_forecast with model='true' is not available with pedestrian_model=%r: the pedestrians' commands "
+                                 "come from a launch in front of the step that has not run yet (model='const_vel' is)" % pedestrian_model)
+            if robot == "plan":
+                if local_planner != "mppi":
+                    raise ValueError("ped_forecast_params: robot='plan' needs local_planner='mppi'")
+                plan_h = _simmod.mppi_params(cfg, self._mppi_overrides(local_planner_params, linvel_range, rotvel_range, cfg),
+                                             robot_type).horizon
+                if plan_h < ped_forecast:
+                    raise ValueError("ped_forecast_params: robot='plan' needs a plan of at least ped_forecast=%d steps; the planner's "
+                                     "horizon is %d" % (ped_forecast, plan_h))
+            self.ped_forecast_h, self.ped_forecast_robot, self.ped_forecast_model = int(ped_forecast), robot, model
+        self.ped_forecast_params = None if ped_forecast_params is None else dict(ped_forecast_params)
+        self._humans_rel = None
         # the launches behind the step (and behind reset() / reset(mask) / load_state_dict), in the order they run -- the planner
         # reads the goal path's sub-goal, the local map the observer's `visible`.  _run_products() runs them; its latest result
         # and, per buffer parity, the views it handed out
@@ -606,7 +655,9 @@ class NavGymEnv(_EnvBase):
             (self.local_planner == "mppi", _Product("planner", "mppi", self._plan_mppi, tuple(abi.MPPI_OUT), None)),
             (self.observe_local_map, _Product("local_map", "local_map", self._local_map, ("map",), operator.itemgetter("map"))),
             (self.scan_labels_on, _Product("scan_labels", "scan_labels", self._scan_labels,
-                                           tuple(k for k in abi.SCAN_LABELS_OUT if k != "hits" or cfg.ped_model != abi.PED_NONE), None))) if on]
+                                           tuple(k for k in abi.SCAN_LABELS_OUT if k != "hits" or cfg.ped_model != abi.PED_NONE), None)),
+            (self.ped_forecast_h, _Product("ped_forecast", "ped_forecast", self._ped_forecast, tuple(abi.FORECAST_OUT),
+                                           self._forecast_row if self.observe_humans else None))) if on]
         self._product_out, self._product_views = {}, {}
         self.cfg = cfg
         self.sim = None
@@ -773,6 +824,12 @@ class NavGymEnv(_EnvBase):
             if self.rollout_k:
                 self.sim.enable_rollout(self.rollout_k, self.rollout_h,
                                         {k: v for k, v in (self.rollout_params or {}).items() if k != "horizon"})
+            if self.ped_forecast_h:
+                self.sim.enable_ped_forecast(self.ped_forecast_h, dict(
+                    robot="actions" if self.ped_forecast_robot == "plan" else self.ped_forecast_robot, model=self.ped_forecast_model))
+                if self.observe_humans:                   # 'humans_rel' [E,H,K,2], one buffer per set of the step's outputs
+                    self._humans_rel = [torch.zeros((self.num_envs, self.ped_forecast_h, self.observe_humans, 2), dtype=torch.float32,
+                                                    device=dev) for _ in range(2)]
         elif "policy_prev_actions" in self.sim.t:
             self.sim.t["policy_prev_actions"].zero_()           # env.py:739
         self._episode_batch += 1
@@ -1029,6 +1086,71 @@ class NavGymEnv(_EnvBase):
 
     def _scan_labels(self, skip, rebuild):
         self.sim.scan_labels(skip=skip)
+
+    # ped_forecast_params: the robot assumed over the horizon ('plan': the first H actions of the MPPI planner's plan) and the model
+    _FORECAST_KEYS = ("robot", "model")
+    _FORECAST_ROBOT = ("hold", "stop", "plan")
+
+    def _ped_forecast(self, skip, rebuild):              # (behind the planner: robot='plan' reads the plan that launch just left, on
+        sim = self.sim                                    # the device; 'external' pedestrians: the state's own commands)
+        plan = sim.mppi_plan()[:, :self.ped_forecast_h] if self.ped_forecast_robot == "plan" else None
+        out = sim.ped_forecast(actions=plan, skip=skip)
+        if self._humans_rel is not None:                  # rel gathered by the observer's index of the same buffer set; 0 where -1
+            index = sim.products["ped_observe"].buf[sim.cur]["index"]                       # [E,K] int32
+            E, K = index.shape
+            at = index.clamp(min=0).long()[:, None, :, None].expand(E, self.ped_forecast_h, K, 2)
+            rows = out["rel"].gather(2, at).masked_fill_((index < 0)[:, None, :, None], 0.0)
+            self._humans_rel[sim.cur].copy_(rows)
+
+    def _forecast_row(self, v):
+        rel = self._humans_rel[self.sim.cur]
+        v["humans_rel"] = rel[0].cpu().numpy() if self.num_envs == 1 else rel
+        return v
+
+    def ped_forecast(self, actions=None, human_actions=None):
+        """Where the pedestrians will be after each of the next H step() calls (NavGymEnv(ped_forecast=H); navsim_ped_forecast, one
+        launch that only reads the state), time-major: {'pose' [E,H,N,3] float64, 'vel' [E,H,N,2] float64, 'rel' [E,H,N,2] float32
+        (the position in the robot's CURRENT frame, observed_humans()' convention), 'robot_pose' [E,H,3] float64 (the robot pose
+        assumed after step h), 'min_dist' [E,N] float64 and 'min_step' [E,N] int32 (the closest approach over the horizon and the
+        first step that attains it; +inf / -1 for an unused slot), 'exact_steps' [E] int32 (the leading steps that are the
+        step's own: H unless a pedestrian reaches its last waypoint inside the horizon, where the real step would re-plan it; 0
+        under model='const_vel'), 'status' [E] uint8 (0 = skipped)}; with observe_humans=K also 'humans_rel' [E,H,K,2] float32,
+        `rel` of the observed pedestrians, row for row as info['humans']['index'] lists them (0 where the index is -1).
+        Without arguments: what info['ped_forecast'] of the latest step() holds; valid after reset() and reset(mask) too.
+        actions / human_actions: an explicit query of the current state into buffers of its own -- actions a float64 device
+        tensor [E,H,2] or an array-like [H,2] that every arena takes, in action_kind's form (None: the robot of
+        ped_forecast_params); human_actions [E,N,2] with pedestrian_model='external', held for the whole horizon (None: the
+        state's own).  Next-step auto-reset: an arena whose `done` is set is skipped (status 0, rows 0) until the step that
+        resets it.  num_envs > 1: torch views, intact through the next step(); num_envs == 1: NumPy rows."""
+        if actions is None and human_actions is None:
+            return self._latest("ped_forecast", self.ped_forecast_h, "ped_forecast", "ped_forecast=H")
+        if not self.ped_forecast_h:
+            raise RuntimeError("ped_forecast() needs NavGymEnv(ped_forecast=H)")
+        if self.sim is None:
+            raise RuntimeError("call reset() before ped_forecast()")
+        sim, E = self.sim, self.num_envs
+        if actions is not None:
+            actions = self._forecast_actions(actions, E, self.ped_forecast_h)
+        skip = sim.out["done"] if self.auto_reset and self.autoreset_mode == "next_step" and sim.out is not None else None
+        out = sim.ped_forecast(actions=actions, ped_cmd=human_actions if self.pedestrian_model == "external" else None, skip=skip,
+                               query=True)
+        if E == 1:
+            return {k: v[0] for k, v in sim.ped_forecast_host(query=True).items()}
+        return dict(out)
+
+    @staticmethod
+    def _forecast_actions(actions, E, H):
+        """ped_forecast()'s actions as [E,H,2]: a device tensor stays one ([H,2] expanded), an array-like becomes a float64 host
+        tensor ([H,2] broadcast over the arenas)."""
+        import torch
+        if hasattr(actions, "is_cuda"):
+            return actions.expand(E, H, 2) if tuple(actions.shape) == (H, 2) else actions
+        a = np.asarray(actions, dtype=np.float64)
+        if a.shape == (H, 2):
+            a = np.broadcast_to(a, (E, H, 2))
+        if a.shape != (E, H, 2):
+            raise ValueError("ped_forecast() takes actions of shape (%d, %d, 2) or (%d, 2), not %r" % (E, H, H, a.shape))
+        return torch.from_numpy(np.array(a, dtype=np.float64, order="C"))               # (a writable copy)
 
     def _latest(self, key, on, what, needs):
         """What info[key] of the latest step() holds; valid after reset() and reset(mask) too."""

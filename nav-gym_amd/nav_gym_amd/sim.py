@@ -437,6 +437,19 @@ def rollout_defaults(cfg, discomfort_max=0.0):
     return dict(range=lookahead_defaults(cfg, discomfort_max)["range"], gamma=1.0)
 
 
+PED_FORECAST_KEYS = ("robot", "model")
+PED_FORECAST_ROBOT = {"hold": abi.FORECAST_HOLD, "stop": abi.FORECAST_STOP, "actions": abi.FORECAST_ACTIONS}
+PED_FORECAST_MODEL = {"true": abi.FORECAST_TRUE, "const_vel": abi.FORECAST_CONST_VEL}
+
+
+def ped_forecast_defaults(cfg):
+    """The parameters of navsim_ped_forecast as a dict: robot -- what the robot is assumed to do over the horizon: 'hold' (the
+    state's prev_action, repeated), 'stop' (the zero twist) or 'actions' (the caller's [E,H,2]) -- and model: 'true' (the
+    configured pedestrian model: the social force, or external commands held) or 'const_vel'.  The horizon H is an argument of
+    NavSim.enable_ped_forecast."""
+    return dict(robot="hold", model="true")
+
+
 MPPI_KEYS = ("n_samples", "horizon", "iterations", "sigma", "lam", "beta", "w_goal", "w_crash", "off_field_cost", "stop_sample",
              "select", "range", "gamma", "init_action", "lo", "hi")
 MPPI_SELECT = {"mean": 0, "best": 1, 0: 0, 1: 1}
@@ -1978,6 +1991,73 @@ class NavSim(object):
     def mppi_plan(self):
         """The plans on the device: float64 [E,H,2], as the latest mppi() left them."""
         return self._product("mppi").extra["plan"]
+
+    # ---- pedestrian forecast: each arena's pedestrians over the next H steps, one launch that only reads the state
+    # (include/navsim.h navsim_ped_forecast)
+    def enable_ped_forecast(self, H, params=None):
+        """Allocates two sets of outputs (abi.FORECAST_OUT, time-major [E,H,N,...]: they flip with self.cur like everything a step
+        returns), an action buffer float64 [E,H,2] and a command buffer float64 [E,N,2].  params: a dict of overrides of
+        ped_forecast_defaults(cfg) -- robot, model -- or None."""
+        cfg = self.cfg
+        if cfg.ped_model == abi.PED_NONE:
+            raise ValueError("the pedestrian forecast needs a pedestrian model")
+        if not 1 <= int(H) <= abi.FORECAST_MAX_H:
+            raise ValueError("the pedestrian forecast looks 1 .. %d steps ahead, not %r" % (abi.FORECAST_MAX_H, H))
+        d = _overridden(ped_forecast_defaults(cfg), params, "pedestrian forecast", PED_FORECAST_KEYS)
+        if d["robot"] not in PED_FORECAST_ROBOT:
+            raise ValueError("the pedestrian forecast's robot is one of %s, not %r" % (", ".join(PED_FORECAST_ROBOT), d["robot"]))
+        if d["model"] not in PED_FORECAST_MODEL:
+            raise ValueError("the pedestrian forecast's model is one of %s, not %r" % (", ".join(PED_FORECAST_MODEL), d["model"]))
+        self.products["ped_forecast"] = self._ped_forecast_product(int(H), PED_FORECAST_ROBOT[d["robot"]], PED_FORECAST_MODEL[d["model"]])
+
+    def _ped_forecast_product(self, H, robot, model):
+        import torch
+        cfg = self.cfg
+        p = abi.NavsimPedForecastParams(horizon=H, robot=robot, model=model)
+        extra = dict(actions=torch.zeros((cfg.n_envs, H, 2), dtype=torch.float64, device=self.device),
+                     ped_cmd=torch.zeros((cfg.n_envs, max(cfg.max_peds, 1), 2), dtype=torch.float64, device=self.device))
+        return _StepProduct(self, p, blob_layout(abi.FORECAST_OUT, cfg.n_envs, {"H": H, "N": cfg.max_peds}),
+                            abi.NavsimPedForecastOut, extra=extra)
+
+    def ped_forecast(self, actions=None, ped_cmd=None, skip=None, query=False):
+        """navsim_ped_forecast of the current state on the current stream: one launch, no device -> host copy, and the state is
+        only read.  actions: [E,H,2] in cfg.action_kind's form -- required when the forecast was enabled with robot='actions'
+        (copied into the product's buffer unless it already is a contiguous float64 tensor on the device); ped_cmd: [E,N,2]
+        commands held for the whole horizon under PED_EXTERNAL with model='true' (None: the state's own); skip: uint8 / bool
+        [E], arenas that are not read and come back all 0 with status 0.  query=True: the call takes `actions` whatever robot
+        the forecast was enabled with (None: that robot) and writes into a buffer set of its own -- made at the first such call
+        -- so that what the call behind the step returned stays intact.  Returns the current set (abi.FORECAST_OUT's keys),
+        intact through the next step."""
+        import torch
+        p, cur = self.products.get("ped_forecast") or self._product("ped_forecast"), self.cur
+        if query:
+            robot = p.params.robot if actions is None else abi.FORECAST_ACTIONS
+            q = self.products.get("ped_forecast_query")
+            if q is None or q.params.robot != robot:
+                q = self.products["ped_forecast_query"] = self._ped_forecast_product(p.params.horizon, robot, p.params.model)
+            p = q
+        if p.params.robot == abi.FORECAST_ACTIONS:
+            if actions is None:
+                raise ValueError("a pedestrian forecast with robot='actions' needs actions")
+            buf = p.extra["actions"]
+            if not (torch.is_tensor(actions) and actions.device == buf.device and actions.dtype == buf.dtype and actions.is_contiguous()
+                    and actions.shape == buf.shape):
+                buf.copy_(torch.as_tensor(actions).to(device=buf.device, dtype=buf.dtype).reshape(buf.shape), non_blocking=True)
+                actions = buf
+        else:
+            actions = None
+        if ped_cmd is not None:
+            cmd = p.extra["ped_cmd"]
+            cmd.copy_(torch.as_tensor(ped_cmd).to(device=cmd.device, dtype=cmd.dtype).reshape(cmd.shape), non_blocking=True)
+            ped_cmd = cmd
+        rc = self.lib.navsim_ped_forecast(p.cfg, p.st, p.par, _ptr(actions), _ptr(ped_cmd), _ptr(skip), p.out[cur], _stream())
+        if rc:
+            check(rc, "navsim_ped_forecast")
+        return p.buf[cur]
+
+    def ped_forecast_host(self, query=False):
+        """The current set of ped_forecast()'s outputs as NumPy arrays, from ONE device -> host copy."""
+        return self._product("ped_forecast_query" if query else "ped_forecast").host(self.cur)
 
     def occupancy(self, e=0):
         """uint8 [H, W] occupancy grid (1 = occupied) of arena e, read back from its distance field
