@@ -110,6 +110,17 @@ for _ in range(50):
     obs, reward, done, info = senv.step(cand[torch.arange(64, device="cuda:0"), safe].contiguous())
 print("shielded, 64 arenas x 50 steps: %d crashes in the last step" % int((info["is_crash"] > 0).sum()))
 
+# ---- a one-step TD target over K actions: r + gamma * max_a' V(obs') with obs' from the exact model -------------------------------
+# lookahead_obs=K returns the WHOLE return of step() per candidate -- the observation too, with the scan noise the step will draw.
+qenv = nav_gym_env.make("NavGym-v0", num_envs=64, map_size=400, lookahead_obs=4)
+qenv.reset()
+value = lambda rows: -rows[..., -7:-5].sub(rows[..., -5:-3]).norm(dim=-1)                # a stand-in for a learned V(obs): minus the last move
+cand = actions[:256].reshape(64, 4, 2).contiguous()
+nxt = qenv.lookahead_obs(cand)                                                           # 'observation' {'observation' [E,K,D], ...}, 'reward', 'done', ...
+target = nxt["reward"] + 0.99 * value(nxt["observation"]["observation"]).double() * (~nxt["done"])
+obs, reward, done, info = qenv.step(cand[torch.arange(64, device="cuda:0"), target.argmax(dim=1)].contiguous())
+print("TD targets, 64 arenas x 4 actions: best target of arena 0 %.3f, the step's reward for it %.3f" % (float(target[0].max()), float(reward[0])))
+
 # ---- random shooting: roll K action sequences H steps ahead, execute the first action of the best one --------------------------------
 # rollout=K evaluates K sequences per arena over the next H steps in one launch that only reads the state: what step() would return.
 renv = nav_gym_env.make("NavGym-v0", num_envs=64, map_size=400, rollout=8, rollout_params=dict(horizon=6))

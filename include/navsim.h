@@ -1475,6 +1475,85 @@ int navsim_lookahead(const navsim_config* cfg, const navsim_state* st, const nav
                      const double* actions /* [E,K,2] */, const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */,
                      const uint8_t* skip /* [E] or NULL */, const navsim_lookahead_out* out, void* stream);
 
+/* ---- lookahead observations: the whole return of navsim_step for each of K candidate actions of an arena, from one launch ---------
+ * navsim_lookahead answers "what would the step return" for the scalars.  A one-step target r + gamma V(obs'), a full-action
+ * backup, a learned value at the leaves of a search or a safety critic on the successor also need obs', the observation, and
+ * with scan noise on they need the outcome the step will really compute: its crash and discomfort tests run on the NOISY
+ * ranges.  The noise is counter-based -- its key is (seed, global arena, episode, step count, beam) -- so a launch that only
+ * reads the state can reproduce the very draw the step is going to make.  Without this entry the answer costs a copy of the
+ * whole state, a step and a restore per candidate.
+ * BUILD-DEFINED as an entry; every value is the step's own arithmetic (env.py:591-728 as DESIGN.md section 6 restates it). */
+#define NAVSIM_LOOKOBS_NOISE_OFF  0   /* no noise: the nine shared outputs are navsim_lookahead's at R = range_max */
+#define NAVSIM_LOOKOBS_NOISE_STEP 1   /* the draw navsim_step itself would make (nothing is added unless cfg.add_scan_noise) */
+typedef struct navsim_lookahead_obs_params {
+    int32_t n_actions;   /* K, 1 .. NAVSIM_LOOKAHEAD_MAX */
+    int32_t noise;       /* NAVSIM_LOOKOBS_NOISE_* */
+} navsim_lookahead_obs_params;
+
+typedef struct navsim_lookahead_obs_out {
+    double*  reward;      /* [E,K] */
+    uint8_t* done;        /* [E,K] success | crash | time limit */
+    float*   is_success;  /* [E,K] */
+    float*   is_crash;    /* [E,K] */
+    uint8_t* discomfort;  /* [E,K] */
+    double*  distance;    /* [E,K] */
+    float*   margin;      /* [E,K] */
+    double*  pose;        /* [E,K,3] pose the step would scan from (before any crash revert) */
+    uint8_t* status;      /* [E] 0 skipped, 1 evaluated */
+    float*   scan;        /* [E,K,B] the newest slot of the row: the candidate's scan, or the re-scan after its crash */
+    float*   tail;        /* [E,K,7] the row's tail */
+    float*   goals;       /* [E,K,4] achieved_goal (2), desired_goal (2) */
+    uint8_t* truncated;   /* [E,K] what io.truncated would hold */
+    float*   obs;         /* [E,K,S*B+7] the full row, or NULL: not written */
+} navsim_lookahead_obs_out;
+
+/* ONE launch (a workgroup per arena; kernels_lookahead_obs.hpp), no device-to-host copy, nothing that blocks, no allocation, and
+ * it WRITES NOTHING BUT `out`: the state is read-only.  actions, ped_cmd and skip as navsim_lookahead's.  obs_prev [E,S*B+7] is the
+ * observation the previous step or reset returned (what io.obs_prev of the step would be).  B = cfg.n_beams, S = cfg.n_scan_stack,
+ * D = S*B + 7, K = p->n_actions.  Per arena e, what navsim_step under NAVSIM_AUTORESET_NONE would return for each candidate:
+ *  1. skip && skip[e]: status[e] = 0 and every other element of the arena's rows 0 (obs included).  Nothing of the arena is
+ *     read.  Else status 1.
+ *  2. The pedestrians at t + 1: navsim_lookahead's rule 2, once per arena, shared by all candidates and by rule 6's re-scan.
+ *  3. Candidate k's pose[e,k], lidar pose and origin cell: navsim_lookahead's rule 3 (the step's phase 0).
+ *  4. Scan A of candidate k: navsim_lookahead's rule 4 at R = range_max -- the march limit, the cull and the clip to
+ *     [0, range_max] are the step's own.  Then the noise (env.py:437-440): with p->noise == NAVSIM_LOOKOBS_NOISE_STEP,
+ *     cfg.add_scan_noise and std = scan_noise_std[e] > 0, a beam b whose clipped range is not range_max becomes
+ *     r + std * gauss_noise(noise_stream(seed, env_index_base + e, step_key), b) in float32 (product, then sum), step_key =
+ *     episode[e] * 2^32 + (steps[e] + 1) * 2: the key and the draw of the step that would run now.  The noisy value is not
+ *     clipped again.  With NAVSIM_LOOKOBS_NOISE_OFF nothing is added.
+ *  5. Outcomes of candidate k on those ranges r_k, as the step's phases 3 and 4: is_crash = any r_k < scan_threshold;
+ *     discomfort = any r_k < scan_discomfort, and not crash; rmin = the minimum of nv::discomfort_ratio over all beams when
+ *     discomfort; (reward, success, crash, distance) = the reference's reward of (prev_pose[e], pose[e,k], vel =
+ *     prev_action[e], robot_goal[e], crash, discomfort, rmin); with cfg.max_episode_steps = T > 0, truncated = not (success or
+ *     crash) and steps[e] + 1 >= T, else 0; done = success or crash or truncated; margin = min over beams of r_k -
+ *     scan_threshold in float32 (navsim_lookahead's rule 6 on these ranges: is_crash holds iff margin < 0).
+ *  6. Crash revert (env.py:707-723): a candidate with is_crash takes the re-scan as its scan -- from prev_pose[e] (its float32
+ *     cast the lidar pose), the pedestrians of rule 2, clipped as rule 4 and with rule 4's noise under the key step_key + 1.  The
+ *     re-scan does not depend on the candidate: it is computed at most once per arena, only if some candidate crashed, and
+ *     copied to every crashing candidate.  Its flags are dropped, as the step drops them.  The row pose of such a candidate is
+ *     (prev_pose[e][0], prev_pose[e][1], prev_pose[e][2]); of every other candidate pose[e,k].
+ *  7. tail[e,k] = float32 of (prev_pose[e][0], prev_pose[e][1], row pose x, row pose y, prev_action[e][0], prev_action[e][1],
+ *     wrap_pi(row pose yaw)); goals[e,k] = float32 of (row pose x, row pose y, robot_goal[e][0], robot_goal[e][1]): the step's
+ *     phase 6 for a row that is not the first of an episode.
+ *  8. obs[e,k] (only if out->obs): slot S - 1 (elements (S-1) B .. S B - 1) is scan[e,k]; slot j < S - 1 is slot j + 1 of
+ *     obs_prev[e] where S - 1 - j <= n_hist[e], else scan[e,k] (env.py:257-279, the step's stack fill and shift); the last 7
+ *     elements are tail[e,k].
+ *  9. PROPERTY with NAVSIM_LOOKOBS_NOISE_STEP, noise on or off: obs / goals, reward, done, truncated, is_success, is_crash and
+ *     distance of candidate k equal, bit for bit, what navsim_step under NAVSIM_AUTORESET_NONE with io.action[e] = actions[e,k]
+ *     and io.obs_prev = obs_prev writes for arena e from the same state.  Under NAVSIM_AUTORESET_SAME_STEP a candidate with done
+ *     set equals io.final_obs / io.final_goals, every other candidate io.obs and the goals.  The first observation of a
+ *     restarted episode is not modelled.  With NAVSIM_LOOKOBS_NOISE_OFF the nine shared outputs equal navsim_lookahead's at
+ *     R = range_max.
+ * NAVSIM_E_ARG, before anything touches the device: everything navsim_lookahead refuses with NAVSIM_E_ARG (there is no R); a
+ * noise that is neither constant; out->scan, tail, goals or truncated NULL; n_scan_stack < 1; out->obs with n_scan_stack > 1 and
+ * obs_prev or st->n_hist NULL; with NAVSIM_LOOKOBS_NOISE_STEP and cfg.add_scan_noise, st->scan_noise_std or st->episode NULL.
+ * NAVSIM_E_UNSUPPORTED: as navsim_lookahead (the LDS is the same: 12 bytes per beam, 56 per candidate, the pedestrians' share).
+ * n_envs == 0: NAVSIM_OK, nothing is launched. */
+int navsim_lookahead_obs(const navsim_config* cfg, const navsim_state* st, const navsim_lookahead_obs_params* p,
+                         const double* actions /* [E,K,2] */, const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */,
+                         const float* obs_prev /* [E,S*B+7] or NULL */, const uint8_t* skip /* [E] or NULL */,
+                         const navsim_lookahead_obs_out* out, void* stream);
+
 /* ---- action-sequence rollout: what the next H navsim_step calls would return for each of K action sequences of an arena ---------
  * The question behind a sampling-based model-predictive controller (random shooting, MPPI, CEM), an n-step return target or a
  * multi-step shield: if this arena executed the actions a_0 .. a_{H-1}, what would the next H steps return?  Without this entry

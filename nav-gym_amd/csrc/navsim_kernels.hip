@@ -26,6 +26,7 @@
 //   kernels_local_map.hpp  egocentric local map: wall and pedestrian grids per arena in the robot's frame (navsim_local_map)
 //   kernels_scan_labels.hpp  scan ground truth: the robot's clean scan and per-beam hit labels (navsim_scan_labels)
 //   kernels_lookahead.hpp    action lookahead: the step's outcomes for K candidate actions per arena (navsim_lookahead)
+//   kernels_lookahead_obs.hpp  lookahead observations: the step's whole return for K candidate actions per arena (navsim_lookahead_obs)
 //   kernels_rollout.hpp      action-sequence rollout: the next H steps' outcomes for K action sequences per arena (navsim_rollout)
 //   kernels_mppi.hpp         MPPI local planner: sampled plans, the rollout's launch, the weighted update (navsim_mppi)
 //   kernels_ped_forecast.hpp pedestrian forecast: the pedestrians' next H poses per arena, one launch (navsim_ped_forecast)
@@ -58,6 +59,7 @@ namespace {
 #include "kernels_local_map.hpp"
 #include "kernels_scan_labels.hpp"
 #include "kernels_lookahead.hpp"
+#include "kernels_lookahead_obs.hpp"
 #include "kernels_rollout.hpp"
 #include "kernels_mppi.hpp"
 #include "kernels_ped_forecast.hpp"
@@ -543,6 +545,18 @@ int launch_lookahead(const navsim_config* c, const navsim_state* st, const Looka
     const size_t lds = lookahead_lds_bytes(c, a.K);
     return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
         auto kernel = lookahead_kernel<F, decltype(rule)::value, RECT>;
+        if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
+        kernel<<<c->n_envs, kLookaheadBlock, lds, s>>>(*c, *st, a);
+        return launch_status();
+    });
+}
+
+// navsim_lookahead_obs: a workgroup per arena, the forms and the LDS of launch_lookahead
+template <typename F, bool RECT>
+int launch_lookahead_obs(const navsim_config* c, const navsim_state* st, const LookObsArgs& a, hipStream_t s) {
+    const size_t lds = lookahead_lds_bytes(c, a.K);
+    return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
+        auto kernel = lookahead_obs_kernel<F, decltype(rule)::value, RECT>;
         if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
         kernel<<<c->n_envs, kLookaheadBlock, lds, s>>>(*c, *st, a);
         return launch_status();
@@ -1684,15 +1698,9 @@ int navsim_scan_labels(const navsim_config* c, const navsim_state* st, const uin
     return launch_scan_labels<FieldF32, false>(c, st, a, s);
 }
 
-int navsim_lookahead(const navsim_config* c, const navsim_state* st, const navsim_lookahead_params* p, const double* actions,
-                     const double* ped_cmd, const uint8_t* skip, const navsim_lookahead_out* out, void* stream) {
-    (void)hipGetLastError();
-    if (!c || !st || !p || !actions || !out) return NAVSIM_E_ARG;
-    if (!out->reward || !out->done || !out->is_success || !out->is_crash || !out->discomfort || !out->distance || !out->margin ||
-        !out->pose || !out->status)
-        return NAVSIM_E_ARG;
-    if (p->n_actions < 1 || p->n_actions > NAVSIM_LOOKAHEAD_MAX) return NAVSIM_E_ARG;
-    if (!std::isfinite(p->range) || !(p->range > 0.0) || !(p->range <= c->range_max)) return NAVSIM_E_ARG;
+// what navsim_lookahead and navsim_lookahead_obs refuse alike, before anything touches the device (K: the number of candidates)
+static int lookahead_check(const navsim_config* c, const navsim_state* st, int K, const double* ped_cmd) {
+    if (K < 1 || K > NAVSIM_LOOKAHEAD_MAX) return NAVSIM_E_ARG;
     if (!st->robot_pose || !st->robot_goal || !st->prev_action || !st->prev_pose || !st->steps || !st->field ||
         !st->scan_threshold || !st->scan_discomfort)
         return NAVSIM_E_ARG;
@@ -1713,7 +1721,20 @@ int navsim_lookahead(const navsim_config* c, const navsim_state* st, const navsi
     if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
     if (st->rect_table && (c->field_format != NAVSIM_FIELD_U16T || c->map_h > 1024 || c->map_w > 1024)) return NAVSIM_E_UNSUPPORTED;
     if (peds && c->angle_last - c->angle_min > nv::kTwoPi) return NAVSIM_E_UNSUPPORTED;     // the culled merge: dispatch_step
-    if (lookahead_lds_bytes(c, p->n_actions) > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;
+    if (lookahead_lds_bytes(c, K) > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;
+    return NAVSIM_OK;
+}
+
+int navsim_lookahead(const navsim_config* c, const navsim_state* st, const navsim_lookahead_params* p, const double* actions,
+                     const double* ped_cmd, const uint8_t* skip, const navsim_lookahead_out* out, void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !p || !actions || !out) return NAVSIM_E_ARG;
+    if (!out->reward || !out->done || !out->is_success || !out->is_crash || !out->discomfort || !out->distance || !out->margin ||
+        !out->pose || !out->status)
+        return NAVSIM_E_ARG;
+    if (!std::isfinite(p->range) || !(p->range > 0.0) || !(p->range <= c->range_max)) return NAVSIM_E_ARG;
+    const int rc = lookahead_check(c, st, p->n_actions, ped_cmd);
+    if (rc != NAVSIM_OK) return rc;
     if (c->n_envs == 0) return NAVSIM_OK;
     LookaheadArgs a = {};
     a.out = *out; a.actions = actions; a.ped_cmd = c->ped_model == NAVSIM_PED_EXTERNAL ? ped_cmd : nullptr; a.skip = skip;
@@ -1722,6 +1743,31 @@ int navsim_lookahead(const navsim_config* c, const navsim_state* st, const navsi
     if (c->field_format == NAVSIM_FIELD_U16T)
         return st->rect_table ? launch_lookahead<FieldU16T, true>(c, st, a, s) : launch_lookahead<FieldU16T, false>(c, st, a, s);
     return launch_lookahead<FieldF32, false>(c, st, a, s);
+}
+
+int navsim_lookahead_obs(const navsim_config* c, const navsim_state* st, const navsim_lookahead_obs_params* p, const double* actions,
+                         const double* ped_cmd, const float* obs_prev, const uint8_t* skip, const navsim_lookahead_obs_out* out,
+                         void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !p || !actions || !out) return NAVSIM_E_ARG;
+    if (!out->reward || !out->done || !out->is_success || !out->is_crash || !out->discomfort || !out->distance || !out->margin ||
+        !out->pose || !out->status || !out->scan || !out->tail || !out->goals || !out->truncated)
+        return NAVSIM_E_ARG;
+    if (p->noise != NAVSIM_LOOKOBS_NOISE_OFF && p->noise != NAVSIM_LOOKOBS_NOISE_STEP) return NAVSIM_E_ARG;
+    if (c->n_scan_stack < 1) return NAVSIM_E_ARG;
+    if (out->obs && c->n_scan_stack > 1 && (!obs_prev || !st->n_hist)) return NAVSIM_E_ARG;
+    const bool noise = p->noise == NAVSIM_LOOKOBS_NOISE_STEP && c->add_scan_noise;
+    if (noise && (!st->scan_noise_std || !st->episode)) return NAVSIM_E_ARG;
+    const int rc = lookahead_check(c, st, p->n_actions, ped_cmd);
+    if (rc != NAVSIM_OK) return rc;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    LookObsArgs a = {};
+    a.out = *out; a.actions = actions; a.ped_cmd = c->ped_model == NAVSIM_PED_EXTERNAL ? ped_cmd : nullptr; a.obs_prev = obs_prev;
+    a.skip = skip; a.K = p->n_actions; a.noise = noise ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (c->field_format == NAVSIM_FIELD_U16T)
+        return st->rect_table ? launch_lookahead_obs<FieldU16T, true>(c, st, a, s) : launch_lookahead_obs<FieldU16T, false>(c, st, a, s);
+    return launch_lookahead_obs<FieldF32, false>(c, st, a, s);
 }
 
 // what navsim_rollout refuses, before anything touches the device (navsim_mppi refuses the same with the same codes)

@@ -286,6 +286,23 @@ class NavsimLookaheadOut(C.Structure):
     _fields_ = [(name, _P) for name in LOOKAHEAD_OUT]
 
 
+# navsim_lookahead_obs: the lookahead's nine arrays, then the row of each candidate (dtype, trailing shape behind E; K = n_actions,
+# B = n_beams, D = n_scan_stack * n_beams + OBS_TAIL; obs is optional: the call takes NULL for it)
+LOOKOBS_NOISE_OFF, LOOKOBS_NOISE_STEP = 0, 1
+
+
+class NavsimLookaheadObsParams(C.Structure):
+    _fields_ = [("n_actions", C.c_int32), ("noise", C.c_int32)]
+
+
+LOOKAHEAD_OBS_OUT = dict(LOOKAHEAD_OUT, scan=("float32", ("K", "B")), tail=("float32", ("K", 7)), goals=("float32", ("K", 4)),
+                         truncated=("uint8", ("K",)), obs=("float32", ("K", "D")))
+
+
+class NavsimLookaheadObsOut(C.Structure):
+    _fields_ = [(name, _P) for name in LOOKAHEAD_OBS_OUT]
+
+
 # navsim_rollout: the rule's parameters and the ten output arrays (dtype, trailing shape behind E; K = n_seq, H = horizon; status is [E])
 ROLLOUT_MAX_K = 256
 ROLLOUT_MAX_H = 32
@@ -575,6 +592,9 @@ def declare(lib, suffix=""):
         sig("navsim_scan_labels", [cfgp, stp, _P, C.POINTER(NavsimScanLabelsOut), _P])
     if not suffix and hasattr(lib, "navsim_lookahead"):                 # (likewise)
         sig("navsim_lookahead", [cfgp, stp, C.POINTER(NavsimLookaheadParams), _P, _P, _P, C.POINTER(NavsimLookaheadOut), _P])
+    if not suffix and hasattr(lib, "navsim_lookahead_obs"):             # (likewise)
+        sig("navsim_lookahead_obs", [cfgp, stp, C.POINTER(NavsimLookaheadObsParams), _P, _P, _P, _P,
+                                     C.POINTER(NavsimLookaheadObsOut), _P])
     if not suffix and hasattr(lib, "navsim_rollout"):                   # (likewise)
         sig("navsim_rollout", [cfgp, stp, C.POINTER(NavsimRolloutParams), _P, _P, _P, C.POINTER(NavsimRolloutOut), _P])
     if not suffix and hasattr(lib, "navsim_mppi"):                      # (likewise)
@@ -601,7 +621,7 @@ EXPORTS = (
     "navsim_step", "navsim_step_sorted", "navsim_step_part", "navsim_step_replan", "navsim_prepare", "navsim_reset_obs", "navsim_restart", "navsim_reset_install", "navsim_step_kernel_name",
     "navsim_episode_stats_update", "navsim_episode_stats_clear", "navsim_ped_observe",
     "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps", "navsim_dwa", "navsim_local_map",
-    "navsim_scan_labels", "navsim_lookahead", "navsim_rollout", "navsim_mppi", "navsim_ped_forecast",
+    "navsim_scan_labels", "navsim_lookahead", "navsim_lookahead_obs", "navsim_rollout", "navsim_mppi", "navsim_ped_forecast",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

@@ -168,6 +168,17 @@ and default to the reference's behaviour for num_envs == 1:
                     lookahead_params: dict(range=), the candidates' scan cap in metres (default: the smallest multiple of 0.25 m
                     that lies 0.1 m above the largest discomfort threshold).  Not with pedestrian_model 'orca' or 'policy', whose
                     commands come from a launch in front of the step.  None (default): nothing is allocated or launched.
+    lookahead_obs   K in 1 .. 64: env.lookahead_obs(actions) returns the WHOLE return of step() for each of K candidate actions per
+                    arena -- lookahead()'s values plus the observation {'observation' [E,K,D], 'achieved_goal', 'desired_goal'
+                    [E,K,2]}, 'scan' [E,K,B] (the row's newest slot), 'tail' [E,K,7] and 'truncated' [E,K] -- from one launch that
+                    only reads the state (navsim_lookahead_obs): the obs' of a one-step target r + gamma V(obs'), of a full-action
+                    backup or of a safety critic.  With scan noise on it draws the noise the step itself will draw, so row, goals,
+                    reward, done, truncated and flags are bit-identical to the step's, noise on or off; a candidate that crashes
+                    carries the reference's re-scan from the reverted pose.  The first observation of a restarted episode is not
+                    modelled: a `done` candidate holds the terminal row (final_observation).  lookahead_obs_params:
+                    dict(noise='step' | 'off', rows='full' | 'scan'); rows='scan' leaves 'observation' out and saves its
+                    E*K*(S*B+7)*4 bytes per set.  Independent of lookahead=.  Not with pedestrian_model 'orca' or 'policy'.  None
+                    (default): nothing is allocated or launched.
     rollout         K in 1 .. 256: env.rollout(actions) returns what the next H step() calls would return if an arena executed each
                     of K action sequences -- per step reward and pose; per sequence the discounted return, the steps evaluated,
                     the outcome bits (1 success, 2 crash, 4 time limit), discomfort steps, the least crash margin, the final
@@ -350,7 +361,8 @@ class NavGymEnv(_EnvBase):
                  final_observation=True, pregen_fallback_poll=None, max_episode_steps=None, orca_params=None,
                  episode_stats=False, observe_humans=None, observe_params=None, goal_path=False, goal_path_params=None,
                  local_planner=None, local_planner_params=None, observe_local_map=None, local_map_params=None,
-                 scan_labels=False, lookahead=None, lookahead_params=None, rollout=None, rollout_params=None,
+                 scan_labels=False, lookahead=None, lookahead_params=None, lookahead_obs=None, lookahead_obs_params=None,
+                 rollout=None, rollout_params=None,
                  ped_forecast=None, ped_forecast_params=None):
         # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
         self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
@@ -597,6 +609,18 @@ class NavGymEnv(_EnvBase):
                                  "front of the step that has not run yet" % pedestrian_model)
         self.lookahead_k = None if lookahead is None else int(lookahead)
         self.lookahead_params = None if lookahead_params is None else dict(lookahead_params)
+        # lookahead observations (navsim_lookahead_obs): the step's whole return for K candidate actions, on request (env.lookahead_obs())
+        _check_params("lookahead_obs_params", lookahead_obs_params, lookahead_obs is not None, "lookahead_obs=K", _simmod.LOOKAHEAD_OBS_KEYS)
+        if lookahead_obs is not None:
+            if not (isinstance(lookahead_obs, numbers.Integral) and not isinstance(lookahead_obs, bool)
+                    and 1 <= lookahead_obs <= abi.LOOKAHEAD_MAX):
+                raise ValueError("lookahead_obs must be None or an int in 1 .. %d, not %r" % (abi.LOOKAHEAD_MAX, lookahead_obs))
+            _simmod.lookahead_obs_choice(dict(_simmod.lookahead_obs_defaults(), **(lookahead_obs_params or {})))
+            if pedestrian_model in ("orca", "policy"):
+                raise ValueError("lookahead_obs is not available with pedestrian_model=%r: the pedestrians' commands come from a launch "
+                                 "in front of the step that has not run yet" % pedestrian_model)
+        self.lookahead_obs_k = None if lookahead_obs is None else int(lookahead_obs)
+        self.lookahead_obs_params = None if lookahead_obs_params is None else dict(lookahead_obs_params)
         # action-sequence rollout (navsim_rollout): the next H steps' outcomes for K action sequences per arena, on request (env.rollout())
         _check_params("rollout_params", rollout_params, rollout is not None, "rollout=K", ("horizon",) + _simmod.ROLLOUT_KEYS)
         if rollout is not None:
@@ -821,6 +845,8 @@ class NavGymEnv(_EnvBase):
                 self.sim.enable_scan_labels()
             if self.lookahead_k:
                 self.sim.enable_lookahead(self.lookahead_k, self.lookahead_params)
+            if self.lookahead_obs_k:
+                self.sim.enable_lookahead_obs(self.lookahead_obs_k, self.lookahead_obs_params)
             if self.rollout_k:
                 self.sim.enable_rollout(self.rollout_k, self.rollout_h,
                                         {k: v for k, v in (self.rollout_params or {}).items() if k != "horizon"})
@@ -1204,6 +1230,47 @@ class NavGymEnv(_EnvBase):
             host = sim.lookahead_host()
             return {k: (v[0].astype(bool) if k in self._LOOKAHEAD_BOOL else v[0]) for k, v in host.items()}
         return {k: (v.view(self._bool) if k in self._LOOKAHEAD_BOOL else v) for k, v in out.items()}
+
+    def lookahead_obs(self, actions, human_actions=None):
+        """The whole return of step() for each of K candidate actions per arena, from the current state, which is only read
+        (NavGymEnv(lookahead_obs=K); navsim_lookahead_obs, one launch): lookahead()'s dict -- here with the scan noise the step
+        itself would draw (lookahead_obs_params: noise='step'), so its values are the step's own, noise on or off -- plus
+        'observation': {'observation' [E,K,D] float32, 'achieved_goal' [E,K,2], 'desired_goal' [E,K,2]} as step() returns it for
+        that action (rows='full' only; behind a crash the reference's re-scan from the reverted pose; for a `done` candidate the
+        terminal row, not the first row of the next episode), 'scan' [E,K,B] float32 (the row's newest slot), 'tail' [E,K,7]
+        float32 and 'truncated' [E,K] bool.
+        actions, human_actions: as lookahead()'s.  Next-step auto-reset: an arena whose `done` is set is skipped (status 0, rows 0).
+        num_envs > 1: torch views, intact through the next step(); num_envs == 1: NumPy rows [K,...] from one device -> host copy
+        (the three arrays of 'observation' as float64, like step()'s)."""
+        if self.lookahead_obs_k is None:
+            raise RuntimeError("lookahead_obs() needs NavGymEnv(lookahead_obs=K)")
+        if self.pedestrian_model == "external" and human_actions is None:
+            raise ValueError("lookahead_obs() with pedestrian_model='external' needs human_actions")
+        if self.sim is None:
+            raise RuntimeError("call reset() before lookahead_obs()")
+        import torch
+        sim, E, K = self.sim, self.num_envs, self.lookahead_obs_k
+        if not hasattr(actions, "is_cuda"):
+            a = np.asarray(actions, dtype=np.float64)
+            if a.shape == (K, 2):
+                a = np.broadcast_to(a, (E, K, 2))
+            actions = torch.from_numpy(np.array(a.reshape(E, K, 2), dtype=np.float64, order="C"))    # (a writable copy)
+        elif tuple(actions.shape) == (K, 2):
+            actions = actions.expand(E, K, 2)
+        skip = sim.out["done"] if self.auto_reset and self.autoreset_mode == "next_step" and sim.out is not None else None
+        out = sim.lookahead_obs(actions, ped_cmd=human_actions if self.pedestrian_model == "external" else None, skip=skip)
+        booleans = self._LOOKAHEAD_BOOL + ("truncated",)
+        if E == 1:
+            out = {k: (v[0].astype(bool) if k in booleans else v[0]) for k, v in sim.lookahead_obs_host().items()}
+            wide = lambda v: v.astype(np.float64)
+        else:
+            out = {k: (v.view(self._bool) if k in booleans else v) for k, v in out.items()}
+            wide = lambda v: v
+        goals = out.pop("goals")
+        if "obs" in out:
+            out["observation"] = {"observation": wide(out.pop("obs")), "achieved_goal": wide(goals[..., :2]),
+                                  "desired_goal": wide(goals[..., 2:])}
+        return out
 
     _ROLLOUT_HORIZON = 8
 

@@ -420,6 +420,26 @@ def lookahead_range_min(discomfort_max):
     return float(discomfort_max) + 0.1
 
 
+LOOKAHEAD_OBS_KEYS = ("noise", "rows")
+LOOKAHEAD_OBS_NOISE = {"off": abi.LOOKOBS_NOISE_OFF, "step": abi.LOOKOBS_NOISE_STEP}
+LOOKAHEAD_OBS_ROWS = ("full", "scan")
+
+
+def lookahead_obs_defaults():
+    """The parameters of navsim_lookahead_obs as a dict: noise 'step' (the scan noise the step itself would draw; 'off': none)
+    and rows 'full' (the whole observation row of every candidate; 'scan': its newest scan slot and its tail only)."""
+    return dict(noise="step", rows="full")
+
+
+def lookahead_obs_choice(d):
+    """(abi.LOOKOBS_NOISE_* constant, 'full' | 'scan') of a parameter dict; anything else raises ValueError."""
+    if not (isinstance(d["noise"], str) and d["noise"] in LOOKAHEAD_OBS_NOISE):
+        raise ValueError("lookahead_obs noise must be 'step' or 'off', not %r" % (d["noise"],))
+    if not (isinstance(d["rows"], str) and d["rows"] in LOOKAHEAD_OBS_ROWS):
+        raise ValueError("lookahead_obs rows must be 'full' or 'scan', not %r" % (d["rows"],))
+    return LOOKAHEAD_OBS_NOISE[d["noise"]], d["rows"]
+
+
 def lookahead_defaults(cfg, discomfort_max=0.0):
     """The parameters of navsim_lookahead as a dict: range, the candidates' scan cap R -- the smallest multiple of 0.25 m that
     lies 0.1 m above the largest discomfort threshold (discomfort_max, metres; NavSim.enable_lookahead reads it from the state),
@@ -1880,6 +1900,52 @@ class NavSim(object):
     def lookahead_host(self):
         """The current set of lookahead()'s outputs as NumPy arrays, from ONE device -> host copy."""
         return self._product("lookahead").host(self.cur)
+
+    # ---- lookahead observations: the WHOLE return of step() -- row, goals, reward, done, truncated, flags -- for each of K
+    # candidate actions per arena, one launch that only reads the state (include/navsim.h navsim_lookahead_obs)
+    def enable_lookahead_obs(self, K, params=None):
+        """Allocates two sets of outputs (abi.LOOKAHEAD_OBS_OUT, [E,K,...] and status [E]: they flip with self.cur like everything
+        a step returns), an action buffer float64 [E,K,2] and a command buffer float64 [E,N,2].  params: a dict of overrides of
+        lookahead_obs_defaults(), or None -- noise 'step' (the draw the step itself would make) or 'off'; rows 'full' (the rows
+        [E,K,S*B+7] as `obs`: E*K*(S*B+7)*4 bytes per set) or 'scan' (no `obs`: scan [E,K,B] and tail [E,K,7] only)."""
+        import torch
+        cfg = self.cfg
+        if not 1 <= int(K) <= abi.LOOKAHEAD_MAX:
+            raise ValueError("lookahead_obs evaluates 1 .. %d actions per arena, not %r" % (abi.LOOKAHEAD_MAX, K))
+        d = _overridden(lookahead_obs_defaults(), params, "lookahead_obs", LOOKAHEAD_OBS_KEYS)
+        noise, rows = lookahead_obs_choice(d)
+        p = abi.NavsimLookaheadObsParams(n_actions=int(K), noise=noise)
+        extra = dict(actions=torch.zeros((cfg.n_envs, int(K), 2), dtype=torch.float64, device=self.device),
+                     ped_cmd=torch.zeros((cfg.n_envs, max(cfg.max_peds, 1), 2), dtype=torch.float64, device=self.device))
+        sym = {"K": int(K), "B": cfg.n_beams, "D": cfg.n_scan_stack * cfg.n_beams + abi.OBS_TAIL}
+        layout = blob_layout(abi.LOOKAHEAD_OBS_OUT, cfg.n_envs, sym, omit=() if rows == "full" else ("obs",))
+        self.products["lookahead_obs"] = _StepProduct(self, p, layout, abi.NavsimLookaheadObsOut, extra=extra)
+
+    def lookahead_obs(self, actions, ped_cmd=None, skip=None):
+        """navsim_lookahead_obs of the current state and the current observation (self.obs: what the next step takes as
+        obs_prev) on the current stream: one launch, no device -> host copy, no allocation, and the state is only read.
+        actions, ped_cmd, skip: as lookahead()'s.  Returns the current set -- lookahead()'s nine arrays, 'scan' [E,K,B], 'tail'
+        [E,K,7], 'goals' [E,K,4], 'truncated' [E,K] and, with rows='full', 'obs' [E,K,S*B+7] -- intact through the next step."""
+        import torch
+        p, cur = self.products.get("lookahead_obs") or self._product("lookahead_obs"), self.cur
+        buf = p.extra["actions"]
+        if not (torch.is_tensor(actions) and actions.device == buf.device and actions.dtype == buf.dtype and actions.is_contiguous()
+                and actions.shape == buf.shape):
+            buf.copy_(torch.as_tensor(actions).to(device=buf.device, dtype=buf.dtype).reshape(buf.shape), non_blocking=True)
+            actions = buf
+        if ped_cmd is not None:
+            cmd = p.extra["ped_cmd"]
+            cmd.copy_(torch.as_tensor(ped_cmd).to(device=cmd.device, dtype=cmd.dtype).reshape(cmd.shape), non_blocking=True)
+            ped_cmd = cmd
+        rc = self.lib.navsim_lookahead_obs(p.cfg, p.st, p.par, _ptr(actions), _ptr(ped_cmd), _ptr(self.obs_buf[cur]), _ptr(skip),
+                                           p.out[cur], _stream())
+        if rc:
+            check(rc, "navsim_lookahead_obs")
+        return p.buf[cur]
+
+    def lookahead_obs_host(self):
+        """The current set of lookahead_obs()'s outputs as NumPy arrays, from ONE device -> host copy."""
+        return self._product("lookahead_obs").host(self.cur)
 
     # ---- action-sequence rollout: what the next H step() calls would return for each of K action sequences per arena, one launch
     # that only reads the state (include/navsim.h navsim_rollout)
