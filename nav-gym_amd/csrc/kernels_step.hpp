@@ -31,8 +31,96 @@ struct StepShared {
     float march_lim;              // ... march_limit(map, range_max, resolution): functions of the configuration alone, two float64
                                   // divisions that every wavefront evaluated in every scan; now two lanes of phase 0, once per step
     double wave_ratio[kMaxWaves];
+    // the arena's state as the step's head read it (StepHead), for the readers behind the phase-0 barrier: an LDS read where
+    // four wavefronts (n_hist, noise_std) or thread 0 with three wavefronts waiting at a barrier (phases 4 and 6) made a global
+    // round trip.  prev_pose / prev_action are the values at the START of the step (phase 6 stores the new ones); goal follows
+    // a restart in place.
+    double prev_pose[3], goal[2], prev_action[2];
+    long long steps64;            // steps[e] after this step's increment, all 64 bits (the pedestrian phase's key)
+    int n_hist;
+    float noise_std;
 };
-#ifndef NAVSIM_STEP_CONSTS_LDS          // leave-one-out builds (profiles/r20_scan_fixed/): 0 = every wavefront divides for itself
+#ifndef NAVSIM_HEAD_ROW_BATCH           // leave-one-out builds (profiles/r22_step_head/): 0 = the index row one uint4 per thread and round trip
+#define NAVSIM_HEAD_ROW_BATCH 1
+#endif
+#ifndef NAVSIM_HEAD_SCALARS             // ... 0 = every scalar of the arena loaded where it is used
+#define NAVSIM_HEAD_SCALARS 1
+#endif
+#ifndef NAVSIM_HEAD_ALL_LANES           // ... 0 = only the lanes of phase 0 load the scalars, behind a branch
+#define NAVSIM_HEAD_ALL_LANES 1
+#endif
+#ifndef NAVSIM_HEAD_EVERYWHERE          // ... 1 = also the instantiations that keep the parent's form (kNewHead in step_arena)
+#define NAVSIM_HEAD_EVERYWHERE 0
+#endif
+#ifndef NAVSIM_HEAD_TAIL              // ... 0 = phases 4 and 6 read prev_pose / robot_goal / prev_action from global memory
+#define NAVSIM_HEAD_TAIL 1
+#endif
+// The arena's index row into LDS.  A thread's share is every BLOCK-th uint4; it takes kRowBatch of them per round trip: the
+// loads back to back into registers, ONE wait, the LDS stores (10 000 bytes at 256 threads: 1 round trip instead of 3; 33 312
+// bytes at 512 threads: 2 instead of 5).  An element beyond the row's end is replaced by the batch's first one (in range,
+// since the batch exists), in the load AND in the store: the thread copies that element again, the same bytes to the same
+// place.  No branch at all, on purpose -- a load whose only use is a conditional store is moved into the condition by the
+// compiler, and the round trips are one by one again.  Short rows and a ragged last batch need no other care.
+constexpr int kRowBatch = 4;
+template <int BLOCK>
+__device__ __forceinline__ void row_batch_load(uint4 (&v)[kRowBatch], const uint4* __restrict__ src, int base, int n16) {
+#pragma unroll
+    for (int k = 0; k < kRowBatch; ++k) {
+        const int i = base + k * BLOCK;
+        v[k] = src[i < n16 ? i : base];
+    }
+}
+template <int BLOCK>
+__device__ __forceinline__ void row_batch_store(const uint4 (&v)[kRowBatch], uint4* dst, int base, int n16) {
+#pragma unroll
+    for (int k = 0; k < kRowBatch; ++k) {
+        const int i = base + k * BLOCK;
+        dst[i < n16 ? i : base] = v[k];
+    }
+}
+// the whole row (first = 0), or what follows a first batch that the caller loaded and stored itself (first = 1)
+template <int BLOCK, bool BATCH = true>
+__device__ __forceinline__ void row_copy(uint4* dst, const uint4* __restrict__ src, int n16, int first = 0) {
+    if constexpr (NAVSIM_HEAD_ROW_BATCH && BATCH) {
+        for (int base = (int)threadIdx.x + first * kRowBatch * BLOCK; base < n16; base += kRowBatch * BLOCK) {
+            uint4 v[kRowBatch];
+            row_batch_load<BLOCK>(v, src, base, n16);
+            row_batch_store<BLOCK>(v, dst, base, n16);
+        }
+    } else {
+        for (int i = threadIdx.x; i < n16; i += BLOCK) dst[i] = src[i];
+    }
+}
+// What a step reads of its arena's state, loaded in ONE round beside the index row's first batch (step_arena): data
+// dependence asks for three round trips at a workgroup's start -- the launch order gives the arena, the arena its row and
+// these scalars, the new pose the origin cell -- and the loads used to be waited for one by one where they were used.
+// Every value comes from the place and goes into the arithmetic it always did.
+struct StepHead {
+    double rp[3], act[2], prev_pose[3], goal[2], prev_action[2];
+    long long steps;
+    unsigned episode_lo;          // the low word of episode[e]: all the noise key takes of it (episode * 2^32), and a dead high word
+                                  // in flight is a register the allocator hands out again, with a wait for the load in front
+    int n_hist;
+    float noise_std;
+};
+__device__ __forceinline__ void step_head_load(StepHead& h, const navsim_config& c, const navsim_state& st, const navsim_step_io& io,
+                                               int e, bool with_action) {
+    const double* rp_g = st.robot_pose + 3 * (size_t)e;
+    const double* pv_g = st.prev_pose + 3 * (size_t)e;
+    const double* goal_g = st.robot_goal + 2 * (size_t)e;
+    const double* pa_g = st.prev_action + 2 * (size_t)e;
+    h.rp[0] = rp_g[0]; h.rp[1] = rp_g[1]; h.rp[2] = rp_g[2];
+    h.act[0] = 0.0; h.act[1] = 0.0;
+    if (with_action) { h.act[0] = io.action[2 * e]; h.act[1] = io.action[2 * e + 1]; }       // (a reset-only launch has no actions)
+    h.steps = st.steps[e];
+    h.episode_lo = *(const unsigned*)(st.episode + e);          // (little-endian: the low word)
+    h.n_hist = st.n_hist[e];
+    h.noise_std = (c.add_scan_noise && st.scan_noise_std) ? st.scan_noise_std[e] : 0.0f;
+    h.prev_pose[0] = pv_g[0]; h.prev_pose[1] = pv_g[1]; h.prev_pose[2] = pv_g[2];
+    h.goal[0] = goal_g[0]; h.goal[1] = goal_g[1];
+    h.prev_action[0] = pa_g[0]; h.prev_action[1] = pa_g[1];
+}
+#ifndef NAVSIM_STEP_CONSTS_LDS         // leave-one-out builds (profiles/r20_scan_fixed/): 0 = every wavefront divides for itself
 #define NAVSIM_STEP_CONSTS_LDS 1
 #endif
 #ifndef NAVSIM_STEP_VOTE_LDS            // ... 0 = two __syncthreads_or
@@ -1331,6 +1419,27 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
     const Field field(st.field, st.field_overflow, ms, c.map_h, c.map_w);
     const uint4* rects = RECT ? (const uint4*)st.rect_table + (size_t)ms * rect_tiles_per_map(c.map_h, c.map_w)
                               : nullptr;
+    // The head of the step (StepHead): every scalar load of the arena is issued BETWEEN the loads and the LDS stores of the index
+    // row's first batch, so that one wait serves the row and the scalars.  (An INSTALL instantiation that takes the new head --
+    // only in a -DNAVSIM_HEAD_EVERYWHERE=1 build -- loads the scalars behind its prelude instead, where phase 0 stands: an
+    // install or regen_lone rewrites the arena's state, and nothing loaded before it may be used after it.)
+    constexpr int kPhase0Thread = (PEDS && BLOCK > 64) ? 64 : 0;
+    // Each variant decides for itself (profiles/r22_step_head/): the plain kernels without pedestrians (c2, c4) and the fused
+    // pedestrian kernels below 1024 threads (c3) gain.  The parent's form stays in
+    //   the INSTALL instantiations and the 1024-thread pedestrian kernels: c5 lost 6.5 % with the new head, all of it to the
+    //       scalars in one round; the batched row and the LDS copies alone gave it nothing (loo_ab.txt);
+    //   the FEAT twins without pedestrians: the new form moved their register allocation in the march and finish code
+    //       (v_readlane / v_writelane 150 / 51 -> 205 / 75 at 256 threads, listing.txt), which this change must not do;
+    //   the pedestrian kernels whose pedestrian phase is a launch of its own (!PINL): scratch 40 -> 64 bytes.
+    // -DNAVSIM_HEAD_EVERYWHERE=1 (diagnostic builds) gives every instantiation the new form.
+    constexpr bool kNewHead = NAVSIM_HEAD_EVERYWHERE != 0 ||
+                              !(INSTALL || (PEDS && BLOCK >= 1024) || (!PEDS && FEAT) || (PEDS && !PINL));
+    constexpr bool kHead = NAVSIM_HEAD_SCALARS != 0 && kNewHead, kTail = NAVSIM_HEAD_TAIL != 0 && kNewHead;
+    const int l0 = tid - kPhase0Thread;
+    const bool phase0_lane = l0 >= 0 && l0 < (NAVSIM_STEP_CONSTS_LDS ? 5 : 3);
+    const bool with_action = !reset_only;                       // (the launch's word: a step launch has actions for every arena)
+    StepHead hd;                                                // (phase-0 lanes only; not initialised: a constant on the other lanes'
+                                                                //  path invites the compiler to do arithmetic, and wait, inside the head)
     if constexpr (RECT == 2) {
         // "Map tiles staged through LDS": the INDEX form of the arena's record table (kernels_rect.hpp: 2 KB of distinct
         // rectangles + 2 bytes per 8x8 tile = 10 KB for 500 x 500 cells) is copied into LDS once, by all threads, beside
@@ -1338,8 +1447,23 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
         const size_t row_bytes = rect_index_row_bytes(c.map_h, c.map_w);
         const uint4* src = (const uint4*)((const char*)st.rect_index + (size_t)ms * row_bytes);
         uint4* tab_lds = (uint4*)dyn_lds_all;
-        for (int i = threadIdx.x; i < (int)(row_bytes / 16); i += BLOCK) tab_lds[i] = src[i];
-        rects = tab_lds;                                        // made visible by the barrier that ends phase 0
+        const int n16 = (int)(row_bytes / 16);
+        if constexpr (NAVSIM_HEAD_ROW_BATCH && kHead && !INSTALL) {
+            uint4 v[kRowBatch];
+            const int base = tid < n16 ? tid : 0;               // (a row shorter than the workgroup: the idle threads re-read element 0)
+            row_batch_load<BLOCK>(v, src, base, n16);
+            if (NAVSIM_HEAD_ALL_LANES || phase0_lane) step_head_load(hd, c, st, io, e, with_action);
+            row_batch_store<BLOCK>(v, tab_lds, base, n16);      // (idle threads: element 0 once more, the same bytes)
+            row_copy<BLOCK>(tab_lds, src, n16, 1);
+        } else {
+            if constexpr (kHead && !INSTALL) {
+                if (NAVSIM_HEAD_ALL_LANES || phase0_lane) step_head_load(hd, c, st, io, e, with_action);
+            }
+            row_copy<BLOCK, kNewHead>(tab_lds, src, n16);
+        }
+        rects = tab_lds;                                       // made visible by the barrier that ends phase 0
+    } else if constexpr (kHead && !INSTALL) {
+        if (NAVSIM_HEAD_ALL_LANES || phase0_lane) step_head_load(hd, c, st, io, e, with_action);
     }
     float* obs_row = io.obs + (size_t)e * D;
     const float* obs_prev = io.obs_prev ? io.obs_prev + (size_t)e * D : nullptr;
@@ -1347,6 +1471,10 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
     double* goal_g = st.robot_goal + 2 * (size_t)e;
     double* pa_g = st.prev_action + 2 * (size_t)e;
     double* pv_g = st.prev_pose + 3 * (size_t)e;
+    // what phases 4-6 READ of the three: phase 0's copies in LDS (the arrays are written in phase 4's restart and in phase 6)
+    const double* pv_r = kTail ? sh.prev_pose : pv_g;
+    const double* goal_r = kTail ? sh.goal : goal_g;
+    const double* pa_r = kTail ? sh.prev_action : pa_g;
 
     // NAVSIM_AUTORESET_NEXT_STEP: an arena of io.reset_mask finished in the previous call and restarted in the STATE there; this
     // call RESETS it instead of stepping it -- the reset-only path for this one workgroup (first observation from the reset key,
@@ -1392,8 +1520,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
                     if constexpr (RECT == 2) {                  // the new map's index row replaces the old one in LDS
                         const size_t row_bytes = rect_index_row_bytes(c.map_h, c.map_w);
                         const uint4* src = (const uint4*)((const char*)st.rect_index + (size_t)ms * row_bytes);
-                        uint4* tab_lds = (uint4*)dyn_lds_all;
-                        for (int i = threadIdx.x; i < (int)(row_bytes / 16); i += BLOCK) tab_lds[i] = src[i];
+                        row_copy<BLOCK, kNewHead>((uint4*)dyn_lds_all, src, (int)(row_bytes / 16));
                     }
                 }
                 // (verdict 0, 5: the ordinary reset path below -- first observation from the state as it stands now)
@@ -1408,7 +1535,8 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
 
     int n = (!PEDS || c.ped_model == NAVSIM_PED_NONE) ? 0 : st.n_peds[e];
     n = n > N ? N : n;
-    const float noise_std = (c.add_scan_noise && st.scan_noise_std) ? st.scan_noise_std[e] : 0.0f;
+    float noise_std = 0.0f;                                     // (kHead: phase 0 publishes it, read behind the barrier)
+    if constexpr (!kHead) noise_std = (c.add_scan_noise && st.scan_noise_std) ? st.scan_noise_std[e] : 0.0f;
 
     NAVSIM_STAMP(0);
     // wavefront 0 of the pedestrian variants: pedestrian i on lane i.  Its loads, the waypoint pop and the staging of the
@@ -1430,7 +1558,6 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
             }
         }
     }
-    constexpr int kPhase0Thread = (PEDS && BLOCK > 64) ? 64 : 0;
     // ---------------------------------------------------------------- phase 0: scalars, robot, lidar pose
     // The robot moves here, ahead of the pedestrians (env.py:664 comes after their commands, but nothing the pedestrian
     // phase computes reads the robot's new pose -- the social force sees old_rp -- and nothing here reads a pedestrian):
@@ -1440,12 +1567,13 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
     // lane or three are live; two sincos fewer are 180 of an arena's 11 500 vector instructions on c2).
     // Lanes 3 and 4 ride along with them and take the scan's two configuration-only quotients (step_consts_publish); this
     // phase's barrier orders their stores before every scan of the step, the re-scans included.
-    const int l0 = tid - kPhase0Thread;
-    if (l0 >= 0 && l0 < (NAVSIM_STEP_CONSTS_LDS ? 5 : 3)) {
-        const double th_old = rp_g[2];
+    if (phase0_lane) {
+        if constexpr (kHead && INSTALL) step_head_load(hd, c, st, io, e, !reset_only);
+        const double th_old = kHead ? hd.rp[2] : rp_g[2];
         double a0 = 0.0, a1 = 0.0;
         if (!reset_only) {
-            a0 = io.action[2 * e]; a1 = io.action[2 * e + 1];
+            if constexpr (kHead) { a0 = hd.act[0]; a1 = hd.act[1]; }
+            else { a0 = io.action[2 * e]; a1 = io.action[2 * e + 1]; }
             if (c.action_kind == NAVSIM_ACTION_WHEELS) {       // skid-steer wheel speeds (left, right) -> twist (include/navsim.h)
                 const double wl = a0, wr = a1;
                 a0 = c.wheel_radius * (wl + wr) * 0.5;
@@ -1472,7 +1600,15 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
         const double sT = __shfl(sn, w0 + 2), cT = __shfl(cs, w0 + 2);
         if (NAVSIM_STEP_CONSTS_LDS && l0 >= 3) step_consts_publish(c, sh, l0 - 3);
         if (l0 == 0) {
-            sh.old_rp[0] = rp_g[0]; sh.old_rp[1] = rp_g[1]; sh.old_rp[2] = th_old;
+            sh.old_rp[0] = kHead ? hd.rp[0] : rp_g[0]; sh.old_rp[1] = kHead ? hd.rp[1] : rp_g[1]; sh.old_rp[2] = th_old;
+            if constexpr (kHead) { sh.n_hist = hd.n_hist; sh.noise_std = hd.noise_std; }
+            if constexpr (kTail) {
+                // (INSTALL: an arena that takes a staged world below -- respawn 3 -- is fresh in phase 6 and reads none of these)
+                sh.prev_pose[0] = kHead ? hd.prev_pose[0] : pv_g[0]; sh.prev_pose[1] = kHead ? hd.prev_pose[1] : pv_g[1];
+                sh.prev_pose[2] = kHead ? hd.prev_pose[2] : pv_g[2];
+                sh.goal[0] = kHead ? hd.goal[0] : goal_g[0]; sh.goal[1] = kHead ? hd.goal[1] : goal_g[1];
+                sh.prev_action[0] = kHead ? hd.prev_action[0] : pa_g[0]; sh.prev_action[1] = kHead ? hd.prev_action[1] : pa_g[1];
+            }
             sh.nseg = 0; sh.ndisc = 0; sh.rescan = 0; sh.respawn = 0; sh.term = 0;
             if constexpr (INSTALL) {
                 if (pending && !in->lone) {
@@ -1500,10 +1636,12 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
                     }
                 }
             }
+            int64_t key_steps = 0;                              // steps[e] as the noise key counts them: 0 in a reset
             if (!reset_only) {
-                const int64_t steps_now = st.steps[e] + 1;     // env.py:592
+                const int64_t steps_now = (kHead ? (int64_t)hd.steps : st.steps[e]) + 1;     // env.py:592
                 st.steps[e] = steps_now;
                 sh.steps_now = (int)steps_now;
+                if constexpr (kHead) { sh.steps64 = steps_now; key_steps = steps_now; }
                 sh.act[0] = a0; sh.act[1] = a1;
                 double p[3] = {sh.old_rp[0], sh.old_rp[1], sh.old_rp[2]};        // env.py:664
                 nv::set_vel_with(p, a0, a1, dt, c.axle_offset, s0, c0, s1, c1, nullptr);
@@ -1515,8 +1653,11 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
             nv::xy_to_ij_f32(sh.lx, sh.ly, c, sh.i0, sh.j0);                              // env.py:419
             sh.sT = sT; sh.cT = cT;                            // sincos((double)sh.lth): sh.rp[2] is th_new
             first_probe<RULE>(field, c.map_h, c.map_w, sh.i0, sh.j0, (float)((long long)c.map_h * c.map_w), sh.t1, sh.r_all);
-            sh.step_key = (unsigned long long)st.episode[e] * 0x100000000ULL +
-                          (unsigned long long)(reset_only ? 0 : st.steps[e]) * 2ULL;
+            if constexpr (kHead)                                // (the values in hand: no load behind the origin cell's)
+                sh.step_key = (unsigned long long)hd.episode_lo * 0x100000000ULL + (unsigned long long)key_steps * 2ULL;
+            else
+                sh.step_key = (unsigned long long)st.episode[e] * 0x100000000ULL +
+                              (unsigned long long)(reset_only ? 0 : st.steps[e]) * 2ULL;
             sh.rescan_key = sh.step_key + 1;
             sh.next_chunk = 0; sh.park_count = 0; sh.park_next = 0; sh.pair_done = 0; sh.vote = 0;
         }
@@ -1551,7 +1692,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
             const int lane = tid;
             if constexpr (PINL) {
                 if (ped_advance)
-                    ped_advance_wave<Field>(c, st, field, e, n, lane, is_ped, pq, dt, genv, (uint64_t)st.steps[e], ps, pair,
+                    ped_advance_wave<Field>(c, st, field, e, n, lane, is_ped, pq, dt, genv, kHead ? (uint64_t)sh.steps64 : (uint64_t)st.steps[e], ps, pair,
                                             ped_head, ped_nw, pp, pvel, &sh.pair_done, pair_shared ? kPairWaves : 1);
             }
             if (reset_only && is_ped) {                             // env.py:809, 812-820
@@ -1599,7 +1740,8 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
     else if (base_prio == 1) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
     // ---------------------------------------------------------------- phase 3: scan A
-    int n_hist = reset_only ? 0 : st.n_hist[e];
+    int n_hist = reset_only ? 0 : (kHead ? sh.n_hist : st.n_hist[e]);
+    if constexpr (kHead) noise_std = sh.noise_std;
     int crash = 0, discomfort = 0;
     const uint64_t step_key = sh.step_key;
     // dynamic LDS: [parked rays][pedestrian variants: float2 dir[B], float rng[B]][PedShared][pair table (fused pedestrian phase)]
@@ -1631,10 +1773,10 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
         if (tid == 0) {
             if (discomfort && !crash)
                 for (int w = 1; w < (BLOCK + 63) / 64; ++w) rmin = sh.wave_ratio[w] < rmin ? sh.wave_ratio[w] : rmin;
-            double prev_xy[2] = {pv_g[0], pv_g[1]};
+            double prev_xy[2] = {pv_r[0], pv_r[1]};
             double pose[2] = {sh.rp[0], sh.rp[1]};
-            double vel[2] = {pa_g[0], pa_g[1]};                 // env.py:453: the PREVIOUS action
-            double goal[2] = {goal_g[0], goal_g[1]};
+            double vel[2] = {pa_r[0], pa_r[1]};                 // env.py:453: the PREVIOUS action
+            double goal[2] = {goal_r[0], goal_r[1]};
             nv::RewardOut o = nv::reward_scalar(c, prev_xy, pose, vel, goal, crash != 0, discomfort != 0, rmin);
             if constexpr (kFeat) {
                 // cfg.max_episode_steps (ABI 7): an episode that reaches T steps without success or crash is truncated -- its
@@ -1658,16 +1800,16 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
                     // the row: tail and goals here; the scan rows from scan A (term 1) or, after a crash, from the re-scan at
                     // the reverted pose (term 2, env.py:707-723) below
                     const bool crashed = o.crash != 0.0f;
-                    const double tx = crashed ? pv_g[0] : sh.rp[0], ty = crashed ? pv_g[1] : sh.rp[1];
-                    const double tyaw = nv::wrap_pi(crashed ? pv_g[2] : sh.rp[2]);
+                    const double tx = crashed ? pv_r[0] : sh.rp[0], ty = crashed ? pv_r[1] : sh.rp[1];
+                    const double tyaw = nv::wrap_pi(crashed ? pv_r[2] : sh.rp[2]);
                     float* ft = io.final_obs + (size_t)e * D + (size_t)S * B;
-                    ft[0] = (float)pv_g[0]; ft[1] = (float)pv_g[1];
+                    ft[0] = (float)pv_r[0]; ft[1] = (float)pv_r[1];
                     ft[2] = (float)tx; ft[3] = (float)ty;
-                    ft[4] = (float)pa_g[0]; ft[5] = (float)pa_g[1];
+                    ft[4] = (float)pa_r[0]; ft[5] = (float)pa_r[1];
                     ft[6] = (float)tyaw;
                     if (io.final_goals) {
                         float* fg = io.final_goals + 4 * (size_t)e;
-                        fg[0] = (float)tx; fg[1] = (float)ty; fg[2] = (float)goal_g[0]; fg[3] = (float)goal_g[1];
+                        fg[0] = (float)tx; fg[1] = (float)ty; fg[2] = (float)goal_r[0]; fg[3] = (float)goal_r[1];
                     }
                     sh.term = crashed ? 2 : 1;
                 }
@@ -1677,6 +1819,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
                 const double* sg = st.spawn_goal + ((size_t)e * c.n_spawn + idx) * 2;
                 sh.rp[0] = sp[0]; sh.rp[1] = sp[1]; sh.rp[2] = sp[2];
                 goal_g[0] = sg[0]; goal_g[1] = sg[1];
+                if constexpr (kTail) { sh.goal[0] = sg[0]; sh.goal[1] = sg[1]; }     // (phase 6: desired_goal of the new episode)
 #ifndef NAVSIM_DIAG_NO_DONE_STEPS    // diagnostic build only: what does the store cost the plain step's code?
                 if (st.done_steps) st.done_steps[e] = sh.steps_now;               // how long the episode lasted (cfg.regen_min_steps)
 #endif
@@ -1706,7 +1849,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
                 // NONE / NEXT_STEP: the outputs are the reference's (env.py:700-728); NEXT_STEP restarts the STATE behind phase 6
                 restart_next = kFeat && restart;
                 if (o.crash != 0.0f) {                          // env.py:707-717
-                    sh.rp[0] = pv_g[0]; sh.rp[1] = pv_g[1]; sh.rp[2] = pv_g[2];
+                    sh.rp[0] = pv_r[0]; sh.rp[1] = pv_r[1]; sh.rp[2] = pv_r[2];
                     sh.rescan = 1;
                 }
             }
@@ -1753,7 +1896,7 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
             for (int pass = (term == 2) ? 0 : 1; pass < 2; ++pass) {
                 if (pass == 1 && !sh.rescan) break;
                 if (tid == 0) {
-                    const double* at = (pass == 0) ? pv_g : sh.rp;  // (pv_g: prev_pose, untouched until phase 6)
+                    const double* at = (pass == 0) ? pv_r : sh.rp;  // (prev_pose as the step found it; the array is untouched until phase 6)
                     sh.next_chunk = 0; sh.park_count = 0; sh.park_next = 0;
                     sh.lx = (float)at[0]; sh.ly = (float)at[1]; sh.lth = (float)at[2];
                     nv::xy_to_ij_f32(sh.lx, sh.ly, c, sh.i0, sh.j0);
@@ -1791,15 +1934,15 @@ __device__ __forceinline__ void step_arena(const navsim_config& c, const navsim_
     if (tid == 0) {
         float* tail = obs_row + (size_t)S * B;
         double yaw = nv::wrap_pi(sh.rp[2]);                     // env.py:454
-        double pxy0 = fresh ? sh.rp[0] : pv_g[0];               // env.py:449-452
-        double pxy1 = fresh ? sh.rp[1] : pv_g[1];
-        double v0 = fresh ? 0.0 : pa_g[0], v1 = fresh ? 0.0 : pa_g[1];
+        double pxy0 = fresh ? sh.rp[0] : pv_r[0];               // env.py:449-452
+        double pxy1 = fresh ? sh.rp[1] : pv_r[1];
+        double v0 = fresh ? 0.0 : pa_r[0], v1 = fresh ? 0.0 : pa_r[1];
         tail[0] = (float)pxy0; tail[1] = (float)pxy1;
         tail[2] = (float)sh.rp[0]; tail[3] = (float)sh.rp[1];
         tail[4] = (float)v0; tail[5] = (float)v1;
         tail[6] = (float)yaw;
         if (io.achieved_goal) { io.achieved_goal[2 * e] = (float)sh.rp[0]; io.achieved_goal[2 * e + 1] = (float)sh.rp[1]; }
-        if (io.desired_goal) { io.desired_goal[2 * e] = (float)goal_g[0]; io.desired_goal[2 * e + 1] = (float)goal_g[1]; }
+        if (io.desired_goal) { io.desired_goal[2 * e] = (float)goal_r[0]; io.desired_goal[2 * e + 1] = (float)goal_r[1]; }
         // state for the next step (env.py:725-727)
         rp_g[0] = sh.rp[0]; rp_g[1] = sh.rp[1]; rp_g[2] = sh.rp[2];
         if (fresh) { pa_g[0] = 0.0; pa_g[1] = 0.0; st.n_hist[e] = (S - 1 < 1) ? S - 1 : 1; }
