@@ -1543,7 +1543,7 @@ typedef struct navsim_lookahead_obs_out {
  *     and io.obs_prev = obs_prev writes for arena e from the same state.  Under NAVSIM_AUTORESET_SAME_STEP a candidate with done
  *     set equals io.final_obs / io.final_goals, every other candidate io.obs and the goals.  The first observation of a
  *     restarted episode is not modelled.  With NAVSIM_LOOKOBS_NOISE_OFF the nine shared outputs equal navsim_lookahead's at
- *     R = range_max.
+ *     R = range_max.  Observations for H > 1 steps: navsim_rollout_obs.
  * NAVSIM_E_ARG, before anything touches the device: everything navsim_lookahead refuses with NAVSIM_E_ARG (there is no R); a
  * noise that is neither constant; out->scan, tail, goals or truncated NULL; n_scan_stack < 1; out->obs with n_scan_stack > 1 and
  * obs_prev or st->n_hist NULL; with NAVSIM_LOOKOBS_NOISE_STEP and cfg.add_scan_noise, st->scan_noise_std or st->episode NULL.
@@ -1604,7 +1604,8 @@ typedef struct navsim_rollout_out {
  *     rows h >= length are 0; the crash revert and any restart are not modelled.  ret, discomfort_steps and min_margin run over
  *     the evaluated steps, outcome and distance are the last evaluated step's.  skip && skip[e]: status[e] = 0 and every other
  *     element of the arena's rows 0, nothing of the arena is read; else status 1.
- *  5. No scan noise, as in the lookahead: with noise on the values are the noise-free outcome.
+ *  5. No scan noise, as in the lookahead: with noise on the values are the noise-free outcome (navsim_rollout_obs draws each
+ *     future step's own noise and returns the observation rows as well).
  *  6. NAVSIM_PED_EXTERNAL: the commands of the call are held for all H steps.  NAVSIM_PED_NONE: no pedestrians.
  *  7. What the rollout leaves out: the real step gives a pedestrian that comes within 0.5 m of its LAST waypoint a new goal and
  *     a new route (env.py:666-680: a draw from the spawn table inside the step, or st->ped_due and the navsim_replan launch).  The
@@ -1643,7 +1644,8 @@ typedef struct navsim_rollout_out {
  * with twenty an arena, about half of the step kernel's time for one real step of the same arenas (80.6 / 145.8 us); (K, H) =
  * (16, 8) is 5.08 / 10.15 ms, (64, 16) 38.5 / 78.3 ms: x 1.44 - 1.53 resp. x 2.39 - 2.76 of H navsim_lookahead launches at the same K.
  * Out of scope: pedestrians driven by navsim_ped_orca or navsim_ped_policy (their commands come from launches of their own);
- * re-plans inside the horizon (rules 7 and 8); anything behind an episode's end (rule 4). */
+ * re-plans inside the horizon (rules 7 and 8); anything behind an episode's end (rule 4).  Noise-aware outcomes and the
+ * observations of the H steps: navsim_rollout_obs. */
 int navsim_rollout(const navsim_config* cfg, const navsim_state* st, const navsim_rollout_params* p,
                    const double* actions /* [E,K,H,2] */, const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */,
                    const uint8_t* skip /* [E] or NULL */, const navsim_rollout_out* out, void* stream);
@@ -1839,6 +1841,84 @@ typedef struct navsim_ped_forecast_out {    /* time-major: at step h the N slots
 int navsim_ped_forecast(const navsim_config* cfg, const navsim_state* st, const navsim_ped_forecast_params* p,
                         const double* actions /* [E,H,2] or NULL */, const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */,
                         const uint8_t* skip /* [E] or NULL */, const navsim_ped_forecast_out* out, void* stream);
+
+/* ---- rollout observations: the whole return of the next H navsim_step calls for each of K action sequences of an arena -----------
+ * navsim_rollout carries an arena through H steps and returns scalars, under a short cap and without scan noise;
+ * navsim_lookahead_obs returns everything the step returns, with the step's own noise draw, for one step.  This entry does both:
+ * the observation row, the goals, the reward and the outcome of every step of every sequence, with the noise the h-th future
+ * step will draw -- the obs of an n-step or model-value-expansion target sum gamma^h r_h + gamma^H V(obs_H), of a learned value
+ * at the leaves of a depth-H search, of terminal-value MPC, of multi-step model-based augmentation with the simulator as the
+ * model.  Without it each costs a copy of the whole state, H steps of EVERY arena and a restore per sequence.
+ * BUILD-DEFINED as an entry; every value is the step's own arithmetic (env.py:591-728 as DESIGN.md section 6 restates it). */
+typedef struct navsim_rollout_obs_params {
+    int32_t n_seq;       /* K, 1 .. NAVSIM_ROLLOUT_MAX_K */
+    int32_t horizon;     /* H, 1 .. NAVSIM_ROLLOUT_MAX_H */
+    int32_t noise;       /* NAVSIM_LOOKOBS_NOISE_OFF / NAVSIM_LOOKOBS_NOISE_STEP */
+    double  gamma;       /* discount of `ret`, 0 .. 1 */
+} navsim_rollout_obs_params;
+
+typedef struct navsim_rollout_obs_out {
+    /* navsim_rollout_out's ten arrays, same shapes and meanings (min_margin: the lookahead observations' margin, i.e. on the
+       noisy full-range ranges) */
+    double*  reward;           /* [E,K,H] */
+    double*  pose;             /* [E,K,H,3] */
+    double*  ret;              /* [E,K] */
+    int32_t* length;           /* [E,K] */
+    uint8_t* outcome;          /* [E,K] */
+    int32_t* discomfort_steps; /* [E,K] */
+    float*   min_margin;       /* [E,K] */
+    double*  distance;         /* [E,K] */
+    int32_t* exact_steps;      /* [E,K] */
+    uint8_t* status;           /* [E] */
+    float*   obs_last;         /* [E,K,S*B+7]   the row of the sequence's last evaluated step */
+    float*   goals_last;       /* [E,K,4]       achieved_goal (2), desired_goal (2) of that step */
+    float*   obs_all;          /* [E,K,H,S*B+7] the row of every step, or NULL: not written */
+    float*   goals_all;        /* [E,K,H,4]     or NULL (both or neither) */
+} navsim_rollout_obs_out;
+
+/* ONE launch (a workgroup per arena and sequence; kernels_rollout_obs.hpp), no device-to-host copy, nothing that blocks, no
+ * allocation, and it WRITES NOTHING BUT `out`: the state is read-only.  actions, ped_cmd and skip as navsim_rollout's, obs_prev
+ * as navsim_lookahead_obs's.  B = cfg.n_beams, S = cfg.n_scan_stack, D = S*B + 7, K = p->n_seq, H = p->horizon.  Per arena e and
+ * sequence k, for h = 0 .. H-1:
+ *  1. Carry, end, external commands, what is left out, exactness and skip are navsim_rollout's rules 2, 3, 4, 6, 7 and 8
+ *     unchanged: a sequence ends at its first done step; length, outcome, exact_steps, ret, discomfort_steps, distance and
+ *     status keep their definitions.  Rows h >= length are 0, in obs_all and goals_all too; a skipped arena's rows are all 0,
+ *     obs_last and goals_last included.
+ *  2. Scan of step h: navsim_lookahead_obs's rule 4 from the carried state -- the march limit, the cull and the clip of
+ *     range_max -- with the noise key step_key_h = episode[e] * 2^32 + (steps[e] + 1 + h) * 2, the draw the h-th future step
+ *     will make.  Crash, discomfort, ratio, reward, time limit and margin come from those ranges: navsim_lookahead_obs's rule 5
+ *     with the carried prev_pose, prev_action and steps.  min_margin is the minimum of that margin over the evaluated steps.
+ *  3. A step h that crashes ends the sequence, and its row takes the reference's re-scan (navsim_lookahead_obs's rule 6): from
+ *     the carried prev_pose -- for h = 0 prev_pose[e], for h >= 1 (pose[e,k,h-1] x, y, wrap_pi of its yaw), what the step's
+ *     phase 6 stores -- with the sequence's OWN pedestrians at t + h + 1 and the key step_key_h + 1.  It is computed per
+ *     sequence: sequences share no pedestrians beyond h = 0.  The row pose of that step is the carried prev_pose;
+ *     pose[e,k,h] stays the pose the step scanned from, as in navsim_rollout.
+ *  4. Row h [D]: the newest slot S - 1 is the scan of rule 2 or 3; slot j < S - 1 is slot j + 1 of the previous row where
+ *     S - 1 - j <= n_hist_h, else the newest scan.  The previous row is the sequence's own row h - 1, obs_prev[e] for h = 0.
+ *     n_hist_0 = st->n_hist[e], n_hist_{h+1} = min(n_hist_h + 1, S - 1) (the step's phase 6).  Tail and goals are
+ *     navsim_lookahead_obs's rule 7 on the carried values: the carried prev_pose xy, the row pose xy, the carried prev_action,
+ *     wrap_pi(row pose yaw); goals = (row pose xy, robot_goal[e]).  obs_last / goals_last are row length - 1; obs_all /
+ *     goals_all, when given, hold every row.
+ *  5. PROPERTY with NAVSIM_LOOKOBS_NOISE_STEP, noise on or off: for every h < min(length, exact_steps), reward, pose, row h and
+ *     goals h equal, bit for bit, what the h-th of H consecutive navsim_step calls under NAVSIM_AUTORESET_NONE writes for arena
+ *     e from the same state, with io.action[e] = actions[e,k,h] and io.obs_prev the previous call's io.obs (obs_prev for the
+ *     first); outcome, distance, obs_last and goals_last do too when length - 1 < exact_steps.  Under
+ *     NAVSIM_AUTORESET_SAME_STEP a done row equals io.final_obs / io.final_goals.  With NAVSIM_LOOKOBS_NOISE_OFF the ten shared
+ *     outputs equal navsim_rollout's at R = range_max.  With H = 1, under either noise setting, every output equals
+ *     navsim_lookahead_obs's: obs_last its obs, goals_last its goals, the scalars as navsim_rollout's PROPERTY maps them.
+ * NAVSIM_E_ARG, before anything touches the device: everything navsim_rollout refuses with NAVSIM_E_ARG (there is no R); a
+ * noise that is neither constant; out->obs_last or goals_last NULL; exactly one of out->obs_all / goals_all NULL;
+ * n_scan_stack < 1; n_scan_stack > 1 with obs_prev or st->n_hist NULL; with NAVSIM_LOOKOBS_NOISE_STEP and cfg.add_scan_noise,
+ * st->scan_noise_std or st->episode NULL.  NAVSIM_E_UNSUPPORTED: as navsim_rollout, the dynamic LDS being the same (12 bytes per
+ * beam and the pedestrians' share: the older scans of a row are read back from the rows the same threads stored, not kept in
+ * LDS); 1.6 KB of static LDS.  n_envs == 0: NAVSIM_OK, nothing is launched.
+ * Cost: profiles/r27_rollout_obs/summary.txt (README, "Rollout observations").
+ * Out of scope: pedestrians driven by navsim_ped_orca or navsim_ped_policy; re-plans inside the horizon; the first observation
+ * of a restarted episode; using this launch inside navsim_mppi. */
+int navsim_rollout_obs(const navsim_config* cfg, const navsim_state* st, const navsim_rollout_obs_params* p,
+                       const double* actions /* [E,K,H,2] */, const double* ped_cmd /* [E,N,2] or NULL: st->ped_cmd */,
+                       const float* obs_prev /* [E,S*B+7] or NULL */, const uint8_t* skip /* [E] or NULL */,
+                       const navsim_rollout_obs_out* out, void* stream);
 
 /* Name of the fused step kernel as rocprofv3 reports it (bench.py / profiles). */
 const char* navsim_step_kernel_name(void);

@@ -28,6 +28,7 @@
 //   kernels_lookahead.hpp    action lookahead: the step's outcomes for K candidate actions per arena (navsim_lookahead)
 //   kernels_lookahead_obs.hpp  lookahead observations: the step's whole return for K candidate actions per arena (navsim_lookahead_obs)
 //   kernels_rollout.hpp      action-sequence rollout: the next H steps' outcomes for K action sequences per arena (navsim_rollout)
+//   kernels_rollout_obs.hpp  rollout observations: the next H steps' whole returns for K action sequences per arena (navsim_rollout_obs)
 //   kernels_mppi.hpp         MPPI local planner: sampled plans, the rollout's launch, the weighted update (navsim_mppi)
 //   kernels_ped_forecast.hpp pedestrian forecast: the pedestrians' next H poses per arena, one launch (navsim_ped_forecast)
 //   step_plan.hpp        launch geometry of the fused step, the descriptors of a launch and the march-rule dispatch (shared by this
@@ -61,6 +62,7 @@ namespace {
 #include "kernels_lookahead.hpp"
 #include "kernels_lookahead_obs.hpp"
 #include "kernels_rollout.hpp"
+#include "kernels_rollout_obs.hpp"
 #include "kernels_mppi.hpp"
 #include "kernels_ped_forecast.hpp"
 
@@ -569,6 +571,18 @@ int launch_rollout(const navsim_config* c, const navsim_state* st, const Rollout
     const size_t lds = rollout_lds_bytes(c);
     return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
         auto kernel = rollout_kernel<F, decltype(rule)::value, RECT>;
+        if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
+        kernel<<<(unsigned)((size_t)c->n_envs * a.K), kRolloutBlock, lds, s>>>(*c, *st, a);
+        return launch_status();
+    });
+}
+
+// navsim_rollout_obs: a workgroup per (arena, sequence), the forms of launch_rollout
+template <typename F, bool RECT>
+int launch_rollout_obs(const navsim_config* c, const navsim_state* st, const RolloutObsArgs& a, hipStream_t s) {
+    const size_t lds = rollout_obs_lds_bytes(c);
+    return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
+        auto kernel = rollout_obs_kernel<F, decltype(rule)::value, RECT>;
         if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
         kernel<<<(unsigned)((size_t)c->n_envs * a.K), kRolloutBlock, lds, s>>>(*c, *st, a);
         return launch_status();
@@ -1824,6 +1838,34 @@ int navsim_rollout(const navsim_config* c, const navsim_state* st, const navsim_
     if (rc != NAVSIM_OK) return rc;
     if (c->n_envs == 0) return NAVSIM_OK;
     return rollout_launch(c, st, p, actions, ped_cmd, skip, out, (hipStream_t)stream);
+}
+
+int navsim_rollout_obs(const navsim_config* c, const navsim_state* st, const navsim_rollout_obs_params* p, const double* actions,
+                       const double* ped_cmd, const float* obs_prev, const uint8_t* skip, const navsim_rollout_obs_out* out,
+                       void* stream) {
+    (void)hipGetLastError();
+    if (!c || !st || !p || !actions || !out) return NAVSIM_E_ARG;
+    if (p->noise != NAVSIM_LOOKOBS_NOISE_OFF && p->noise != NAVSIM_LOOKOBS_NOISE_STEP) return NAVSIM_E_ARG;
+    if (!out->obs_last || !out->goals_last || (out->obs_all == nullptr) != (out->goals_all == nullptr)) return NAVSIM_E_ARG;
+    if (c->n_scan_stack < 1) return NAVSIM_E_ARG;
+    if (c->n_scan_stack > 1 && (!obs_prev || !st->n_hist)) return NAVSIM_E_ARG;
+    const bool noise = p->noise == NAVSIM_LOOKOBS_NOISE_STEP && c->add_scan_noise;
+    if (noise && (!st->scan_noise_std || !st->episode)) return NAVSIM_E_ARG;
+    // everything navsim_rollout refuses, at R = range_max (a range_max that is no valid R is refused as its R would be); the
+    // dynamic LDS is the rollout's (rollout_obs_lds_bytes)
+    const navsim_rollout_params rp = {p->n_seq, p->horizon, c->range_max, p->gamma};
+    const navsim_rollout_out ro = {out->reward, out->pose, out->ret, out->length, out->outcome, out->discomfort_steps,
+                                   out->min_margin, out->distance, out->exact_steps, out->status};
+    const int rc = rollout_check(c, st, &rp, actions, ped_cmd, &ro);
+    if (rc != NAVSIM_OK) return rc;
+    if (c->n_envs == 0) return NAVSIM_OK;
+    RolloutObsArgs a = {};
+    a.out = *out; a.actions = actions; a.ped_cmd = c->ped_model == NAVSIM_PED_EXTERNAL ? ped_cmd : nullptr; a.obs_prev = obs_prev;
+    a.skip = skip; a.K = p->n_seq; a.H = p->horizon; a.noise = noise ? 1 : 0; a.gamma = p->gamma;
+    hipStream_t s = (hipStream_t)stream;
+    if (c->field_format == NAVSIM_FIELD_U16T)
+        return st->rect_table ? launch_rollout_obs<FieldU16T, true>(c, st, a, s) : launch_rollout_obs<FieldU16T, false>(c, st, a, s);
+    return launch_rollout_obs<FieldF32, false>(c, st, a, s);
 }
 
 int navsim_ped_forecast(const navsim_config* c, const navsim_state* st, const navsim_ped_forecast_params* p, const double* actions,

@@ -323,6 +323,20 @@ class NavsimRolloutOut(C.Structure):
     _fields_ = [(name, _P) for name in ROLLOUT_OUT]
 
 
+# navsim_rollout_obs: the rule's parameters, the rollout's ten arrays and the rows (dtype, trailing shape behind E; K = n_seq,
+# H = horizon, D = n_scan_stack * n_beams + OBS_TAIL; obs_all and goals_all are optional: the call takes NULL for both)
+class NavsimRolloutObsParams(C.Structure):
+    _fields_ = [("n_seq", C.c_int32), ("horizon", C.c_int32), ("noise", C.c_int32), ("gamma", C.c_double)]
+
+
+ROLLOUT_OBS_OUT = dict(ROLLOUT_OUT, obs_last=("float32", ("K", "D")), goals_last=("float32", ("K", 4)),
+                       obs_all=("float32", ("K", "H", "D")), goals_all=("float32", ("K", "H", 4)))
+
+
+class NavsimRolloutObsOut(C.Structure):
+    _fields_ = [(name, _P) for name in ROLLOUT_OBS_OUT]
+
+
 # navsim_mppi: the rule's parameters, the persistent workspace (with navsim_rollout's ten arrays inside) and the five output arrays
 # (dtype, trailing shape behind E; K = n_samples, H = horizon)
 MPPI_MAX_ITERATIONS = 8
@@ -602,6 +616,9 @@ def declare(lib, suffix=""):
                             _P, _P, C.POINTER(NavsimMppiWs), C.POINTER(NavsimMppiOut), _P])
     if not suffix and hasattr(lib, "navsim_ped_forecast"):              # (likewise)
         sig("navsim_ped_forecast", [cfgp, stp, C.POINTER(NavsimPedForecastParams), _P, _P, _P, C.POINTER(NavsimPedForecastOut), _P])
+    if not suffix and hasattr(lib, "navsim_rollout_obs"):               # (likewise)
+        sig("navsim_rollout_obs", [cfgp, stp, C.POINTER(NavsimRolloutObsParams), _P, _P, _P, _P,
+                                   C.POINTER(NavsimRolloutObsOut), _P])
     sig("navsim_reset_obs", [cfgp, stp, iop, _P] + stream)
     sig("navsim_restart", [cfgp, stp, _P] + stream)
     return lib
@@ -622,6 +639,7 @@ EXPORTS = (
     "navsim_episode_stats_update", "navsim_episode_stats_clear", "navsim_ped_observe",
     "navsim_goal_path", "navsim_goal_field_bytes", "navsim_debug_goal_path_sweeps", "navsim_dwa", "navsim_local_map",
     "navsim_scan_labels", "navsim_lookahead", "navsim_lookahead_obs", "navsim_rollout", "navsim_mppi", "navsim_ped_forecast",
+    "navsim_rollout_obs",
     "navsim_sizeof_config", "navsim_sizeof_state", "navsim_sizeof_step_io", "navsim_debug_math", "navsim_debug_xy_to_ij",
     "navsim_debug_gather", "navsim_debug_kernarg_layout", "navsim_debug_set_stamps", "navsim_debug_spawn_decisions",
 )

@@ -188,6 +188,18 @@ and default to the reference's behaviour for num_envs == 1:
                     rows are the step's own, bit for bit with scan noise off (without pedestrians: the whole horizon).
                     rollout_params: dict(horizon=8, range=, gamma=1.0); range as lookahead_params'.  Not with pedestrian_model
                     'orca' or 'policy'.  None (default): nothing is allocated or launched.
+    rollout_obs     K in 1 .. 256: env.rollout_obs(actions) returns the WHOLE return of the next H step() calls for each of K action
+                    sequences per arena -- rollout()'s values plus 'observation' {'observation' [E,K,D], 'achieved_goal',
+                    'desired_goal' [E,K,2]} of every sequence's last evaluated step -- from one launch that only reads the state
+                    (navsim_rollout_obs): the obs of an n-step target sum gamma^h r_h + gamma^H V(obs_H), of a learned value at
+                    the leaves of a depth-H search, of terminal-value MPC.  Every step scans at the lidar's full range and draws
+                    the noise that future step itself will draw, so rows, goals, rewards and outcomes below exact_steps are
+                    bit-identical to the steps', noise on or off; a step that crashes ends its sequence and carries the
+                    reference's re-scan from the reverted pose.  rollout_obs_params: dict(horizon=8, gamma=1.0, noise='step' |
+                    'off', rows='last' | 'all'); rows='all' adds 'observations', the same three keys with an H axis
+                    ([E,K,H,D], [E,K,H,2]: E*K*H*(S*B+7)*4 bytes per set; rows behind a sequence's end are 0).  Independent of
+                    rollout= and lookahead_obs=.  Not with pedestrian_model 'orca' or 'policy'.  None (default): nothing is
+                    allocated or launched.
     ped_forecast    H in 1 .. 32: info['ped_forecast'] holds where every pedestrian will be after each of the next H step() calls,
                     time-major -- 'pose' [E,H,N,3], 'vel' [E,H,N,2], 'rel' [E,H,N,2] (the position in the robot's CURRENT frame),
                     'robot_pose' [E,H,3] (the robot pose assumed after step h), 'min_dist' / 'min_step' [E,N] (the predicted
@@ -362,7 +374,7 @@ class NavGymEnv(_EnvBase):
                  episode_stats=False, observe_humans=None, observe_params=None, goal_path=False, goal_path_params=None,
                  local_planner=None, local_planner_params=None, observe_local_map=None, local_map_params=None,
                  scan_labels=False, lookahead=None, lookahead_params=None, lookahead_obs=None, lookahead_obs_params=None,
-                 rollout=None, rollout_params=None,
+                 rollout=None, rollout_params=None, rollout_obs=None, rollout_obs_params=None,
                  ped_forecast=None, ped_forecast_params=None):
         # EzPickle (env.py:56-78): what the environment was made with -- this call's own arguments -- is what a pickle of it carries
         self._ctor_kwargs = {k: v for k, v in locals().items() if k != "self"}
@@ -638,6 +650,24 @@ class NavGymEnv(_EnvBase):
         self.rollout_k = None if rollout is None else int(rollout)
         self.rollout_h = None if rollout is None else int((rollout_params or {}).get("horizon", self._ROLLOUT_HORIZON))
         self.rollout_params = None if rollout_params is None else dict(rollout_params)
+        # rollout observations (navsim_rollout_obs): the next H steps' whole returns for K action sequences, on request (env.rollout_obs())
+        _check_params("rollout_obs_params", rollout_obs_params, rollout_obs is not None, "rollout_obs=K",
+                      ("horizon",) + _simmod.ROLLOUT_OBS_KEYS)
+        if rollout_obs is not None:
+            if not (isinstance(rollout_obs, numbers.Integral) and not isinstance(rollout_obs, bool)
+                    and 1 <= rollout_obs <= abi.ROLLOUT_MAX_K):
+                raise ValueError("rollout_obs must be None or an int in 1 .. %d, not %r" % (abi.ROLLOUT_MAX_K, rollout_obs))
+            horizon = (rollout_obs_params or {}).get("horizon", self._ROLLOUT_HORIZON)
+            if not (isinstance(horizon, numbers.Integral) and not isinstance(horizon, bool) and 1 <= horizon <= abi.ROLLOUT_MAX_H):
+                raise ValueError("rollout_obs_params: horizon must be an int in 1 .. %d, not %r" % (abi.ROLLOUT_MAX_H, horizon))
+            _simmod.rollout_obs_choice(dict(_simmod.rollout_obs_defaults(),
+                                            **{k: v for k, v in (rollout_obs_params or {}).items() if k != "horizon"}))
+            if pedestrian_model in ("orca", "policy"):
+                raise ValueError("rollout_obs is not available with pedestrian_model=%r: the pedestrians' commands come from a launch "
+                                 "in front of the step that has not run yet" % pedestrian_model)
+        self.rollout_obs_k = None if rollout_obs is None else int(rollout_obs)
+        self.rollout_obs_h = None if rollout_obs is None else int((rollout_obs_params or {}).get("horizon", self._ROLLOUT_HORIZON))
+        self.rollout_obs_params = None if rollout_obs_params is None else dict(rollout_obs_params)
         # pedestrian forecast (navsim_ped_forecast): the pedestrians' next H poses per arena, one launch behind the step
         _check_params("ped_forecast_params", ped_forecast_params, ped_forecast is not None, "ped_forecast=H", self._FORECAST_KEYS)
         self.ped_forecast_h = self.ped_forecast_robot = self.ped_forecast_model = None
@@ -850,6 +880,9 @@ class NavGymEnv(_EnvBase):
             if self.rollout_k:
                 self.sim.enable_rollout(self.rollout_k, self.rollout_h,
                                         {k: v for k, v in (self.rollout_params or {}).items() if k != "horizon"})
+            if self.rollout_obs_k:
+                self.sim.enable_rollout_obs(self.rollout_obs_k, self.rollout_obs_h,
+                                            {k: v for k, v in (self.rollout_obs_params or {}).items() if k != "horizon"})
             if self.ped_forecast_h:
                 self.sim.enable_ped_forecast(self.ped_forecast_h, dict(
                     robot="actions" if self.ped_forecast_robot == "plan" else self.ped_forecast_robot, model=self.ped_forecast_model))
@@ -1302,6 +1335,42 @@ class NavGymEnv(_EnvBase):
         if E == 1:
             return {k: v[0] for k, v in sim.rollout_host().items()}
         return dict(out)
+
+    def rollout_obs(self, actions, human_actions=None):
+        """The whole return of the next H step() calls if an arena executed each of K action sequences, from the current state,
+        which is only read (NavGymEnv(rollout_obs=K, rollout_obs_params=dict(horizon=H)); navsim_rollout_obs, one launch):
+        rollout()'s dict -- here every step scans at the lidar's full range with the scan noise that future step itself would draw
+        (rollout_obs_params: noise='step'), so the values below exact_steps are the steps' own, noise on or off, and 'min_margin'
+        is taken on those ranges -- plus 'observation': {'observation' [E,K,D] float32, 'achieved_goal' [E,K,2], 'desired_goal'
+        [E,K,2]} as step() returns it at the sequence's last evaluated step (behind a crash the reference's re-scan from the
+        reverted pose; for a sequence that ends the terminal row, not the first row of the next episode).  With rows='all' also
+        'observations': the same three keys for every step, [E,K,H,D] and [E,K,H,2], 0 behind the last evaluated step.
+        actions, human_actions: as rollout()'s.  Next-step auto-reset: an arena whose `done` is set is skipped (status 0, rows 0).
+        num_envs > 1: torch views, intact through the next step(); num_envs == 1: NumPy rows [K,...] from one device -> host copy
+        (the arrays of 'observation' and 'observations' as float64, like step()'s)."""
+        if self.rollout_obs_k is None:
+            raise RuntimeError("rollout_obs() needs NavGymEnv(rollout_obs=K)")
+        if self.pedestrian_model == "external" and human_actions is None:
+            raise ValueError("rollout_obs() with pedestrian_model='external' needs human_actions")
+        if self.sim is None:
+            raise RuntimeError("call reset() before rollout_obs()")
+        sim, E = self.sim, self.num_envs
+        actions = self._rollout_actions(actions, E, self.rollout_obs_k, self.rollout_obs_h)
+        skip = sim.out["done"] if self.auto_reset and self.autoreset_mode == "next_step" and sim.out is not None else None
+        out = sim.rollout_obs(actions, ped_cmd=human_actions if self.pedestrian_model == "external" else None, skip=skip)
+        if E == 1:
+            out = {k: v[0] for k, v in sim.rollout_obs_host().items()}
+            wide = lambda v: v.astype(np.float64)
+        else:
+            out = dict(out)
+            wide = lambda v: v
+        obs, goals = out.pop("obs_last"), out.pop("goals_last")
+        out["observation"] = {"observation": wide(obs), "achieved_goal": wide(goals[..., :2]), "desired_goal": wide(goals[..., 2:])}
+        if "obs_all" in out:
+            obs, goals = out.pop("obs_all"), out.pop("goals_all")
+            out["observations"] = {"observation": wide(obs), "achieved_goal": wide(goals[..., :2]),
+                                   "desired_goal": wide(goals[..., 2:])}
+        return out
 
     @staticmethod
     def _rollout_actions(actions, E, K, H):

@@ -5,6 +5,7 @@ path happens in libnavsim_hip.so.
 """
 import collections
 import ctypes as C
+import numbers
 import os
 
 import numpy as np
@@ -455,6 +456,30 @@ def rollout_defaults(cfg, discomfort_max=0.0):
     (lookahead_defaults, lookahead_range_min), and gamma, the discount of `ret` (1.0: the plain sum of rewards).  The sequence
     count K and the horizon H are arguments of NavSim.enable_rollout."""
     return dict(range=lookahead_defaults(cfg, discomfort_max)["range"], gamma=1.0)
+
+
+ROLLOUT_OBS_KEYS = ("gamma", "noise", "rows")
+ROLLOUT_OBS_ROWS = ("last", "all")
+
+
+def rollout_obs_defaults():
+    """The parameters of navsim_rollout_obs as a dict: gamma, the discount of `ret` (1.0: the plain sum of rewards); noise 'step'
+    (the scan noise each future step itself would draw; 'off': none); rows 'last' (the observation row of every sequence's last
+    evaluated step; 'all': the rows of all H steps as well).  The sequence count K and the horizon H are arguments of
+    NavSim.enable_rollout_obs."""
+    return dict(gamma=1.0, noise="step", rows="last")
+
+
+def rollout_obs_choice(d):
+    """(gamma, abi.LOOKOBS_NOISE_* constant, 'last' | 'all') of a parameter dict; anything else raises ValueError."""
+    gamma = d["gamma"]
+    if isinstance(gamma, bool) or not isinstance(gamma, numbers.Real) or not 0.0 <= gamma <= 1.0:
+        raise ValueError("rollout_obs gamma must lie in [0, 1], not %r" % (gamma,))
+    if not (isinstance(d["noise"], str) and d["noise"] in LOOKAHEAD_OBS_NOISE):
+        raise ValueError("rollout_obs noise must be 'step' or 'off', not %r" % (d["noise"],))
+    if not (isinstance(d["rows"], str) and d["rows"] in ROLLOUT_OBS_ROWS):
+        raise ValueError("rollout_obs rows must be 'last' or 'all', not %r" % (d["rows"],))
+    return float(gamma), LOOKAHEAD_OBS_NOISE[d["noise"]], d["rows"]
 
 
 PED_FORECAST_KEYS = ("robot", "model")
@@ -1999,6 +2024,55 @@ class NavSim(object):
     def rollout_host(self):
         """The current set of rollout()'s outputs as NumPy arrays, from ONE device -> host copy."""
         return self._product("rollout").host(self.cur)
+
+    # ---- rollout observations: the WHOLE return of the next H step() calls -- row, goals, reward, pose, outcome -- for each of K
+    # action sequences per arena, one launch that only reads the state (include/navsim.h navsim_rollout_obs)
+    def enable_rollout_obs(self, K, H, params=None):
+        """Allocates two sets of outputs (abi.ROLLOUT_OBS_OUT, [E,K,...] and status [E]: they flip with self.cur like everything a
+        step returns), an action buffer float64 [E,K,H,2] and a command buffer float64 [E,N,2].  params: a dict of overrides of
+        rollout_obs_defaults(), or None -- gamma in [0, 1]; noise 'step' (the draw each future step itself would make) or 'off';
+        rows 'last' (obs_last [E,K,S*B+7] and goals_last [E,K,4] only) or 'all' (obs_all [E,K,H,S*B+7] and goals_all [E,K,H,4] as
+        well: E*K*H*(S*B+7)*4 bytes per set).  Independent of enable_rollout and enable_lookahead_obs."""
+        import torch
+        cfg = self.cfg
+        if not 1 <= int(K) <= abi.ROLLOUT_MAX_K:
+            raise ValueError("rollout_obs evaluates 1 .. %d sequences per arena, not %r" % (abi.ROLLOUT_MAX_K, K))
+        if not 1 <= int(H) <= abi.ROLLOUT_MAX_H:
+            raise ValueError("rollout_obs looks 1 .. %d steps ahead, not %r" % (abi.ROLLOUT_MAX_H, H))
+        d = _overridden(rollout_obs_defaults(), params, "rollout_obs", ROLLOUT_OBS_KEYS)
+        gamma, noise, rows = rollout_obs_choice(d)
+        p = abi.NavsimRolloutObsParams(n_seq=int(K), horizon=int(H), noise=noise, gamma=gamma)
+        extra = dict(actions=torch.zeros((cfg.n_envs, int(K), int(H), 2), dtype=torch.float64, device=self.device),
+                     ped_cmd=torch.zeros((cfg.n_envs, max(cfg.max_peds, 1), 2), dtype=torch.float64, device=self.device))
+        sym = {"K": int(K), "H": int(H), "D": cfg.n_scan_stack * cfg.n_beams + abi.OBS_TAIL}
+        layout = blob_layout(abi.ROLLOUT_OBS_OUT, cfg.n_envs, sym, omit=() if rows == "all" else ("obs_all", "goals_all"))
+        self.products["rollout_obs"] = _StepProduct(self, p, layout, abi.NavsimRolloutObsOut, extra=extra)
+
+    def rollout_obs(self, actions, ped_cmd=None, skip=None):
+        """navsim_rollout_obs of the current state and the current observation (self.obs: what the next step takes as obs_prev)
+        on the current stream: one launch, no device -> host copy, no allocation, and the state is only read.  actions, ped_cmd,
+        skip: as rollout()'s.  Returns the current set -- rollout()'s ten arrays, 'obs_last' [E,K,S*B+7], 'goals_last' [E,K,4]
+        and, with rows='all', 'obs_all' [E,K,H,S*B+7] and 'goals_all' [E,K,H,4] -- intact through the next step."""
+        import torch
+        p, cur = self.products.get("rollout_obs") or self._product("rollout_obs"), self.cur
+        buf = p.extra["actions"]
+        if not (torch.is_tensor(actions) and actions.device == buf.device and actions.dtype == buf.dtype and actions.is_contiguous()
+                and actions.shape == buf.shape):
+            buf.copy_(torch.as_tensor(actions).to(device=buf.device, dtype=buf.dtype).reshape(buf.shape), non_blocking=True)
+            actions = buf
+        if ped_cmd is not None:
+            cmd = p.extra["ped_cmd"]
+            cmd.copy_(torch.as_tensor(ped_cmd).to(device=cmd.device, dtype=cmd.dtype).reshape(cmd.shape), non_blocking=True)
+            ped_cmd = cmd
+        rc = self.lib.navsim_rollout_obs(p.cfg, p.st, p.par, _ptr(actions), _ptr(ped_cmd), _ptr(self.obs_buf[cur]), _ptr(skip),
+                                         p.out[cur], _stream())
+        if rc:
+            check(rc, "navsim_rollout_obs")
+        return p.buf[cur]
+
+    def rollout_obs_host(self):
+        """The current set of rollout_obs()'s outputs as NumPy arrays, from ONE device -> host copy."""
+        return self._product("rollout_obs").host(self.cur)
 
     # ---- MPPI local planner: sampled plans, the rollout's launch and the weighted update on the device, 3 launches an iteration
     # (include/navsim.h navsim_mppi).  Independent of enable_rollout: its K and H are its own
