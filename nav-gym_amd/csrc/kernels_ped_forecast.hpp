@@ -7,7 +7,7 @@
 // One wavefront per arena (a workgroup of kForecastBlock = 64 threads), pedestrian i on lane i (N <= 64), the horizon loop inside,
 // no scan.  Nothing of the robot depends on a pedestrian, so its whole trajectory comes first:
 //   (0) thread RT (thread 0; lane 0 of wavefront 1 in a build of several wavefronts): the step's phase 0 for h = 0 .. H-1 on the
-//       assumed actions, operation for operation as rollout_kernel's thread 64, from the carried pose and with the carried
+//       assumed actions (replay_twist of kernels_replay.hpp; HOLD and STOP are this kernel's own), from the carried pose and the carried
 //       prev_action -- robot_pose[e,h] goes to global memory, and rob[h] = (x, y, prev_v cos th, prev_v sin th) of time t + h to
 //       static LDS: the staged robot of step h (ped_stage_wave's four values; cos / sin are the ones phase 0 needs anyway) and, as
 //       rob[h + 1], the pose min_dist measures from.  Barrier.
@@ -22,7 +22,8 @@
 //   the pair table is written behind barrier (1) of h + 1, and rob is read-only after (0).
 //   External commands and NAVSIM_FORECAST_CONST_VEL need neither LDS nor a barrier inside the loop: nv::set_vel on the held
 //   command, resp. x + vx ((h + 1) dt).
-// Carried per pedestrian, in registers: pose, velocity, waypoint head.  Leg odometry, ped_prev_yaw and the scan are not computed.
+// Carried per pedestrian, in registers (CarriedPed of kernels_replay.hpp, loaded without the lidar's members): pose, velocity,
+// waypoint head.  Leg odometry, ped_prev_yaw and the scan are not computed.
 //
 // Dynamic LDS (ped_forecast_lds_bytes; only with the social force under NAVSIM_FORECAST_TRUE): the four staging arrays
 // [N + 1] float64, rounded up to 16 bytes, and the pair table 16 (N (N - 1) / 2 + N) bytes -- 0.7 + 3.4 KB at 20 pedestrians,
@@ -44,9 +45,9 @@
 // a quarter of the compute unit's wave slots each, so four arenas are resident where sixteen wavefront-arenas are.  What the
 // wide form buys is an ARENA's latency (one round of pair terms instead of four; nine instead of thirty-three at 64
 // pedestrians): a caller with a few arenas and full crowds may build it.  Not measured: 128 threads, a pack of two arenas.
-// Resources (gfx950, -Rpass-analysis=kernel-resource-usage, FieldF32 / FieldU16T / FieldU16TN): 115 VGPRs, 106 SGPRs, 29 / 44 / 35
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage, FieldF32 / FieldU16T / FieldU16TN): 115 VGPRs, 106 SGPRs, 35 / 41 / 34
 // SGPRs spilled to VGPR lanes, no VGPR spill, scratch 0 bytes per lane, occupancy 4 waves per SIMD (sixteen arenas a compute
-// unit; LDS would allow thirty-nine at 20 pedestrians), 1072 bytes of static LDS.  The 256-thread build reports the same
+// unit; LDS would allow thirty-nine at 20 pedestrians), 1072 bytes of static LDS.  The 256-thread build reported the same
 // registers (29 / 42 / 35 SGPR spills).  No scratch in either.
 
 struct PedForecastArgs {
@@ -113,24 +114,8 @@ __global__ __launch_bounds__(kForecastBlock) void ped_forecast_kernel(navsim_con
     // ---- the carried values at h = 0: the state's.  Pedestrian i on lane i of wavefront 0
     const bool is_slot = tid < N, is_ped = tid < n;
     const size_t pq = (size_t)e * N + (is_ped ? tid : 0);
-    double pp[3] = {0.0, 0.0, 0.0}, pvel[2] = {0.0, 0.0}, vpref = 0.0;
-    int head = 0, nw = 1;
-    const double* wp = nullptr;
-    const double* cmd = nullptr;
-    if (is_ped) {
-        pp[0] = st.ped_pose[pq * 3]; pp[1] = st.ped_pose[pq * 3 + 1]; pp[2] = st.ped_pose[pq * 3 + 2];
-        pvel[0] = st.ped_vel[pq * 2]; pvel[1] = st.ped_vel[pq * 2 + 1];
-        if (sfm) {
-            wp = st.ped_waypoints + (pq * c.max_waypoints) * 2;
-            nw = st.ped_n_waypoints[pq];
-            nw = nw < 1 ? 1 : (nw > c.max_waypoints ? c.max_waypoints : nw);         // (a state the step accepts holds 1 .. max_waypoints)
-            head = st.ped_wp_head[pq];
-            head = head < 0 ? 0 : (head > nw - 1 ? nw - 1 : head);
-            vpref = st.ped_v_pref[pq];
-        } else if (truth) {
-            cmd = (a.ped_cmd ? a.ped_cmd : st.ped_cmd) + pq * 2;                     // held for the whole horizon
-        }
-    }
+    CarriedPed cp;                                                                   // (nothing of the lidar's: no scan here)
+    if (is_ped) carried_ped_load<false>(cp, c, st, pq, sfm, truth, a.ped_cmd);       // a command is held for the whole horizon
     // ---- (0) the robot's H poses: the step's phase 0 on the assumed actions, operation for operation
     if (tid == RT) {
         double rp[3] = {st.robot_pose[3 * (size_t)e], st.robot_pose[3 * (size_t)e + 1], st.robot_pose[3 * (size_t)e + 2]};
@@ -140,23 +125,10 @@ __global__ __launch_bounds__(kForecastBlock) void ped_forecast_kernel(navsim_con
             double a0 = 0.0, a1 = 0.0;                                               // NAVSIM_FORECAST_STOP: the zero twist
             if (a.robot == NAVSIM_FORECAST_ACTIONS) {
                 a0 = a.actions[2 * (row0 + h)]; a1 = a.actions[2 * (row0 + h) + 1];
-                if (c.action_kind == NAVSIM_ACTION_WHEELS) {
-                    const double wl = a0, wr = a1;
-                    a0 = c.wheel_radius * (wl + wr) * 0.5;
-                    a1 = c.wheel_radius * (wr - wl) / c.wheel_track;
-                }
             } else if (a.robot == NAVSIM_FORECAST_HOLD) {
                 a0 = hold[0]; a1 = hold[1];                                          // a twist already: the step stored it
             }
-            if (c.clamp_action) {
-                a0 = a0 < c.linvel_lo ? c.linvel_lo : (a0 > c.linvel_hi ? c.linvel_hi : a0);
-                a1 = a1 < c.rotvel_lo ? c.rotvel_lo : (a1 > c.rotvel_hi ? c.rotvel_hi : a1);
-            }
-            if (c.min_turning_radius > 0.0) {                                        // env.py:595-600
-                const double lim = fabs(a1) * c.min_turning_radius;
-                if (a0 >= 0.0) a0 = (a0 > lim) ? a0 : lim;
-                else           a0 = (a0 < -lim) ? a0 : -lim;
-            }
+            replay_twist(c, a.robot == NAVSIM_FORECAST_ACTIONS, a0, a1);
             const double th_old = rp[2];
             const double th = th_old + a1 * dt;                                      // set_vel's intermediate heading
             double s0, c0, s1, c1;
@@ -175,7 +147,7 @@ __global__ __launch_bounds__(kForecastBlock) void ped_forecast_kernel(navsim_con
     __syncthreads();
 
     const double rx0 = rob[0][0], ry0 = rob[0][1], fc = frame[0], fs = frame[1];
-    const double x0 = pp[0], y0 = pp[1];                                             // NAVSIM_FORECAST_CONST_VEL starts every row here
+    const double x0 = cp.pp[0], y0 = cp.pp[1];                                       // NAVSIM_FORECAST_CONST_VEL starts every row here
     const int n_terms = n * (n - 1) / 2 + n;
     int exact = truth ? HZ : 0;
     double md = INFINITY;
@@ -185,8 +157,8 @@ __global__ __launch_bounds__(kForecastBlock) void ped_forecast_kernel(navsim_con
         if (sfm && n > 0) {
             // ---- (1) waypoint pop and staging (ped_stage_wave on the carried values)
             if (is_ped) {
-                head = ped_pop_waypoints(wp, head, nw, pp);
-                ps.ax[tid] = pp[0]; ps.ay[tid] = pp[1]; ps.avx[tid] = pvel[0]; ps.avy[tid] = pvel[1];
+                cp.head = ped_pop_waypoints(cp.wp, cp.head, cp.nw, cp.pp);
+                ps.ax[tid] = cp.pp[0]; ps.ay[tid] = cp.pp[1]; ps.avx[tid] = cp.pvel[0]; ps.avy[tid] = cp.pvel[1];
             }
             if (tid == 0) { ps.ax[n] = rob[h][0]; ps.ay[n] = rob[h][1]; ps.avx[n] = rob[h][2]; ps.avy[n] = rob[h][3]; }
             __syncthreads();
@@ -195,18 +167,18 @@ __global__ __launch_bounds__(kForecastBlock) void ped_forecast_kernel(navsim_con
             __syncthreads();
             // ---- (3) the pedestrians at t + h + 1
             if (is_ped) {
-                ped_sfm_step(c, field, ps, pair, n, tid, vpref, wp + 2 * head, dt, pp, pvel);
+                ped_sfm_step(c, field, ps, pair, n, tid, cp.vpref, cp.wp + 2 * cp.head, dt, cp.pp, cp.pvel);
                 // the step's predicate for ped_due (ped_finish): the post-move distance to the LAST waypoint under 0.5 m
-                const double ddx = pp[0] - wp[2 * (nw - 1)], ddy = pp[1] - wp[2 * (nw - 1) + 1];
+                const double ddx = cp.pp[0] - cp.wp[2 * (cp.nw - 1)], ddy = cp.pp[1] - cp.wp[2 * (cp.nw - 1) + 1];
                 due = sqrt(ddx * ddx + ddy * ddy) < 0.5;
             }
         } else if (is_ped) {
             if (truth) {
-                nv::set_vel(pp, cmd[0], cmd[1], dt, 0.0, pvel);                      // env.py:662
+                nv::set_vel(cp.pp, cp.cmd[0], cp.cmd[1], dt, 0.0, cp.pvel);          // env.py:662
             } else {
                 const double span = (double)(h + 1) * dt;
-                pp[0] = x0 + pvel[0] * span;
-                pp[1] = y0 + pvel[1] * span;
+                cp.pp[0] = x0 + cp.pvel[0] * span;
+                cp.pp[1] = y0 + cp.pvel[1] * span;
             }
         }
         if (tid < 64 && mask_of(due) != 0 && exact == HZ) exact = h + 1;             // wave-uniform; thread 0 reports it
@@ -214,14 +186,14 @@ __global__ __launch_bounds__(kForecastBlock) void ped_forecast_kernel(navsim_con
             const size_t r = (row0 + h) * N + tid;
             double ax = 0.0, ay = 0.0, x = 0.0, y = 0.0;
             if (is_ped) {
-                ax = pp[0] - rx0; ay = pp[1] - ry0;
+                ax = cp.pp[0] - rx0; ay = cp.pp[1] - ry0;
                 x = fc * ax + fs * ay; y = fc * ay - fs * ax;                        // navsim_ped_observe's rule 3
-                const double dx = pp[0] - rob[h + 1][0], dy = pp[1] - rob[h + 1][1];
+                const double dx = cp.pp[0] - rob[h + 1][0], dy = cp.pp[1] - rob[h + 1][1];
                 const double dist = sqrt(dx * dx + dy * dy);
                 if (dist < md) { md = dist; mstep = h; }
             }
-            a.out.pose[3 * r] = pp[0]; a.out.pose[3 * r + 1] = pp[1]; a.out.pose[3 * r + 2] = pp[2];
-            a.out.vel[2 * r] = pvel[0]; a.out.vel[2 * r + 1] = pvel[1];
+            a.out.pose[3 * r] = cp.pp[0]; a.out.pose[3 * r + 1] = cp.pp[1]; a.out.pose[3 * r + 2] = cp.pp[2];
+            a.out.vel[2 * r] = cp.pvel[0]; a.out.vel[2 * r + 1] = cp.pvel[1];
             a.out.rel[2 * r] = (float)x; a.out.rel[2 * r + 1] = (float)y;
         }
     }

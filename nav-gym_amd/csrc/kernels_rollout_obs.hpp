@@ -2,11 +2,12 @@
 // calls -- observation row, goals, reward, pose, outcome -- if an arena executed the action sequence a_0 .. a_{H-1}, for K sequences
 // per arena, from the current state, which is only read, with the scan noise each of those steps would draw.  Part of the single
 // translation unit navsim_kernels.hip (included inside its anonymous namespace, behind kernels_lookahead_obs.hpp and
-// kernels_rollout.hpp: RollShared's carry, lookobs_scan and lookobs_finish are theirs).
+// kernels_rollout.hpp: lookobs_finish, RollShared's carry and rollout_advance are theirs; the re-scan, the verdict and the reward are
+// kernels_replay.hpp's).
 //
 // rollout_kernel's shape: one workgroup of kRolloutBlock threads per (arena, sequence), the carry of its header (the robot in
-// static LDS, pedestrian i in the registers of lane i of wavefront 0), its step (1) - (5) line for line at the step's own march
-// limit (range_max).  What is new here:
+// static LDS, pedestrian i in the registers of lane i of wavefront 0), its steps (1) - (4) through rollout_advance at the step's own
+// march limit (range_max).  What is new here:
 //   the finish pass -- ONE pass over the beams per step reads the merged range from LDS, clips it, adds the noise of the h-th
 //     future step (the stream of step_key_h = episode << 32 | (steps + 1 + h) * 2; steps and episode are the state's: no carried
 //     value enters the key but h), takes the flags and the margin from the NOISY value as the step does, keeps it in LDS for the
@@ -19,7 +20,7 @@
 //     element is also stored to row h of it; that row is never read back.  When the loop ends, obs_last holds the row of the
 //     last evaluated step with nothing copied;
 //   the crash re-scan -- BEHIND the horizon loop, at most once per sequence: a crash ends the sequence, so the pedestrians of
-//     t + h + 1 still stand in LDS when the loop is left.  lookobs_scan from the carried prev_pose, the key step_key_h + 1; each
+//     t + h + 1 still stand in LDS when the loop is left.  replay_scan from the carried prev_pose, the key step_key_h + 1; each
 //     thread overwrites its beams of the newest slot and of the filled slots, in obs_last and in row h of obs_all;
 //   tail and goals -- behind the loop, all steps at once, step h on lane h of wavefront 1, from the poses and actions the loop
 //     left in static LDS (5 doubles a step), as lookahead_obs_kernel does for its candidates: the float64 atan2 of wrap_pi stays
@@ -27,20 +28,19 @@
 //     the re-scan's lidar pose.
 // Barriers per step: rollout_kernel's.  The re-scan adds four or five per sequence.
 //
-// Dynamic LDS (rollout_obs_lds_bytes): rollout_kernel's, 12 B per beam and the pedestrians' share.  Static LDS: RollObsShared
+// Dynamic LDS (rollout_lds_bytes): rollout_kernel's, 12 B per beam and the pedestrians' share.  Static LDS: RollObsShared
 // (1.5 KB) + the wavefronts' minima.
 //
-// Resources (gfx950, -Rpass-analysis=kernel-resource-usage) of the eleven forms under __launch_bounds__(256, 3): 168 VGPRs in
-// every one, 106 SGPRs, 153 - 160 SGPRs spilled to VGPR lanes, 2 VGPRs spilled, scratch 12 bytes per lane, occupancy 3 waves per
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage) of the eleven forms under __launch_bounds__(256, 3): 167 VGPRs in
+// every one, 106 SGPRs, 144 - 166 SGPRs spilled to VGPR lanes, 2 VGPRs spilled, scratch 12 bytes per lane, occupancy 3 waves per
 // SIMD (rollout_kernel's), 1488 bytes of static LDS.  Without the second bound (NAVSIM_ROLLOUT_OBS_WAVES=2) the compiler settles
 // on 170 VGPRs, two above what three waves allow: no VGPR spill, scratch 0, 146 - 157 spilled SGPRs, occupancy 2.  rollout_kernel
-// holds 164.  Both forms were measured, alternating in one call (profiles/r27_rollout_obs/summary.txt): (K, H) = (16, 8) on
+// holds 168.  Both forms were measured, alternating in one call (profiles/r27_rollout_obs/summary.txt): (K, H) = (16, 8) on
 // the c3-shaped world takes 22.4 ms bounded against 30.9 ms unbounded -- the march is bound by the latency of its dependent
 // loads, the time follows the resident waves, and the two spilled registers do not show.  Where the spill sits was not looked up.
 // Tried and not taken: tail and goals on thread 0 inside the loop (lookahead_obs_kernel's first form; its float64 atan2 was
 // that kernel's register high-water mark) was not built at all -- the loop only records 5 doubles a step.  Not tried: an LDS
 // ring for the older scans, directions by rotation, a bound of four waves (rollout_kernel's spilled 34 VGPRs there).
-// rollout_kernel, lookahead_obs_kernel and the step kernels compile to the reports they had (untouched sources).
 #ifndef NAVSIM_ROLLOUT_OBS_WAVES
 #define NAVSIM_ROLLOUT_OBS_WAVES 3
 #endif
@@ -63,9 +63,6 @@ struct RollObsShared {
     double hact[NAVSIM_ROLLOUT_MAX_H][2];            // the action of step h as the step stores it
     int crashed;                                     // the last evaluated step crashed
 };
-
-// Dynamic LDS of one (arena, sequence): rollout_kernel's
-inline size_t rollout_obs_lds_bytes(const navsim_config* c) { return rollout_lds_bytes(c); }
 
 template <typename Field, int RULE, bool RECT>
 __global__ __launch_bounds__(kRolloutBlock, NAVSIM_ROLLOUT_OBS_WAVES) void rollout_obs_kernel(navsim_config c_, navsim_state st_, RolloutObsArgs a_) {
@@ -103,57 +100,20 @@ __global__ __launch_bounds__(kRolloutBlock, NAVSIM_ROLLOUT_OBS_WAVES) void rollo
         }
         return;
     }
-    float2* dir = (float2*)dyn;
-    float* rng = (float*)(dyn + sizeof(float2) * (size_t)B);
-    char* behind = dyn + lookahead_align16((size_t)B * (sizeof(float2) + sizeof(float)));
-    const bool ped_model = c.ped_model != NAVSIM_PED_NONE;
-    const bool sfm = c.ped_model == NAVSIM_PED_SFM;
-    PedShared ps = {};
-    double2* pair = nullptr;
-    if (ped_model) {
-        ps = ped_lds_carve(behind, N);
-        pair = (double2*)(behind + lookahead_align16(ped_lds_bytes(N)));
-    }
-    const Prims pr = {ps.seg, ps.disc, ps.info};
+    const ReplayLds l = replay_lds_carve(dyn, c, 0);
+    float* const rng = l.rng;
 
     int n = 0;
-    if (ped_model) { n = st.n_peds[e]; n = n > N ? N : n; n = n < 0 ? 0 : n; }
-    const double dt = c.time_step;
+    if (c.ped_model != NAVSIM_PED_NONE) { n = st.n_peds[e]; n = n > N ? N : n; n = n < 0 ? 0 : n; }
     const int ms = map_slot_of(c, st, e);
     const Field field(st.field, st.field_overflow, ms, H, W);
 
-    // ---- the carried values at h = 0: the state's (rollout_kernel's, line for line)
+    // ---- the carried values at h = 0: the state's (rollout_kernel's)
     const bool is_ped = wave == 0 && tid < n;
-    const size_t pq = (size_t)e * N + (is_ped ? tid : 0);
-    double pp[3] = {0.0, 0.0, 0.0}, pvel[2] = {0.0, 0.0}, pdist[3] = {0.0, 0.0, 0.0}, pyaw = 0.0, vpref = 0.0;
-    int head = 0, nw = 1;
-    bool legged = false;
-    const double* wp = nullptr;
-    const double* cmd = nullptr;
-    if (is_ped) {
-        pp[0] = st.ped_pose[pq * 3]; pp[1] = st.ped_pose[pq * 3 + 1]; pp[2] = st.ped_pose[pq * 3 + 2];
-        pvel[0] = st.ped_vel[pq * 2]; pvel[1] = st.ped_vel[pq * 2 + 1];
-        pdist[0] = st.ped_dist[pq * 3]; pdist[1] = st.ped_dist[pq * 3 + 1]; pdist[2] = st.ped_dist[pq * 3 + 2];
-        pyaw = st.ped_prev_yaw[pq];
-        legged = st.ped_has_legs[pq] && c.lidar_legs;
-        if (sfm) {
-            wp = st.ped_waypoints + (pq * c.max_waypoints) * 2;
-            nw = st.ped_n_waypoints[pq];
-            nw = nw < 1 ? 1 : (nw > c.max_waypoints ? c.max_waypoints : nw);         // (a state the step accepts holds 1 .. max_waypoints)
-            head = st.ped_wp_head[pq];
-            head = head < 0 ? 0 : (head > nw - 1 ? nw - 1 : head);
-            vpref = st.ped_v_pref[pq];
-        } else {
-            cmd = (a.ped_cmd ? a.ped_cmd : st.ped_cmd) + pq * 2;                     // held for the whole horizon
-        }
-    }
+    CarriedPed cp;
+    if (is_ped) carried_ped_load<true>(cp, c, st, (size_t)e * N + tid, c.ped_model == NAVSIM_PED_SFM, true, a.ped_cmd);
     if (tid == 64) {
-        const double* rp_g = st.robot_pose + 3 * (size_t)e;
-        sh.rp[0] = rp_g[0]; sh.rp[1] = rp_g[1]; sh.rp[2] = rp_g[2];
-        sh.prev_xy[0] = st.prev_pose[3 * (size_t)e]; sh.prev_xy[1] = st.prev_pose[3 * (size_t)e + 1];
-        sh.prev_act[0] = st.prev_action[2 * (size_t)e]; sh.prev_act[1] = st.prev_action[2 * (size_t)e + 1];
-        sh.steps = (long long)st.steps[e];
-        sh.nseg = 0; sh.ndisc = 0; sh.stop = 0; sh.length = 0;
+        rollout_carry_load(sh, st, e);
         so.crashed = 0;
         if (kseq == 0) a.out.status[e] = 1;
     }
@@ -163,14 +123,10 @@ __global__ __launch_bounds__(kRolloutBlock, NAVSIM_ROLLOUT_OBS_WAVES) void rollo
     const float rmax = (float)c.range_max;
     const float rcull = prim_cull_range(c.range_max);
     const float max_range = march_limit(H, W, c.range_max, c.resolution);
-    const float res = (float)c.resolution;
-    const bool int_range = int_range_ok(H, W);
     const char* rects = RECT ? (const char*)st.rect_table + (size_t)ms * rect_tiles_per_map(H, W) * sizeof(uint4) : nullptr;
-    const unsigned tpr = (unsigned)((W + 7) >> kRectShift);
     const float* thr = st.scan_threshold;
     const float* dthr = st.scan_discomfort;
     const double goal[2] = {st.robot_goal[2 * (size_t)e], st.robot_goal[2 * (size_t)e + 1]};
-    const int n_terms = n * (n - 1) / 2 + n;
     // rule 2's noise: one value per arena each, made scalars (lookahead_obs_kernel's)
     const float noise_std = a.noise ? uniform_f32(st.scan_noise_std[e]) : 0.0f;
     const bool noise_on = noise_std > 0.0f;
@@ -193,216 +149,51 @@ __global__ __launch_bounds__(kRolloutBlock, NAVSIM_ROLLOUT_OBS_WAVES) void rollo
     int dsteps = 0, exact = HZ, outcome = 0;
 
     for (int h = 0; h < HZ; ++h) {
-        // ---- (1) wavefront 0: waypoint pop and staging (ped_stage_wave on the carried values)
-        if (wave == 0 && n > 0 && sfm) {
-            if (is_ped) {
-                head = ped_pop_waypoints(wp, head, nw, pp);
-                ps.ax[tid] = pp[0]; ps.ay[tid] = pp[1]; ps.avx[tid] = pvel[0]; ps.avy[tid] = pvel[1];
-            }
-            if (tid == 0) {
-                double s, cs;
-                nv::sincos(sh.rp[2], s, cs);
-                const double prev_v = sh.prev_act[0];
-                ps.ax[n] = sh.rp[0]; ps.ay[n] = sh.rp[1];
-                ps.avx[n] = prev_v * cs; ps.avy[n] = prev_v * s;
-            }
-        }
-        // ---- (1) thread 64: the step's phase 0 on actions[e,k,h], operation for operation
-        if (tid == 64) {
-            double a0 = a.actions[2 * (row + h)], a1 = a.actions[2 * (row + h) + 1];
-            if (c.action_kind == NAVSIM_ACTION_WHEELS) {
-                const double wl = a0, wr = a1;
-                a0 = c.wheel_radius * (wl + wr) * 0.5;
-                a1 = c.wheel_radius * (wr - wl) / c.wheel_track;
-            }
-            if (c.clamp_action) {
-                a0 = a0 < c.linvel_lo ? c.linvel_lo : (a0 > c.linvel_hi ? c.linvel_hi : a0);
-                a1 = a1 < c.rotvel_lo ? c.rotvel_lo : (a1 > c.rotvel_hi ? c.rotvel_hi : a1);
-            }
-            if (c.min_turning_radius > 0.0) {                                        // env.py:595-600
-                const double lim = fabs(a1) * c.min_turning_radius;
-                if (a0 >= 0.0) a0 = (a0 > lim) ? a0 : lim;
-                else           a0 = (a0 < -lim) ? a0 : -lim;
-            }
-            const double th_old = sh.rp[2];
-            const double th = th_old + a1 * dt;                                      // set_vel's intermediate heading
-            double s0, c0, s1, c1;
-            nv::sincos(th_old, s0, c0);
-            nv::sincos(th, s1, c1);
-            double p[3] = {sh.rp[0], sh.rp[1], th_old};                              // env.py:664
-            nv::set_vel_with(p, a0, a1, dt, c.axle_offset, s0, c0, s1, c1, nullptr);
-            sh.np[0] = p[0]; sh.np[1] = p[1]; sh.np[2] = p[2];
-            sh.act[0] = a0; sh.act[1] = a1;
-            so.hp[h][0] = p[0]; so.hp[h][1] = p[1]; so.hp[h][2] = p[2];
-            so.hact[h][0] = a0; so.hact[h][1] = a1;
-            const float lth = (float)p[2];                                           // env.py:386
-            double sT, cT;
-            nv::sincos((double)lth, sT, cT);
-            sh.cT = cT; sh.sT = sT;
-            int i0, j0;
-            nv::xy_to_ij_f32((float)p[0], (float)p[1], c, i0, j0);                   // env.py:419
-            sh.i0 = i0; sh.j0 = j0;
-            sh.next_chunk = 0; sh.vote = 0;
-            a.out.pose[3 * (row + h)] = p[0]; a.out.pose[3 * (row + h) + 1] = p[1]; a.out.pose[3 * (row + h) + 2] = p[2];
-        }
-        __syncthreads();
-        // ---- (2) the pair terms, shared out over the workgroup
-        if (sfm && n > 0) {
-            for (int t = tid; t < n_terms; t += BLOCK) ped_pair_term(c, ps, pair, n, t);
-            __syncthreads();
-        }
-        const float lx = (float)sh.np[0], ly = (float)sh.np[1], lth = (float)sh.np[2];            // env.py:386
-        // ---- (3) wavefront 0: the pedestrians at t + h + 1 and what the lidar sees of them
-        if (wave == 0 && n > 0) {
-            bool due = false;
-            if (is_ped) {
-                if (sfm) {
-                    ped_sfm_step(c, field, ps, pair, n, tid, vpref, wp + 2 * head, dt, pp, pvel);
-                    // the step's predicate for ped_due (ped_finish): the post-move distance to the LAST waypoint under 0.5 m
-                    const double ddx = pp[0] - wp[2 * (nw - 1)], ddy = pp[1] - wp[2 * (nw - 1) + 1];
-                    due = sqrt(ddx * ddx + ddy * ddy) < 0.5;
-                } else {
-                    nv::set_vel(pp, cmd[0], cmd[1], dt, 0.0, pvel);                  // env.py:662
-                }
-                nv::leg_odometry(pp, pvel, pyaw, dt, pdist);
-                pyaw = nv::wrap_pi(pp[2]);
-            }
-            if (mask_of(due) != 0 && exact == HZ) exact = h + 1;                     // navsim_rollout's rule 8 (wave-uniform)
-            const lanemask_t lm = mask_of(legged);
-            const int legs_all = __popcll(lm), legs_below = __popcll(lm & ((1ull << tid) - 1ull));
-            const int nseg_w = 4 * (n - legs_all);
-            if (tid == 0) { sh.nseg = nseg_w; sh.ndisc = 2 * legs_all; }
-            if (is_ped) {                                                            // env.py:392-414
-                if (legged) {
-                    float cc[4];
-                    nv::leg_centres((float)pp[0], (float)pp[1], (float)pp[2], (float)pdist[0], (float)pdist[1], (float)pdist[2], cc);
-                    const int q = 2 * legs_below;
-                    ps.disc[q][0] = cc[0]; ps.disc[q][1] = cc[1];
-                    ps.disc[q + 1][0] = cc[2]; ps.disc[q + 1][1] = cc[3];
-                } else {
-                    const double fpx[4] = {0.22, -0.22, -0.22, 0.22};   // human.py:5-10
-                    const double fpy[4] = {0.19, 0.19, -0.19, -0.19};
-                    double s, cs;
-                    nv::sincos(pp[2], s, cs);
-                    float vx[4], vy[4];
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        vx[v] = (float)((cs * fpx[v] - s * fpy[v]) + pp[0]);
-                        vy[v] = (float)((s * fpx[v] + cs * fpy[v]) + pp[1]);
-                    }
-                    const int q = 4 * (tid - legs_below);
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int w = (v + 1) & 3;
-                        ps.seg[q + v][0] = vx[v]; ps.seg[q + v][1] = vy[v]; ps.seg[q + v][2] = vx[w]; ps.seg[q + v][3] = vy[w];
-                    }
-                }
-            }
-            wave_lds_sync();
-            prim_in_range<64>(nseg_w + 2 * legs_all, nseg_w, lx, ly, rcull, pr, (float)step, (float)(c.angle_min + (double)lth));
-        }
-        // ---- (4) the static ray of every beam, 64 adjacent beams at a time, handed out as wavefronts finish
-        {
-            const int i0 = __builtin_amdgcn_readfirstlane(sh.i0), j0 = __builtin_amdgcn_readfirstlane(sh.j0);
-            const float x0 = (float)i0, y0 = (float)j0;
-            const double cT = sh.cT, sT = sh.sT;
-            for (;;) {
-                int chunk = 0;
-                if (lane == 0) chunk = atomicAdd(&sh.next_chunk, 1);
-                chunk = __builtin_amdgcn_readfirstlane(chunk);
-                if (chunk * 64 >= B) break;
-                const int k = chunk * 64 + lane;
-                if (k < B) {
-                    float dx, dy;
-                    beam_dir_k(c, st.beam_table, k, step, (double)lth, cT, sT, dx, dy);
-                    dir[k] = make_float2(dx, dy);
-                    float t = 0.0f;
-                    lanemask_t active = mask_of(true), hit = 0;
-                    while (active != 0)
-                        probe_round<Field, RULE, RECT>(field, rects, tpr, x0, y0, dx, dy, (unsigned)W, (unsigned)H, max_range, t, active, hit);
-                    rng[k] = ray_result<RULE>(hit, int_range, i0, j0, x0, y0, dx, dy, t, max_range) * res;
-                }
-            }
-        }
-        __syncthreads();
-        {
-            const int nseg = sh.nseg, ndisc = sh.ndisc;
-            if (nseg + ndisc) {
-                merge_prims_culled_core<BLOCK>(B, lx, ly, (float)step, nseg, ndisc, pr, dir, rng);
-                __syncthreads();
-            }
-        }
+        // ---- (1) - (4): the scan of step h (rollout_kernel's rollout_advance); thread 64 keeps the pose and the action for the tail
+        rollout_advance<BLOCK, Field, RULE, RECT>(c, st, field, rects, l, sh, cp, n, is_ped, a.actions + 2 * (row + h),
+                                                  a.out.pose + 3 * (row + h), so.hp[h], so.hact[h], h, HZ, exact, step, rcull, max_range);
         // ---- (5) rules 2 and 4: clip, noise, flags and margin in one pass; the row of step h from the same register
-        {
-            const uint64_t nkey = noise_key(h, 0);
-            const int n_fill = S - 1 - n_hist;                                       // (0 .. S - 1: n_hist lies in 0 .. S - 1)
-            const float* const src = h == 0 ? prev_e : last;
-            float* const all_h = a.out.obs_all ? a.out.obs_all + (row + h) * D : nullptr;
-            int cr = 0, dc = 0;
-            float mg = INFINITY;
-            for (int k = tid; k < B; k += BLOCK) {
-                const float r = lookobs_finish(rng[k], rmax, noise_on, noise_std, nkey, k);
-                const float thr_k = thr[k];
-                cr |= (r < thr_k);
-                dc |= (r < dthr[k]);
-                const float m = r - thr_k;
-                mg = m < mg ? m : mg;
-                rng[k] = r;                                                          // (for the ratio: read back by this thread)
-                for (int j = 0; j < S - 1; ++j) {                                    // env.py:257-279; in place: slot j + 1 is read first
-                    const float v = j < n_fill ? r : src[(size_t)(j + 1) * B + k];
-                    last[(size_t)j * B + k] = v;
-                    if (all_h) all_h[(size_t)j * B + k] = v;
-                }
-                last[(size_t)(S - 1) * B + k] = r;
-                if (all_h) all_h[(size_t)(S - 1) * B + k] = r;
+        const uint64_t nkey = noise_key(h, 0);
+        const int n_fill = S - 1 - n_hist;                                       // (0 .. S - 1: n_hist lies in 0 .. S - 1)
+        const float* const src = h == 0 ? prev_e : last;
+        float* const all_h = a.out.obs_all ? a.out.obs_all + (row + h) * D : nullptr;
+        int cr = 0, dc = 0;
+        float mg = INFINITY;
+        for (int k = tid; k < B; k += BLOCK) {
+            const float r = lookobs_finish(rng[k], rmax, noise_on, noise_std, nkey, k);
+            const float thr_k = thr[k];
+            cr |= (r < thr_k);
+            dc |= (r < dthr[k]);
+            const float m = r - thr_k;
+            mg = m < mg ? m : mg;
+            rng[k] = r;                                                          // (for the ratio: read back by this thread)
+            for (int j = 0; j < S - 1; ++j) {                                    // env.py:257-279; in place: slot j + 1 is read first
+                const float v = j < n_fill ? r : src[(size_t)(j + 1) * B + k];
+                last[(size_t)j * B + k] = v;
+                if (all_h) all_h[(size_t)j * B + k] = v;
             }
-            mg = wave_min_f32(mg);
-            const int v = (int)(mask_of(cr != 0) != 0) | ((int)(mask_of(dc != 0) != 0) << 1);
-            if (lane == 0) {
-                if (v != 0) atomicOr(&sh.vote, v);
-                wave_margin[wave] = mg;
-            }
+            last[(size_t)(S - 1) * B + k] = r;
+            if (all_h) all_h[(size_t)(S - 1) * B + k] = r;
         }
-        __syncthreads();
-        const int vote = __builtin_amdgcn_readfirstlane(sh.vote);
-        const int crash = vote & 1, discomfort = (vote >> 1) & 1;
-        double rmin = 1.0e300;
-        if (discomfort && !crash) {                                                  // env.py:563-569, as the step's phase 3
-            for (int k = tid; k < B; k += BLOCK) {
-                const double ratio = nv::discomfort_ratio((double)rng[k], thr[k], dthr[k]);
-                rmin = ratio < rmin ? ratio : rmin;
-            }
-            rmin = wave_min_f64(rmin);
-            if (lane == 0) wave_ratio[wave] = rmin;
-            __syncthreads();
-        }
+        const BeamVerdict v = replay_verdict<BLOCK, false>(B, cr, dc, mg, &sh.vote, wave_margin, wave_ratio, rng, thr, dthr, rmax);
         if (tid == 0) {
-            float margin = wave_margin[0];
-            for (int w = 1; w < WAVES; ++w) margin = wave_margin[w] < margin ? wave_margin[w] : margin;
-            if (discomfort && !crash)
-                for (int w = 1; w < WAVES; ++w) rmin = wave_ratio[w] < rmin ? wave_ratio[w] : rmin;
-            const double prev_xy[2] = {sh.prev_xy[0], sh.prev_xy[1]};
-            const double pose[2] = {sh.np[0], sh.np[1]};
-            const double vel[2] = {sh.prev_act[0], sh.prev_act[1]};                  // env.py:453: the PREVIOUS action
-            const nv::RewardOut o = nv::reward_scalar(c, prev_xy, pose, vel, goal, crash != 0, discomfort != 0, rmin);
             const long long steps_now = sh.steps + 1;                                // env.py:592
-            const int limit = !o.done && c.max_episode_steps > 0 && steps_now >= (long long)c.max_episode_steps;
-            const int done = o.done || limit;
-            a.out.reward[row + h] = o.reward;
-            ret = ret + g * o.reward;
+            const StepVerdict r = replay_reward(c, sh.prev_xy, sh.sp.p, sh.prev_act, goal, v, steps_now);
+            a.out.reward[row + h] = r.o.reward;
+            ret = ret + g * r.o.reward;
             g = g * a.gamma;
-            min_margin = margin < min_margin ? margin : min_margin;
-            dsteps += (discomfort && !crash) ? 1 : 0;
-            distance = o.distance;
-            outcome = (o.success != 0.0f ? 1 : 0) | (o.crash != 0.0f ? 2 : 0) | (limit ? 4 : 0);
+            min_margin = v.margin < min_margin ? v.margin : min_margin;
+            dsteps += (v.discomfort && !v.crash) ? 1 : 0;
+            distance = r.o.distance;
+            outcome = (r.o.success != 0.0f ? 1 : 0) | (r.o.crash != 0.0f ? 2 : 0) | (r.truncated ? 4 : 0);
             // the carry (navsim_rollout's rule 2): what phase 6 of the step stores when the episode goes on
-            sh.rp[0] = sh.np[0]; sh.rp[1] = sh.np[1]; sh.rp[2] = sh.np[2];
-            sh.prev_xy[0] = sh.np[0]; sh.prev_xy[1] = sh.np[1];
+            sh.rp[0] = sh.sp.p[0]; sh.rp[1] = sh.sp.p[1]; sh.rp[2] = sh.sp.p[2];
+            sh.prev_xy[0] = sh.sp.p[0]; sh.prev_xy[1] = sh.sp.p[1];
             sh.prev_act[0] = sh.act[0]; sh.prev_act[1] = sh.act[1];
             sh.steps = steps_now;
             sh.length = h + 1;
-            sh.stop = done;
-            so.crashed = o.crash != 0.0f;
+            sh.stop = r.done;
+            so.crashed = r.o.crash != 0.0f;
         }
         __syncthreads();
         if (sh.stop) break;                                                          // nothing behind a done step
@@ -449,14 +240,7 @@ __global__ __launch_bounds__(kRolloutBlock, NAVSIM_ROLLOUT_OBS_WAVES) void rollo
             for (int i = 0; i < 4; ++i) gl[i] = g4[i];
         }
         if (rev) {                                                                   // the re-scan's lidar pose: the carried prev_pose
-            const float lth = (float)pth;
-            sh.np[0] = px; sh.np[1] = py; sh.np[2] = pth;
-            double sT, cT;
-            nv::sincos((double)lth, sT, cT);
-            sh.cT = cT; sh.sT = sT;
-            int i0, j0;
-            nv::xy_to_ij_f32((float)px, (float)py, c, i0, j0);
-            sh.i0 = i0; sh.j0 = j0;
+            scan_pose_set(sh.sp, c, px, py, pth);
             sh.next_chunk = 0;
         }
     }
@@ -464,10 +248,8 @@ __global__ __launch_bounds__(kRolloutBlock, NAVSIM_ROLLOUT_OBS_WAVES) void rollo
     // ---- rule 3: the crash re-scan, from the carried prev_pose, the sequence's own pedestrians of t + hl + 1 (still in LDS)
     if (crashed) {
         __syncthreads();
-        const float lx = (float)sh.np[0], ly = (float)sh.np[1], lth = (float)sh.np[2];
-        const int i0 = __builtin_amdgcn_readfirstlane(sh.i0), j0 = __builtin_amdgcn_readfirstlane(sh.j0);
-        lookobs_scan<BLOCK, Field, RULE, RECT>(c, st, field, rects, pr, sh.nseg, sh.ndisc, lx, ly, lth, i0, j0, sh.cT, sh.sT, step, rcull,
-                                               max_range, &sh.next_chunk, dir, rng);
+        replay_scan<BLOCK, Field, RULE, RECT>(c, st, field, rects, l.pr, sh.nseg, sh.ndisc, sh.sp, step, rcull, max_range, &sh.next_chunk,
+                                              l.dir, rng);
         const uint64_t nkey2 = noise_key(hl, 1);                                     // the re-scan's key: step_key_h + 1
         const int n_fill = S - 1 - n_hist;
         float* const all_h = a.out.obs_all ? a.out.obs_all + (row + hl) * D : nullptr;

@@ -25,6 +25,8 @@
 //   kernels_dwa.hpp  local planner: a dynamic-window action per arena (navsim_dwa)
 //   kernels_local_map.hpp  egocentric local map: wall and pedestrian grids per arena in the robot's frame (navsim_local_map)
 //   kernels_scan_labels.hpp  scan ground truth: the robot's clean scan and per-beam hit labels (navsim_scan_labels)
+//   kernels_replay.hpp   the pieces of the step that the read-only kernels below re-enact (twist, scan pose, primitives, march,
+//                        verdict, reward, carried pedestrian, LDS layout), each stated once
 //   kernels_lookahead.hpp    action lookahead: the step's outcomes for K candidate actions per arena (navsim_lookahead)
 //   kernels_lookahead_obs.hpp  lookahead observations: the step's whole return for K candidate actions per arena (navsim_lookahead_obs)
 //   kernels_rollout.hpp      action-sequence rollout: the next H steps' outcomes for K action sequences per arena (navsim_rollout)
@@ -59,6 +61,7 @@ namespace {
 #include "kernels_dwa.hpp"
 #include "kernels_local_map.hpp"
 #include "kernels_scan_labels.hpp"
+#include "kernels_replay.hpp"
 #include "kernels_lookahead.hpp"
 #include "kernels_lookahead_obs.hpp"
 #include "kernels_rollout.hpp"
@@ -528,64 +531,36 @@ int launch_local_map(const navsim_config* c, const navsim_state* st, const Local
     return launch_status();
 }
 
-// navsim_scan_labels: a workgroup per arena; one kernel per (field type, march rule, rect records or not) as the pedestrian
-// scans have them (launch_ped_scan) -- eleven forms
-template <typename F, bool RECT>
-int launch_scan_labels(const navsim_config* c, const navsim_state* st, const ScanLabelsArgs& a, hipStream_t s) {
-    const size_t lds = scan_labels_lds_bytes(c);
-    return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
-        auto kernel = scan_labels_kernel<F, decltype(rule)::value, RECT>;
-        if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
-        kernel<<<c->n_envs, kScanLabelsBlock, lds, s>>>(*c, *st, a);
-        return launch_status();
-    });
+// The marched launches -- navsim_scan_labels, navsim_lookahead, navsim_lookahead_obs, navsim_rollout, navsim_rollout_obs -- have one
+// kernel per (field type, march rule, rect records or not) as the pedestrian scans have them (launch_ped_scan): eleven forms
+// each.  A family names its kernel template; launch_marched picks the form and launches it.
+#define NAVSIM_MARCHED_FAMILY(NAME, KERNEL) \
+    struct NAME { template <typename F, int RULE, bool RECT> static constexpr auto kernel() { return KERNEL<F, RULE, RECT>; } }
+NAVSIM_MARCHED_FAMILY(ScanLabelsFamily, scan_labels_kernel);
+NAVSIM_MARCHED_FAMILY(LookaheadFamily, lookahead_kernel);
+NAVSIM_MARCHED_FAMILY(LookObsFamily, lookahead_obs_kernel);
+NAVSIM_MARCHED_FAMILY(RolloutFamily, rollout_kernel);
+NAVSIM_MARCHED_FAMILY(RolloutObsFamily, rollout_obs_kernel);
+#undef NAVSIM_MARCHED_FAMILY
+
+// f(field_tag<Field>, std::bool_constant<RECT>) for the state's field format and rect records (the argument checks have refused
+// every other format, and rect records beside a float32 field)
+template <typename F>
+int with_field_rects(const navsim_config* c, const navsim_state* st, F&& f) {
+    if (c->field_format != NAVSIM_FIELD_U16T) return f(field_tag<FieldF32>{}, std::false_type{});
+    return st->rect_table ? f(field_tag<FieldU16T>{}, std::true_type{}) : f(field_tag<FieldU16T>{}, std::false_type{});
 }
 
-// navsim_lookahead: a workgroup per arena, the forms of launch_scan_labels
-template <typename F, bool RECT>
-int launch_lookahead(const navsim_config* c, const navsim_state* st, const LookaheadArgs& a, hipStream_t s) {
-    const size_t lds = lookahead_lds_bytes(c, a.K);
-    return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
-        auto kernel = lookahead_kernel<F, decltype(rule)::value, RECT>;
-        if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
-        kernel<<<c->n_envs, kLookaheadBlock, lds, s>>>(*c, *st, a);
-        return launch_status();
-    });
-}
-
-// navsim_lookahead_obs: a workgroup per arena, the forms and the LDS of launch_lookahead
-template <typename F, bool RECT>
-int launch_lookahead_obs(const navsim_config* c, const navsim_state* st, const LookObsArgs& a, hipStream_t s) {
-    const size_t lds = lookahead_lds_bytes(c, a.K);
-    return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
-        auto kernel = lookahead_obs_kernel<F, decltype(rule)::value, RECT>;
-        if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
-        kernel<<<c->n_envs, kLookaheadBlock, lds, s>>>(*c, *st, a);
-        return launch_status();
-    });
-}
-
-// navsim_rollout: a workgroup per (arena, sequence), the forms of launch_scan_labels
-template <typename F, bool RECT>
-int launch_rollout(const navsim_config* c, const navsim_state* st, const RolloutArgs& a, hipStream_t s) {
-    const size_t lds = rollout_lds_bytes(c);
-    return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
-        auto kernel = rollout_kernel<F, decltype(rule)::value, RECT>;
-        if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
-        kernel<<<(unsigned)((size_t)c->n_envs * a.K), kRolloutBlock, lds, s>>>(*c, *st, a);
-        return launch_status();
-    });
-}
-
-// navsim_rollout_obs: a workgroup per (arena, sequence), the forms of launch_rollout
-template <typename F, bool RECT>
-int launch_rollout_obs(const navsim_config* c, const navsim_state* st, const RolloutObsArgs& a, hipStream_t s) {
-    const size_t lds = rollout_obs_lds_bytes(c);
-    return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
-        auto kernel = rollout_obs_kernel<F, decltype(rule)::value, RECT>;
-        if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
-        kernel<<<(unsigned)((size_t)c->n_envs * a.K), kRolloutBlock, lds, s>>>(*c, *st, a);
-        return launch_status();
+template <typename Family, typename Args>
+int launch_marched(const navsim_config* c, const navsim_state* st, const Args& a, size_t grid, int block, size_t lds, hipStream_t s) {
+    return with_field_rects(c, st, [&](auto field, auto rect) {
+        using F = typename decltype(field)::type;
+        return with_march_rule<F>(march_rule_variant(c), [&](auto rule) {
+            auto kernel = Family::template kernel<F, decltype(rule)::value, decltype(rect)::value>();
+            if (allow_lds((const void*)kernel, lds) != NAVSIM_OK) return (int)NAVSIM_E_UNSUPPORTED;
+            kernel<<<(unsigned)grid, block, lds, s>>>(*c, *st, a);
+            return launch_status();
+        });
     });
 }
 
@@ -1706,22 +1681,21 @@ int navsim_scan_labels(const navsim_config* c, const navsim_state* st, const uin
     if (c->n_envs == 0) return NAVSIM_OK;
     ScanLabelsArgs a = {};
     a.out = *out; a.skip = skip;
-    hipStream_t s = (hipStream_t)stream;
-    if (c->field_format == NAVSIM_FIELD_U16T)
-        return st->rect_table ? launch_scan_labels<FieldU16T, true>(c, st, a, s) : launch_scan_labels<FieldU16T, false>(c, st, a, s);
-    return launch_scan_labels<FieldF32, false>(c, st, a, s);
+    return launch_marched<ScanLabelsFamily>(c, st, a, c->n_envs, kScanLabelsBlock, scan_labels_lds_bytes(c), (hipStream_t)stream);
 }
 
-// what navsim_lookahead and navsim_lookahead_obs refuse alike, before anything touches the device (K: the number of candidates)
-static int lookahead_check(const navsim_config* c, const navsim_state* st, int K, const double* ped_cmd) {
-    if (K < 1 || K > NAVSIM_LOOKAHEAD_MAX) return NAVSIM_E_ARG;
+// what navsim_lookahead, navsim_lookahead_obs, navsim_rollout, navsim_rollout_obs and navsim_mppi refuse alike of a state and its
+// configuration, before anything touches the device.  wp_cap: the rollouts also refuse max_waypoints > NAVSIM_MAX_WAYPOINTS;
+// lds: the entry's dynamic LDS
+static int replay_check(const navsim_config* c, const navsim_state* st, const double* ped_cmd, bool wp_cap, size_t lds) {
     if (!st->robot_pose || !st->robot_goal || !st->prev_action || !st->prev_pose || !st->steps || !st->field ||
         !st->scan_threshold || !st->scan_discomfort)
         return NAVSIM_E_ARG;
     if (c->ped_model != NAVSIM_PED_NONE && c->ped_model != NAVSIM_PED_EXTERNAL && c->ped_model != NAVSIM_PED_SFM) return NAVSIM_E_ARG;
     const bool peds = c->ped_model != NAVSIM_PED_NONE;
     if (peds && (!st->n_peds || !st->ped_pose || !st->ped_vel || !st->ped_prev_yaw || !st->ped_dist || !st->ped_has_legs)) return NAVSIM_E_ARG;
-    if (c->ped_model == NAVSIM_PED_SFM && (!st->ped_v_pref || !st->ped_waypoints || !st->ped_n_waypoints || !st->ped_wp_head || c->max_waypoints < 1))
+    if (c->ped_model == NAVSIM_PED_SFM && (!st->ped_v_pref || !st->ped_waypoints || !st->ped_n_waypoints || !st->ped_wp_head ||
+                                           c->max_waypoints < 1 || (wp_cap && c->max_waypoints > NAVSIM_MAX_WAYPOINTS)))
         return NAVSIM_E_ARG;
     if (c->ped_model == NAVSIM_PED_EXTERNAL && !ped_cmd && !st->ped_cmd) return NAVSIM_E_ARG;
     if (c->n_envs < 0 || c->n_beams < 1 || c->map_h < 1 || c->map_w < 1) return NAVSIM_E_ARG;
@@ -1735,8 +1709,14 @@ static int lookahead_check(const navsim_config* c, const navsim_state* st, int K
     if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
     if (st->rect_table && (c->field_format != NAVSIM_FIELD_U16T || c->map_h > 1024 || c->map_w > 1024)) return NAVSIM_E_UNSUPPORTED;
     if (peds && c->angle_last - c->angle_min > nv::kTwoPi) return NAVSIM_E_UNSUPPORTED;     // the culled merge: dispatch_step
-    if (lookahead_lds_bytes(c, K) > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;
+    if (lds > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;
     return NAVSIM_OK;
+}
+
+// navsim_lookahead and navsim_lookahead_obs (K: the number of candidates)
+static int lookahead_check(const navsim_config* c, const navsim_state* st, int K, const double* ped_cmd) {
+    if (K < 1 || K > NAVSIM_LOOKAHEAD_MAX) return NAVSIM_E_ARG;
+    return replay_check(c, st, ped_cmd, false, lookahead_lds_bytes(c, K));
 }
 
 int navsim_lookahead(const navsim_config* c, const navsim_state* st, const navsim_lookahead_params* p, const double* actions,
@@ -1753,10 +1733,7 @@ int navsim_lookahead(const navsim_config* c, const navsim_state* st, const navsi
     LookaheadArgs a = {};
     a.out = *out; a.actions = actions; a.ped_cmd = c->ped_model == NAVSIM_PED_EXTERNAL ? ped_cmd : nullptr; a.skip = skip;
     a.K = p->n_actions; a.range = p->range;
-    hipStream_t s = (hipStream_t)stream;
-    if (c->field_format == NAVSIM_FIELD_U16T)
-        return st->rect_table ? launch_lookahead<FieldU16T, true>(c, st, a, s) : launch_lookahead<FieldU16T, false>(c, st, a, s);
-    return launch_lookahead<FieldF32, false>(c, st, a, s);
+    return launch_marched<LookaheadFamily>(c, st, a, c->n_envs, kLookaheadBlock, lookahead_lds_bytes(c, a.K), (hipStream_t)stream);
 }
 
 int navsim_lookahead_obs(const navsim_config* c, const navsim_state* st, const navsim_lookahead_obs_params* p, const double* actions,
@@ -1778,10 +1755,7 @@ int navsim_lookahead_obs(const navsim_config* c, const navsim_state* st, const n
     LookObsArgs a = {};
     a.out = *out; a.actions = actions; a.ped_cmd = c->ped_model == NAVSIM_PED_EXTERNAL ? ped_cmd : nullptr; a.obs_prev = obs_prev;
     a.skip = skip; a.K = p->n_actions; a.noise = noise ? 1 : 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (c->field_format == NAVSIM_FIELD_U16T)
-        return st->rect_table ? launch_lookahead_obs<FieldU16T, true>(c, st, a, s) : launch_lookahead_obs<FieldU16T, false>(c, st, a, s);
-    return launch_lookahead_obs<FieldF32, false>(c, st, a, s);
+    return launch_marched<LookObsFamily>(c, st, a, c->n_envs, kLookaheadBlock, lookahead_lds_bytes(c, a.K), (hipStream_t)stream);
 }
 
 // what navsim_rollout refuses, before anything touches the device (navsim_mppi refuses the same with the same codes)
@@ -1794,28 +1768,8 @@ static int rollout_check(const navsim_config* c, const navsim_state* st, const n
     if (p->n_seq < 1 || p->n_seq > NAVSIM_ROLLOUT_MAX_K || p->horizon < 1 || p->horizon > NAVSIM_ROLLOUT_MAX_H) return NAVSIM_E_ARG;
     if (!std::isfinite(p->range) || !(p->range > 0.0) || !(p->range <= c->range_max)) return NAVSIM_E_ARG;
     if (!(p->gamma >= 0.0) || !(p->gamma <= 1.0)) return NAVSIM_E_ARG;
-    if (!st->robot_pose || !st->robot_goal || !st->prev_action || !st->prev_pose || !st->steps || !st->field ||
-        !st->scan_threshold || !st->scan_discomfort)
-        return NAVSIM_E_ARG;
-    if (c->ped_model != NAVSIM_PED_NONE && c->ped_model != NAVSIM_PED_EXTERNAL && c->ped_model != NAVSIM_PED_SFM) return NAVSIM_E_ARG;
-    const bool peds = c->ped_model != NAVSIM_PED_NONE;
-    if (peds && (!st->n_peds || !st->ped_pose || !st->ped_vel || !st->ped_prev_yaw || !st->ped_dist || !st->ped_has_legs)) return NAVSIM_E_ARG;
-    if (c->ped_model == NAVSIM_PED_SFM && (!st->ped_v_pref || !st->ped_waypoints || !st->ped_n_waypoints || !st->ped_wp_head ||
-                                           c->max_waypoints < 1 || c->max_waypoints > NAVSIM_MAX_WAYPOINTS))
-        return NAVSIM_E_ARG;
-    if (c->ped_model == NAVSIM_PED_EXTERNAL && !ped_cmd && !st->ped_cmd) return NAVSIM_E_ARG;
-    if (c->n_envs < 0 || c->n_beams < 1 || c->map_h < 1 || c->map_w < 1) return NAVSIM_E_ARG;
-    if (c->max_peds < (peds ? 1 : 0) || c->max_peds > NAVSIM_MAX_PEDS) return NAVSIM_E_ARG;
-    if (c->march_rule < NAVSIM_MARCH_F64 || c->march_rule > NAVSIM_MARCH_F32_FMA) return NAVSIM_E_ARG;
-    if (!(c->resolution > 0.0) || !std::isfinite(c->resolution) || !(c->time_step > 0.0) || !std::isfinite(c->time_step)) return NAVSIM_E_ARG;
-    if (c->action_kind != NAVSIM_ACTION_TWIST && c->action_kind != NAVSIM_ACTION_WHEELS) return NAVSIM_E_ARG;
-    if (c->action_kind == NAVSIM_ACTION_WHEELS && (!(c->wheel_radius > 0.0) || !std::isfinite(c->wheel_radius) || !std::isfinite(c->wheel_track)))
-        return NAVSIM_E_ARG;
-    if (st->map_slot && c->shared_field) return NAVSIM_E_ARG;
-    if (c->field_format != NAVSIM_FIELD_F32 && c->field_format != NAVSIM_FIELD_U16T) return NAVSIM_E_UNSUPPORTED;
-    if (st->rect_table && (c->field_format != NAVSIM_FIELD_U16T || c->map_h > 1024 || c->map_w > 1024)) return NAVSIM_E_UNSUPPORTED;
-    if (peds && c->angle_last - c->angle_min > nv::kTwoPi) return NAVSIM_E_UNSUPPORTED;     // the culled merge: dispatch_step
-    if (rollout_lds_bytes(c) > kLdsPerCu) return NAVSIM_E_UNSUPPORTED;
+    const int rc = replay_check(c, st, ped_cmd, true, rollout_lds_bytes(c));
+    if (rc != NAVSIM_OK) return rc;
     if ((long long)c->n_envs * p->n_seq > 0x7FFFFFFFLL) return NAVSIM_E_UNSUPPORTED;         // one workgroup per (arena, sequence)
     return NAVSIM_OK;
 }
@@ -1826,9 +1780,7 @@ static int rollout_launch(const navsim_config* c, const navsim_state* st, const 
     RolloutArgs a = {};
     a.out = *out; a.actions = actions; a.ped_cmd = c->ped_model == NAVSIM_PED_EXTERNAL ? ped_cmd : nullptr; a.skip = skip;
     a.K = p->n_seq; a.H = p->horizon; a.range = p->range; a.gamma = p->gamma;
-    if (c->field_format == NAVSIM_FIELD_U16T)
-        return st->rect_table ? launch_rollout<FieldU16T, true>(c, st, a, s) : launch_rollout<FieldU16T, false>(c, st, a, s);
-    return launch_rollout<FieldF32, false>(c, st, a, s);
+    return launch_marched<RolloutFamily>(c, st, a, (size_t)c->n_envs * a.K, kRolloutBlock, rollout_lds_bytes(c), s);
 }
 
 int navsim_rollout(const navsim_config* c, const navsim_state* st, const navsim_rollout_params* p, const double* actions,
@@ -1852,7 +1804,7 @@ int navsim_rollout_obs(const navsim_config* c, const navsim_state* st, const nav
     const bool noise = p->noise == NAVSIM_LOOKOBS_NOISE_STEP && c->add_scan_noise;
     if (noise && (!st->scan_noise_std || !st->episode)) return NAVSIM_E_ARG;
     // everything navsim_rollout refuses, at R = range_max (a range_max that is no valid R is refused as its R would be); the
-    // dynamic LDS is the rollout's (rollout_obs_lds_bytes)
+    // dynamic LDS is the rollout's
     const navsim_rollout_params rp = {p->n_seq, p->horizon, c->range_max, p->gamma};
     const navsim_rollout_out ro = {out->reward, out->pose, out->ret, out->length, out->outcome, out->discomfort_steps,
                                    out->min_margin, out->distance, out->exact_steps, out->status};
@@ -1862,10 +1814,7 @@ int navsim_rollout_obs(const navsim_config* c, const navsim_state* st, const nav
     RolloutObsArgs a = {};
     a.out = *out; a.actions = actions; a.ped_cmd = c->ped_model == NAVSIM_PED_EXTERNAL ? ped_cmd : nullptr; a.obs_prev = obs_prev;
     a.skip = skip; a.K = p->n_seq; a.H = p->horizon; a.noise = noise ? 1 : 0; a.gamma = p->gamma;
-    hipStream_t s = (hipStream_t)stream;
-    if (c->field_format == NAVSIM_FIELD_U16T)
-        return st->rect_table ? launch_rollout_obs<FieldU16T, true>(c, st, a, s) : launch_rollout_obs<FieldU16T, false>(c, st, a, s);
-    return launch_rollout_obs<FieldF32, false>(c, st, a, s);
+    return launch_marched<RolloutObsFamily>(c, st, a, (size_t)c->n_envs * a.K, kRolloutBlock, rollout_lds_bytes(c), (hipStream_t)stream);
 }
 
 int navsim_ped_forecast(const navsim_config* c, const navsim_state* st, const navsim_ped_forecast_params* p, const double* actions,
